@@ -10,14 +10,20 @@ of T are inside the timed region (§8(d): host xyz in -> T out). Each rank runs 
 (weak scaling); RCCL all-gathers the per-reading {T, iterations, inlier ratio}.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|single|app|prefilter]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line. --dump-outputs DIR
+writes what the last timed step returned as DIR/<name>.npy. --full adds everything else the line can
+carry: the oracle as cpu_baseline with parity_vs_oracle, the batched / resident-input variants of the
+same workload and the figures that take runs of their own.
 
 Other configs: c3 (KITTI HDL-64 stream, N = 600 000), c4 (localization against a resident
 1 M-point map, device crops as references, r = 0.5), c5 (1024 independent pairs of 60 000 points
 sharded i mod G), single (one C2 pair through aicp_hip_register, latency), app (the C2 readings
 through App's per-reading calls, overlap + registerClouds, with the reference cache), prefilter
-(§8(f) rank 2). The line carries the NN kernel's roofline (HIP events on its stream), the oracle as
-cpu_baseline (median of 5 bounded samples on this host) and parity against it.
+(§8(f) rank 2). The line carries the NN kernel's roofline (HIP events on its stream), and with --full
+the oracle as cpu_baseline (median of 5 bounded samples on this host) and parity against it.
 """
 from __future__ import annotations
 
@@ -34,6 +40,29 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
+
+
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs writes at most, all arrays together
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: the arrays the timed path returned in its last step, one <name>.npy each,
+    float64 for 64-bit values and float32 for the rest. An array over its share of DUMP_LIMIT is
+    cut to a fixed seeded sample of its rows (ascending row order)."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype.itemsize == 8 else np.float32)
+        if a.nbytes > share:
+            rows = max(1, share // max(1, a.nbytes // len(a)))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), size=rows, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def stats_arrays(stats):
+    """The per-pair aicp_icp_stats a call returned (list of dicts) as one array per field."""
+    return {k: np.array([s[k] for s in stats]) for k in stats[0]} if stats else {}
 
 
 def cpu_model():
@@ -150,7 +179,9 @@ def bench_prefilter(args):
                 "bytes_model": "Q*(16 + 4*30) + 16*(touched points + touched nodes)",
             },
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"kept_points": o})
+        if world == 1 and args.cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import pyoracle as po
 
@@ -411,7 +442,7 @@ def bench_stream(args):
     # the same readings as a batch of independent pairs (r02's workload shape): reading i against
     # the first cloud (i < 5) or the UNcorrected reading 5*(i//5)-1, uploaded once, run resident
     batched = None
-    if rank == 0 and not args.no_batched:
+    if rank == 0 and args.batched:
         refs = [(st.first, st.first_origin)] + [(st.readings[j], st.origins[j]) for j in range(4, n_read, 5)]
         pairs = [dict(ref=refs[i // 5][0], read=st.readings[i], ref_origin=refs[i // 5][1],
                       read_origin=st.origins[i]) for i in range(n_read)]
@@ -472,7 +503,11 @@ def bench_stream(args):
             "batched_independent": batched,
         })
         add_traffic(out_line["roofline"], "nn_traffic_%s.json" % args.config)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            seq = {k: np.array([o[k] for o in out]) for k in ("status", "accepted", "reference", "is_reference",
+                                                               "corrected_origin")}
+            dump_outputs(args.dump_outputs, {"T": T, **seq, **stats_arrays([o["icp"] for o in out])})
+        if world == 1 and args.cpu_baseline:
             out_line["cpu_baseline"], out_line["parity_vs_oracle"] = cpu_stream(st, T, out, args)
         print(json.dumps(out_line))
     ctx.close()
@@ -551,7 +586,7 @@ def bench_c4(args):
         elapsed = sh.max_over_ranks(elapsed, dist, device="cuda")
     if rank == 0:
         value = world * n_read * args.steps / elapsed
-        crops = [len(pm.crop(-15.0, 15.0, poses[i])) for i in (0, n_read - 1)]
+        crops = [len(pm.crop(-15.0, 15.0, poses[i])) for i in (0, n_read - 1)] if args.full else None
         config = {"workload": "C4: localization-only, %d-pt map resident on the device, %d VLP-16 readings of N=%d, "
                               "reference = map cropped to +-15 m around each prior pose on the device "
                               "(getPointsInOrientedBox), overlap fixed 50%% (r = 0.5)" % (len(mp), n_read, n_pts),
@@ -567,7 +602,9 @@ def bench_c4(args):
                      "accuracy_vs_ground_truth": {"median_rot_rad": float(np.median([e[0] for e in errs])),
                                                   "median_trans_m": float(np.median([e[1] for e in errs]))},
                      "roofline": roofline_nn(nn, "k_icp_nn, one launch per ICP iteration of the 64-reading batch")})
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"T": T, **stats_arrays(st)})
+        if world == 1 and args.cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import pyoracle as po
 
@@ -640,19 +677,22 @@ def bench_c5(args):
     elapsed = time.perf_counter() - t0
     # the same batch with its inputs resident in HBM (aicp_hip_batch_upload once, then
     # aicp_hip_batch_run per step): the device-only rate beside the host-buffer `value`
-    b = ctx.upload([{k: v for k, v in p.items() if k != "T_gt"} for p in pairs])
-    b.run(cfg, res, flags)
-    sync(dist)
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
+    resident = None
+    if args.full:
+        b = ctx.upload([{k: v for k, v in p.items() if k != "T_gt"} for p in pairs])
         b.run(cfg, res, flags)
-    sync(dist)
-    resident = time.perf_counter() - t1
-    same = bool(np.array_equal(b.transforms(), T))
-    b.free()
+        sync(dist)
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            b.run(cfg, res, flags)
+        sync(dist)
+        resident = time.perf_counter() - t1
+        same = bool(np.array_equal(b.transforms(), T))
+        b.free()
     if dist is not None:
         elapsed = sh.max_over_ranks(elapsed, dist, device="cuda")
-        resident = sh.max_over_ranks(resident, dist, device="cuda")
+        if resident is not None:
+            resident = sh.max_over_ranks(resident, dist, device="cuda")
         iters = int(sh.sum_over_ranks(float(iters), dist, device="cuda"))
     if rank == 0:
         value = n_total * args.steps / elapsed
@@ -667,14 +707,17 @@ def bench_c5(args):
                      "mean_iterations": float(np.mean([s["iterations"] for s in st])),
                      "accuracy_vs_ground_truth": {"median_rot_rad": float(np.median([e[0] for e in errs])),
                                                   "median_trans_m": float(np.median([e[1] for e in errs]))},
-                     "roofline": roofline_nn(nn, "k_icp_nn, one launch per ICP iteration of the 1024-pair batch"),
-                     "inputs_resident": {"clouds_per_s": round(n_total * args.steps / resident, 1),
-                                         "ms_per_step": round(1e3 * resident / args.steps, 3),
-                                         "same_transforms": same,
-                                         "note": "aicp_hip_batch_upload once, aicp_hip_batch_run per step: "
-                                                 "no packing or H2D in the timed region"}})
+                     "roofline": roofline_nn(nn, "k_icp_nn, one launch per ICP iteration of the 1024-pair batch")})
+        if resident is not None:
+            line["inputs_resident"] = {"clouds_per_s": round(n_total * args.steps / resident, 1),
+                                       "ms_per_step": round(1e3 * resident / args.steps, 3),
+                                       "same_transforms": same,
+                                       "note": "aicp_hip_batch_upload once, aicp_hip_batch_run per step: "
+                                               "no packing or H2D in the timed region"}
         add_traffic(line["roofline"], "nn_traffic_c5.json")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"T": T, **stats_arrays(st)})
+        if world == 1 and args.cpu_baseline:
             line["cpu_baseline"], line["cpu_baseline_all_cores"], line["parity_vs_oracle"] = cpu_c5(pairs, T, args)
         print(json.dumps(line))
     ctx.close()
@@ -747,19 +790,20 @@ def bench_single(args):
     # reference of DESIGN 5.2); the same pair called again (App's readings 2-5 of a window reuse
     # the reference, not the reading) is reported beside it as latency_ms_resident
     refs, reads = [first, first.copy()], [read, read.copy()]
-    for i in range(max(1, args.warmup)):
+    for i in range(args.warmup):
         ctx.register(refs[i % 2], reads[i % 2], cfg)
     lat = []
-    for i in range(max(5, args.steps)):
+    for i in range(args.steps):
         t = time.perf_counter()
         T1, s1 = ctx.register(refs[i % 2], reads[i % 2], cfg)  # aicp_hip_register: host xyz -> T
         lat.append(time.perf_counter() - t)
     warm = []
-    for _ in range(max(5, args.steps)):
-        t = time.perf_counter()
-        Tw, _ = ctx.register(first, reads[0], cfg)
-        warm.append(time.perf_counter() - t)
-    assert np.array_equal(Tw, T1), "a resident reference changed the result"
+    if args.full:
+        for _ in range(max(5, args.steps)):
+            t = time.perf_counter()
+            Tw, _ = ctx.register(first, reads[0], cfg)
+            warm.append(time.perf_counter() - t)
+        assert np.array_equal(Tw, T1), "a resident reference changed the result"
     T, st = T1[None], [s1]
     med = float(np.median(lat))
     line = base_line(args, 1, "single-pair registration latency (aicp_hip_register, host xyz -> T)", 1e3 * med, "ms",
@@ -767,11 +811,14 @@ def bench_single(args):
                      {"workload": "one C2 pair (first cloud vs reading 0 of the C2 stream), N=M=%d, ratio 0.70 "
                                   "(registerClouds re-reads the chain; no overlap in this call)" % n_pts,
                       "chain": CHAIN}, scaling="strong", hib=False)
-    line.update({"latency_ms_samples": [round(1e3 * x, 3) for x in lat], "iterations": st[0]["iterations"],
-                 "latency_ms_resident": {"median": round(1e3 * float(np.median(warm)), 3),
-                                         "note": "the same pair again: reference and reading resident "
-                                                 "(aicp_hip_reference_cache_stats hits)"}})
-    if not args.no_cpu_baseline:
+    line.update({"latency_ms_samples": [round(1e3 * x, 3) for x in lat], "iterations": st[0]["iterations"]})
+    if warm:
+        line["latency_ms_resident"] = {"median": round(1e3 * float(np.median(warm)), 3),
+                                       "note": "the same pair again: reference and reading resident "
+                                               "(aicp_hip_reference_cache_stats hits)"}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"T": T, **stats_arrays(st)})
+    if args.cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import pyoracle as po
 
@@ -869,7 +916,9 @@ def bench_app(args):
                             "register_icp_loop_device": round(float(np.median([x[2]["icp_loop"] for x in split])), 3)},
         "mean_iterations": float(np.mean(its)),
     })
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"T": np.array(Ts), "iterations": np.array(its)})
+    if args.cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import pyoracle as po
 
@@ -903,13 +952,22 @@ def main():
     ap.add_argument("--points", type=int, default=None)
     ap.add_argument("--data", default=None,
                     help="recorded directory (aicp_input_poses.csv + cloud_*.pcd) replayed as the stream")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the oracle as cpu_baseline with parity_vs_oracle, the batched / "
+                         "resident-input variants of the workload (see --no-cpu-baseline, --no-batched)")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--cpu-reps", type=int, default=5, help="repetitions of the bounded CPU sample (median)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-batched", action="store_true", help="skip the batched-independent extra figure")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-batched", action="store_true", help="--full without the batched-independent extra figure")
     ap.add_argument("--opt", action="append", default=[], metavar="K=V",
                     help="context option (aicp_hip_options, include/aicp_hip.h) for every context, e.g. profile=1")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    args.batched = args.full and not args.no_batched
     if args.opt:
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         import aicp_mapping_amd._lib as L
