@@ -41,12 +41,16 @@ EXPORTS = [
     "aicp_hip_multi_context", "aicp_hip_multi_last_error", "aicp_hip_multi_align_batch",
     "aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_hip_set_options", "aicp_hip_get_options",
     "aicp_hip_test_force_scan_stall", "aicp_hip_sequence_run_raw", "aicp_hip_build_info",
+    "aicp_hip_fov_overlap", "aicp_hip_cluster_match", "aicp_hip_alignment_features",
+    "aicp_hip_default_risk_params", "aicp_hip_last_risk_stats",
 ]
 
 
 _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_hip_set_options",
            "aicp_hip_get_options", "aicp_hip_test_force_scan_stall",
-           "aicp_hip_sequence_run_raw", "aicp_hip_build_info"}  # added in r05 / r06
+           "aicp_hip_sequence_run_raw", "aicp_hip_build_info",  # added in r05 / r06
+           "aicp_hip_fov_overlap", "aicp_hip_cluster_match", "aicp_hip_alignment_features",
+           "aicp_hip_default_risk_params", "aicp_hip_last_risk_stats"}  # the alignment-risk features
 
 
 class IcpConfig(C.Structure):
@@ -126,6 +130,44 @@ class PrefilterStats(C.Structure):
         ("propagation_passes", C.c_int32),
         ("pad", C.c_int32),
     ]
+
+
+class RiskParams(C.Structure):
+    """aicp_risk_params (include/aicp_hip.h)."""
+    _fields_ = [
+        ("range", C.c_float),
+        ("angular_view", C.c_float),
+        ("max_angle_deg", C.c_float),
+        ("box_scale", C.c_float * 3),
+        ("prefilter", PrefilterParams),
+    ]
+
+
+class RiskBox(C.Structure):
+    _fields_ = [("centre", C.c_double * 3), ("rot", C.c_double * 9), ("half", C.c_double * 3)]
+
+
+class RiskResult(C.Structure):
+    _fields_ = [
+        ("fov_overlap", C.c_float),
+        ("alignability", C.c_float),
+        ("accepted_a", C.c_uint64),
+        ("accepted_b", C.c_uint64),
+        ("sampled_a", C.c_uint32),
+        ("sampled_b", C.c_uint32),
+        ("clusters_a", C.c_int32),
+        ("clusters_b", C.c_int32),
+        ("n_matches", C.c_int32),
+        ("pad", C.c_int32),
+        ("eigenvalues", C.c_double * 3),
+        ("eigenvectors", C.c_double * 9),
+        ("centroid", C.c_double * 3),
+    ]
+
+
+class RiskStats(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("fov_ms", "prefilter_a_ms", "prefilter_b_ms", "clusters_ms", "counts_ms",
+                                          "match_ms", "device_ms", "wall_ms")]
 
 
 class Cloud(C.Structure):
@@ -288,6 +330,18 @@ def _load():
     L.aicp_hip_multi_last_error.argtypes = [vp]
     L.aicp_hip_multi_last_error.restype = C.c_char_p
     L.aicp_hip_multi_align_batch.argtypes = [vp, cfgp, pp, sz, C.c_double, C.c_int, fp, stp, ip]
+    if hasattr(L, "aicp_hip_alignment_features"):
+        clp = C.POINTER(Cloud)
+        u32p = C.POINTER(C.c_uint32)
+        boxp = C.POINTER(RiskBox)
+        L.aicp_hip_default_risk_params.argtypes = [C.POINTER(RiskParams)]
+        L.aicp_hip_default_risk_params.restype = None
+        L.aicp_hip_fov_overlap.argtypes = [vp, clp, clp, dp, dp, C.c_float, C.c_float, fp, fp, szp, fp, szp]
+        L.aicp_hip_cluster_match.argtypes = [vp, fp, ip, sz, fp, ip, sz, C.c_float, fp, fp, ip, ip, fp, fp, dp, dp, dp,
+                                             boxp, boxp, u32p, u32p]
+        L.aicp_hip_alignment_features.argtypes = [vp, C.POINTER(RiskParams), clp, clp, dp, dp, C.POINTER(RiskResult),
+                                                  fp, szp, fp, szp, sz]
+        L.aicp_hip_last_risk_stats.argtypes = [vp, C.POINTER(RiskStats)]
     return L
 
 
@@ -453,6 +507,32 @@ def default_prefilter(**kw) -> PrefilterParams:
         else:
             setattr(p, k, v)
     return p
+
+
+def default_risk_params(**kw) -> RiskParams:
+    """aicp_hip_default_risk_params: range 100 m, view 360 deg, 20 deg between mean normals, box
+    scale (1, 1, 3) (filteringUtils.cpp:258, 520-528) and the pre-filter defaults; keyword
+    overrides (box_scale: 3 values, prefilter: a PrefilterParams)."""
+    p = RiskParams()
+    lib.aicp_hip_default_risk_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "box_scale":
+            for i in range(3):
+                p.box_scale[i] = float(v[i])
+        elif not hasattr(p, k):
+            raise AttributeError(f"aicp_risk_params has no field {k}")
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def _pose16(pose):
+    """4x4 row-major pose -> column-major double[16] (Eigen::Isometry3d::data())."""
+    return np.ascontiguousarray(np.asarray(pose, np.float64).reshape(4, 4).T.reshape(16))
+
+
+def _dptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 # aicp_hip_options overrides every new Context starts with (bench.py --opt k=v); empty: the
@@ -711,6 +791,95 @@ class Context:
         V = ns.value
         return dict(out=out[:m.value].copy(), sampled=sampled[:V].copy(), labels=labels[:V].copy(),
                     n_clusters=nc.value)
+
+
+    # -------------------------------------------------------------- alignment risk ---------
+    def fov_overlap(self, cloud_a, cloud_b, pose_a, pose_b, range_m=100.0, angular_view=360.0):
+        """overlapFilter (filteringUtils.cpp:111-193): returns (fov_overlap, accepted A, accepted B),
+        the accepted clouds (M, 3) float32 in the global frame, input order."""
+        ca, ka = make_cloud(cloud_a)
+        cb, kb = make_cloud(cloud_b)
+        pa, pb = _pose16(pose_a), _pose16(pose_b)
+        oa = np.zeros((max(ka.shape[0], 1), 3), np.float32)
+        ob = np.zeros((max(kb.shape[0], 1), 3), np.float32)
+        na, nb = C.c_size_t(0), C.c_size_t(0)
+        ov = C.c_float(0)
+        self.check(lib.aicp_hip_fov_overlap(self.h, C.byref(ca), C.byref(cb), _dptr(pa), _dptr(pb), float(range_m),
+                                            float(angular_view), C.byref(ov), _fptr(oa), C.byref(na), _fptr(ob),
+                                            C.byref(nb)))
+        return ov.value, oa[:na.value].copy(), ob[:nb.value].copy()
+
+    def cluster_match(self, sampled_a, labels_a, sampled_b, labels_b, max_angle_deg=20.0, box_scale=(1.0, 1.0, 3.0)):
+        """aicp_hip_cluster_match on two pre-filtered clouds (sampled (V, 8), labels (V,)): a dict
+        with alignability, n_matches, matching_indeces / _overlap / _distance (per cluster of B),
+        eigenvalues, eigenvectors (3, 3; column k for eigenvalue k), centroid, boxes_a / boxes_b
+        (dicts of centre (n, 3), rot (n, 3, 3), half (n, 3)), cnt_a_in_box_b (clusters_B,
+        clusters_A) and cnt_b_in_box_a (clusters_A, clusters_B)."""
+        sa = np.ascontiguousarray(sampled_a, np.float32).reshape(-1, 8)
+        sb = np.ascontiguousarray(sampled_b, np.float32).reshape(-1, 8)
+        la = np.ascontiguousarray(labels_a, np.int32).ravel()
+        lb = np.ascontiguousarray(labels_b, np.int32).ravel()
+        if la.size != sa.shape[0] or lb.size != sb.shape[0]:
+            raise ValueError("one label per sampled point")
+        nca = int(la.max()) + 1 if la.size and la.max() >= 0 else 0
+        ncb = int(lb.max()) + 1 if lb.size and lb.max() >= 0 else 0
+        i32 = C.POINTER(C.c_int32)
+        u32 = C.POINTER(C.c_uint32)
+        al, nm = C.c_float(0), C.c_int32(0)
+        mi = np.full(max(ncb, 1), -1, np.int32)
+        mo = np.full(max(ncb, 1), -1, np.float32)
+        md = np.full(max(ncb, 1), -1, np.float32)
+        ev, evec, cen = np.zeros(3), np.zeros(9), np.zeros(3)
+        ba, bb = (RiskBox * max(nca, 1))(), (RiskBox * max(ncb, 1))()
+        cab = np.zeros((max(ncb, 1), max(nca, 1)), np.uint32)
+        cba = np.zeros((max(nca, 1), max(ncb, 1)), np.uint32)
+        sc = np.asarray(box_scale, np.float32)
+        self.check(lib.aicp_hip_cluster_match(
+            self.h, _fptr(sa), la.ctypes.data_as(i32), sa.shape[0], _fptr(sb), lb.ctypes.data_as(i32), sb.shape[0],
+            float(max_angle_deg), _fptr(sc), C.byref(al), C.byref(nm), mi.ctypes.data_as(i32), _fptr(mo), _fptr(md),
+            _dptr(ev), _dptr(evec), _dptr(cen), ba, bb, cab.ctypes.data_as(u32), cba.ctypes.data_as(u32)))
+
+        def boxes(arr, n):
+            return dict(centre=np.array([list(arr[i].centre) for i in range(n)], np.float64).reshape(n, 3),
+                        rot=np.array([list(arr[i].rot) for i in range(n)], np.float64).reshape(n, 3, 3),
+                        half=np.array([list(arr[i].half) for i in range(n)], np.float64).reshape(n, 3))
+
+        return dict(alignability=al.value, n_matches=nm.value, matching_indeces=mi[:ncb].copy(),
+                    matching_overlap=mo[:ncb].copy(), matching_distance=md[:ncb].copy(), eigenvalues=ev,
+                    eigenvectors=evec.reshape(3, 3), centroid=cen, boxes_a=boxes(ba, nca), boxes_b=boxes(bb, ncb),
+                    cnt_a_in_box_b=cab[:ncb, :nca].copy() if nca and ncb else np.zeros((ncb, nca), np.uint32),
+                    cnt_b_in_box_a=cba[:nca, :ncb].copy() if nca and ncb else np.zeros((nca, ncb), np.uint32))
+
+    def alignment_features(self, cloud_a, cloud_b, pose_a, pose_b, params=None, planes=False):
+        """aicp_hip_alignment_features (App::computeAlignmentRisk up to the classifier): a dict of
+        the aicp_risk_result fields; with planes=True also planes_a / planes_b, (M, 8) rows
+        {x, y, z, nx, ny, nz, cluster, 0} of the matched planes."""
+        prm = params or default_risk_params()
+        ca, ka = make_cloud(cloud_a)
+        cb, kb = make_cloud(cloud_b)
+        pa, pb = _pose16(pose_a), _pose16(pose_b)
+        res = RiskResult()
+        cap = max(ka.shape[0], kb.shape[0], 1) if planes else 0
+        qa = np.zeros((cap, 8), np.float32) if planes else None
+        qb = np.zeros((cap, 8), np.float32) if planes else None
+        na, nb = C.c_size_t(0), C.c_size_t(0)
+        self.check(lib.aicp_hip_alignment_features(
+            self.h, C.byref(prm), C.byref(ca), C.byref(cb), _dptr(pa), _dptr(pb), C.byref(res),
+            _fptr(qa) if planes else None, C.byref(na), _fptr(qb) if planes else None, C.byref(nb), cap))
+        d = {k: getattr(res, k) for k, _ in RiskResult._fields_ if k not in ("pad", "eigenvalues", "eigenvectors",
+                                                                              "centroid")}
+        d["eigenvalues"] = np.array(list(res.eigenvalues))
+        d["eigenvectors"] = np.array(list(res.eigenvectors)).reshape(3, 3)
+        d["centroid"] = np.array(list(res.centroid))
+        if planes:
+            d["planes_a"] = qa[:na.value].copy()
+            d["planes_b"] = qb[:nb.value].copy()
+        return d
+
+    def last_risk_stats(self):
+        st = RiskStats()
+        self.check(lib.aicp_hip_last_risk_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in RiskStats._fields_}
 
 
 class ResidentBatch:

@@ -1244,6 +1244,10 @@ void aicp_hip_destroy(aicp_hip_ctx* ctx) {
   release(ctx->ovl_sp);
   release(ctx->ovl_keys);
   release(ctx->isync);
+  for (auto& b : ctx->risk) release(b);
+  release(ctx->pin_risk);
+  for (auto e : ctx->risk_ev)
+    if (e) (void)hipEventDestroy(e);
   release(ctx->refc.gst);
   release(ctx->pin_crop);
   release(ctx->pin_maps);
@@ -1496,51 +1500,15 @@ int aicp_hip_transform(aicp_hip_ctx* ctx, const float T[16], const float* in, si
   return AICP_OK;
 }
 
-// Box frame of getPointsInOrientedBox (filteringUtils.cpp:619-637): Eigen eulerAngles(0,1,2)
-// of origin.R, pcl::getTransformation(0,0,0,rx,ry,rz) = Rz Ry Rx, Affine3f::inverse() by
-// cofactors, and CropBox's fuzzy isIdentity() skip. Scalar float setup on the host; the
-// per-point test runs in k_crop_count / k_crop_scatter.
+// Box frame of getPointsInOrientedBox (filteringUtils.cpp:619-637): the rotation part by
+// crop_rotation_inverse (icp_math.hpp), the translation the pose's. Scalar float setup on the
+// host; the per-point test runs in k_crop_count / k_crop_scatter.
 static void crop_box_frame(const float origin[16], float inv[9], float t[3], float rpy[3]) {
-  auto R = [&](int r, int c) { return origin[c * 4 + r]; };
-  float a0 = std::atan2(R(1, 2), R(2, 2)), a1;
-  const float c2 = std::sqrt(R(0, 0) * R(0, 0) + R(0, 1) * R(0, 1));
-  if (a0 > 0.f) {
-    a0 -= float(M_PI);
-    a1 = std::atan2(-R(0, 2), -c2);
-  } else {
-    a1 = std::atan2(-R(0, 2), c2);
-  }
-  const float s1 = std::sin(a0), c1 = std::cos(a0);
-  const float a2 = std::atan2(s1 * R(2, 0) - c1 * R(1, 0), c1 * R(1, 1) - s1 * R(2, 1));
-  rpy[0] = -a0;
-  rpy[1] = -a1;
-  rpy[2] = -a2;
+  float R[9];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) R[3 * r + c] = origin[c * 4 + r];
   for (int q = 0; q < 3; ++q) t[q] = origin[12 + q];
-  for (int q = 0; q < 9; ++q) inv[q] = (q % 4 == 0) ? 1.f : 0.f;
-  if (rpy[0] == 0.f && rpy[1] == 0.f && rpy[2] == 0.f) return;
-  const float A = std::cos(rpy[2]), B = std::sin(rpy[2]), C = std::cos(rpy[1]), D = std::sin(rpy[1]),
-              E = std::cos(rpy[0]), F = std::sin(rpy[0]);
-  const float DE = D * E, DF = D * F;
-  const float m[3][3] = {{A * C, A * DF - B * E, B * F + A * DE}, {B * C, A * E + B * DF, B * DE - A * F},
-                         {-D, C * F, C * E}};
-  const float k00 = m[1][1] * m[2][2] - m[1][2] * m[2][1], k10 = m[1][2] * m[2][0] - m[1][0] * m[2][2],
-              k20 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
-  const float id = 1.f / (m[0][0] * k00 + m[0][1] * k10 + m[0][2] * k20);
-  const float w[9] = {k00 * id,
-                      (m[0][2] * m[2][1] - m[0][1] * m[2][2]) * id,
-                      (m[0][1] * m[1][2] - m[0][2] * m[1][1]) * id,
-                      k10 * id,
-                      (m[0][0] * m[2][2] - m[0][2] * m[2][0]) * id,
-                      (m[0][2] * m[1][0] - m[0][0] * m[1][2]) * id,
-                      k20 * id,
-                      (m[0][1] * m[2][0] - m[0][0] * m[2][1]) * id,
-                      (m[0][0] * m[1][1] - m[0][1] * m[1][0]) * id};
-  bool ident = true;
-  for (int q = 0; q < 9; ++q)
-    ident = ident && (q % 4 == 0 ? std::fabs(w[q] - 1.f) <= 1e-5f * std::fmin(std::fabs(w[q]), 1.f)
-                                 : std::fabs(w[q]) <= 1e-5f);
-  if (!ident)
-    for (int q = 0; q < 9; ++q) inv[q] = w[q];
+  crop_rotation_inverse(R, inv, rpy);
 }
 
 // the crop kernels on n device points; kept points (input order) to host out, capacity cap
@@ -2336,6 +2304,419 @@ int aicp_hip_sequence_run_raw(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, con
 int aicp_hip_last_prefilter_stats(const aicp_hip_ctx* ctx, aicp_prefilter_stats* out) {
   if (!ctx || !out) return AICP_ERR_INVALID;
   *out = ctx->last_pf;
+  return AICP_OK;
+}
+
+// ---- alignment risk (App::computeAlignmentRisk, app.cpp:143-185; kernels_risk.hip) -------------
+void aicp_hip_default_risk_params(aicp_risk_params* p) {
+  if (!p) return;
+  *p = aicp_risk_params{};
+  p->range = 100.f;
+  p->angular_view = 360.f;
+  p->max_angle_deg = 20.f;  // filteringUtils.cpp:258
+  p->box_scale[0] = 1.f;    // :520-528
+  p->box_scale[1] = 1.f;
+  p->box_scale[2] = 3.f;
+  aicp_hip_default_prefilter(&p->prefilter);
+}
+
+namespace {
+
+constexpr uint32_t kRiskMaxClusters = 4096;
+constexpr uint64_t kRiskMaxPairs = 1ull << 22;
+
+struct RiskSide {  // one pre-filtered cloud on the device
+  const float* s8 = nullptr;
+  const int32_t* lab = nullptr;
+  uint32_t V = 0, nc = 0;
+  RiskCluster* cl = nullptr;  // nc records
+};
+struct RiskHost {  // pin_risk: this, then m_idx / m_ov / m_dist of kRiskMaxClusters entries each
+  RiskOut out;
+  uint32_t totals[2];
+};
+constexpr size_t kRiskPinBytes = 256 + 3 * (size_t)kRiskMaxClusters * 4;
+struct RiskView {  // risk_core's results: host (pinned) and device
+  const RiskOut* out;
+  const int32_t* m_idx;
+  const float *m_ov, *m_dist;
+  const uint32_t *d_a_in_b, *d_b_in_a;  // device; null with zero clusters on a side
+};
+
+bool valid_cloud(const aicp_cloud* c) {
+  return c && c->pts && c->n >= 1 && c->n < (1ull << 31) && c->stride >= 12 && (c->stride % 4) == 0;
+}
+
+// the FOV filter of a cloud against `other` (column-major Isometry3d): the inverse in double as
+// R^T and -R^T t with explicit left-to-right sums, the pose itself as float for the way back
+FovArgs fov_args(const double other[16], float range, float angular_view) {
+  FovArgs a{};
+  auto R = [&](int r, int c) { return other[c * 4 + r]; };
+  const double t[3] = {other[12], other[13], other[14]};
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) {
+      a.pinv[4 * r + c] = R(c, r);
+      a.R[3 * r + c] = (float)R(r, c);
+    }
+    a.pinv[4 * r + 3] = -((R(0, r) * t[0] + R(1, r) * t[1]) + R(2, r) * t[2]);
+    a.t[r] = (float)t[r];
+  }
+  a.thresh = (double)(float)(180.0 - ((360.0 - (double)angular_view) / 2));  // float thresh (:117)
+  a.range = (double)range;
+  return a;
+}
+
+float fov_overlap_value(size_t kept_a, size_t n_a, size_t kept_b, size_t n_b) {
+  const float pa = (float)kept_a / (float)n_a, pb = (float)kept_b / (float)n_b;  // :180-192
+  const float ov = pa * pb;
+  return (float)((double)ov * 100.0);
+}
+
+// moments + boxes of both sides, the two count matrices, matching + PCA; everything enqueued on
+// ctx->stream, the result read into pin_risk, the stream idle on return. ev (nullable): 3 events
+// recorded after the clusters, the counts and the match.
+int risk_core(aicp_hip_ctx* ctx, const RiskSide& A, const RiskSide& B, float max_angle, const float scale[3],
+              hipEvent_t* ev, RiskView* view) {
+  hipStream_t s = ctx->stream;
+  if (A.nc > kRiskMaxClusters || B.nc > kRiskMaxClusters)
+    FAIL(AICP_ERR_UNSUPPORTED, "more than 4096 clusters in a cloud");
+  if ((uint64_t)A.nc * B.nc > kRiskMaxPairs) FAIL(AICP_ERR_UNSUPPORTED, "clusters_A * clusters_B exceeds 2^22");
+  const size_t Vm = std::max<size_t>(std::max(A.V, B.V), 1);
+  const size_t wv = (Vm + 63) & ~size_t(63);
+  const size_t temp_b = (risk_sort_temp_bytes(Vm) + 255) & ~size_t(255);
+  const size_t pairs = (size_t)A.nc * B.nc;
+  const size_t pw = (pairs + 63) & ~size_t(63);
+  const size_t cw = kRiskMaxClusters + 64;
+  const size_t part_b = (risk_partial_bytes(Vm, kRiskMaxClusters) + 255) & ~size_t(255);
+  const size_t off_seg = 4 * wv * 4, off_temp = off_seg + cw * 4, off_cnt = off_temp + temp_b,
+               off_m = off_cnt + 2 * pw * 4, off_out = off_m + 6 * cw * 4, off_part = off_out + 256;
+  HIPC(ensure(ctx->risk[2], off_part + part_b));
+  HIPC(ensure(ctx->pin_risk, kRiskPinBytes));
+  char* W = ctx->risk[2].as<char>();
+  uint32_t* k0 = (uint32_t*)W;
+  uint32_t *k1 = k0 + wv, *v0 = k0 + 2 * wv, *idx = k0 + 3 * wv;
+  uint32_t* seg = (uint32_t*)(W + off_seg);
+  uint32_t* a_in_b = (uint32_t*)(W + off_cnt);
+  uint32_t* b_in_a = a_in_b + pw;
+  int32_t* best_j = (int32_t*)(W + off_m);
+  float* best_ov = (float*)(best_j + cw);
+  float* best_d = best_ov + cw;
+  int32_t* m_idx = (int32_t*)(best_d + cw);
+  float* m_ov = (float*)(m_idx + cw);
+  float* m_dist = m_ov + cw;
+  RiskOut* dout = (RiskOut*)(W + off_out);
+  double* partial = (double*)(W + off_part);
+  RiskHost* H = ctx->pin_risk.as<RiskHost>();
+  int32_t* h_idx = (int32_t*)(ctx->pin_risk.as<char>() + 256);
+  float* h_ov = (float*)(h_idx + kRiskMaxClusters);
+  float* h_dist = h_ov + kRiskMaxClusters;
+  HIPC(launch_risk_clusters(s, A.V, A.nc, A.s8, A.lab, k0, k1, v0, idx, seg, W + off_temp, temp_b, partial, scale, A.cl));
+  HIPC(launch_risk_clusters(s, B.V, B.nc, B.s8, B.lab, k0, k1, v0, idx, seg, W + off_temp, temp_b, partial, scale, B.cl));
+  if (ev) HIPC(hipEventRecord(ev[0], s));
+  const bool both = A.nc && B.nc;
+  if (both) {
+    HIPC(hipMemsetAsync(a_in_b, 0, 2 * pw * 4, s));
+    launch_risk_counts(s, A.V, A.nc, B.nc, A.s8, A.lab, B.cl, a_in_b);
+    launch_risk_counts(s, B.V, B.nc, A.nc, B.s8, B.lab, A.cl, b_in_a);
+    HIPC(hipGetLastError());
+  }
+  if (ev) HIPC(hipEventRecord(ev[1], s));
+  if (both) {
+    launch_risk_match(s, A.nc, B.nc, A.cl, B.cl, a_in_b, b_in_a, max_angle, best_j, best_ov, best_d, m_idx, m_ov,
+                      m_dist, dout);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(&H->out, dout, sizeof(RiskOut), hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(h_idx, m_idx, (size_t)B.nc * 4, hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(h_ov, m_ov, (size_t)B.nc * 4, hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(h_dist, m_dist, (size_t)B.nc * 4, hipMemcpyDeviceToHost, s));
+  }
+  if (ev) HIPC(hipEventRecord(ev[2], s));
+  HIPC(hipStreamSynchronize(s));
+  if (!both) {
+    H->out = RiskOut{};
+    for (uint32_t j = 0; j < B.nc; ++j) {
+      h_idx[j] = -1;
+      h_ov[j] = -1.f;
+      h_dist[j] = -1.f;
+    }
+  }
+  *view = RiskView{&H->out, h_idx, h_ov, h_dist, both ? a_in_b : nullptr, both ? b_in_a : nullptr};
+  return AICP_OK;
+}
+
+int risk_download_boxes(aicp_hip_ctx* ctx, const RiskSide& X, aicp_risk_box* out) {
+  if (!out || !X.nc) return AICP_OK;
+  std::vector<RiskCluster> h(X.nc);
+  HIPC(hipMemcpy(h.data(), X.cl, (size_t)X.nc * sizeof(RiskCluster), hipMemcpyDeviceToHost));
+  for (uint32_t c = 0; c < X.nc; ++c) {
+    for (int k = 0; k < 3; ++k) {
+      out[c].centre[k] = h[c].centre[k];
+      out[c].half[k] = h[c].half[k];
+    }
+    for (int k = 0; k < 9; ++k) out[c].rot[k] = h[c].rot[k];
+  }
+  return AICP_OK;
+}
+
+}  // namespace
+
+int aicp_hip_fov_overlap(aicp_hip_ctx* ctx, const aicp_cloud* cloud_a, const aicp_cloud* cloud_b,
+                         const double pose_a[16], const double pose_b[16], float range, float angular_view,
+                         float* fov_overlap, float* accepted_a, size_t* n_accepted_a, float* accepted_b,
+                         size_t* n_accepted_b) {
+  if (!ctx || !pose_a || !pose_b || !fov_overlap || !valid_cloud(cloud_a) || !valid_cloud(cloud_b))
+    return AICP_ERR_INVALID;
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const aicp_cloud* cl[2] = {cloud_a, cloud_b};
+  const double* other[2] = {pose_b, pose_a};
+  float* acc[2] = {accepted_a, accepted_b};
+  size_t kept[2] = {0, 0};
+  for (int x = 0; x < 2; ++x) {
+    const size_t n = cl[x]->n, tiles = fov_tiles(n);
+    const size_t tile_b = (2 * tiles * 4 + 255) & ~size_t(255);
+    HIPC(ensure(ctx->risk[x], 2 * n * 16));
+    HIPC(ensure(ctx->risk[2], 256 + tile_b));
+    HIPC(ensure(ctx->pin_io, n * 16 + 64));
+    HIPC(ensure(ctx->pin_risk, kRiskPinBytes));
+    float4* din = ctx->risk[x].as<float4>();
+    float4* dacc = din + n;
+    char* W = ctx->risk[2].as<char>();
+    pack_xyz4(cl[x]->pts, n, cl[x]->stride, ctx->pin_io.as<float>());
+    HIPC(hipMemcpyAsync(din, ctx->pin_io.p, n * 16, hipMemcpyHostToDevice, s));
+    launch_fov_filter(s, (uint32_t)n, fov_args(other[x], range, angular_view), din, (uint32_t*)(W + 256),
+                      (uint32_t*)(W + 256) + tiles, (uint32_t*)W, dacc);
+    HIPC(hipGetLastError());
+    RiskHost* H = ctx->pin_risk.as<RiskHost>();
+    HIPC(hipMemcpyAsync(&H->totals[x], W, 4, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    const uint32_t m = H->totals[x];
+    if (m > n) FAIL(AICP_ERR_HIP, "FOV filter: kept count exceeds the input");
+    kept[x] = m;
+    if (acc[x] && m) {
+      float* h = ctx->pin_io.as<float>();
+      HIPC(hipMemcpy(h, dacc, (size_t)m * 16, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < m; ++i)
+        for (int k = 0; k < 3; ++k) acc[x][3 * i + k] = h[4 * i + k];
+    }
+  }
+  if (n_accepted_a) *n_accepted_a = kept[0];
+  if (n_accepted_b) *n_accepted_b = kept[1];
+  *fov_overlap = fov_overlap_value(kept[0], cloud_a->n, kept[1], cloud_b->n);
+  return AICP_OK;
+}
+
+int aicp_hip_cluster_match(aicp_hip_ctx* ctx, const float* sampled_a, const int32_t* labels_a, size_t n_a,
+                           const float* sampled_b, const int32_t* labels_b, size_t n_b, float max_angle_deg,
+                           const float box_scale[3], float* alignability, int32_t* n_matches,
+                           int32_t* matching_indeces, float* matching_overlap, float* matching_distance,
+                           double eigenvalues[3], double eigenvectors[9], double centroid[3],
+                           aicp_risk_box* boxes_a, aicp_risk_box* boxes_b, uint32_t* cnt_a_in_box_b,
+                           uint32_t* cnt_b_in_box_a) {
+  if (!ctx || !box_scale || !alignability || (n_a && (!sampled_a || !labels_a)) ||
+      (n_b && (!sampled_b || !labels_b)) || n_a >= (1ull << 31) || n_b >= (1ull << 31))
+    return AICP_ERR_INVALID;
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const float* hs[2] = {sampled_a, sampled_b};
+  const int32_t* hl[2] = {labels_a, labels_b};
+  const size_t hn[2] = {n_a, n_b};
+  RiskSide S[2];
+  for (int x = 0; x < 2; ++x) {
+    int64_t mx = -1;
+    for (size_t i = 0; i < hn[x]; ++i) mx = std::max<int64_t>(mx, hl[x][i]);
+    S[x].V = (uint32_t)hn[x];
+    S[x].nc = (uint32_t)(mx + 1);
+    if (S[x].nc > kRiskMaxClusters) FAIL(AICP_ERR_UNSUPPORTED, "more than 4096 clusters in a cloud");
+    const size_t n = std::max<size_t>(hn[x], 1);
+    const size_t off_lab = n * 32, off_cl = (off_lab + n * 4 + 255) & ~size_t(255);
+    HIPC(ensure(ctx->risk[x], off_cl + (size_t)kRiskMaxClusters * sizeof(RiskCluster)));
+    char* D = ctx->risk[x].as<char>();
+    S[x].s8 = (const float*)D;
+    S[x].lab = (const int32_t*)(D + off_lab);
+    S[x].cl = (RiskCluster*)(D + off_cl);
+    if (hn[x]) {
+      HIPC(hipMemcpyAsync(D, hs[x], hn[x] * 32, hipMemcpyHostToDevice, s));
+      HIPC(hipMemcpyAsync(D + off_lab, hl[x], hn[x] * 4, hipMemcpyHostToDevice, s));
+    }
+  }
+  HIPC(hipStreamSynchronize(s));  // (pageable sources: the copies have left the caller's arrays)
+  RiskView v;
+  const int rc = risk_core(ctx, S[0], S[1], max_angle_deg, box_scale, nullptr, &v);
+  if (rc) return rc;
+  *alignability = v.out->alignability;
+  if (n_matches) *n_matches = v.out->n_matches;
+  for (uint32_t j = 0; j < S[1].nc; ++j) {
+    if (matching_indeces) matching_indeces[j] = v.m_idx[j];
+    if (matching_overlap) matching_overlap[j] = v.m_ov[j];
+    if (matching_distance) matching_distance[j] = v.m_dist[j];
+  }
+  for (int k = 0; k < 3; ++k) {
+    if (eigenvalues) eigenvalues[k] = v.out->eigenvalues[k];
+    if (centroid) centroid[k] = v.out->centroid[k];
+  }
+  if (eigenvectors)
+    for (int k = 0; k < 9; ++k) eigenvectors[k] = v.out->eigenvectors[k];
+  int rb = risk_download_boxes(ctx, S[0], boxes_a);
+  if (rb) return rb;
+  rb = risk_download_boxes(ctx, S[1], boxes_b);
+  if (rb) return rb;
+  const size_t pairs = (size_t)S[0].nc * S[1].nc;
+  if (pairs && v.d_a_in_b) {
+    if (cnt_a_in_box_b) HIPC(hipMemcpy(cnt_a_in_box_b, v.d_a_in_b, pairs * 4, hipMemcpyDeviceToHost));
+    if (cnt_b_in_box_a) HIPC(hipMemcpy(cnt_b_in_box_a, v.d_b_in_a, pairs * 4, hipMemcpyDeviceToHost));
+  }
+  return AICP_OK;
+}
+
+int aicp_hip_alignment_features(aicp_hip_ctx* ctx, const aicp_risk_params* prm, const aicp_cloud* cloud_a,
+                                const aicp_cloud* cloud_b, const double pose_a[16], const double pose_b[16],
+                                aicp_risk_result* out, float* planes_a, size_t* n_planes_a, float* planes_b,
+                                size_t* n_planes_b, size_t planes_cap) {
+  if (!ctx || !prm || !pose_a || !pose_b || !out || !valid_cloud(cloud_a) || !valid_cloud(cloud_b))
+    return AICP_ERR_INVALID;
+  int rc = pf_check(ctx, &prm->prefilter);
+  if (rc) return rc;
+  const auto t_wall = std::chrono::steady_clock::now();
+  *out = aicp_risk_result{};
+  if (n_planes_a) *n_planes_a = 0;
+  if (n_planes_b) *n_planes_b = 0;
+  ctx->last_risk = aicp_risk_stats{};
+  ctx->last_pf = aicp_prefilter_stats{};
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  for (auto& e : ctx->risk_ev)
+    if (!e) HIPC(hipEventCreate(&e));
+  hipEvent_t* E = ctx->risk_ev;  // 0 inputs ready, 1 FOV, 2 pre-filter A, 3 pre-filter B, 4 clusters, 5 counts, 6 match
+  const aicp_cloud* cl[2] = {cloud_a, cloud_b};
+  const double* own[2] = {pose_a, pose_b};
+  const double* other[2] = {pose_b, pose_a};
+  // per cloud: in[n] | accepted[n] | s8[n] (32 B) | labels[n] | cluster records
+  float4* din[2];
+  float4* dacc[2];
+  size_t off_s8[2], off_lab[2], off_cl[2];
+  size_t tiles_max = 0;
+  for (int x = 0; x < 2; ++x) {
+    const size_t n = cl[x]->n;
+    off_s8[x] = 2 * n * 16;
+    off_lab[x] = off_s8[x] + n * 32;
+    off_cl[x] = (off_lab[x] + n * 4 + 255) & ~size_t(255);
+    HIPC(ensure(ctx->risk[x], off_cl[x] + (size_t)kRiskMaxClusters * sizeof(RiskCluster)));
+    din[x] = ctx->risk[x].as<float4>();
+    dacc[x] = din[x] + n;
+    tiles_max = std::max(tiles_max, fov_tiles(n));
+  }
+  const size_t tile_b = (2 * tiles_max * 4 + 255) & ~size_t(255);
+  HIPC(ensure(ctx->risk[2], 256 + 2 * tile_b));
+  HIPC(ensure(ctx->pin_risk, kRiskPinBytes));
+  HIPC(ensure(ctx->pin_io, (cl[0]->n + cl[1]->n) * 16 + 64));
+  {
+    float* h = ctx->pin_io.as<float>();
+    pack_xyz4(cl[0]->pts, cl[0]->n, cl[0]->stride, h);
+    pack_xyz4(cl[1]->pts, cl[1]->n, cl[1]->stride, h + 4 * cl[0]->n);
+    HIPC(hipMemcpyAsync(din[0], h, cl[0]->n * 16, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(din[1], h + 4 * cl[0]->n, cl[1]->n * 16, hipMemcpyHostToDevice, s));
+  }
+  HIPC(hipEventRecord(E[0], s));
+  char* W = ctx->risk[2].as<char>();
+  for (int x = 0; x < 2; ++x) {
+    uint32_t* tc = (uint32_t*)(W + 256 + x * tile_b);
+    launch_fov_filter(s, (uint32_t)cl[x]->n, fov_args(other[x], prm->range, prm->angular_view), din[x], tc,
+                      tc + tiles_max, (uint32_t*)W + x, dacc[x]);
+  }
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(E[1], s));
+  RiskHost* H = ctx->pin_risk.as<RiskHost>();
+  HIPC(hipMemcpyAsync(H->totals, W, 8, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  const size_t kept[2] = {H->totals[0], H->totals[1]};
+  if (kept[0] > cl[0]->n || kept[1] > cl[1]->n) FAIL(AICP_ERR_HIP, "FOV filter: kept count exceeds the input");
+  out->accepted_a = kept[0];
+  out->accepted_b = kept[1];
+  out->fov_overlap = fov_overlap_value(kept[0], cl[0]->n, kept[1], cl[1]->n);
+  // the two pre-filters on the accepted clouds (device data), results gathered into the clouds'
+  // own buffers before the next pre-filter reuses the context's work space
+  RiskSide S[2];
+  for (int x = 0; x < 2; ++x) {
+    char* D = ctx->risk[x].as<char>();
+    S[x].s8 = (const float*)(D + off_s8[x]);
+    S[x].lab = (const int32_t*)(D + off_lab[x]);
+    S[x].cl = (RiskCluster*)(D + off_cl[x]);
+    if (kept[x]) {
+      aicp_prefilter_params pp = prm->prefilter;
+      for (int k = 0; k < 3; ++k) pp.viewpoint[k] = (float)own[x][12 + k];
+      PfLayout Lo;
+      rc = pf_layout(ctx, kept[x], &Lo);
+      if (rc) return rc;
+      HIPC(hipMemcpyAsync(Lo.pts4, dacc[x], kept[x] * 16, hipMemcpyDeviceToDevice, s));
+      PfRun o;
+      rc = pf_core(ctx, &pp, kept[x], Lo, &o);
+      if (rc) return rc;
+      S[x].V = o.V;
+      S[x].nc = o.V ? o.n_clusters : 0u;
+      if (o.V)
+        launch_risk_gather(s, o.V, ctx->ref1.as<float4>(), o.nrm, o.inv, o.cluster_of, (float*)S[x].s8,
+                           (int32_t*)S[x].lab);
+      HIPC(hipGetLastError());
+    }
+    HIPC(hipEventRecord(E[2 + x], s));
+  }
+  out->sampled_a = S[0].V;
+  out->sampled_b = S[1].V;
+  out->clusters_a = (int32_t)S[0].nc;
+  out->clusters_b = (int32_t)S[1].nc;
+  RiskView v;
+  rc = risk_core(ctx, S[0], S[1], prm->max_angle_deg, prm->box_scale, E + 4, &v);
+  if (rc) return rc;
+  out->alignability = v.out->alignability;
+  out->n_matches = v.out->n_matches;
+  for (int k = 0; k < 3; ++k) {
+    out->eigenvalues[k] = v.out->eigenvalues[k];
+    out->centroid[k] = v.out->centroid[k];
+  }
+  for (int k = 0; k < 9; ++k) out->eigenvectors[k] = v.out->eigenvectors[k];
+  aicp_risk_stats& rs = ctx->last_risk;
+  rs.fov_ms = ev_ms(E[0], E[1]);
+  rs.prefilter_a_ms = ev_ms(E[1], E[2]);
+  rs.prefilter_b_ms = ev_ms(E[2], E[3]);
+  rs.clusters_ms = ev_ms(E[3], E[4]);
+  rs.counts_ms = ev_ms(E[4], E[5]);
+  rs.match_ms = ev_ms(E[5], E[6]);
+  rs.device_ms = ev_ms(E[0], E[6]);
+  // optional: the matched planes (cloudA_planes / cloudB_planes, :293-315), assembled on the host
+  if (v.out->n_matches && (planes_a || planes_b)) {
+    float* dst[2] = {planes_a, planes_b};
+    size_t* cnt[2] = {n_planes_a, n_planes_b};
+    for (int x = 0; x < 2; ++x) {
+      if (!dst[x]) continue;
+      std::vector<float> hs(8 * (size_t)S[x].V);
+      std::vector<int32_t> hl(S[x].V);
+      HIPC(hipMemcpy(hs.data(), S[x].s8, hs.size() * 4, hipMemcpyDeviceToHost));
+      HIPC(hipMemcpy(hl.data(), S[x].lab, hl.size() * 4, hipMemcpyDeviceToHost));
+      size_t m = 0;
+      for (uint32_t j = 0; j < S[1].nc; ++j) {
+        if (v.m_idx[j] < 0) continue;
+        const int32_t c = x == 0 ? v.m_idx[j] : (int32_t)j;
+        for (uint32_t i = 0; i < S[x].V; ++i) {
+          if (hl[i] != c) continue;
+          if (m >= planes_cap) FAIL(AICP_ERR_INVALID, "matched planes: output capacity too small");
+          const float* q = &hs[8 * (size_t)i];
+          float* d = dst[x] + 8 * m++;
+          d[0] = q[0], d[1] = q[1], d[2] = q[2], d[3] = q[4], d[4] = q[5], d[5] = q[6];
+          d[6] = (float)c;
+          d[7] = 0.f;
+        }
+      }
+      if (cnt[x]) *cnt[x] = m;
+    }
+  }
+  rs.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wall).count();
+  return AICP_OK;
+}
+
+int aicp_hip_last_risk_stats(const aicp_hip_ctx* ctx, aicp_risk_stats* out) {
+  if (!ctx || !out) return AICP_ERR_INVALID;
+  *out = ctx->last_risk;
   return AICP_OK;
 }
 

@@ -469,6 +469,51 @@ AICP_HD bool normal_from_cov(const double* C, float* nrm) {
   return true;
 }
 
+// pcl::CropBox's local frame of a box with rotation R (row-major), as getPointsInOrientedBox sets it
+// up (filteringUtils.cpp:484-499, 619-637): Eigen eulerAngles(0,1,2) of R,
+// pcl::getTransformation(0,0,0,rx,ry,rz) = Rz Ry Rx, Affine3f::inverse() by cofactors, and
+// CropBox's fuzzy isIdentity() skip (inv = identity then). Scalar float, on the host for the map
+// crop and on the device for the clusters' boxes.
+AICP_HD void crop_rotation_inverse(const float* Rm, float* inv, float* rpy) {
+  float a0 = atan2f(Rm[5], Rm[8]), a1;
+  const float c2 = sqrtf(Rm[0] * Rm[0] + Rm[1] * Rm[1]);
+  if (a0 > 0.f) {
+    a0 -= float(M_PI);
+    a1 = atan2f(-Rm[2], -c2);
+  } else {
+    a1 = atan2f(-Rm[2], c2);
+  }
+  const float s1 = sinf(a0), c1 = cosf(a0);
+  const float a2 = atan2f(s1 * Rm[6] - c1 * Rm[3], c1 * Rm[4] - s1 * Rm[7]);
+  rpy[0] = -a0;
+  rpy[1] = -a1;
+  rpy[2] = -a2;
+  for (int q = 0; q < 9; ++q) inv[q] = (q % 4 == 0) ? 1.f : 0.f;
+  if (rpy[0] == 0.f && rpy[1] == 0.f && rpy[2] == 0.f) return;
+  const float A = cosf(rpy[2]), B = sinf(rpy[2]), C = cosf(rpy[1]), D = sinf(rpy[1]), E = cosf(rpy[0]),
+              F = sinf(rpy[0]);
+  const float DE = D * E, DF = D * F;
+  const float m[3][3] = {{A * C, A * DF - B * E, B * F + A * DE}, {B * C, A * E + B * DF, B * DE - A * F},
+                         {-D, C * F, C * E}};
+  const float k00 = m[1][1] * m[2][2] - m[1][2] * m[2][1], k10 = m[1][2] * m[2][0] - m[1][0] * m[2][2],
+              k20 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
+  const float id = 1.f / (m[0][0] * k00 + m[0][1] * k10 + m[0][2] * k20);
+  const float w[9] = {k00 * id,
+                      (m[0][2] * m[2][1] - m[0][1] * m[2][2]) * id,
+                      (m[0][1] * m[1][2] - m[0][2] * m[1][1]) * id,
+                      k10 * id,
+                      (m[0][0] * m[2][2] - m[0][2] * m[2][0]) * id,
+                      (m[0][2] * m[1][0] - m[0][0] * m[1][2]) * id,
+                      k20 * id,
+                      (m[0][1] * m[2][0] - m[0][0] * m[2][1]) * id,
+                      (m[0][0] * m[1][1] - m[0][1] * m[1][0]) * id};
+  bool ident = true;
+  for (int q = 0; q < 9; ++q)
+    ident = ident && (q % 4 == 0 ? fabsf(w[q] - 1.f) <= 1e-5f * fminf(fabsf(w[q]), 1.f) : fabsf(w[q]) <= 1e-5f);
+  if (!ident)
+    for (int q = 0; q < 9; ++q) inv[q] = w[q];
+}
+
 // Translation of the corrected pose of an accepted reading: correction_iso * prior_pose
 // (AlignedCloud::updateCloud, aligned_cloud.cpp:61-70; removePitchRollCorrection keeps the
 // translation), with correction_iso = fromMatrix4fToIsometry3d(T) (common.cpp:4-23):

@@ -120,6 +120,9 @@ size_t crop_tiles(size_t n);
 void launch_crop_box(hipStream_t s, int n, const float inv[9], const float t[3], float mn, float mx,
                      const float4* pts, uint32_t* tile_cnt, uint32_t* tile_off, uint32_t* total,
                      float4* out);
+// the crop's exclusive scan of n_tiles tile counts (one workgroup) and their total, for other
+// order-preserving compactions (the FOV filter)
+void launch_tile_scan(hipStream_t s, int n_tiles, const uint32_t* cnt, uint32_t* off, uint32_t* total);
 // many crops of one map (one per localization reading): args = n_crops packed CropBoxArgs
 // (pack_crop_args, crop_args_bytes each); tile_cnt / tile_off: n_crops * crop_tiles(n) words;
 // totals: n_crops words. The scatter writes crop c at out + base_of[c], in input order.
@@ -335,5 +338,59 @@ void launch_rg_phaseb(hipStream_t s, uint32_t V, int nnb, const int32_t* nbp, co
 hipError_t launch_rg_extract(hipStream_t s, uint32_t V, uint32_t min_size, uint32_t max_size, const uint32_t* label,
                              const uint32_t* inv, const float4* sampled, const PfWork& w, float4* out,
                              int32_t* cluster_of, PfCtl* ctl);
+
+// ---- alignment-risk features (kernels_risk.hip): overlapFilter, alignabilityFilter ----------
+struct FovArgs {
+  double pinv[12];  // inverse of the other cloud's pose, rows of 3 x 4 (host, double)
+  float R[9];       // that pose as float (row-major) and its translation: kept points go back
+  float t[3];
+  double thresh;    // |theta| bound (degrees), range (metres)
+  double range;
+};
+struct RiskBox {  // a cluster's box as CropBox sees it
+  float inv[9];   // row-major local-frame rotation
+  float t[3];     // box position
+  float half[3];  // min = -half, max = half
+  float pad;
+};
+struct RiskCluster {
+  double sum_p[3], sum_n[3], sum_nn[6];  // fp64 sums in the fixed order (xx, xy, xz, yy, yz, zz)
+  double centre[3], rot[9], half[3];     // getOBB after overlapBoxFilter's scaling; rot row-major, columns = axes
+  RiskBox box;
+  uint32_t count, pad;
+  // between the cluster kernels: mean (relative to p0) and axes as rows, the cluster's first
+  // point, order-preserving bits of the extents' min[3], max[3]
+  double frame[12], p0[3];
+  unsigned long long ext[6];
+};
+struct RiskOut {
+  double eigenvalues[3];   // normalised, descending
+  double eigenvectors[9];  // row-major, column k belongs to eigenvalue k
+  double centroid[3];      // of the matched planes of cloud A
+  float alignability;
+  int32_t n_matches;
+};
+size_t fov_tiles(size_t n);
+// kept points (input order, back in the global frame) to out (capacity n); tile_cnt / tile_off:
+// fov_tiles(n) words
+void launch_fov_filter(hipStream_t s, uint32_t n, const FovArgs& a, const float4* pts, uint32_t* tile_cnt,
+                       uint32_t* tile_off, uint32_t* total, float4* out);
+// pf_core's results -> s8 = {x, y, z, curvature, nx, ny, nz, 0} per sampled point, lab = its cluster
+void launch_risk_gather(hipStream_t s, uint32_t V, const float4* sampled, const float4* nrm, const uint32_t* inv,
+                        const int32_t* cluster_of, float* s8, int32_t* lab);
+size_t risk_sort_temp_bytes(size_t n);
+size_t risk_partial_bytes(size_t V, size_t nc);
+// per cluster c in [0, nc): moments, box. k0, k1, v0, idx: V words; seg: nc + 1 words; partial:
+// risk_partial_bytes(V, nc)
+hipError_t launch_risk_clusters(hipStream_t s, uint32_t V, uint32_t nc, const float* s8, const int32_t* lab,
+                                uint32_t* k0, uint32_t* k1, uint32_t* v0, uint32_t* idx, uint32_t* seg, void* temp,
+                                size_t temp_bytes, double* partial, const float scale[3], RiskCluster* out);
+// cnt[box_of_Y * ncx + label_of_X_point] += 1 (cnt zeroed by the caller)
+void launch_risk_counts(hipStream_t s, uint32_t V, uint32_t ncx, uint32_t ncy, const float* s8, const int32_t* lab,
+                        const RiskCluster* boxes, uint32_t* cnt);
+// a_in_b: [ncb][nca], b_in_a: [nca][ncb]; best_*: nca, m_*: ncb
+void launch_risk_match(hipStream_t s, uint32_t nca, uint32_t ncb, const RiskCluster* ca, const RiskCluster* cb,
+                       const uint32_t* a_in_b, const uint32_t* b_in_a, float max_angle, int32_t* best_j,
+                       float* best_ov, float* best_d, int32_t* m_idx, float* m_ov, float* m_dist, RiskOut* out);
 
 }  // namespace aicp

@@ -205,6 +205,10 @@ void launch_crop_scatter_multi(hipStream_t s, int n, int n_crops, const void* ar
                                                                     base_of, out);
 }
 
+void launch_tile_scan(hipStream_t s, int n_tiles, const uint32_t* cnt, uint32_t* off, uint32_t* total) {
+  k_crop_scan<<<1, 1024, 0, s>>>(n_tiles, cnt, off, total);
+}
+
 void launch_crop_box(hipStream_t s, int n, const float inv[9], const float t[3], float mn, float mx,
                      const float4* pts, uint32_t* tile_cnt, uint32_t* tile_off, uint32_t* total,
                      float4* out) {

@@ -310,6 +310,13 @@ struct aicp_hip_ctx {
   aicp::rt::WorkerPool* pool = nullptr;  // host threads of the one-shot calls (packing, the reference compare)
   uint32_t* poll_host = nullptr;  // the batch loop's active counts (hipHostMalloc, mapped), kBatchPolls words
   uint32_t* poll_dev = nullptr;
+  // alignment-risk features: [0], [1] the two clouds (input, accepted points, then the sampled
+  // cloud, labels and cluster records: the pre-filter's context buffers are workspace that the next
+  // pre-filter rewrites), [2] sort, count and matching work space
+  aicp::rt::DevBuf risk[3];
+  aicp::rt::PinBuf pin_risk;
+  hipEvent_t risk_ev[7] = {};
+  aicp_risk_stats last_risk{};
   aicp_hip_options opt{};  // aicp_hip_set_options (read by the calls; nothing reads the environment)
 };
 constexpr int kBatchPolls = 64;

@@ -78,3 +78,57 @@ def regionGrowingUniformPlaneSegmentationFilter(cloud_in, *args, ctx=None, param
         prev = np.asarray(args[0], np.float32).reshape(-1, 3)
         return np.concatenate([prev, kept], 0)
     return kept
+
+
+def overlapFilter(cloudA, cloudB, poseA, poseB, range, angularView, accepted_pointsA=None, accepted_pointsB=None,
+                  ctx=None):
+    """filteringUtils.cpp:111-193 on the device (aicp_hip_fov_overlap): the FOV overlap in percent.
+    cloudA / cloudB: (N, 3|4|8|12) float32 rows in the global frame; poseA / poseB: 4x4 poses.
+    accepted_pointsA / accepted_pointsB: lists that receive the accepted points as one (M, 3)
+    float32 array each (the reference appends to the clouds it is given)."""
+    ov, ka, kb = _ctx(ctx).fov_overlap(cloudA, cloudB, poseA, poseB, range, angularView)
+    if accepted_pointsA is not None:
+        accepted_pointsA.append(ka)
+    if accepted_pointsB is not None:
+        accepted_pointsB.append(kb)
+    return ov
+
+
+def alignabilityFilter(cloudA, cloudB, poseA, poseB, cloudA_planes=None, cloudB_planes=None, eigenvectors=None,
+                       ctx=None, params=None):
+    """filteringUtils.cpp:196-430 on the device: the alignability in percent of two clouds that
+    lie in the region of overlap (overlapFilter's accepted points): both are pre-filtered with the
+    pose's translation as viewpoint, their plane clusters matched by box overlap and mean normal,
+    and the matched normals analysed by PCA; 0 when no planes match. As the reference, it takes
+    the accepted clouds from the host: aicp_hip_prefilter twice, then aicp_hip_cluster_match
+    (Context.alignment_features is the call that chains the FOV filter, both pre-filters and the
+    matching on the device). params: RiskParams (default_risk_params()).
+    cloudA_planes / cloudB_planes / eigenvectors: lists that receive the matched planes ((M, 8)
+    rows {x, y, z, nx, ny, nz, cluster, 0}) and the PCA frame ((3, 6) rows: the matched planes'
+    centroid and one eigenvector each)."""
+    c = _ctx(ctx)
+    prm = params if params is not None else _lib.default_risk_params()
+    pre = []
+    for cloud, pose in ((cloudA, poseA), (cloudB, poseB)):
+        pf = _lib.PrefilterParams.from_buffer_copy(prm.prefilter)
+        T = np.asarray(pose, np.float64).reshape(4, 4)
+        for i in range(3):
+            pf.viewpoint[i] = float(np.float32(T[i, 3]))
+        pre.append(c.prefilter(cloud, pf, details=True))
+    (fa, fb) = pre
+    r = c.cluster_match(fa["sampled"], fa["labels"], fb["sampled"], fb["labels"], prm.max_angle_deg,
+                        tuple(prm.box_scale))
+    for dst, f, ids in ((cloudA_planes, fa, [i for i in r["matching_indeces"] if i >= 0]),
+                        (cloudB_planes, fb, [j for j, i in enumerate(r["matching_indeces"]) if i >= 0])):
+        if dst is None:
+            continue
+        rows = [np.nonzero(f["labels"] == k)[0] for k in ids]
+        idx = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+        out = np.zeros((len(idx), 8), np.float32)
+        out[:, :3] = f["sampled"][idx, :3]
+        out[:, 3:6] = f["sampled"][idx, 4:7]
+        out[:, 6] = f["labels"][idx]
+        dst.append(out)
+    if eigenvectors is not None and r["n_matches"]:
+        eigenvectors.append(np.concatenate([np.tile(r["centroid"], (3, 1)), r["eigenvectors"].T], 1))
+    return r["alignability"]

@@ -277,6 +277,95 @@ typedef struct {
 } aicp_prefilter_stats;
 int aicp_hip_last_prefilter_stats(const aicp_hip_ctx* ctx, aicp_prefilter_stats* out);
 
+/* ---- alignment risk (failure_prediction_mode, App::computeAlignmentRisk, app.cpp:143-185) ------
+ * The two features App feeds its classifier (app.cpp:179: octree_overlap_, alignability_) and
+ * fov_overlap_. The SVM itself (two floats in, an OpenCV model file) stays with the caller.
+ * Poses are column-major double[16] (Eigen::Isometry3d::data()). Rules and the one deliberate
+ * deviation (the clamped cosine): DESIGN.md §4.5. */
+
+/* overlapFilter (aicp_core/src/utils/filteringUtils.cpp:111-193): cloud A is filtered in pose B's
+ * frame and cloud B in pose A's: a point is kept when |atan2(y, x)| < 180 - (360 - angular_view)/2
+ * degrees and its distance < range; kept points go back to the global frame (float) in input
+ * order. *fov_overlap = 100 * kept_A/|A| * kept_B/|B| (float). accepted_a / accepted_b: packed
+ * xyz, capacity |A| / |B| points, nullable. An input cloud of 0 points is AICP_ERR_INVALID (the
+ * reference divides by zero). */
+int aicp_hip_fov_overlap(aicp_hip_ctx* ctx, const aicp_cloud* cloud_a, const aicp_cloud* cloud_b,
+                         const double pose_a[16], const double pose_b[16], float range, float angular_view,
+                         float* fov_overlap, float* accepted_a /* 3*|A|, nullable */, size_t* n_accepted_a,
+                         float* accepted_b /* 3*|B|, nullable */, size_t* n_accepted_b);
+
+typedef struct {
+  float range;              /* sensor range, metres (the caller's configuration) */
+  float angular_view;       /* field of view, degrees */
+  float max_angle_deg;      /* matching: largest angle between mean normals, 20 (filteringUtils.cpp:258) */
+  float box_scale[3];       /* overlapBoxFilter's enlargement of the box, (1, 1, 3) (:520-528) */
+  aicp_prefilter_params prefilter; /* the viewpoint is overwritten with each pose's translation (:72) */
+} aicp_risk_params;
+void aicp_hip_default_risk_params(aicp_risk_params* out);
+
+/* One cluster's oriented box: MomentOfInertiaEstimation::getOBB (axes = eigenvectors of the
+ * covariance, major / middle = minor x major / minor as columns of rot, row-major) after
+ * overlapBoxFilter's scaling; half = the symmetric max point. */
+typedef struct {
+  double centre[3];
+  double rot[9];
+  double half[3];
+} aicp_risk_box;
+
+/* The matching and PCA of alignabilityFilter (filteringUtils.cpp:222-430) on two pre-filtered
+ * clouds in the layout aicp_hip_prefilter returns (sampled: 8 floats per point, labels: cluster or
+ * -1; clusters = 1 + the largest label). The kernel-level test surface of the risk kernels.
+ * Outputs (each nullable): matching_indeces / matching_overlap / matching_distance per cluster of
+ * B (-1: no match); eigenvalues (normalised, descending), eigenvectors (row-major, column k for
+ * eigenvalue k), centroid of A's matched planes; boxes per cluster; cnt_a_in_box_b [clusters_B]
+ * [clusters_A] and cnt_b_in_box_a [clusters_A][clusters_B]. More than 4096 clusters in a cloud or
+ * clusters_A * clusters_B > 2^22: AICP_ERR_UNSUPPORTED. Zero clusters on a side: alignability 0. */
+int aicp_hip_cluster_match(aicp_hip_ctx* ctx, const float* sampled_a, const int32_t* labels_a, size_t n_a,
+                           const float* sampled_b, const int32_t* labels_b, size_t n_b, float max_angle_deg,
+                           const float box_scale[3], float* alignability, int32_t* n_matches,
+                           int32_t* matching_indeces, float* matching_overlap, float* matching_distance,
+                           double eigenvalues[3], double eigenvectors[9], double centroid[3],
+                           aicp_risk_box* boxes_a, aicp_risk_box* boxes_b, uint32_t* cnt_a_in_box_b,
+                           uint32_t* cnt_b_in_box_a);
+
+typedef struct {
+  float fov_overlap;        /* overlapFilter's value */
+  float alignability;       /* alignabilityFilter's value; 0 with no matching planes (:344-348) */
+  uint64_t accepted_a, accepted_b; /* points the FOV filter kept */
+  uint32_t sampled_a, sampled_b;   /* points of the two sampled clouds */
+  int32_t clusters_a, clusters_b;
+  int32_t n_matches;
+  int32_t pad;
+  double eigenvalues[3];    /* normalised, descending */
+  double eigenvectors[9];   /* row-major, column k for eigenvalue k */
+  double centroid[3];       /* of A's matched planes (the reference's `eigenvectors` cloud, :402-424) */
+} aicp_risk_result;
+
+/* computeAlignmentRisk up to the classifier: overlapFilter -> regionGrowingUniformPlane-
+ * SegmentationFilter of both accepted clouds (viewpoint = the pose's translation) -> matching
+ * and PCA, chained on the device: the accepted clouds, sampled clouds and labels never cross to
+ * the host (the host reads the accepted and cluster counts to size launches, and the result).
+ * planes_a / planes_b (nullable, capacity planes_cap points of 8 floats: x, y, z, nx, ny, nz,
+ * cluster index, 0): the matched planes of both clouds (cloudA_planes / cloudB_planes, :314-315;
+ * the index stands where the reference puts a random colour), in matching order. An accepted cloud
+ * of 0 points or zero clusters on a side: AICP_OK with alignability 0. */
+int aicp_hip_alignment_features(aicp_hip_ctx* ctx, const aicp_risk_params* prm, const aicp_cloud* cloud_a,
+                                const aicp_cloud* cloud_b, const double pose_a[16], const double pose_b[16],
+                                aicp_risk_result* out, float* planes_a, size_t* n_planes_a, float* planes_b,
+                                size_t* n_planes_b, size_t planes_cap);
+
+/* Timing of the last aicp_hip_alignment_features (HIP events on the context stream). */
+typedef struct {
+  double fov_ms;            /* both FOV filters */
+  double prefilter_a_ms, prefilter_b_ms; /* hand-off copy, pre-filter, gather */
+  double clusters_ms;       /* moments + boxes of both clouds */
+  double counts_ms;         /* both count matrices */
+  double match_ms;          /* matching + PCA */
+  double device_ms;         /* inputs uploaded -> result ready */
+  double wall_ms;           /* the whole call */
+} aicp_risk_stats;
+int aicp_hip_last_risk_stats(const aicp_hip_ctx* ctx, aicp_risk_stats* out);
+
 /* ---- device-resident prior map (localization mode) ------------------------------------------
  * App keeps prior_map_ and, per reading, crops it around the prior pose (setReference,
  * app.cpp:41-51), appends the aligned reference reading every reference_update_frequency clouds
