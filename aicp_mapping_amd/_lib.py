@@ -42,7 +42,7 @@ EXPORTS = [
     "aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_hip_set_options", "aicp_hip_get_options",
     "aicp_hip_test_force_scan_stall", "aicp_hip_sequence_run_raw", "aicp_hip_build_info",
     "aicp_hip_fov_overlap", "aicp_hip_cluster_match", "aicp_hip_alignment_features",
-    "aicp_hip_default_risk_params", "aicp_hip_last_risk_stats",
+    "aicp_hip_default_risk_params", "aicp_hip_last_risk_stats", "aicp_hip_test_select",
 ]
 
 
@@ -50,7 +50,8 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_get_options", "aicp_hip_test_force_scan_stall",
            "aicp_hip_sequence_run_raw", "aicp_hip_build_info",  # added in r05 / r06
            "aicp_hip_fov_overlap", "aicp_hip_cluster_match", "aicp_hip_alignment_features",
-           "aicp_hip_default_risk_params", "aicp_hip_last_risk_stats"}  # the alignment-risk features
+           "aicp_hip_default_risk_params", "aicp_hip_last_risk_stats",  # the alignment-risk features
+           "aicp_hip_test_select"}
 
 
 class IcpConfig(C.Structure):
@@ -342,6 +343,10 @@ def _load():
         L.aicp_hip_alignment_features.argtypes = [vp, C.POINTER(RiskParams), clp, clp, dp, dp, C.POINTER(RiskResult),
                                                   fp, szp, fp, szp, sz]
         L.aicp_hip_last_risk_stats.argtypes = [vp, C.POINTER(RiskStats)]
+    if hasattr(L, "aicp_hip_test_select"):
+        u32p = C.POINTER(C.c_uint32)
+        L.aicp_hip_test_select.argtypes = [vp, sz, u32p, fp, C.POINTER(C.c_uint8), sz, ip, fp, fp, ip, ip, u32p, u32p,
+                                           up]
     return L
 
 
@@ -732,6 +737,43 @@ class Context:
         rc = lib.aicp_hip_dists_quantile(self.h, _fptr(d2), d2.size, float(quantile), C.byref(out))
         self.check(rc)
         return out.value
+
+    def test_select(self, d2_steps, counts, ratios, variants, active=None):
+        """aicp_hip_test_select: one select per step (variants[s]: 0 separate launches, 1 two
+        launches with tails, 2 fused, 3 / 4 fused with 2048 / 8192 candidates in LDS, 5 one workgroup
+        per pair) on d2_steps[s], the pairs' distances one after another (counts[p] each), on the
+        same pair states. Returns limit, status, n_finite, b1 and miss as (n_steps, n_pairs) arrays
+        and dirty, the non-zero words the last step left in the select's work space."""
+        counts = np.ascontiguousarray(counts, np.uint32).ravel()
+        ratios = np.ascontiguousarray(ratios, np.float32).ravel()
+        variants = np.ascontiguousarray(variants, np.int32).ravel()
+        P, S, total = counts.size, variants.size, int(counts.sum(dtype=np.uint64))
+        if ratios.size != P or len(d2_steps) != S:
+            raise ValueError("one ratio per pair and one distance array per step")
+        d2 = np.empty((S, total), np.float32)
+        for s, d in enumerate(d2_steps):
+            d = np.ascontiguousarray(d, np.float32).ravel()
+            if d.size != total:
+                raise ValueError(f"step {s}: {d.size} distances for {total} readings")
+            d2[s] = d
+        act = None
+        if active is not None:
+            act = np.ascontiguousarray(active, np.uint8).ravel()
+            if act.size != P:
+                raise ValueError("one active flag per pair")
+        out = dict(limit=np.zeros((S, P), np.float32), status=np.zeros((S, P), np.int32),
+                   n_finite=np.zeros((S, P), np.int32), b1=np.zeros((S, P), np.uint32),
+                   miss=np.zeros((S, P), np.uint32))
+        dirty = C.c_uint64()
+        ip, u32p = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+        rc = lib.aicp_hip_test_select(
+            self.h, P, counts.ctypes.data_as(u32p), _fptr(ratios),
+            act.ctypes.data_as(C.POINTER(C.c_uint8)) if act is not None else None, S, variants.ctypes.data_as(ip),
+            _fptr(d2), _fptr(out["limit"]), out["status"].ctypes.data_as(ip), out["n_finite"].ctypes.data_as(ip),
+            out["b1"].ctypes.data_as(u32p), out["miss"].ctypes.data_as(u32p), C.byref(dirty))
+        self.check(rc)
+        out["dirty"] = int(dirty.value)
+        return out
 
     def solve6(self, A, b):
         A = np.ascontiguousarray(A, np.float64).reshape(36)

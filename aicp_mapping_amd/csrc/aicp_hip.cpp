@@ -1700,6 +1700,115 @@ int aicp_hip_solve6(aicp_hip_ctx* ctx, const double* A, const double* b, double*
   return AICP_OK;
 }
 
+// Any select variant on given distances, set up as batch_run sets the ICP loop up (descriptors,
+// states, the 4096-reading block map, zeroed work space, active list, IcpIterSync); between steps
+// the update kernel's part of an iteration: the group's pairs counter zeroed, the active list rebuilt.
+int aicp_hip_test_select(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* counts, const float* ratios,
+                         const uint8_t* active, size_t n_steps, const int32_t* variant, const float* d2,
+                         float* out_limit, int32_t* out_status, int32_t* out_n_finite, uint32_t* out_b1,
+                         uint32_t* out_miss, uint64_t* out_dirty) {
+  if (!ctx || !counts || !ratios || !variant || !d2 || !out_limit || !out_status || !out_n_finite || !out_b1 ||
+      !out_miss || !out_dirty)
+    return AICP_ERR_INVALID;
+  if (n_pairs == 0 || n_pairs > (size_t)kMaxPairs || n_steps == 0) return AICP_ERR_INVALID;
+  const size_t P = n_pairs;
+  uint64_t total = 0;
+  uint32_t max_read = 0;
+  for (size_t p = 0; p < P; ++p) {
+    if (counts[p] == 0 || !(ratios[p] >= 0.f && ratios[p] <= 1.f)) return AICP_ERR_INVALID;
+    total += counts[p];
+    max_read = std::max(max_read, counts[p]);
+  }
+  if (total >= (1ull << 31) || total * n_steps >= (1ull << 32)) return AICP_ERR_INVALID;
+  for (size_t s = 0; s < n_steps; ++s) {
+    if (variant[s] < 0 || variant[s] > 5) return AICP_ERR_INVALID;
+    if (variant[s] == 5 && !sel_pair_fits(P, max_read, 1)) return AICP_ERR_INVALID;
+  }
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t st_ = ctx->stream;
+  std::vector<PairDesc> desc(P, PairDesc{});
+  Maps ms;
+  uint32_t off = 0;
+  for (size_t p = 0; p < P; ++p) {
+    desc[p].read_off = off;
+    desc[p].n_read = counts[p];
+    desc[p].ratio = ratios[p];
+    ms.add((int)p, counts[p], kNNBlock * kSelPerThread);
+    off += counts[p];
+  }
+  const size_t nb = ms.pair.size();
+  HIPC(ensure(ctx->desc, P * sizeof(PairDesc)));
+  HIPC(ensure(ctx->state, P * sizeof(PairState)));
+  HIPC(ensure(ctx->d2, total * n_steps * 4));
+  HIPC(ensure(ctx->qmap, nb * 8));
+  HIPC(ensure(ctx->sel_hist, P * kHistBins * 4));
+  HIPC(ensure(ctx->sel_cand, total * 4));
+  HIPC(ensure(ctx->sel_cnt, P * 4));
+  HIPC(ensure(ctx->isync, icp_sync_words(P) * 4));
+  HIPC(ensure(ctx->active, active_list_bytes(total, P)));
+  HIPC(ensure(ctx->ctrs, kCtrWords * 4));
+  PairDesc* dDesc = ctx->desc.as<PairDesc>();
+  PairState* dState = ctx->state.as<PairState>();
+  uint32_t* hist = ctx->sel_hist.as<uint32_t>();
+  uint32_t* cand = ctx->sel_cand.as<uint32_t>();
+  uint32_t* cnt = ctx->sel_cnt.as<uint32_t>();
+  uint32_t* sync = ctx->isync.as<uint32_t>();
+  ActiveList* al = ctx->active.as<ActiveList>();
+  HIPC(hipMemcpy(dDesc, desc.data(), P * sizeof(PairDesc), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(ctx->d2.p, d2, total * n_steps * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(ctx->qmap.p, ms.pair.data(), nb * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(ctx->qmap.as<uint32_t>() + nb, ms.start.data(), nb * 4, hipMemcpyHostToDevice));
+  const BlockMap m{ctx->qmap.as<int32_t>(), ctx->qmap.as<uint32_t>() + nb, (uint32_t)nb};
+  HIPC(hipMemsetAsync(hist, 0, P * kHistBins * 4, st_));
+  HIPC(hipMemsetAsync(cnt, 0, P * 4, st_));
+  HIPC(hipMemsetAsync(sync, 0, icp_sync_words(P) * 4, st_));
+  HIPC(hipMemsetAsync(ctx->ctrs.p, 0, kCtrWords * 4, st_));
+  launch_init_state(st_, (int)P, dDesc, dState);
+  for (size_t p = 0; p < P && active; ++p)
+    if (!active[p]) HIPC(hipMemsetAsync(&dState[p].active, 0, sizeof(int32_t), st_));
+  IcpIterSync y = icp_sync_layout(sync, P, 0);
+  y.np = (int)P;
+  y.pd = dDesc;
+  y.st = dState;
+  y.al = al;
+  y.ctr = ctx->ctrs.as<uint32_t>();
+  std::vector<PairState> hs(P);
+  for (size_t s = 0; s < n_steps; ++s) {
+    HIPC(hipMemsetAsync(y.pairs, 0, 4, st_));  // (stopped pairs arrived there; the update kernel's arrivals complete it)
+    launch_active_list(st_, (int)P, dDesc, dState, al, y.ctr);
+    const float* d = ctx->d2.as<float>() + s * total;
+    switch (variant[s]) {
+      case 0: launch_icp_select(st_, m, (int)P, dDesc, dState, d, hist, cand, cnt); break;
+      case 1: launch_icp_select_f(st_, m, dDesc, dState, d, hist, cand, cnt, y); break;
+      case 2: launch_icp_select_fused(st_, m, dDesc, dState, d, hist, cand, cnt, y); break;
+      case 3: launch_icp_select_fused(st_, m, dDesc, dState, d, hist, cand, cnt, y, (uint32_t)kHistBins); break;
+      case 4: launch_icp_select_fused(st_, m, dDesc, dState, d, hist, cand, cnt, y, kFinalLds); break;
+      default: launch_icp_select_pair(st_, (int)P, dDesc, dState, d, cand, y); break;
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(hs.data(), dState, P * sizeof(PairState), hipMemcpyDeviceToHost, st_));
+    HIPC(hipStreamSynchronize(st_));
+    for (size_t p = 0; p < P; ++p) {
+      const size_t o = s * P + p;
+      out_limit[o] = hs[p].limit;
+      out_status[o] = hs[p].status;
+      out_n_finite[o] = hs[p].n_finite;
+      out_b1[o] = hs[p].sel_b1;
+      out_miss[o] = hs[p].sel_miss;
+    }
+  }
+  // what the selects leave for the next iteration: the histograms, the candidate counts and the
+  // arrival counters of both select launches, all zero
+  std::vector<uint32_t> w(P * kHistBins + 3 * P);
+  HIPC(hipMemcpy(w.data(), hist, P * kHistBins * 4, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(w.data() + P * kHistBins, cnt, P * 4, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(w.data() + P * kHistBins + P, sync, 2 * P * 4, hipMemcpyDeviceToHost));  // sel1 | sel2
+  uint64_t dirty = 0;
+  for (uint32_t v : w) dirty += v != 0;
+  *out_dirty = dirty;
+  return AICP_OK;
+}
+
 void aicp_hip_default_prefilter(aicp_prefilter_params* p) {
   if (!p) return;
   *p = aicp_prefilter_params{};

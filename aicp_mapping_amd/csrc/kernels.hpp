@@ -82,8 +82,12 @@ void launch_icp_select_pair(hipStream_t s, int n_pairs, const PairDesc* pd, Pair
                             uint32_t* cand, const IcpIterSync& y);
 // force: aicp_hip_options::select_pair (-1 auto, 0 off, 1 on)
 bool sel_pair_fits(size_t n_pairs, uint64_t max_read, int force);
+constexpr uint32_t kFinalLds = 8192;  // candidates the final select of a pair copies into LDS
+// force_cl (aicp_hip_test_select): 0 = the template by the launch's size, else the candidates the
+// final select keeps in LDS, kHistBins or kFinalLds
 void launch_icp_select_fused(hipStream_t s, BlockMap m, const PairDesc* pd, PairState* st, const float* d2,
-                             uint32_t* hist1, uint32_t* cand, uint32_t* cand_cnt, const IcpIterSync& y);
+                             uint32_t* hist1, uint32_t* cand, uint32_t* cand_cnt, const IcpIterSync& y,
+                             uint32_t force_cl = 0);
 void launch_icp_reduce_f(hipStream_t s, BlockMap m, const PairDesc* pd, PairState* st, const float4* read_c,
                          const int32_t* match, const float* d2, const uint32_t* touched, const float4* bpts,
                          const float4* bnrm, double* slab, const IcpParams& prm, const IcpIterSync& y);

@@ -1932,8 +1932,8 @@ __global__ __launch_bounds__(256) void k_sel_compact(BlockMap m, const PairDesc*
 // per pair (one workgroup, any size): digits 2 (bits 20..10) and 3 (bits 9..0) over the candidates.
 // The candidates were written by the other workgroups (other XCDs: each load is a fabric round
 // trip), so up to kFinalLds of them are read once, eight loads in flight per thread, into LDS and
-// both passes run there (the passes over global memory took ~11 us of a C2 iteration, r03).
-constexpr uint32_t kFinalLds = 8192;
+// both passes run there (the passes over global memory took ~11 us of a C2 iteration, r03):
+// kFinalLds (kernels.hpp).
 // b1 / r1: digit 1's bin and the rank in it (s.sel_b1 / sel_r1; passed in, since in k_sel_fused
 // they were just written by another thread of the workgroup)
 __device__ void sel_final_body(PairState& s, uint32_t b1, uint32_t r1, const uint32_t* __restrict__ cv,
@@ -3132,9 +3132,11 @@ void launch_icp_select_f(hipStream_t s, BlockMap m, const PairDesc* pd, PairStat
   k_sel_compact_f<kSelCompactThreads><<<m.n_blocks, kSelCompactThreads, 0, s>>>(m, pd, st, d2, cand, cand_cnt, y);
 }
 void launch_icp_select_fused(hipStream_t s, BlockMap m, const PairDesc* pd, PairState* st, const float* d2,
-                             uint32_t* hist1, uint32_t* cand, uint32_t* cand_cnt, const IcpIterSync& y) {
+                             uint32_t* hist1, uint32_t* cand, uint32_t* cand_cnt, const IcpIterSync& y,
+                             uint32_t force_cl) {
   if (!m.n_blocks) return;
-  if (m.n_blocks > 2048)  // more workgroups than fit the chip at once: occupancy over the tail's LDS copy
+  // more workgroups than fit the chip at once: occupancy over the tail's LDS copy
+  if (force_cl ? force_cl == (uint32_t)kHistBins : m.n_blocks > 2048)
     k_sel_fused<256, kHistBins><<<m.n_blocks, 256, 0, s>>>(m, pd, st, d2, hist1, cand, cand_cnt, y);
   else
     k_sel_fused<256, kFinalLds><<<m.n_blocks, 256, 0, s>>>(m, pd, st, d2, hist1, cand, cand_cnt, y);

@@ -507,6 +507,24 @@ int aicp_hip_dists_quantile(aicp_hip_ctx* ctx, const float* d2, size_t n, float 
 /* solvePossiblyUnderdeterminedLinearSystem on the device (A row-major 6x6, double). */
 int aicp_hip_solve6(aicp_hip_ctx* ctx, const double* A, const double* b, double* out_x,
                     int32_t* out_path /* 0 LLT, 1 QR min-norm, 2 eigen pseudo-inverse */);
+/* Test surface: any implementation of the TrimmedDist limit on given distances. Runs n_steps
+ * selects, one after another on the same pair states, as successive ICP iterations would. Step s
+ * uses variant[s] on d2 + s * total, where total = sum(counts), pair p's slice at its prefix
+ * offset. variant: 0 the separate launches (aicp_hip_dists_quantile's), 1 the two launches with
+ * tails, 2 the fused launch with the launcher's own choice of template, 3 / 4 the fused launch
+ * with 2048 / 8192 candidates in LDS, 5 one workgroup per pair (counts <= 65536). Between steps
+ * the entry does the update kernel's part only (the next active list); the digit-1 guess of a
+ * fused step is what the previous step left (0 before the first), and a pair that stopped (no
+ * finite distance: status 1) or started inactive keeps its outputs. out_dirty: non-zero words
+ * left in the select's self-resetting work space after the last step (0 expected).
+ * AICP_ERR_INVALID: a null pointer, no pair or more than 4096, no step, a count of 0, a ratio
+ * outside [0, 1], an unknown variant, variant 5 with a count above 65536, n_steps * total >= 2^32. */
+int aicp_hip_test_select(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* counts, const float* ratios,
+                         const uint8_t* active /* nullable: 0 = pair starts inactive */,
+                         size_t n_steps, const int32_t* variant, const float* d2,
+                         float* out_limit, int32_t* out_status, int32_t* out_n_finite,
+                         uint32_t* out_b1, uint32_t* out_miss /* each n_steps * n_pairs */,
+                         uint64_t* out_dirty);
 
 #ifdef __cplusplus
 }

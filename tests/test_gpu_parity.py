@@ -400,6 +400,28 @@ def test_select_one_workgroup_per_pair_equals_chip_wide(ctx, L):
         assert s0 == s1, k
 
 
+def test_select_options_give_identical_registrations(ctx, L):
+    """Which select kernels an ICP loop runs (the fused launch from iteration select_fused_from on,
+    0 = never; one workgroup per pair) changes nothing: on a ragged batch of three readings against
+    one shared reference, transforms, iteration counts, trimmed_ratio and every other per-pair
+    statistic are bit-identical across the options."""
+    prs = [sy.make_pair(9000, n, seed=120, move=1.0 + 0.4 * i) for i, n in enumerate((6000, 7531, 9000))]
+    ref = prs[0].ref  # (the reference depends on the seed alone)
+    pairs = [dict(ref=ref, read=p.read, ref_origin=p.ref_origin, read_origin=p.read_origin) for p in prs]
+    flags = L.AICP_RUN_OVERLAP | L.AICP_RUN_ICP
+    out = {}
+    for ff in (0, 1, 3):
+        for sp in (0, 1):
+            with ctx.options(select_fused_from=ff, select_pair=sp):
+                out[ff, sp] = ctx.align_batch(pairs, flags=flags, resolution=RES)
+    T0, s0, rc0 = out[0, 0]
+    assert rc0 == 0 and all(s["iterations"] > 3 for s in s0), s0
+    for key, (T1, s1, rc1) in out.items():
+        assert rc1 == rc0, key
+        np.testing.assert_array_equal(T0, T1, err_msg=str(key))
+        assert s0 == s1, key
+
+
 def test_concurrent_contexts_identical(ctx, L):
     """Two contexts on one device driven by two host threads at once (bench.py --lanes): each
     batch's transforms and touch counts equal a lone run's (no shared device state)."""
