@@ -25,6 +25,7 @@ AICP_RUN_OVERLAP = 1
 AICP_RUN_ICP = 2
 AICP_RUN_TIME_NN = 4
 AICP_SEQ_DEBUG = 8  # aicp_sequence_params.flags: App's "debug" working_mode
+AICP_MON_PAIRED = 1  # aicp_monitor_params.flags: also the chain matcher's paired mean distance
 
 EXPORTS = [
     "aicp_hip_create", "aicp_hip_destroy", "aicp_hip_last_error", "aicp_hip_version",
@@ -43,6 +44,7 @@ EXPORTS = [
     "aicp_hip_test_force_scan_stall", "aicp_hip_sequence_run_raw", "aicp_hip_build_info",
     "aicp_hip_fov_overlap", "aicp_hip_cluster_match", "aicp_hip_alignment_features",
     "aicp_hip_default_risk_params", "aicp_hip_last_risk_stats", "aicp_hip_test_select",
+    "aicp_hip_default_monitor_params", "aicp_hip_monitor", "aicp_hip_monitor_batch", "aicp_hip_last_monitor_stats",
 ]
 
 
@@ -51,7 +53,9 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_sequence_run_raw", "aicp_hip_build_info",  # added in r05 / r06
            "aicp_hip_fov_overlap", "aicp_hip_cluster_match", "aicp_hip_alignment_features",
            "aicp_hip_default_risk_params", "aicp_hip_last_risk_stats",  # the alignment-risk features
-           "aicp_hip_test_select"}
+           "aicp_hip_test_select",
+           "aicp_hip_default_monitor_params", "aicp_hip_monitor", "aicp_hip_monitor_batch",
+           "aicp_hip_last_monitor_stats"}  # the registration quality monitor
 
 
 class IcpConfig(C.Structure):
@@ -169,6 +173,38 @@ class RiskResult(C.Structure):
 class RiskStats(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("fov_ms", "prefilter_a_ms", "prefilter_b_ms", "clusters_ms", "counts_ms",
                                           "match_ms", "device_ms", "wall_ms")]
+
+
+class MonitorParams(C.Structure):
+    """aicp_monitor_params (include/aicp_hip.h)."""
+    _fields_ = [("quantile", C.c_float), ("max_accepted_dist", C.c_double), ("flags", C.c_int32)]
+
+
+class MonitorResult(C.Structure):
+    """aicp_monitor_result: 56 bytes without implicit padding, so bytes(result) compares results."""
+    _fields_ = [
+        ("hausdorff", C.c_float),
+        ("hausdorff_quantile", C.c_float),
+        ("max_d2", C.c_float * 2),
+        ("quantile_d2", C.c_float * 2),
+        ("knn_mean_dist", C.c_float),
+        ("pad", C.c_int32),
+        ("knn_valid", C.c_uint64),
+        ("paired_mean_dist", C.c_float),
+        ("paired_limit_d2", C.c_float),
+        ("paired_kept", C.c_uint64),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("pad", "max_d2", "quantile_d2")}
+        d["max_d2"] = [float(x) for x in self.max_d2]
+        d["quantile_d2"] = [float(x) for x in self.quantile_d2]
+        d["bytes"] = bytes(self)
+        return d
+
+
+class MonitorStats(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("trees_ms", "nn_ms", "reduce_ms", "device_ms", "wall_ms")]
 
 
 class Cloud(C.Structure):
@@ -343,6 +379,14 @@ def _load():
         L.aicp_hip_alignment_features.argtypes = [vp, C.POINTER(RiskParams), clp, clp, dp, dp, C.POINTER(RiskResult),
                                                   fp, szp, fp, szp, sz]
         L.aicp_hip_last_risk_stats.argtypes = [vp, C.POINTER(RiskStats)]
+    if hasattr(L, "aicp_hip_monitor"):
+        clp = C.POINTER(Cloud)
+        mpp, mrp = C.POINTER(MonitorParams), C.POINTER(MonitorResult)
+        L.aicp_hip_default_monitor_params.argtypes = [mpp]
+        L.aicp_hip_default_monitor_params.restype = None
+        L.aicp_hip_monitor.argtypes = [vp, mpp, cfgp, clp, clp, fp, mrp, fp, fp]
+        L.aicp_hip_monitor_batch.argtypes = [vp, mpp, cfgp, pp, sz, fp, mrp]
+        L.aicp_hip_last_monitor_stats.argtypes = [vp, C.POINTER(MonitorStats)]
     if hasattr(L, "aicp_hip_test_select"):
         u32p = C.POINTER(C.c_uint32)
         L.aicp_hip_test_select.argtypes = [vp, sz, u32p, fp, C.POINTER(C.c_uint8), sz, ip, fp, fp, ip, ip, u32p, u32p,
@@ -528,6 +572,18 @@ def default_risk_params(**kw) -> RiskParams:
             raise AttributeError(f"aicp_risk_params has no field {k}")
         else:
             setattr(p, k, v)
+    return p
+
+
+def default_monitor_params(**kw) -> MonitorParams:
+    """aicp_hip_default_monitor_params: quantile 0.60 (icpMonitor.cpp:31), max_accepted_dist 0.20
+    (:128), no flags; keyword overrides."""
+    p = MonitorParams()
+    lib.aicp_hip_default_monitor_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(f"aicp_monitor_params has no field {k}")
+        setattr(p, k, v)
     return p
 
 
@@ -922,6 +978,66 @@ class Context:
         st = RiskStats()
         self.check(lib.aicp_hip_last_risk_stats(self.h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in RiskStats._fields_}
+
+
+    # -------------------------------------------------------------- quality monitor ---------
+    @staticmethod
+    def _monitor_params(cfg, params):
+        prm = MonitorParams.from_buffer_copy(params) if params is not None else default_monitor_params()
+        if cfg is not None:
+            prm.flags |= AICP_MON_PAIRED
+        return prm
+
+    @staticmethod
+    def _T16(T, n):
+        if T is None:
+            return None
+        t = np.asarray(T, np.float32).reshape(n, 4, 4)
+        return np.ascontiguousarray(t.transpose(0, 2, 1).reshape(n, 16))
+
+    def monitor(self, ref, out, T=None, cfg=None, params=None, distances=False):
+        """aicp_hip_monitor (icpMonitor.cpp: hausdorffDistance, distancesKNN and, with a chain
+        configuration `cfg`, pairedPointsMeanDistance) of the reference and the aligned reading
+        `out`; with T (4x4 row-major) out = T * the given cloud, moved on the device. Returns the
+        aicp_monitor_result fields as a dict ("bytes": the struct's bytes); with distances=True also
+        dist_out / dist_ref, sqrtf(d2) per point of out / of ref."""
+        cr, kr = make_cloud(ref)
+        co, ko = make_cloud(out)
+        prm = self._monitor_params(cfg, params)
+        t = self._T16(T, 1)
+        res = MonitorResult()
+        do = np.zeros(ko.shape[0], np.float32) if distances else None
+        dr = np.zeros(kr.shape[0], np.float32) if distances else None
+        self.check(lib.aicp_hip_monitor(self.h, C.byref(prm), C.byref(cfg) if cfg is not None else None, C.byref(cr),
+                                        C.byref(co), _fptr(t) if t is not None else None, C.byref(res),
+                                        _fptr(do) if distances else None, _fptr(dr) if distances else None))
+        d = res.as_dict()
+        if distances:
+            d["dist_out"], d["dist_ref"] = do, dr
+        return d
+
+    def monitor_batch(self, pairs, T=None, cfg=None, params=None):
+        """aicp_hip_monitor_batch: pairs as align_batch takes them (dict(ref, read); read is the
+        aligned reading, or the cloud that T[i] moves), T (n, 4, 4) row-major or None. One launch
+        sequence for the whole batch; returns a list of result dicts."""
+        n = len(pairs)
+        arr = (Pair * max(n, 1))()
+        keep = []
+        for i, pr in enumerate(pairs):
+            p, k = make_pair(pr["ref"], pr["read"])
+            arr[i] = p
+            keep.append(k)
+        prm = self._monitor_params(cfg, params)
+        t = self._T16(T, n)
+        res = (MonitorResult * max(n, 1))()
+        self.check(lib.aicp_hip_monitor_batch(self.h, C.byref(prm), C.byref(cfg) if cfg is not None else None, arr, n,
+                                              _fptr(t) if t is not None else None, res))
+        return [res[i].as_dict() for i in range(n)]
+
+    def last_monitor_stats(self):
+        st = MonitorStats()
+        self.check(lib.aicp_hip_last_monitor_stats(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in MonitorStats._fields_}
 
 
 class ResidentBatch:

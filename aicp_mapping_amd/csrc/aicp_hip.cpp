@@ -1248,6 +1248,10 @@ void aicp_hip_destroy(aicp_hip_ctx* ctx) {
   release(ctx->pin_risk);
   for (auto e : ctx->risk_ev)
     if (e) (void)hipEventDestroy(e);
+  for (DevBuf* b : {&ctx->mon_bpts, &ctx->mon_nodes, &ctx->mon_bpts2, &ctx->mon_nodes2, &ctx->mon_ws}) release(*b);
+  release(ctx->pin_mon);
+  for (auto e : ctx->mon_ev)
+    if (e) (void)hipEventDestroy(e);
   release(ctx->refc.gst);
   release(ctx->pin_crop);
   release(ctx->pin_maps);

@@ -397,4 +397,56 @@ void launch_risk_match(hipStream_t s, uint32_t nca, uint32_t ncb, const RiskClus
                        const uint32_t* a_in_b, const uint32_t* b_in_a, float max_angle, int32_t* best_j,
                        float* best_ov, float* best_d, int32_t* m_idx, float* m_ov, float* m_dist, RiskOut* out);
 
+// ---- registration quality monitor (kernels_monitor.hip): icpMonitor.cpp's metrics -------------
+struct MonSeg {       // one tree/query segment of a 1-NN launch (32 bytes)
+  uint32_t slot_off;  // its first slot in the launch's slot space (whole 64-slot chunks per segment)
+  uint32_t nq;        // queries
+  uint32_t q_off;     // the first of them in the point array
+  uint32_t tree;      // descriptor of its tree (node_off, ref_off)
+  uint32_t d2_off;    // where its squared distances go
+  uint32_t pad[3];
+};
+// d2 of every segment's queries in its tree (libnabo order, 1-NN, node records); ctr:
+// kPersistCtrWords zeroed words. The kernel is in kernels_icp.hip, beside the other searches.
+void launch_mon_nn(hipStream_t s, uint32_t slots, const MonSeg* segs, const uint32_t* chunk_seg, const PairDesc* trees,
+                   const float4* q, const uint4* nodes, const float4* bpts, float maxE2, float maxR2, float* d2,
+                   uint32_t* ctr);
+constexpr uint32_t kMonChunk = 16 * 256;  // values per workgroup of the reduction: 16 slabs of 256
+struct MonRed {       // one segment of squared distances of the reduction
+  uint32_t d2_off, n;
+  uint32_t slot0;     // its first chunk slot (partial sums; the slots of a segment are consecutive)
+  int32_t lim;        // select state whose limit gates the kept count and sum (paired mean); -1: none
+  int32_t knn;        // 1: distancesKNN's valid count and sum
+  uint32_t acc;       // its accumulator
+  uint32_t pad[2];
+};
+struct MonAcc {       // integer tallies of a segment (zero at the start): order-free
+  uint32_t max_bits;  // the largest finite d2, as the bits of a non-negative float
+  uint32_t pad;
+  unsigned long long n_valid, kept;
+};
+struct MonPair {      // where one pair's result comes from
+  int32_t red[3];     // reduction segments: out -> ref, ref -> out, paired (-1: none; may be red[0])
+  int32_t sel_q[2];   // quantile selects of the two directions
+  int32_t sel_p;      // paired select (-1: none)
+  int32_t pad[2];
+};
+struct MonOut {       // aicp_monitor_result's layout (include/aicp_hip.h)
+  float hausdorff, hausdorff_quantile;
+  float max_d2[2], quantile_d2[2];
+  float knn_mean_dist;
+  int32_t pad;
+  uint64_t knn_valid;
+  float paired_mean_dist, paired_limit_d2;
+  uint64_t paired_kept;
+};
+// out cloud i (xf[i] = first point, count) = T[16 i ..] * itself, in k_transform's arithmetic
+void launch_mon_transform(hipStream_t s, BlockMap m, const uint2* xf, const float* T, float4* pts);
+// partial[2 slot], [2 slot + 1]: the chunk's sums of sqrt(d2) over the valid / the kept values;
+// dist (nullable): sqrt(d2) of every value, at d2's index
+void launch_mon_reduce(hipStream_t s, BlockMap m, const MonRed* red, const float* d2, const PairState* lim_st,
+                       double max_accepted, MonAcc* acc, double* partial, float* dist);
+void launch_mon_finish(hipStream_t s, int n_pairs, const MonPair* mp, const MonRed* red, const MonAcc* acc,
+                       const double* partial, const PairState* sel_q, const PairState* sel_p, MonOut* out);
+
 }  // namespace aicp

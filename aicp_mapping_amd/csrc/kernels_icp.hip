@@ -2854,6 +2854,43 @@ __global__ __launch_bounds__(256) void k_knn1_generic(uint32_t nq, const float4*
   }
 }
 
+// The monitor's 1-NN (kernels_monitor.hip): many tree/query segments in one launch, squared
+// distances only. Slot space: every segment padded to whole 64-slot chunks, chunk_seg names the
+// segment of each chunk (k_icp_nn's scheme without an active list); a segment's tree is read from
+// its descriptor, which the tree build filled in on the device. Node records (Trav<1>), libnabo
+// order, as k_knn1_generic.
+__global__ __launch_bounds__(256) void k_mon_nn(uint32_t slots, const MonSeg* __restrict__ segs,
+                                                const uint32_t* __restrict__ chunk_seg,
+                                                const PairDesc* __restrict__ trees, const float4* __restrict__ q,
+                                                const uint4* __restrict__ nodes, const float4* __restrict__ bpts,
+                                                float maxE2, float maxR2, float* __restrict__ d2, uint32_t* ctr) {
+  uint32_t c_lo = 0, c_n = 0, c_q = 0, c_node = 0, c_ref = 0, c_d2 = 0;  // chunk context (wave-uniform)
+  uint32_t oidx = 0;
+  persistent_xcd<Trav<1>>(
+      slots, ctr, maxE2, maxR2, nodes, bpts,
+      [&](uint32_t base) {
+        const uint32_t e = __builtin_amdgcn_readfirstlane(chunk_seg[base >> 6]);
+        const MonSeg& g = segs[e];
+        c_lo = __builtin_amdgcn_readfirstlane(g.slot_off);
+        c_n = __builtin_amdgcn_readfirstlane(g.nq);
+        c_q = __builtin_amdgcn_readfirstlane(g.q_off);
+        c_d2 = __builtin_amdgcn_readfirstlane(g.d2_off);
+        const PairDesc& t = trees[__builtin_amdgcn_readfirstlane(g.tree)];
+        c_node = __builtin_amdgcn_readfirstlane(t.node_off);
+        c_ref = __builtin_amdgcn_readfirstlane(t.ref_off);
+      },
+      [&](uint32_t s, Trav<1>& t) {
+        const uint32_t j = s - c_lo;
+        if (j >= c_n) return false;  // padding slot
+        t.bind(nodes, bpts, c_node, c_ref);
+        const float4 x = q[c_q + j];
+        oidx = c_d2 + j;
+        t.reset(x.x, x.y, x.z);
+        return true;
+      },
+      [&](uint32_t, Trav<1>& t) { d2[oidx] = t.res_d2(); });
+}
+
 __global__ void k_transform(int n, const float* __restrict__ T, const float4* __restrict__ in,
                             float4* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3184,6 +3221,13 @@ bool launch_knn_generic(hipStream_t s, uint32_t nq, const float4* q, const uint4
     default: return false;
   }
   return true;
+}
+void launch_mon_nn(hipStream_t s, uint32_t slots, const MonSeg* segs, const uint32_t* chunk_seg, const PairDesc* trees,
+                   const float4* q, const uint4* nodes, const float4* bpts, float maxE2, float maxR2, float* d2,
+                   uint32_t* ctr) {
+  if (!slots) return;
+  k_mon_nn<<<persistent_grid((int)slots), 256, 0, s>>>(slots, segs, chunk_seg, trees, q, nodes, bpts, maxE2, maxR2, d2,
+                                                       ctr);
 }
 void launch_transform(hipStream_t s, int n, const float* T, const float4* in, float4* out) {
   if (n > 0) k_transform<<<(n + 255) / 256, 256, 0, s>>>(n, T, in, out);

@@ -206,6 +206,7 @@ int device_trees_check(TreeBufs& T, std::string& err);
 // force: aicp_hip_options::tree_plan
 int plan_levels(uint64_t n_max, const TreeBufs& T, int force, bool lean = false);
 int check_cfg(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, int flags);
+WorkerPool* ctx_pool(aicp_hip_ctx* ctx);  // the context's packing threads, created on first use
 
 // The drop-in path's reference cache. App registers reading after reading against one reference
 // (app.cpp:72-73, a new one every reference_update_frequency readings, app.cpp:383-391) and calls
@@ -317,6 +318,12 @@ struct aicp_hip_ctx {
   aicp::rt::PinBuf pin_risk;
   hipEvent_t risk_ev[7] = {};
   aicp_risk_stats last_risk{};
+  // registration quality monitor (monitor.cpp): trees and work space of its own (the reference
+  // cache keeps bpts / nodes; mon_*2: the chain matcher's trees when its bucket size is not 8)
+  aicp::rt::DevBuf mon_bpts, mon_nodes, mon_bpts2, mon_nodes2, mon_ws;
+  aicp::rt::PinBuf pin_mon;
+  hipEvent_t mon_ev[5] = {};
+  aicp_monitor_stats last_mon{};
   aicp_hip_options opt{};  // aicp_hip_set_options (read by the calls; nothing reads the environment)
 };
 constexpr int kBatchPolls = 64;

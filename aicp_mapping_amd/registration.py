@@ -93,6 +93,7 @@ class HipRegistration(AbstractRegistrator):
         self._ctx = ctx
         self.cfg = _lib.default_config()
         self.stats = None
+        self.monitor = None  # the quality monitor's result of the last registration (printOutputStatistics)
         self._read = None
         self._out = None
 
@@ -139,6 +140,12 @@ class HipRegistration(AbstractRegistrator):
         self._read = read
         self._out = None
         self._T = T[0]
+        if self.params_.pointmatcher.printOutputStatistics:
+            # the statistics PointmatcherRegistration leaves as a comment block
+            # (pointmatcher_registration.cpp:138-150; icpMonitor.cpp), on the device
+            self.monitor = self.ctx.monitor(ref, read, T=T[0], cfg=self.cfg)
+            print(f"Hausdorff distance: {self.monitor['hausdorff']} m")
+            print(f"Paired points mean distance: {self.monitor['paired_mean_dist']} m")
         if final_transform is not None:
             final_transform[...] = T[0]
         return T[0]

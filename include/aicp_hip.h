@@ -366,6 +366,69 @@ typedef struct {
 } aicp_risk_stats;
 int aicp_hip_last_risk_stats(const aicp_hip_ctx* ctx, aicp_risk_stats* out);
 
+/* ---- registration quality monitor (aicp_core/src/utils/icpMonitor.cpp) -------------------------
+ * What PointmatcherRegistration would print with pointmatcher.printOutputStatistics
+ * (pointmatcher_registration.cpp:138-150, common.hpp:21): how good an alignment is, with no ground
+ * truth. ref is the reference, out the reading after alignment; with T (column-major, nullable)
+ * out = T * cloud is computed on the device first, in aicp_hip_transform's arithmetic. Trees are
+ * built over the coordinates as given (no centring, as aicp_hip_knn). Rules: DESIGN.md §4.6.
+ *   hausdorffDistance (:12-81): KDTreeMatcher knn 1, epsilon 0, both directions ([0]: tree on ref,
+ *     queries from out; [1]: tree on out, queries from ref); per direction max_d2 =
+ *     getDistsQuantile(1.0), quantile_d2 = getDistsQuantile(quantile); hausdorff =
+ *     sqrt(max(max_d2[0], max_d2[1])), hausdorff_quantile = sqrt(max(quantile_d2[0], quantile_d2[1])).
+ *   distancesKNN(ref, out) (:89-138): d = sqrtf(d2) of direction 0; valid when (double)d <=
+ *     max_accepted_dist; knn_mean_dist = sum d / knn_valid (NaN with knn_valid = 0: the reference
+ *     divides 0 by 0).
+ *   pairedPointsMeanDistance (:146-231), with AICP_MON_PAIRED: the chain's matcher (cfg->nn_epsilon,
+ *     nn_max_dist, bucket_size; tree on ref, queries from out) and its TrimmedDist filter:
+ *     paired_limit_d2 = getDistsQuantile(cfg->trimmed_ratio), a pair is kept when d2 <= limit,
+ *     paired_mean_dist = sum sqrtf(d2) / paired_kept, from the matcher's own d2. Without the flag,
+ *     or when the matcher found nothing within nn_max_dist: NaN, NaN and 0.
+ * The sums are fp64 in a fixed order: results are byte-identical across runs, contexts and batch
+ * compositions. */
+typedef struct {
+  float quantile;           /* hausdorffDistance's robust quantile, in [0, 1] (0.60) */
+  double max_accepted_dist; /* distancesKNN's maxAcceptedDist (0.20) */
+  int32_t flags;            /* AICP_MON_PAIRED */
+} aicp_monitor_params;
+#define AICP_MON_PAIRED 1   /* also the chain-matcher paired mean (needs cfg) */
+/* 56 bytes, no implicit padding (pad is 0): two results compare with memcmp */
+typedef struct {
+  float hausdorff, hausdorff_quantile;   /* metres */
+  float max_d2[2], quantile_d2[2];       /* squared metres; [0] out -> ref, [1] ref -> out */
+  float knn_mean_dist;
+  int32_t pad;
+  uint64_t knn_valid;
+  float paired_mean_dist, paired_limit_d2;
+  uint64_t paired_kept;
+} aicp_monitor_result;
+void aicp_hip_default_monitor_params(aicp_monitor_params* out);
+/* dist_out (|out| floats) / dist_ref (|ref| floats), nullable: sqrtf(d2) per point of out (direction
+ * 0) and of ref (direction 1), the values1 / values2 arrays the reference writes to VTK.
+ * AICP_ERR_INVALID: a null argument, a cloud of 0 points, a stride below 12 or no multiple of 4, a
+ * quantile outside [0, 1], AICP_MON_PAIRED without cfg; AICP_ERR_UNSUPPORTED: a kd-tree deeper than
+ * the device stack (48 levels), more than 2^28 points in a call; AICP_ERR_CONVERGENCE: a direction
+ * with no finite distance (non-finite coordinates). */
+int aicp_hip_monitor(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_icp_config* cfg /* nullable */,
+                     const aicp_cloud* ref, const aicp_cloud* out, const float T[16] /* nullable */,
+                     aicp_monitor_result* result, float* dist_out /* nullable */, float* dist_ref /* nullable */);
+/* n pairs (ref, read = out or the cloud T moves; init_T and the origins are not read) in one launch
+ * sequence: all trees in one device build, one 1-NN launch for the exact searches and one for the
+ * chain matcher's, one reduction. T: 16 floats per pair, nullable. At most 4096 pairs. Nothing but
+ * the results crosses back to the host. */
+int aicp_hip_monitor_batch(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_icp_config* cfg /* nullable */,
+                           const aicp_pair* pairs, size_t n, const float* T /* 16*n, nullable */,
+                           aicp_monitor_result* out /* n */);
+/* Timing of the last monitor call (HIP events on the context stream). */
+typedef struct {
+  double trees_ms;          /* transform + every kd-tree */
+  double nn_ms;             /* the 1-NN launches */
+  double reduce_ms;         /* selects, reduction, results */
+  double device_ms;         /* inputs uploaded -> results ready */
+  double wall_ms;           /* the whole call */
+} aicp_monitor_stats;
+int aicp_hip_last_monitor_stats(const aicp_hip_ctx* ctx, aicp_monitor_stats* out);
+
 /* ---- device-resident prior map (localization mode) ------------------------------------------
  * App keeps prior_map_ and, per reading, crops it around the prior pose (setReference,
  * app.cpp:41-51), appends the aligned reference reading every reference_update_frequency clouds

@@ -19,6 +19,9 @@
 //     throws std::runtime_error for AICP_ERR_CONVERGENCE / AICP_ERR_TRANSFORMATION.
 //   - A missing chain file exits the process (pointmatcher_registration.cpp:59-64).
 //   - getOutputReading = T * reading (pointmatcher_registration.cpp:128-131).
+//   - pointmatcher.printOutputStatistics (common.hpp:21): the statistics the reference leaves as a
+//     comment block (pointmatcher_registration.cpp:138-150; icpMonitor.cpp) are computed on the
+//     device (aicp_hip_monitor) and printed; getMonitor() returns them.
 //   - computeOverlap: sensor origins = pose translations (octrees_overlap.cpp:184,229-230),
 //     resolution read as float (yaml_configurator.cpp:81); App ignores the returned tree
 //     (app.cpp:132-135), so nullptr is returned.
@@ -120,6 +123,8 @@ class HipRegistration : public AbstractRegistrator {
   }
 
   const aicp_icp_stats& lastStats() const { return stats_; }
+  // the quality monitor's result of the last registration (zeros unless printOutputStatistics)
+  const aicp_monitor_result& getMonitor() const { return monitor_; }
 
   // &points[0].x, or nullptr for an empty cloud (points[0] of an empty vector is undefined);
   // the C-ABI rejects a null cloud with AICP_ERR_INVALID, which throws below
@@ -174,11 +179,23 @@ class HipRegistration : public AbstractRegistrator {
       read_xyz_[3 * i + 1] = q[1];
       read_xyz_[3 * i + 2] = q[2];
     }
+    if (params_.pointmatcher.printOutputStatistics) {
+      aicp_monitor_params mp;
+      aicp_hip_default_monitor_params(&mp);
+      mp.flags = AICP_MON_PAIRED;
+      aicp_cloud cr{}, cd{};
+      cr.pts = ref, cr.n = n_ref, cr.stride = ref_stride;
+      cd.pts = read, cd.n = n_read, cd.stride = read_stride;
+      hip_throw_on_error(aicp_hip_monitor(hip_shared_ctx(), &mp, &cfg_, &cr, &cd, T_, &monitor_, nullptr, nullptr));
+      std::cout << "Hausdorff distance: " << monitor_.hausdorff << " m" << std::endl;
+      std::cout << "Paired points mean distance: " << monitor_.paired_mean_dist << " m" << std::endl;
+    }
   }
 
   RegistrationParams params_;
   aicp_icp_config cfg_{};
   aicp_icp_stats stats_{};
+  aicp_monitor_result monitor_{};
   float T_[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   std::vector<float> read_xyz_;
 };
