@@ -26,6 +26,7 @@ AICP_RUN_ICP = 2
 AICP_RUN_TIME_NN = 4
 AICP_SEQ_DEBUG = 8  # aicp_sequence_params.flags: App's "debug" working_mode
 AICP_MON_PAIRED = 1  # aicp_monitor_params.flags: also the chain matcher's paired mean distance
+AICP_LOC_MERGE = 16  # aicp_localization_params.flags: merge_aligned_clouds_to_map
 
 EXPORTS = [
     "aicp_hip_create", "aicp_hip_destroy", "aicp_hip_last_error", "aicp_hip_version",
@@ -45,6 +46,8 @@ EXPORTS = [
     "aicp_hip_fov_overlap", "aicp_hip_cluster_match", "aicp_hip_alignment_features",
     "aicp_hip_default_risk_params", "aicp_hip_last_risk_stats", "aicp_hip_test_select",
     "aicp_hip_default_monitor_params", "aicp_hip_monitor", "aicp_hip_monitor_batch", "aicp_hip_last_monitor_stats",
+    "aicp_hip_default_localization_params", "aicp_hip_localization_window", "aicp_hip_map_sequence_run",
+    "aicp_hip_last_localization_timing",
 ]
 
 
@@ -55,7 +58,9 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_default_risk_params", "aicp_hip_last_risk_stats",  # the alignment-risk features
            "aicp_hip_test_select",
            "aicp_hip_default_monitor_params", "aicp_hip_monitor", "aicp_hip_monitor_batch",
-           "aicp_hip_last_monitor_stats"}  # the registration quality monitor
+           "aicp_hip_last_monitor_stats",  # the registration quality monitor
+           "aicp_hip_default_localization_params", "aicp_hip_localization_window", "aicp_hip_map_sequence_run",
+           "aicp_hip_last_localization_timing"}  # the localization stream
 
 
 class IcpConfig(C.Structure):
@@ -275,6 +280,48 @@ class SequenceTiming(C.Structure):
     ]
 
 
+class LocalizationParams(C.Structure):
+    """aicp_localization_params: App's localization stream on the prior map."""
+    _fields_ = [
+        ("reference_update_frequency", C.c_int32),
+        ("map_refilter_every", C.c_int32),
+        ("max_correction_magnitude", C.c_float),
+        ("crop_min", C.c_float),
+        ("crop_max", C.c_float),
+        ("flags", C.c_int32),
+    ]
+
+
+class LocalizationResult(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32),
+        ("accepted", C.c_int32),
+        ("merged", C.c_int32),
+        ("refiltered", C.c_int32),
+        ("map_points", C.c_uint64),
+        ("crop_points", C.c_uint64),
+        ("corrected_origin", C.c_double * 3),
+        ("icp", IcpStats),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k in ("status", "accepted", "merged", "refiltered", "map_points", "crop_points")}
+        d["corrected_origin"] = [float(x) for x in self.corrected_origin]
+        d["icp"] = self.icp.as_dict()
+        return d
+
+
+class LocalizationTiming(C.Structure):
+    _fields_ = [
+        ("windows", C.c_int32),
+        ("merges", C.c_int32),
+        ("refilters", C.c_int32),
+        ("pad", C.c_int32),
+        ("wall_ms", C.c_double),
+        ("device_ms", C.c_double),
+    ]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -387,6 +434,15 @@ def _load():
         L.aicp_hip_monitor.argtypes = [vp, mpp, cfgp, clp, clp, fp, mrp, fp, fp]
         L.aicp_hip_monitor_batch.argtypes = [vp, mpp, cfgp, pp, sz, fp, mrp]
         L.aicp_hip_last_monitor_stats.argtypes = [vp, C.POINTER(MonitorStats)]
+    if hasattr(L, "aicp_hip_map_sequence_run"):
+        lpp = C.POINTER(LocalizationParams)
+        L.aicp_hip_default_localization_params.argtypes = [lpp]
+        L.aicp_hip_default_localization_params.restype = None
+        L.aicp_hip_localization_window.argtypes = [C.c_uint64, lpp, sz]
+        L.aicp_hip_localization_window.restype = sz
+        L.aicp_hip_map_sequence_run.argtypes = [vp, cfgp, lpp, C.POINTER(PrefilterParams), vp, C.POINTER(Cloud), fp, sz,
+                                                fp, C.POINTER(LocalizationResult), szp]
+        L.aicp_hip_last_localization_timing.argtypes = [vp, C.POINTER(LocalizationTiming)]
     if hasattr(L, "aicp_hip_test_select"):
         u32p = C.POINTER(C.c_uint32)
         L.aicp_hip_test_select.argtypes = [vp, sz, u32p, fp, C.POINTER(C.c_uint8), sz, ip, fp, fp, ip, ip, u32p, u32p,
@@ -531,6 +587,28 @@ def default_sequence_params(**kw) -> SequenceParams:
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def default_localization_params(**kw) -> LocalizationParams:
+    """App's localization settings (aicp_hip_default_localization_params): a merge every 5 accepted
+    readings, a re-filter every 30, max_correction_magnitude 1.0, crop -15..15, merging on.
+    Keyword overrides; merge=/debug= set or clear AICP_LOC_MERGE / AICP_SEQ_DEBUG in flags."""
+    p = LocalizationParams()
+    lib.aicp_hip_default_localization_params(C.byref(p))
+    for k, v in kw.items():
+        if k in ("merge", "debug"):
+            bit = AICP_LOC_MERGE if k == "merge" else AICP_SEQ_DEBUG
+            p.flags = (p.flags | bit) if v else (p.flags & ~bit)
+        elif not hasattr(p, k):
+            raise AttributeError(f"aicp_localization_params has no field {k}")
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def localization_window(n_clouds: int, params: LocalizationParams, remaining: int) -> int:
+    """aicp_hip_localization_window (host only): the length of the next window of the stream."""
+    return int(lib.aicp_hip_localization_window(int(n_clouds), C.byref(params), int(remaining)))
 
 
 def make_cloud(pts, origin=(0, 0, 0)):
@@ -750,6 +828,13 @@ class Context:
         t = SequenceTiming()
         self.check(lib.aicp_hip_last_sequence_timing(self.h, C.byref(t)))
         return {k: getattr(t, k) for k, _ in SequenceTiming._fields_}
+
+    def last_localization_timing(self):
+        """aicp_hip_last_localization_timing: windows, merges, refilters, wall_ms, device_ms of the
+        last PriorMap.sequence_run."""
+        t = LocalizationTiming()
+        self.check(lib.aicp_hip_last_localization_timing(self.h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in LocalizationTiming._fields_ if k != "pad"}
 
     def last_nn_timing(self):
         n = C.c_int()

@@ -132,7 +132,7 @@ int check_cfg(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, int flags) {
 // nosync: the caller synchronises the stream before the pinned staging is written again (a one-shot
 // call does, at its end); otherwise this returns once the copies are done
 int upload_pairs(aicp_hip_ctx* ctx, const aicp_pair* pairs, size_t n, aicp_hip_batch* B, bool refs_on_device,
-                 bool skip_refs = false, bool skip_reads = false, bool nosync = false) {
+                 bool skip_refs, bool skip_reads, bool nosync) {
   if (!pairs || n == 0) FAIL(AICP_ERR_INVALID, "no pairs");
   B->P = n;
   B->desc.assign(n, PairDesc{});
@@ -1258,6 +1258,7 @@ void aicp_hip_destroy(aicp_hip_ctx* ctx) {
   if (ctx->poll_host) (void)hipHostFree(ctx->poll_host);
   delete ctx->pool;
   seq_state_free(ctx->seq);
+  loc_bufs_free(ctx->loc);
   for (PinBuf* b : {&ctx->pin_desc, &ctx->pin_state, &ctx->pin_out, &ctx->pin_io, &ctx->pin_ovl,
                     &ctx->pin_rdesc, &ctx->pin_gdesc, &ctx->pin_gstate, &ctx->pin_pf})
     release(*b);

@@ -297,6 +297,31 @@ void launch_ovl_size(hipStream_t s, int n, PairState* st, OvlDesc* od, const uin
 // zero the n maps of od[] (device-side sizes, each at most max_bytes)
 void launch_ovl_clear(hipStream_t s, int n, const OvlDesc* od, uint8_t* maps, uint64_t max_bytes);
 
+// ---- App's localization stream on the prior map (kernels_localization.hip, localization.cpp) ----
+struct LocState {       // the stream's state on the device
+  float initT[16];      // initialT_ (app.cpp:414), column-major
+  int32_t n_clouds;     // aligned_clouds_graph_->getNbClouds()
+  int32_t pad[3];
+};
+struct LocRules {       // aicp_localization_params as the commit kernel reads them
+  int32_t freq, refilter_every, merge;
+  float max_corr;
+};
+struct LocRec {         // one reading's decisions (the host reads a window's records once)
+  int32_t status;       // AICP_* of its registration; -1: after the reading that ended the stream
+  int32_t accepted, merged, refiltered;
+  double corrected_origin[3];
+};
+// debug working mode (app.cpp:87-96): pts := initialT_ * pts in place (k_transform's expression)
+// and origin := translation of initialT_ * prior pose (k_debug_prep's)
+void launch_loc_move(hipStream_t s, int n, const LocState* S, double* origin, float4* pts);
+// one thread walks the window's np readings in order (app.cpp:366-373, 414, 469-493): status,
+// drop test, count, corrected origin, initialT_ = correction * initialT_, merge / re-filter flags
+void launch_loc_commit(hipStream_t s, int np, const PairState* st, const float* T, const double* origin,
+                       LocRules r, LocState* S, LocRec* rec);
+// out = T * in (the map's tail: transformPointCloud(reading, correction), k_transform's expression)
+void launch_loc_merge(hipStream_t s, int n, const float* T, const float4* in, float4* out);
+
 // ---- pre-filter (kernels_prefilter.hip): regionGrowingUniformPlaneSegmentationFilter -------
 constexpr int kPfMaxNbrs = 16;  // RegionGrowing neighbours per point (edge mask bits)
 struct PfCtl {                  // device control block; lo = 0xFFFFFFFF, everything else 0 at start

@@ -1,0 +1,107 @@
+// kernels_localization.hip — the device side of App's localization stream on the prior map
+// (localization.cpp; localize_against_prior_map, app.cpp:41-58, 366-373, 414, 469-493).
+//
+// A window's readings are registered as one batch (run_batch). What follows stays on the device:
+// k_loc_commit walks the window in order and takes App's decisions (drop, count, corrected
+// origin, initialT_, merge, re-filter), and k_loc_merge appends an accepted reading, moved by the
+// device's own correction, to the map's tail from the batch's copy of it. In the debug working
+// mode k_loc_move moves the reading by the device-resident initialT_ before it is registered.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "aicp_common.hpp"
+#include "icp_math.hpp"
+#include "kernels.hpp"
+
+namespace aicp {
+
+// setAndFilterReading's debug branch (app.cpp:87-96): every point by initialT_ in
+// pcl::transformPointCloud's float order (apply4, as k_transform), in place; thread 0 of block 0
+// also makes the prior pose initialT_ * prior pose, of which only the translation is used
+// (fromMatrix4fToIsometry3d, common.cpp:4-23: corrected_origin's arithmetic, as k_debug_prep).
+__global__ __launch_bounds__(256) void k_loc_move(int n, const LocState* __restrict__ S, double* origin,
+                                                  float4* pts) {
+  float Tl[16];
+  for (int k = 0; k < 16; ++k) Tl[k] = S->initT[k];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    double o[3];
+    corrected_origin(Tl, origin, o);
+    for (int k = 0; k < 3; ++k) origin[k] = o[k];
+  }
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = pts[i];
+  float q[3];
+  apply4(Tl, p.x, p.y, p.z, q);
+  pts[i] = make_float4(q[0], q[1], q[2], 1.f);
+}
+
+// The window's readings in order, one thread (a window holds at most kMaxPairs readings and the
+// walk is a few hundred flops each). st / T: the batch's states and corrections after k_finalize.
+__global__ void k_loc_commit(int np, const PairState* __restrict__ st, const float* __restrict__ T,
+                             const double* __restrict__ origin, LocRules r, LocState* S, LocRec* rec) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  int n = S->n_clouds;
+  float I[16];
+  for (int k = 0; k < 16; ++k) I[k] = S->initT[k];
+  bool ended = false;
+  for (int i = 0; i < np; ++i) {
+    LocRec o;
+    o.status = -1;
+    o.accepted = o.merged = o.refiltered = 0;
+    for (int k = 0; k < 3; ++k) o.corrected_origin[k] = 0.0;
+    if (!ended) {
+      o.status = st[i].status;
+      if (o.status != 0) {
+        ended = true;  // the worker ends here (app.cpp:210): nothing after this reading happens
+      } else {
+        float C[16];
+        for (int k = 0; k < 16; ++k) C[k] = T[16 * (size_t)i + k];
+        // app.cpp:366-373: the first cloud of the graph is never dropped (getNbClouds() != 0)
+        if (!(n != 0 && correction_rejected(C, r.max_corr))) {
+          ++n;
+          o.accepted = 1;
+          corrected_origin(C, origin + 3 * (size_t)i, o.corrected_origin);
+          float N[16];
+          mul4(C, I, N);  // initialT_ = correction * initialT_ (app.cpp:414)
+          for (int k = 0; k < 16; ++k) I[k] = N[k];
+          if (r.merge) {
+            o.merged = (n - 1) % r.freq == 0;                                         // app.cpp:469-483
+            o.refiltered = r.refilter_every > 0 && (n - 1) % r.refilter_every == 0;  // app.cpp:485-493
+          }
+        }
+      }
+    }
+    rec[i] = o;
+  }
+  S->n_clouds = n;
+  for (int k = 0; k < 16; ++k) S->initT[k] = I[k];
+}
+
+// *merged_map = *prior_map + transformPointCloud(reading, correction) (app.cpp:469-483): the tail
+// of the map from the batch's device copy of the reading, T the device's own correction
+__global__ __launch_bounds__(256) void k_loc_merge(int n, const float* __restrict__ T, const float4* __restrict__ in,
+                                                   float4* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float Tl[16];
+  for (int k = 0; k < 16; ++k) Tl[k] = T[k];
+  const float4 p = in[i];
+  float q[3];
+  apply4(Tl, p.x, p.y, p.z, q);
+  out[i] = make_float4(q[0], q[1], q[2], 1.f);
+}
+
+void launch_loc_move(hipStream_t s, int n, const LocState* S, double* origin, float4* pts) {
+  k_loc_move<<<(unsigned)std::max(1, (n + 255) / 256), 256, 0, s>>>(n, S, origin, pts);
+}
+void launch_loc_commit(hipStream_t s, int np, const PairState* st, const float* T, const double* origin, LocRules r,
+                       LocState* S, LocRec* rec) {
+  if (np > 0) k_loc_commit<<<1, 64, 0, s>>>(np, st, T, origin, r, S, rec);
+}
+void launch_loc_merge(hipStream_t s, int n, const float* T, const float4* in, float4* out) {
+  if (n > 0) k_loc_merge<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, T, in, out);
+}
+
+}  // namespace aicp

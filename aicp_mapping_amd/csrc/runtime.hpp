@@ -255,6 +255,14 @@ struct ReadCache {
 
 struct SeqState;  // sequence.cpp
 void seq_state_free(SeqState* s);
+struct LocBufs;  // localization.cpp
+void loc_bufs_free(LocBufs* s);
+
+// the batch pipeline (aicp_hip.cpp), for the entry points that compose a batch on the device
+int upload_pairs(aicp_hip_ctx* ctx, const aicp_pair* pairs, size_t n, aicp_hip_batch* B, bool refs_on_device,
+                 bool skip_refs = false, bool skip_reads = false, bool nosync = false);
+int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, double res, int flags, float* outT,
+              aicp_icp_stats* stats, float* out_overlap);
 
 }  // namespace rt
 }  // namespace aicp
@@ -300,6 +308,7 @@ struct aicp_hip_ctx {
   aicp_hip_batch* oneshot = nullptr;  // buffers of aicp_hip_align_batch, kept across calls
   hipEvent_t pf_ev[8] = {};
   aicp::rt::SeqState* seq = nullptr;  // aicp_hip_sequence_run's buffers (sequence.cpp), kept across calls
+  aicp::rt::LocBufs* loc = nullptr;    // aicp_hip_map_sequence_run's buffers (localization.cpp), kept across calls
   aicp_hip_batch* mapbatch = nullptr;  // aicp_hip_map_register_batch's batch buffers
   aicp::rt::DevBuf crop_ws;            // its crop work space
   aicp::rt::DevBuf ovl_sp, ovl_keys;   // sparse overlap: clouds, counts, offsets / key words

@@ -81,6 +81,40 @@ class PriorMap:
             self.ctx.check(rc)
         return outT.reshape(-1, 4, 4).transpose(0, 2, 1).copy(), [x.as_dict() for x in st], rc
 
+    def sequence_run(self, readings, poses, cfg=None, params=None, prefilter=None, raise_on_error=True):
+        """App's localization stream on this map (aicp_hip_map_sequence_run, app.cpp:282-414 with
+        app.cpp:41-58, 469-493): reading i is registered against the map cropped around poses[i]
+        (4x4 row-major prior pose; its translation is the reading's origin), dropped on a large
+        correction, merged into the map every reference_update_frequency-th accepted reading, and
+        the map re-filtered every map_refilter_every-th; the map is updated in place. params:
+        LocalizationParams (default_localization_params); prefilter: the re-filter's
+        PrefilterParams (None: the defaults). Returns (T[n, 4, 4] row-major corrections, list of
+        result dicts of the readings processed, n_done, rc); a registration error ends the stream
+        at reading n_done - 1 and raises unless raise_on_error is False."""
+        cfg = cfg or L.default_config()
+        prm = params or L.default_localization_params()
+        n = len(readings)
+        arr = (L.Cloud * max(n, 1))()
+        keep = []
+        for i, r in enumerate(readings):
+            P = np.asarray(poses[i], np.float64).reshape(4, 4)
+            c, k = L.make_cloud(r, P[:3, 3])
+            arr[i] = c
+            keep.append(k)
+        pz = np.zeros((max(n, 1), 16), np.float32)
+        for i in range(n):
+            pz[i] = np.asarray(poses[i], np.float32).reshape(4, 4).T.reshape(16)
+        outT = np.zeros((max(n, 1), 16), np.float32)
+        res = (L.LocalizationResult * max(n, 1))()
+        done = C.c_size_t(0)
+        rc = L.lib.aicp_hip_map_sequence_run(self.ctx.h, C.byref(cfg), C.byref(prm),
+                                             C.byref(prefilter) if prefilter is not None else None, self.h, arr,
+                                             L._fptr(pz), n, L._fptr(outT), res, C.byref(done))
+        if raise_on_error and rc != L.AICP_OK:
+            self.ctx.check(rc)
+        T = outT[:n].reshape(-1, 4, 4).transpose(0, 2, 1).copy()
+        return T, [res[i].as_dict() for i in range(done.value)], done.value, rc
+
     def merge(self, points, correction) -> None:
         """*map = *map + transformPointCloud(points, correction); correction a 4x4 (row-major)."""
         pts = L.as_points(points)

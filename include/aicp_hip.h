@@ -460,6 +460,78 @@ int aicp_hip_map_merge(aicp_hip_ctx* ctx, aicp_hip_map* map, const float* pts, s
 /* map = regionGrowingUniformPlaneSegmentationFilter(map) (aicp_hip_prefilter on device data) */
 int aicp_hip_map_prefilter(aicp_hip_ctx* ctx, aicp_hip_map* map, const aicp_prefilter_params* prm);
 
+/* App's localization stream on the map (localize_against_prior_map: aicp_localization_only.launch,
+ * processCloud app.cpp:282-414 with the aligned-cloud graph empty at the start, so the "first
+ * cloud" branch app.cpp:286-289 is skipped). State: the map, n_clouds = 0
+ * (aligned_clouds_graph_->getNbClouds()), initialT_ = I. For reading i with prior pose P_i:
+ *   1. reference = getPointsInOrientedBox(map, crop_min, crop_max, P_i) (app.cpp:41-58), from the
+ *      prior pose as given (setReference runs before setAndFilterReading, app.cpp:333, 337);
+ *   2. AICP_SEQ_DEBUG only: reading = transformPointCloud(reading, initialT_) (float) and the prior
+ *      pose becomes initialT_ * prior pose (app.cpp:87-96); clouds come in pre-filtered, with
+ *      aicp_hip_sequence_run's caveat about the filter order;
+ *   3. ICP at the ratio aicp_hip_autotune_ratio(50) (the overlap is bypassed at 50 %,
+ *      app.cpp:123-127). An empty crop is AICP_ERR_INVALID for that reading. A non-zero status ends
+ *      the stream at that reading (app.cpp:210); everything before it stays committed;
+ *   4. the reading is dropped when n_clouds != 0 and some |T(k,3)| > max_correction_magnitude
+ *      (app.cpp:366-373, float compare); a dropped reading changes nothing;
+ *   5. accepted: ++n_clouds, corrected_origin = translation(correction * prior pose) as
+ *      aicp_hip_sequence_run computes it, initialT_ = correction * initialT_ (app.cpp:414);
+ *   6. with AICP_LOC_MERGE and (n_clouds - 1) % reference_update_frequency == 0:
+ *      map += transformPointCloud(reading, correction) (app.cpp:375, 469-483; the moved reading in
+ *      debug mode), so the first accepted reading merges;
+ *   7. with AICP_LOC_MERGE and (n_clouds - 1) % map_refilter_every == 0:
+ *      map = regionGrowingUniformPlaneSegmentationFilter(map), after that reading's merge
+ *      (app.cpp:485-493, where the period is 30).
+ * Readings between two map changes are independent and run as one batch (a window, see
+ * aicp_hip_localization_window); the decisions 4-7 are taken on the device, the merged reading is
+ * appended from the batch's device copy by the device's own correction, and the host reads one
+ * record per reading once per window. */
+#define AICP_LOC_MERGE 16       /* aicp_localization_params.flags: merge_aligned_clouds_to_map */
+typedef struct {
+  int32_t reference_update_frequency; /* 5 (aicp_localization_only.launch) */
+  int32_t map_refilter_every;         /* 30 (app.cpp:485); 0: never */
+  float max_correction_magnitude;     /* 1.0 */
+  float crop_min, crop_max;           /* -15, 15: the crop cube around the prior pose */
+  int32_t flags;                      /* AICP_LOC_MERGE | AICP_SEQ_DEBUG | AICP_RUN_TIME_NN */
+} aicp_localization_params;
+/* 128 bytes, no implicit padding */
+typedef struct {
+  int32_t status;          /* AICP_* of this reading's registration */
+  int32_t accepted;        /* 0: dropped */
+  int32_t merged;          /* 1: appended to the map */
+  int32_t refiltered;      /* 1: the map was pre-filtered after this reading */
+  uint64_t map_points;     /* size of the map it was cropped from */
+  uint64_t crop_points;    /* size of its reference */
+  double corrected_origin[3]; /* as aicp_sequence_result (accepted readings) */
+  aicp_icp_stats icp;
+} aicp_localization_result;
+typedef struct {
+  int32_t windows;         /* batches run */
+  int32_t merges, refilters;
+  int32_t pad;
+  double wall_ms;          /* the whole call */
+  double device_ms;        /* first crop enqueued -> last map change done (HIP events) */
+} aicp_localization_timing;
+void aicp_hip_default_localization_params(aicp_localization_params* out);
+/* Host-only: the length of the next window when n_clouds readings have been accepted and
+ * `remaining` are left: debug mode 1; else min(remaining, 4096, k) with k the smallest k >= 1 such
+ * that (n_clouds + k - 1) % reference_update_frequency == 0 or (n_clouds + k - 1) %
+ * map_refilter_every == 0 (each only with AICP_LOC_MERGE, the second only when the period is not 0;
+ * without AICP_LOC_MERGE k is unbounded). If every reading of the window is accepted the map
+ * changes exactly after its last one; if some are dropped it does not change and the next window is
+ * shorter; nothing is ever run twice. 0 for invalid parameters or remaining = 0. */
+size_t aicp_hip_localization_window(uint64_t n_clouds, const aicp_localization_params* prm, size_t remaining);
+/* readings: aicp_cloud[n] (origin = the prior pose's translation); poses: 16*n floats, column-major,
+ * as aicp_hip_map_register_batch; pf: the re-filter's parameters (nullable: the defaults). The map
+ * is updated in place (a failed growth leaves it as it was). out_T / out / n_done as
+ * aicp_hip_sequence_run: *n_done = readings processed, the return value the status that ended the
+ * stream (at reading *n_done - 1) or AICP_OK. */
+int aicp_hip_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* prm,
+                              const aicp_prefilter_params* pf, aicp_hip_map* map, const aicp_cloud* readings,
+                              const float* poses /* 16*n */, size_t n, float* out_T /* 16*n */,
+                              aicp_localization_result* out /* n */, size_t* n_done);
+int aicp_hip_last_localization_timing(const aicp_hip_ctx* ctx, aicp_localization_timing* out);
+
 /* ---- device-resident batches (inputs uploaded once, run many times) ----------------------- */
 int aicp_hip_batch_upload(aicp_hip_ctx* ctx, const aicp_pair* pairs, size_t n_pairs,
                           aicp_hip_batch** out);
