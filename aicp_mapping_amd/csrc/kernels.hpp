@@ -23,8 +23,6 @@ size_t read_order_temp_bytes(size_t n, int n_pairs);
 hipError_t launch_read_order(hipStream_t s, BlockMap m, int n_pairs, const PairDesc* pd, const float4* raw,
                              uint32_t total, uint64_t* keys0, uint64_t* keys1, uint32_t* vals0, uint32_t* vals1,
                              void* temp, size_t temp_bytes, float4* out);
-void launch_gather_ref(hipStream_t s, BlockMap m, const PairDesc* pd, const float4* ref_raw,
-                       const int32_t* perm, float4* bpts);
 void launch_init_state(hipStream_t s, int n_pairs, const PairDesc* pd, PairState* st);
 // SurfaceNormal of the reference points (bucket order); ids: scratch of total_ref * knn;
 // ctr: kPersistCtrWords work counters (zeroed on s when the persistent engine runs). engine:
@@ -45,7 +43,7 @@ bool launch_knn_ids(hipStream_t s, int n_pairs, uint32_t total_ref, const PairDe
 void launch_active_list(hipStream_t s, int n_pairs, const PairDesc* pd, const PairState* st,
                         ActiveList* al, uint32_t* ctr, uint32_t* host_n = nullptr, uint64_t* done_sig = nullptr,
                         const uint64_t* ticket = nullptr, float* outT = nullptr, int src_pair = -1);
-// Fused ICP iteration (AICP_ICP_FUSE=0 restores one launch per step): the last workgroup of a
+// Fused ICP iteration: the last workgroup of a
 // pair to finish the histogram / compaction / reduction runs that pair's find1 / final select /
 // update, and the last pair of the group rebuilds the active list for the next iteration (and,
 // when none is left, publishes the corrections and the sequence ticket). Four launches per
@@ -102,11 +100,6 @@ void launch_icp_nn(hipStream_t s, int grid_items, const PairDesc* pd, const Pair
 // m covers pairs p0 .. p0 + n_pairs - 1 (absolute pair indices into pd / st / hist1 / cand_cnt).
 void launch_icp_select(hipStream_t s, BlockMap m, int n_pairs, const PairDesc* pd, PairState* st,
                        const float* d2, uint32_t* hist1, uint32_t* cand, uint32_t* cand_cnt, int p0 = 0);
-void launch_icp_reduce(hipStream_t s, BlockMap m, const PairDesc* pd, const PairState* st,
-                       const float4* read_c, const int32_t* match, const float* d2,
-                       const uint32_t* touched, const float4* bpts, const float4* bnrm, double* slab);
-void launch_icp_update(hipStream_t s, int n_pairs, const PairDesc* pd, PairState* st,
-                       const double* slab, const IcpParams& prm);
 void launch_finalize(hipStream_t s, int n_pairs, const PairDesc* pd, PairState* st,
                      float* outT);
 
@@ -212,11 +205,9 @@ void launch_pairs_degenerate_part(hipStream_t s, int n_pairs, const PairDesc* pd
 void launch_ovl_init(hipStream_t s, int n, const PairDesc* pd, PairState* st, double res, int sides);
 void launch_ovl_bbox(hipStream_t s, BlockMap m, const PairDesc* pd, PairState* st,
                      const float4* pts, int side, double res);
-// od[i]: the map of entry i (group or pair) of the side being marked; max_blocks > 0: at most
-// that many workgroups, each marking every max_blocks-th block of the map
+// od[i]: the map of entry i (group or pair) of the side being marked; one workgroup per block of m
 void launch_ovl_mark(hipStream_t s, BlockMap m, const PairDesc* pd, const OvlDesc* od, PairState* st,
-                     const float4* pts, int side, double res, uint8_t* maps, bool filter,
-                     unsigned max_blocks = 0);
+                     const float4* pts, int side, double res, uint8_t* maps, bool filter);
 // |A| per group (gst.ovl_counts[0]), |B| and |A∩B| per pair (st.ovl_counts[1], [2])
 void launch_ovl_count(hipStream_t s, int n_pairs, int n_groups, const PairDesc* pd, const OvlDesc* od_read,
                       const OvlDesc* od_ref, PairState* st, PairState* gst, const uint8_t* maps);

@@ -12,7 +12,7 @@
 //   k_icp_reduce   TrimmedDist weights + getMatchedPoints gather + point-to-plane F, dot and the
 //                  27-entry normal-equation sums in double from exact float products; DPP row
 //                  sums + LDS, one deterministic partial row per workgroup (no atomics)
-//   k_icp_update   fixed-order sum of the partial rows, 6x6 solve, AngleAxis update of T_iter,
+//   k_icp_update_f fixed-order sum of the partial rows, 6x6 solve, AngleAxis update of T_iter,
 //                  Counter + Differential checkers, per-pair active flag
 // SurfaceNormal: k_knn_ids (persistent kNN, eps 0, ids only) + k_normals_from_ids (uniform
 // covariance / eigen work per point).
@@ -57,15 +57,11 @@ __device__ __forceinline__ void best_init(Best<K>& b) {
   }
 }
 
-#ifndef AICP_BEST_NOCHAIN
-#define AICP_BEST_NOCHAIN 1
-#endif
 template <int K>
 __device__ __forceinline__ void best_replace(Best<K>& b, int32_t id, float val) {
-#if AICP_BEST_NOCHAIN
-  // the same insertion without the serial `placed` chain: with c(i) = v[i-1] > val (the list is
+  // sorted insertion without a serial `placed` chain: with c(i) = v[i-1] > val (the list is
   // ascending, so c(i) implies c(i+1)), slot i takes v[i-1] when c(i), val when c(i+1) alone and
-  // keeps v[i] otherwise -- equal values stay ahead of the new one, as in the loop below. Each
+  // keeps v[i] otherwise -- equal values stay ahead of the new one (libnabo's replaceHead). Each
   // compare reads a slot not yet written (slots go downwards).
   bool cn = true;  // c(i+1); the last slot takes val unless shifted into
 #pragma unroll
@@ -78,26 +74,6 @@ __device__ __forceinline__ void best_replace(Best<K>& b, int32_t id, float val) 
     cn = ci;
   }
   if (cn) {
-    b.v[0] = val;
-    b.id[0] = id;
-  }
-  return;
-#endif
-  bool placed = false;
-#pragma unroll
-  for (int i = K - 1; i > 0; --i) {
-    if (!placed) {
-      if (b.v[i - 1] > val) {
-        b.v[i] = b.v[i - 1];
-        b.id[i] = b.id[i - 1];
-      } else {
-        b.v[i] = val;
-        b.id[i] = id;
-        placed = true;
-      }
-    }
-  }
-  if (!placed) {
     b.v[0] = val;
     b.id[0] = id;
   }
@@ -140,36 +116,10 @@ struct NnLdsFrame {
 struct NnFarStack {
   NnLdsFrame f[kFarStack];
 };
-__device__ __forceinline__ void put_far(NnFarStack& fs, int32_t sp, const NnLdsFrame& g, const FarFrame&) {
-  fs.f[sp] = g;
-}
-__device__ __forceinline__ void put_far(FarStack& fs, int32_t sp, const NnLdsFrame&, const FarFrame& f) {
-  fs.f[sp] = f;
-}
 
 constexpr int kLeafBatch = 8;  // = libnabo's default bucket size
-#ifndef AICP_NN_COOP
-#define AICP_NN_COOP 0  // Trav2C: 1 = cooperative octet bucket scan, 0 = each lane scans its own bucket
-#endif
-#ifndef AICP_NN_PREFMIN
-#define AICP_NN_PREFMIN 0  // Trav2C: per-depth running minimum of the far bounds in LDS (climb pruning; off: C2 -1 %, C4 +20 %)
-#endif
-[[maybe_unused]] constexpr int kPmDepth = 24;  // depths whose running minimum is kept (deeper levels climb unpruned)
-#ifndef AICP_NN_POPCHK
-#define AICP_NN_POPCHK 1  // Trav2C (CLIMB2): after a frame pop, skip the rest of the climb when no level above the frame's node can pass (per-depth prefix minima, one byte each, in LDS)
-#endif
-[[maybe_unused]] constexpr int kPopDepth = 16;  // depths whose prefix minimum is kept (frames deeper than this climb unchecked)
-[[maybe_unused]] constexpr int kStartBits = 26;  // LDS frames keep P's depth above the start node id
-#ifndef AICP_NN_CLIMB2
-#define AICP_NN_CLIMB2 1  // Trav2C: climb one treelet (record + parent, up to two levels) per iteration
-#endif
-#ifndef AICP_NN_CLIMB4
-#define AICP_NN_CLIMB4 0  // Trav2C (with CLIMB2): two treelets per climb round trip through the treelet links (measured 6 % slower: the extra records are mostly not needed)
-#endif
-#if AICP_NN_POPCHK && (!AICP_NN_CLIMB2 || AICP_NN_CLIMB4 || AICP_NN_PREFMIN)
-#undef AICP_NN_POPCHK
-#define AICP_NN_POPCHK 0  // the pop check belongs to the one-treelet climb
-#endif
+constexpr int kPopDepth = 16;  // Trav2C: depths whose prefix minimum is kept (frames deeper than this climb unchecked)
+constexpr int kStartBits = 26;  // Trav2C: LDS frames keep P's depth above the start node id
 #ifndef AICP_NN_LDS_FRAMES
 #define AICP_NN_LDS_FRAMES 3  // Trav2C: innermost far-descent frames kept in LDS (20 B each per lane; 4 measured no faster)
 #endif
@@ -320,12 +270,8 @@ struct Trav {
 // redundant copies (about 5 B per node against 32 B for two-level node records), so the trees
 // of the references an XCD serves stay in its L2.
 //
-// The bucket scan is done by the wave cooperatively: lanes 8g..8g+7 (an "octet") read the 8
-// points of one owner's bucket together -- one 128-byte run -- and compute their distances to
-// the owner's query; a min over the octet (DPP) and the lowest lane holding it (ballot) give
-// the owner the result of libnabo's in-order scan (first strictly smaller d^2 wins). Eight
-// rounds serve the octet's eight owners. The split into descend() / (wave-wide bucket) /
-// climb() keeps libnabo recurseKnn's visit order, far tests and counts.
+// Each lane scans its own bucket. The split into descend() / bucket_lane() / climb() keeps
+// libnabo recurseKnn's visit order, far tests and counts.
 // one 16-byte treelet record as a single dwordx4: the empty asm keeps the compiler from narrowing
 // the load into the words used first plus a dependent load of the rest
 __device__ __forceinline__ uint4 ld_rec(const uint4* p) {
@@ -352,8 +298,8 @@ __device__ __forceinline__ float min_bound(float a, float b) {
   return __int_as_float(min(__float_as_int(a), __float_as_int(b)));
 }
 
-// One-byte lower bound of a non-negative float (the prefix minima of AICP_NN_POPCHK): code 0 is
-// 0.0, code c >= 1 is the float with bits kPmBase + ((c - 1) << 21) (two mantissa bits), and a
+// One-byte lower bound of a non-negative float (the prefix minima of the climb's pop check): code
+// 0 is 0.0, code c >= 1 is the float with bits kPmBase + ((c - 1) << 21) (two mantissa bits), and a
 // value always encodes to a code that decodes to <= itself (truncation, clamping at 255 only
 // lowers it), so a failed far test on the decoded bound implies a failed test on the true one.
 constexpr uint32_t kPmBase = 0x30000000u;  // 2^-31
@@ -366,20 +312,14 @@ __device__ __forceinline__ float pm_dec(uint32_t c) {
   return c == 0 ? 0.f : __uint_as_float(kPmBase + ((c - 1u) << 21));
 }
 
-#if AICP_NN_POPCHK
 // the NN kernel's one-byte prefix minima, depth-major: lane t of the block at [d * kNNBlock + t]
 // (module scope, addressed from threadIdx.x at each use: the fetch, the descent and the climb
 // all reach it, from the first round on)
 __shared__ uint8_t g_pmb[kPopDepth * kNNBlock];
 __device__ __forceinline__ uint8_t& pmb_at(int d) { return g_pmb[d * kNNBlock + threadIdx.x]; }
-#endif
 
 struct Trav2C {
-#if AICP_NN_CLIMB2 && !AICP_NN_CLIMB4
   using Stack = NnFarStack;
-#else
-  using Stack = FarStack;
-#endif
   const uint4* tlb;      // the batch's treelets (uniform: set per chunk)
   const uint2* ptlb;     // the batch's treelet links {parent of the root, parent of the parent treelet's root}
   uint32_t tlo;          // the pair's first treelet: one VGPR instead of two 64-bit pointers
@@ -388,7 +328,6 @@ struct Trav2C {
   float noc0, noc1, noc2, rd, minFar;  // noc = -(off * off) per axis (libnabo's off[] enters only so)
   int32_t n, start, sp, pl;  // node ids; pl: parent of the node the last descent ended in
   int32_t dep;               // depth of n (descent) / of the node climbed from (climb)
-  uint16_t* pm;              // this lane's prefix-minimum column in LDS (AICP_NN_PREFMIN)
   uint32_t lb0, lcnt;        // bucket of the leaf the last descent ended in
   NnLdsFrame* lf;            // this lane's LDS frames (AICP_NN_LDS_FRAMES, stride kNNBlock)
   uint32_t tp, tn;
@@ -429,22 +368,15 @@ struct Trav2C {
     return s == 0 ? r.x : (s == 1 ? r.y : r.z);
   }
 
-  // one inner slot: fold its far bound into minFar, return true if the query goes right. With
-  // AICP_NN_PREFMIN the running minimum after this level is kept per depth in LDS, rounded down
-  // to bf16 (the upper half of the float bits, exact for the skip test's direction): the climb
-  // then knows, before loading an ancestor, whether it or any level above it in this descent
-  // can still pass the far test.
+  // one inner slot: fold its far bound into minFar, return true if the query goes right. The
+  // running minimum after this level is kept per depth in LDS as a one-byte lower bound
+  // (pm_enc), for the climb's pop check.
   __device__ __forceinline__ bool decide(uint32_t w, uint32_t cd) {
     const float no = sel3(cd, q0, q1, q2) - __uint_as_float(w);
     minFar = min_bound(minFar, rd + (sel3(cd, noc0, noc1, noc2) + no * no));
     ++tn;
-#if AICP_NN_PREFMIN
-    if (dep < kPmDepth) pm[dep * kNNBlock] = (uint16_t)(__float_as_uint(minFar) >> 16);
-    ++dep;
-#elif AICP_NN_POPCHK
     if (dep < kPopDepth) pmb_at(dep) = (uint8_t)pm_enc(minFar);
     ++dep;
-#endif
     return no > 0.f;
   }
 
@@ -480,7 +412,7 @@ struct Trav2C {
     lcnt = w >> 28;
   }
 
-  // the whole bucket by this lane (AICP_NN_COOP 0): the first kLeafBatch points loaded before
+  // the whole bucket by this lane: the first kLeafBatch points loaded before
   // any is used, then scanned in order
   __device__ __forceinline__ void bucket_lane(const float4* __restrict__ pts, float maxR2) {
     float3 P[kLeafBatch];
@@ -517,12 +449,11 @@ struct Trav2C {
     tp += lcnt;
   }
 
-#if AICP_NN_CLIMB2
   // far test of node p (slot s of record r, parent pp); on a pass: push the frame, start the far
   // descent and return true
-  // dp: depth of p (AICP_NN_POPCHK: kept in the frame, the far descent starts at dp + 1)
+  // dp: depth of p (kept in the frame for the pop check, the far descent starts at dp + 1)
   __device__ __forceinline__ bool far_push(Stack& fs, const uint4& r, int32_t p, uint32_t s, int32_t pp,
-                                           float maxE2, float maxR2, int32_t dp = 0) {
+                                           float maxE2, float maxR2, int32_t dp) {
     const uint32_t T = (uint32_t)p >> 2;
     const uint32_t w = slot_word(r, s), cd = (r.w >> (2 * s)) & 3u;
     const float no = sel3(cd, q0, q1, q2) - __uint_as_float(w);
@@ -533,15 +464,11 @@ struct Trav2C {
     const int32_t far = s == 0 ? (int32_t)(T << 2 | (1u + fr)) : (int32_t)(((r.w >> 6) + 2 * (s - 1) + fr) << 2);
     // the innermost frames live in LDS (no scratch traffic: scratch frames are written back
     // to HBM through L2), deeper nesting in the scratch stack
-#if AICP_NN_POPCHK
     const int32_t sdp = start | (dp << kStartBits);  // node ids < 2^kStartBits (host-checked)
-#else
-    const int32_t sdp = start;
-#endif
     const NnLdsFrame frame{(int32_t)(((uint32_t)pp & 0x3fffffffu) | (cd << 30)), rd, oc, sdp,
                            __int_as_float(max(__float_as_int(minFar), 0) | (p == start ? (int32_t)0x80000000 : 0))};
     if (sp < AICP_NN_LDS_FRAMES) lf[sp * kNNBlock] = frame;
-    else put_far(fs, sp, frame, FarFrame{(int32_t)((uint32_t)far | (cd << 30)), rd, oc, minFar, start, p, pp, dp});
+    else fs.f[sp] = frame;
     ++sp;
     const float nn = -no * no;
     if (cd == 0) noc0 = nn;
@@ -551,93 +478,13 @@ struct Trav2C {
     n = far;
     start = far;
     pl = p;
-#if AICP_NN_POPCHK
     dep = dp + 1;
-#endif
     return true;
   }
 
-#if AICP_NN_CLIMB4
-  // far tests of node p (slot s of record r) and, for a child slot, of the treelet root above
-  // it: true on a far push; else c / pc advance to the highest node tested / its parent (stopping
-  // at start)
-  __device__ __forceinline__ bool climb_treelet(FarStack& fs, const uint4& r, int32_t p, int32_t rootpp, int32_t& c,
-                                                int32_t& pc, float maxE2, float maxR2) {
-    const uint32_t T = (uint32_t)p >> 2, s = (uint32_t)p & 3u;
-    const int32_t root = (int32_t)(T << 2);
-    if (far_push(fs, r, p, s, s != 0 ? root : rootpp, maxE2, maxR2)) return true;
-    c = p;
-    pc = s != 0 ? root : rootpp;
-    if (s == 0 || c == start) return false;
-    if (far_push(fs, r, root, 0, rootpp, maxE2, maxR2)) return true;
-    c = root;
-    pc = rootpp;
-    return false;
-  }
-
-  // the climb two treelets (up to four levels) per round trip: the links {parent of the
-  // treelet's root, parent of the parent treelet's root} name the next two treelets before
-  // their records arrive. After a descent or a frame pop the first step knows only the node to
-  // test, so it loads one record and its link.
-  __device__ __forceinline__ bool climb(FarStack& fs, float maxE2, float maxR2) {
-    int32_t c = n, pc = pl;
-    int32_t px = 0;
-    bool have_px = false;  // px: parent node of pc's treelet's root
-    if (!(minFar <= maxR2 && minFar * maxE2 < best.v[0])) c = start;
-    for (;;) {
-      if (c == start) {
-        if (sp == 0) return true;
-        --sp;
-        FarFrame f;
-        if (sp < AICP_NN_LDS_FRAMES) {
-          const NnLdsFrame g = lf[sp * kNNBlock];
-          const int32_t mi = __float_as_int(g.mnf);
-          f = FarFrame{g.PPcd, g.rd, g.old, __int_as_float(mi & 0x7fffffff), g.start, mi < 0 ? g.start : -2,
-                       g.PPcd & 0x3fffffff, 0};
-        } else {
-          f = fs.f[sp];
-        }
-        const uint32_t pcd = (uint32_t)f.F >> 30;
-        rd = f.rd;
-        if (pcd == 0) noc0 = f.old;
-        else if (pcd == 1) noc1 = f.old;
-        else noc2 = f.old;
-        minFar = f.mn;
-        start = f.start;
-        c = f.P;
-        pc = f.PP;
-        have_px = false;
-        if (!(minFar <= maxR2 && minFar * maxE2 < best.v[0])) c = start;
-        continue;
-      }
-      const uint32_t X = (uint32_t)pc >> 2;
-      if (!have_px) {
-        uint2 lk = *tlink(X);
-        uint4 r = *trec(X);
-        asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w), "+v"(lk.x), "+v"(lk.y));
-        if (climb_treelet(fs, r, pc, (int32_t)lk.x, c, pc, maxE2, maxR2)) return false;
-        px = (int32_t)lk.y;
-        have_px = c != start;
-        continue;
-      }
-      // pc in treelet X, px = parent of X's root in treelet Y (px < 0: X is the root treelet)
-      // three independent loads, one wait
-      const uint32_t Y = (uint32_t)max(px, 0) >> 2;
-      uint2 ly = *tlink(Y);
-      uint4 rx = *trec(X);
-      uint4 ry = *trec(Y);
-      asm volatile("" : "+v"(rx.x), "+v"(rx.y), "+v"(rx.z), "+v"(rx.w), "+v"(ry.x), "+v"(ry.y), "+v"(ry.z),
-                   "+v"(ry.w), "+v"(ly.x), "+v"(ly.y));
-      if (climb_treelet(fs, rx, pc, px, c, pc, maxE2, maxR2)) return false;
-      if (c == start || px < 0) continue;  // px < 0: X's root is the tree root, so c == start there
-      if (climb_treelet(fs, ry, px, (int32_t)ly.x, c, pc, maxE2, maxR2)) return false;
-      px = (int32_t)ly.y;
-    }
-  }
-#else
   // the climb one treelet per iteration: one record (and its root's parent) per round trip, the
   // node and, for a child slot, the treelet root above it.
-  // With AICP_NN_POPCHK, dep tracks the depth of c: after a frame pop, the prefix minimum of the
+  // The pop check: dep tracks the depth of c, and after a frame pop the prefix minimum of the
   // far bounds from the frame's start down to P's parent (written by that descent and untouched
   // by the deeper far descents since) decides at once whether any level left to climb can pass.
   // The far tests it skips are ones the climb would have made and failed, so the visit order,
@@ -657,14 +504,9 @@ struct Trav2C {
           if (sp < AICP_NN_LDS_FRAMES) g = lf[sp * kNNBlock];
           else g = fs.f[sp];
           const int32_t mi = __float_as_int(g.mnf);
-#if AICP_NN_POPCHK
           const int32_t gs = g.start & ((1 << kStartBits) - 1);
           f = FarFrame{g.PPcd, g.rd, g.old, __int_as_float(mi & 0x7fffffff), gs, mi < 0 ? gs : -2,
                        g.PPcd & 0x3fffffff, (int32_t)((uint32_t)g.start >> kStartBits)};
-#else
-          f = FarFrame{g.PPcd, g.rd, g.old, __int_as_float(mi & 0x7fffffff), g.start, mi < 0 ? g.start : -2,
-                       g.PPcd & 0x3fffffff, 0};
-#endif
         }
         const uint32_t pcd = (uint32_t)f.F >> 30;
         rd = f.rd;
@@ -676,13 +518,11 @@ struct Trav2C {
         c = f.P;
         pc = f.PP;
         if (!(minFar <= maxR2 && minFar * maxE2 < best.v[0])) c = start;
-#if AICP_NN_POPCHK
         dep = f.pad;  // depth of P
         if (c != start && dep <= kPopDepth) {
           const float b = pm_dec(pmb_at(dep - 1));
           if (!(b <= maxR2 && b * maxE2 < best.v[0])) c = start;
         }
-#endif
         continue;
       }
       const int32_t p = pc;
@@ -693,89 +533,27 @@ struct Trav2C {
       if (far_push(fs, r, p, s, s != 0 ? root : rootpp, maxE2, maxR2, dep - 1)) return false;
       c = p;
       pc = s != 0 ? root : rootpp;
-#if AICP_NN_POPCHK
       --dep;
-#endif
       if (s == 0 || c == start) continue;
       if (far_push(fs, r, root, 0, rootpp, maxE2, maxR2, dep - 1)) return false;
       c = root;
       pc = rootpp;
-#if AICP_NN_POPCHK
       --dep;
-#endif
     }
   }
-#endif  // AICP_NN_CLIMB4
-#else
-#error "AICP_NN_CLIMB2=0: the one-node-per-step climb was removed in r05 (it no longer built)"
-#endif
 };
 
+// engines whose round persistent_xcd runs as separate descend() / bucket_lane() / climb()
+// phases (Trav2C, over treelets); the others do a whole round in advance() (Trav<K>, over node
+// records)
 template <class E>
-struct is_coop {
+struct has_phases {
   static constexpr bool value = false;
 };
 template <>
-struct is_coop<Trav2C> {
+struct has_phases<Trav2C> {
   static constexpr bool value = true;
 };
-
-// DPP row controls (gfx9): quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror
-constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141;
-
-__device__ __forceinline__ float octet_min(float v) {
-  v = fminf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), kDppXor1, 0xF, 0xF, false)));
-  v = fminf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), kDppXor2, 0xF, 0xF, false)));
-  v = fminf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), kDppHalfMirror, 0xF, 0xF, false)));
-  return v;
-}
-
-// Wave-wide cooperative scan of the first kLeafBatch points of every active lane's bucket
-// (Trav2C). Called by all 64 lanes in wave-uniform control flow; `act` = the lane has a
-// bucket this round. xch = this wave's 64 exchange slots in LDS.
-template <class Eng>
-__device__ __forceinline__ void coop_bucket(Eng& t, bool act, const float4* __restrict__ pts, float maxR2,
-                                            float4* xch) {
-  const int lane = threadIdx.x & 63;
-  const int oct = lane & ~7, i = lane & 7;
-  const uint32_t cnt = act ? min(t.lcnt, (uint32_t)kLeafBatch) : 0u;
-  xch[lane] = make_float4(t.q0, t.q1, t.q2, __uint_as_float(((t.pbase + t.lb0) << 4) | cnt));
-  __builtin_amdgcn_wave_barrier();
-  // only the owners' bucket words stay live across the loads; their queries are re-read from
-  // LDS when used (keeps the kernel at <= 64 VGPRs, 8 waves/SIMD)
-  float3 P[kLeafBatch];
-#pragma unroll
-  for (int j = 0; j < kLeafBatch; ++j) {
-    const uint32_t w = __float_as_uint(xch[oct + j].w);
-    if ((uint32_t)i < (w & 15u)) {
-      const float4 p = pts[(w >> 4) + i];
-      P[j] = make_float3(p.x, p.y, p.z);
-    }
-  }
-  float res_d = __builtin_inff();
-  uint32_t res_i = 0;
-#pragma unroll
-  for (int j = 0; j < kLeafBatch; ++j) {
-    float dist = __builtin_inff();
-    const float4 Q = xch[oct + j];
-    if ((uint32_t)i < (__float_as_uint(Q.w) & 15u)) {
-      const float d0 = Q.x - P[j].x, d1 = Q.y - P[j].y, d2 = Q.z - P[j].z;
-      float d = 0.f;
-      d += d0 * d0;
-      d += d1 * d1;
-      d += d2 * d2;
-      if (d <= maxR2) dist = d;
-    }
-    const float m = octet_min(dist);
-    const uint32_t hit = (uint32_t)(__ballot(dist == m) >> oct) & 0xFFu;
-    if (i == j) {
-      res_d = m;
-      res_i = (uint32_t)__builtin_ctz(hit | 0x100u);
-    }
-  }
-  __builtin_amdgcn_wave_barrier();  // every lane's reads of xch precede the next round's writes
-  if (act && res_d < t.best.v[0]) best_replace<1>(t.best, (int32_t)(t.lb0 + res_i), res_d);
-}
 
 #if AICP_XCD_PROF
 __device__ unsigned long long g_xcd_prof[64 * kXcdGroups * 2];
@@ -924,31 +702,15 @@ __device__ __forceinline__ void persistent_xcd(uint32_t total, uint32_t* ctr, fl
     ++pf_rounds;
     pf_lanes += __popcll(__ballot(has));
 #endif
-    if constexpr (is_coop<Eng>::value) {
-#if AICP_NN_PREFMIN
-      __shared__ uint16_t pm_lds[kPmDepth * kNNBlock];
-      t.pm = pm_lds + threadIdx.x;
-#endif
+    if constexpr (has_phases<Eng>::value) {
       if (has) t.descend();
       AICP_PF(pf_desc);
-#if AICP_NN_COOP
-      __shared__ float4 xch_all[kNNBlock];
-      coop_bucket(t, has, pts, maxR2, xch_all + (threadIdx.x & ~63));
-#endif
-      if (has) {
-#if AICP_NN_COOP
-        t.bucket_tail(pts, maxR2);
-#else
-        t.bucket_lane(pts, maxR2);
-#endif
-      }
+      if (has) t.bucket_lane(pts, maxR2);
       AICP_PF(pf_buck);
-#if AICP_NN_LDS_FRAMES > 0
       {  // used by the climb only
         __shared__ NnLdsFrame lds_frames[AICP_NN_LDS_FRAMES * kNNBlock];
         t.lf = lds_frames + threadIdx.x;
       }
-#endif
       if (has && t.climb(fs, maxE2, maxR2)) {
         done(my, t);
         has = false;
@@ -993,21 +755,6 @@ __global__ __launch_bounds__(256) void k_prepare_read(BlockMap m, const PairDesc
   float o[3];
   apply4(d.Tinit, p.x, p.y, p.z, o);
   out[d.read_off + j] = make_float4(o[0], o[1], o[2], 1.f);
-}
-
-__global__ __launch_bounds__(256) void k_gather_ref(BlockMap m, const PairDesc* __restrict__ pd,
-                                                    const float4* __restrict__ raw,
-                                                    const int32_t* __restrict__ perm,
-                                                    float4* __restrict__ bpts) {
-  int pair;
-  uint32_t j;
-  block_map(m, pair, j);
-  const PairDesc& d = pd[pair];
-  if (j >= d.n_ref) return;
-  const int32_t id = perm[d.ref_off + j];
-  const float4 p = raw[d.ref_off + id];
-  bpts[d.ref_off + j] =
-      make_float4(p.x - d.mean[0], p.y - d.mean[1], p.z - d.mean[2], __int_as_float(id));
 }
 
 __global__ void k_init_state(int n_pairs, const PairDesc* __restrict__ pd, PairState* st) {
@@ -1140,7 +887,7 @@ __global__ __launch_bounds__(256) void k_active_list(int n_pairs, const PairDesc
 }
 
 // The last workgroup to arrive at a per-pair (or per-group) counter runs the serial step that
-// follows (fused ICP iteration, AICP_ICP_FUSE): every wave's stores complete, one lane releases
+// follows (fused ICP iteration): every wave's stores complete, one lane releases
 // them at agent scope and adds; the last one acquires before reading what the others wrote
 // (cdna_hip_programming.md Guideline 16 / MI355X_MICROARCH.md: release fence, vmcnt wait, then
 // the counter; acquire on the reading side). The counter is reset for the next launch.
@@ -1180,15 +927,7 @@ __device__ __forceinline__ int pair_of_ref(const PairDesc* __restrict__ pd, int 
 }
 
 template <int K>
-#ifndef AICP_KNN_WAVES
-#define AICP_KNN_WAVES 0  // k_knn_ids: waves per SIMD to compile for (0: the compiler's choice)
-#endif
-#if AICP_KNN_WAVES > 0
-#define AICP_KNN_ATTR __attribute__((amdgpu_waves_per_eu(AICP_KNN_WAVES)))
-#else
-#define AICP_KNN_ATTR
-#endif
-__global__ __launch_bounds__(256) AICP_KNN_ATTR void k_knn_ids(int n_pairs, uint32_t total, const PairDesc* __restrict__ pd,
+__global__ __launch_bounds__(256) void k_knn_ids(int n_pairs, uint32_t total, const PairDesc* __restrict__ pd,
                                                  const uint4* __restrict__ nodes,
                                                  const int32_t* __restrict__ parent,
                                                  const float4* __restrict__ bpts,
@@ -1567,10 +1306,10 @@ __device__ __forceinline__ void apply_cols(const float4& c0, const float4& c1, c
 
 // NN kernel: also stores the query's touch counts (inner nodes << 16 | bucket points, each
 // saturated at 65535) for the reduce kernel to sum per pair without atomics.
-template <class Eng>
 #ifndef AICP_NN_WAVES
 #define AICP_NN_WAVES 8  // waves per SIMD the NN kernel is compiled for (VGPR budget 512 / waves)
 #endif
+template <class Eng>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(AICP_NN_WAVES))) void k_icp_nn(
                                                 const PairDesc* __restrict__ pd, const PairState* __restrict__ st,
                                                 const ActiveList* __restrict__ al,
@@ -1613,14 +1352,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(AICP_NN_WAV
         c_lo = __builtin_amdgcn_readfirstlane(en.off);
         c_n = __builtin_amdgcn_readfirstlane(en.n_read);
         c_read = __builtin_amdgcn_readfirstlane(en.read_off);
-        if constexpr (is_coop<Eng>::value) c_node = __builtin_amdgcn_readfirstlane(en.tl_off);
+        if constexpr (has_phases<Eng>::value) c_node = __builtin_amdgcn_readfirstlane(en.tl_off);
         else c_node = __builtin_amdgcn_readfirstlane(en.node_off);
         c_ref = __builtin_amdgcn_readfirstlane(en.ref_off);
       },
       [&](uint32_t s, Eng& t) {
         const uint32_t j = s - c_lo;
         if (j >= c_n) return false;  // padding slot
-        if constexpr (is_coop<Eng>::value) t.bind(nodes, ptl, c_node, c_ref);
+        if constexpr (has_phases<Eng>::value) t.bind(nodes, ptl, c_node, c_ref);
         else t.bind(nodes, bpts, c_node, c_ref);
         qidx = c_read + j;
         const float4 r = read_c[qidx];
@@ -2330,62 +2069,59 @@ __device__ __forceinline__ void icp_reduce_body(BlockMap m, const PairDesc& d, c
 #pragma unroll
   for (int i = 0; i < kRedCols; ++i) acc[i] = 0.0;
   uint32_t tpts = 0, tnod = 0;
-  // kReduceChunks chunks of kReducePerThread readings per thread (the block's reduction below
-  // is paid once per kNNBlock * kReducePerThread * kReduceChunks readings). Per chunk: all
-  // loads of the thread's readings first (independent), then the gathers of the kept ones,
-  // then the arithmetic: two round trips instead of three per reading.
-  for (int ch = 0; ch < kReduceChunks; ++ch) {
-    const uint32_t base = m.start[blockIdx.x] + ch * kReducePerThread * kNNBlock;
-    bool keep[kReducePerThread];
-    int32_t pos[kReducePerThread];
-    float4 r[kReducePerThread];
+  // kReducePerThread readings per thread (the block's reduction below is paid once per
+  // kReduceBlock readings): all loads of the thread's readings first (independent), then the
+  // gathers of the kept ones, then the arithmetic: two round trips instead of three per reading.
+  const uint32_t base = m.start[blockIdx.x];
+  bool keep[kReducePerThread];
+  int32_t pos[kReducePerThread];
+  float4 r[kReducePerThread];
 #pragma unroll
-    for (int it = 0; it < kReducePerThread; ++it) {
-      const uint32_t j = base + it * kNNBlock + threadIdx.x;
-      keep[it] = false;
-      pos[it] = 0;
-      if (j < d.n_read) {
-        const uint32_t tc = touched[d.read_off + j];
-        tpts += tc & 0xFFFFu;
-        tnod += tc >> 16;
-        keep[it] = d2[d.read_off + j] <= limit;
-        pos[it] = match[d.read_off + j];
-        r[it] = read_c[d.read_off + j];
-      }
+  for (int it = 0; it < kReducePerThread; ++it) {
+    const uint32_t j = base + it * kNNBlock + threadIdx.x;
+    keep[it] = false;
+    pos[it] = 0;
+    if (j < d.n_read) {
+      const uint32_t tc = touched[d.read_off + j];
+      tpts += tc & 0xFFFFu;
+      tnod += tc >> 16;
+      keep[it] = d2[d.read_off + j] <= limit;
+      pos[it] = match[d.read_off + j];
+      r[it] = read_c[d.read_off + j];
     }
-    float4 q[kReducePerThread], nr[kReducePerThread];
+  }
+  float4 q[kReducePerThread], nr[kReducePerThread];
 #pragma unroll
-    for (int it = 0; it < kReducePerThread; ++it)
-      if (keep[it]) {
-        q[it] = bpts[d.ref_off + pos[it]];
-        nr[it] = bnrm[d.ref_off + pos[it]];
-      }
-#pragma unroll
-    for (int it = 0; it < kReducePerThread; ++it) {
-      if (!keep[it]) continue;
-      float p[3];
-      apply4(T, r[it].x, r[it].y, r[it].z, p);
-      const float4 n4 = nr[it];
-      float F[6];
-      F[0] = p[1] * n4.z - p[2] * n4.y;
-      F[1] = p[2] * n4.x - p[0] * n4.z;
-      F[2] = p[0] * n4.y - p[1] * n4.x;
-      F[3] = n4.x;
-      F[4] = n4.y;
-      F[5] = n4.z;
-      const float dl0 = p[0] - q[it].x, dl1 = p[1] - q[it].y, dl2 = p[2] - q[it].z;
-      float dot = dl0 * n4.x;
-      dot += dl1 * n4.y;
-      dot += dl2 * n4.z;
-      int c = 0;
-#pragma unroll
-      for (int a = 0; a < 6; ++a)
-#pragma unroll
-        for (int b = a; b < 6; ++b) acc[c++] += (double)F[a] * (double)F[b];
-#pragma unroll
-      for (int a = 0; a < 6; ++a) acc[21 + a] += (double)F[a] * (double)dot;
-      acc[27] += 1.0;
+  for (int it = 0; it < kReducePerThread; ++it)
+    if (keep[it]) {
+      q[it] = bpts[d.ref_off + pos[it]];
+      nr[it] = bnrm[d.ref_off + pos[it]];
     }
+#pragma unroll
+  for (int it = 0; it < kReducePerThread; ++it) {
+    if (!keep[it]) continue;
+    float p[3];
+    apply4(T, r[it].x, r[it].y, r[it].z, p);
+    const float4 n4 = nr[it];
+    float F[6];
+    F[0] = p[1] * n4.z - p[2] * n4.y;
+    F[1] = p[2] * n4.x - p[0] * n4.z;
+    F[2] = p[0] * n4.y - p[1] * n4.x;
+    F[3] = n4.x;
+    F[4] = n4.y;
+    F[5] = n4.z;
+    const float dl0 = p[0] - q[it].x, dl1 = p[1] - q[it].y, dl2 = p[2] - q[it].z;
+    float dot = dl0 * n4.x;
+    dot += dl1 * n4.y;
+    dot += dl2 * n4.z;
+    int c = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int b = a; b < 6; ++b) acc[c++] += (double)F[a] * (double)F[b];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) acc[21 + a] += (double)F[a] * (double)dot;
+    acc[27] += 1.0;
   }
   acc[28] = (double)tpts;
   acc[29] = (double)tnod;
@@ -2406,7 +2142,7 @@ __device__ __forceinline__ void icp_reduce_body(BlockMap m, const PairDesc& d, c
 #pragma unroll
     for (int w = 0; w < kRows; ++w) v += part[w][threadIdx.x];
     // the pair's partial rows start at red_blk_off (m may cover a subset of the pairs)
-    const uint32_t row = d.red_blk_off + m.start[blockIdx.x] / (kNNBlock * kReducePerThread * kReduceChunks);
+    const uint32_t row = d.red_blk_off + m.start[blockIdx.x] / kReduceBlock;
     slab[(size_t)row * kRedCols + threadIdx.x] = v;
   }
 }
@@ -2740,15 +2476,7 @@ __device__ void icp_update_body(const PairDesc& d, PairState& s, const double* _
   if (t == 0) update_serial(d, s, tot, prm, rank_llt[0] == 6 && rank_llt[1] ? xs : nullptr);
 }
 
-__global__ __launch_bounds__(256) void k_icp_update(const PairDesc* __restrict__ pd, PairState* st,
-                                                    const double* __restrict__ slab, IcpParams prm) {
-  const int pair = blockIdx.x;
-  PairState& s = st[pair];
-  if (!s.active) return;
-  icp_update_body(pd[pair], s, slab, prm);
-}
-
-// k_icp_update + (last pair of the group) the next active list. Kept out of the reduce kernel:
+// a pair's update + (last pair of the group) the next active list. Kept out of the reduce kernel:
 // the update's solve (pivoted QR, LLT / min-norm QR / SVD fallback, fp64) needs 256 VGPRs, and a
 // kernel's register allocation is its largest path's, so a fused reduce ran its gathers at one
 // wave per SIMD (35-40 us per C2 window iteration against 12.5 + 12.3 us for the two kernels).
@@ -2956,10 +2684,6 @@ static int persistent_grid(int n_items, int blocks_per_cu = 8) {
 void launch_prepare_read(hipStream_t s, BlockMap m, const PairDesc* pd, const float4* raw, float4* out) {
   if (m.n_blocks) k_prepare_read<<<m.n_blocks, 256, 0, s>>>(m, pd, raw, out);
 }
-void launch_gather_ref(hipStream_t s, BlockMap m, const PairDesc* pd, const float4* raw, const int32_t* perm,
-                       float4* bpts) {
-  if (m.n_blocks) k_gather_ref<<<m.n_blocks, 256, 0, s>>>(m, pd, raw, perm, bpts);
-}
 void launch_init_state(hipStream_t s, int n_pairs, const PairDesc* pd, PairState* st) {
   k_init_state<<<(n_pairs + 63) / 64, 64, 0, s>>>(n_pairs, pd, st);
 }
@@ -3103,12 +2827,12 @@ void nn_prof_dump() {
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_xcd_cost), zc, sizeof(zc));
 #endif
 #if AICP_NN_PROF
-  unsigned long long h[8];
-  if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_nn_prof), sizeof(h)) == hipSuccess) {
-    const double tot = (double)(h[0] + h[1] + h[2] + h[3]);
+  unsigned long long np[8];
+  if (hipMemcpyFromSymbol(np, HIP_SYMBOL(g_nn_prof), sizeof(np)) == hipSuccess) {
+    const double tot = (double)(np[0] + np[1] + np[2] + np[3]);
     fprintf(stderr, "nn_prof: fill %.1f%% descent %.1f%% bucket %.1f%% climb %.1f%% | rounds %llu, mean active lanes %.1f | cached starts %llu, full %llu\n",
-            100.0 * h[0] / tot, 100.0 * h[1] / tot, 100.0 * h[2] / tot, 100.0 * h[3] / tot, h[4],
-            h[4] ? (double)h[5] / h[4] : 0.0, h[6], h[7]);
+            100.0 * np[0] / tot, 100.0 * np[1] / tot, 100.0 * np[2] / tot, 100.0 * np[3] / tot, np[4],
+            np[4] ? (double)np[5] / np[4] : 0.0, np[6], np[7]);
   }
   unsigned long long z[8] = {};
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_nn_prof), z, sizeof(z));
@@ -3193,16 +2917,6 @@ void launch_icp_reduce_f(hipStream_t s, BlockMap m, const PairDesc* pd, PairStat
   if (!m.n_blocks) return;
   k_icp_reduce<<<m.n_blocks, kNNBlock, 0, s>>>(m, pd, st, read_c, match, d2, touched, bpts, bnrm, slab);
   k_icp_update_f<<<y.np, 256, 0, s>>>(y.pd, y.st, slab, prm, y);
-}
-void launch_icp_reduce(hipStream_t s, BlockMap m, const PairDesc* pd, const PairState* st, const float4* read_c,
-                       const int32_t* match, const float* d2, const uint32_t* touched, const float4* bpts,
-                       const float4* bnrm, double* slab) {
-  if (m.n_blocks)
-    k_icp_reduce<<<m.n_blocks, kNNBlock, 0, s>>>(m, pd, st, read_c, match, d2, touched, bpts, bnrm, slab);
-}
-void launch_icp_update(hipStream_t s, int n_pairs, const PairDesc* pd, PairState* st, const double* slab,
-                       const IcpParams& prm) {
-  k_icp_update<<<n_pairs, 256, 0, s>>>(pd, st, slab, prm);
 }
 void launch_finalize(hipStream_t s, int n_pairs, const PairDesc* pd, PairState* st, float* outT) {
   k_finalize<<<(n_pairs + 63) / 64, 64, 0, s>>>(n_pairs, pd, st, outT);

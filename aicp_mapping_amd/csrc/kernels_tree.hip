@@ -1969,8 +1969,9 @@ __global__ __launch_bounds__(256) void k_tl_build(int n_refs, uint32_t cap, cons
     const uint32_t p = nd[u].z, gp = nd[p].z;
     return id_of(gp) << 2 | (p != gp + 1 ? 2u : 1u);
   };
-  // link = {parent of this treelet's root, parent of the parent treelet's root}: the climb
-  // names two treelets ahead (kernels_icp.hip, AICP_NN_CLIMB4)
+  // link = {parent of this treelet's root, parent of the parent treelet's root}: the climb reads
+  // the first (kernels_icp.hip, ld_rec_up); the second named two treelets ahead for a two-treelet
+  // climb that measured slower and was removed
   const uint32_t up = up_of(v);
   link[r.tl_off + id] = make_uint2(up, v == 0 ? 0xffffffffu : up_of(nd[a.z].z));  // nd[a.z].z: the grandparent, root of the parent treelet
   uint4 rec = make_uint4(tl_slot(a), 0u, 0u, a.y & 3u);

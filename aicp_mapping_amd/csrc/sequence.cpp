@@ -401,7 +401,7 @@ static int win_upload(C* ctx, SeqState* S, const aicp_icp_config* cfg, const aic
   // slot buffers (sizes grow to the largest window seen)
   const size_t tl_cap = 4 * (size_t)n_ref + 4;
   const bool use_tl = cfg->bucket_size <= 15 && n_ref <= 4000000u && tl_cap < (1ull << 28) && S->opt.nn_engine != 1;
-  constexpr uint32_t kRedBlk = kNNBlock * kReducePerThread * kReduceChunks;
+  constexpr uint32_t kRedBlk = kReduceBlock;
   if (sl.used) {
     // the slot's previous window (w - K) must be done before its buffers are rewritten, and so
     // must window w - K + 1, whose reference was built from a reading in this slot: its ICP
