@@ -44,7 +44,7 @@ EXPORTS = [
     "aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_hip_set_options", "aicp_hip_get_options",
     "aicp_hip_test_force_scan_stall", "aicp_hip_sequence_run_raw", "aicp_hip_build_info",
     "aicp_hip_fov_overlap", "aicp_hip_cluster_match", "aicp_hip_alignment_features",
-    "aicp_hip_default_risk_params", "aicp_hip_last_risk_stats", "aicp_hip_test_select",
+    "aicp_hip_default_risk_params", "aicp_hip_last_risk_stats", "aicp_hip_test_select", "aicp_hip_test_step",
     "aicp_hip_default_monitor_params", "aicp_hip_monitor", "aicp_hip_monitor_batch", "aicp_hip_last_monitor_stats",
     "aicp_hip_default_localization_params", "aicp_hip_localization_window", "aicp_hip_map_sequence_run",
     "aicp_hip_last_localization_timing",
@@ -56,7 +56,7 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_sequence_run_raw", "aicp_hip_build_info",  # added in r05 / r06
            "aicp_hip_fov_overlap", "aicp_hip_cluster_match", "aicp_hip_alignment_features",
            "aicp_hip_default_risk_params", "aicp_hip_last_risk_stats",  # the alignment-risk features
-           "aicp_hip_test_select",
+           "aicp_hip_test_select", "aicp_hip_test_step",
            "aicp_hip_default_monitor_params", "aicp_hip_monitor", "aicp_hip_monitor_batch",
            "aicp_hip_last_monitor_stats",  # the registration quality monitor
            "aicp_hip_default_localization_params", "aicp_hip_localization_window", "aicp_hip_map_sequence_run",
@@ -447,6 +447,10 @@ def _load():
         u32p = C.POINTER(C.c_uint32)
         L.aicp_hip_test_select.argtypes = [vp, sz, u32p, fp, C.POINTER(C.c_uint8), sz, ip, fp, fp, ip, ip, u32p, u32p,
                                            up]
+    if hasattr(L, "aicp_hip_test_step"):
+        u32p, u8p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
+        L.aicp_hip_test_step.argtypes = [vp, sz, u32p, u32p, u32p, sz, fp, fp, fp, fp, u8p, C.c_int32, C.c_int32,
+                                         C.c_float, C.c_float, sz, fp, ip, fp, u32p, dp, fp, ip, fp, up, dp, up]
     return L
 
 
@@ -914,6 +918,60 @@ class Context:
             out["b1"].ctypes.data_as(u32p), out["miss"].ctypes.data_as(u32p), C.byref(dirty))
         self.check(rc)
         out["dirty"] = int(dirty.value)
+        return out
+
+    def test_step(self, n_read, n_ref, ref_off, read_c, ref_pts, ref_nrm, limit, match, d2, touched, init_T=None,
+                  active=None, max_iter=20, smooth=4, min_rot=1e-3, min_trans=1e-2):
+        """aicp_hip_test_step: the production reduce + update launch, once per step, on given matches.
+        n_read, n_ref, ref_off: per pair; read_c (total, 3); ref_pts, ref_nrm (total_ref, 3); limit
+        (n_steps, n_pairs); match, d2, touched (n_steps, total). Returns per step and pair: slab (a list
+        over steps of (rows, 30) arrays), T (S, P, 16), kept, iters, status, active, converged,
+        hist_count, inlier_ratio, touched_pts, touched_nodes, dq, dt as (S, P) arrays, and dirty."""
+        n_read = np.ascontiguousarray(n_read, np.uint32).ravel()
+        n_ref = np.ascontiguousarray(n_ref, np.uint32).ravel()
+        ref_off = np.ascontiguousarray(ref_off, np.uint32).ravel()
+        read_c = np.ascontiguousarray(read_c, np.float32).reshape(-1, 3)
+        ref_pts = np.ascontiguousarray(ref_pts, np.float32).reshape(-1, 3)
+        ref_nrm = np.ascontiguousarray(ref_nrm, np.float32).reshape(-1, 3)
+        P, total, total_ref = n_read.size, int(n_read.sum(dtype=np.uint64)), ref_pts.shape[0]
+        limit = np.ascontiguousarray(limit, np.float32)
+        S = limit.shape[0] if limit.ndim == 2 else 0
+        match = np.ascontiguousarray(match, np.int32)
+        d2 = np.ascontiguousarray(d2, np.float32)
+        touched = np.ascontiguousarray(touched, np.uint32)
+        if n_ref.size != P or ref_off.size != P or read_c.shape[0] != total or ref_nrm.shape[0] != total_ref:
+            raise ValueError("per-pair arrays of one length; read_c of sum(n_read) rows; one normal per reference point")
+        if limit.shape != (S, P) or any(a.shape != (S, total) for a in (match, d2, touched)):
+            raise ValueError("limit (n_steps, n_pairs); match, d2, touched (n_steps, sum(n_read))")
+        T0 = act = None
+        if init_T is not None:
+            T0 = np.ascontiguousarray(init_T, np.float32).reshape(P, 16)
+        if active is not None:
+            act = np.ascontiguousarray(active, np.uint8).ravel()
+            if act.size != P:
+                raise ValueError("one active flag per pair")
+        rows = int(((n_read.astype(np.int64) + 1023) // 1024).sum())
+        slab = np.zeros((S, rows, 30), np.float64)
+        T = np.zeros((S, P, 16), np.float32)
+        state = np.zeros((S, P, 6), np.int32)
+        inl = np.zeros((S, P), np.float32)
+        tch = np.zeros((S, P, 2), np.uint64)
+        dqdt = np.zeros((S, P, 2), np.float64)
+        dirty = C.c_uint64()
+        ip, u32p, dp = C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+        u8p, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)
+        rc = lib.aicp_hip_test_step(
+            self.h, P, n_read.ctypes.data_as(u32p), n_ref.ctypes.data_as(u32p), ref_off.ctypes.data_as(u32p), total_ref,
+            _fptr(read_c), _fptr(ref_pts), _fptr(ref_nrm), _fptr(T0) if T0 is not None else None,
+            act.ctypes.data_as(u8p) if act is not None else None, int(max_iter), int(smooth), float(min_rot),
+            float(min_trans), S, _fptr(limit), match.ctypes.data_as(ip), _fptr(d2), touched.ctypes.data_as(u32p),
+            slab.ctypes.data_as(dp), _fptr(T), state.ctypes.data_as(ip), _fptr(inl), tch.ctypes.data_as(u64p),
+            dqdt.ctypes.data_as(dp), C.byref(dirty))
+        self.check(rc)
+        out = dict(slab=slab, T=T, inlier_ratio=inl, touched_pts=tch[..., 0].copy(), touched_nodes=tch[..., 1].copy(),
+                   dq=dqdt[..., 0].copy(), dt=dqdt[..., 1].copy(), dirty=int(dirty.value))
+        for i, k in enumerate(("kept", "iters", "status", "active", "converged", "hist_count")):
+            out[k] = state[..., i].copy()
         return out
 
     def solve6(self, A, b):

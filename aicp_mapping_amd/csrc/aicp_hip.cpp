@@ -1814,6 +1814,172 @@ int aicp_hip_test_select(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* coun
   return AICP_OK;
 }
 
+// The tail of an ICP iteration (launch_active_list, then launch_icp_reduce_f: k_icp_reduce and
+// k_icp_update_f) on given matches, set up as batch_run sets the ICP loop up (descriptors with
+// red_blk_off / n_red_blk, states, the kReduceBlock-reading block map, zeroed work space,
+// IcpIterSync). Every argument is checked before the device is touched. The readings, reference
+// points and normals live in buffers of this call (the context's hold the resident reference).
+int aicp_hip_test_step(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read, const uint32_t* n_ref,
+                       const uint32_t* ref_off, size_t total_ref, const float* read_c, const float* ref_pts,
+                       const float* ref_nrm, const float* init_T, const uint8_t* active, int32_t max_iter,
+                       int32_t smooth, float min_rot, float min_trans, size_t n_steps, const float* limit,
+                       const int32_t* match, const float* d2, const uint32_t* touched, double* out_slab,
+                       float* out_T, int32_t* out_state, float* out_inlier, uint64_t* out_touched,
+                       double* out_dqdt, uint64_t* out_dirty) {
+  if (!ctx || !n_read || !n_ref || !ref_off || !read_c || !ref_pts || !ref_nrm || !limit || !match || !d2 ||
+      !touched || !out_slab || !out_T || !out_state || !out_inlier || !out_touched || !out_dqdt || !out_dirty)
+    return AICP_ERR_INVALID;
+  if (n_pairs == 0 || n_pairs > (size_t)kMaxPairs || n_steps == 0 || total_ref == 0) return AICP_ERR_INVALID;
+  if (smooth < 1 || smooth >= kHistRing) return AICP_ERR_INVALID;
+  if (total_ref >= (1ull << 28)) return AICP_ERR_INVALID;
+  const size_t P = n_pairs;
+  uint64_t total = 0, rows = 0;
+  for (size_t p = 0; p < P; ++p) {
+    if (n_read[p] == 0 || n_ref[p] == 0 || (uint64_t)ref_off[p] + n_ref[p] > total_ref) return AICP_ERR_INVALID;
+    total += n_read[p];
+    rows += (n_read[p] + (uint32_t)kReduceBlock - 1) / (uint32_t)kReduceBlock;
+  }
+  if (total >= (1ull << 31) || total * n_steps >= (1ull << 32)) return AICP_ERR_INVALID;
+  for (size_t s = 0; s < n_steps; ++s) {
+    uint64_t o = s * total;
+    for (size_t p = 0; p < P; ++p) {
+      const float lim = limit[s * P + p];
+      if (!std::isfinite(lim)) return AICP_ERR_INVALID;
+      for (uint32_t j = 0; j < n_read[p]; ++j, ++o)  // what the reduce would gather
+        if (d2[o] <= lim && (match[o] < 0 || (uint32_t)match[o] >= n_ref[p])) return AICP_ERR_INVALID;
+    }
+  }
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t st_ = ctx->stream;
+  std::vector<PairDesc> desc(P, PairDesc{});
+  Maps md;
+  uint32_t off = 0, red = 0;
+  for (size_t p = 0; p < P; ++p) {
+    PairDesc& d = desc[p];
+    d.ref_off = ref_off[p];
+    d.n_ref = n_ref[p];
+    d.read_off = off;
+    d.n_read = n_read[p];
+    d.red_blk_off = red;
+    d.n_red_blk = (n_read[p] + (uint32_t)kReduceBlock - 1) / (uint32_t)kReduceBlock;
+    d.ratio = 1.f;
+    ident4(d.Tin);
+    ident4(d.Tinit);
+    ident4(d.Tmean);
+    md.add((int)p, n_read[p], kReduceBlock);
+    off += n_read[p];
+    red += d.n_red_blk;
+  }
+  const size_t nb = md.pair.size();  // one block per slab row
+  struct Local {  // freed on every return
+    DevBuf read_c, bpts, bnrm;
+    ~Local() {
+      release(read_c);
+      release(bpts);
+      release(bnrm);
+    }
+  } loc;
+  HIPC(ensure(loc.read_c, total * 16));
+  HIPC(ensure(loc.bpts, total_ref * 16));
+  HIPC(ensure(loc.bnrm, total_ref * 16));
+  HIPC(ensure(ctx->desc, P * sizeof(PairDesc)));
+  HIPC(ensure(ctx->state, P * sizeof(PairState)));
+  HIPC(ensure(ctx->match, total * n_steps * 4));
+  HIPC(ensure(ctx->d2, total * n_steps * 4));
+  HIPC(ensure(ctx->touch, total * n_steps * 4));
+  HIPC(ensure(ctx->slab, rows * kRedCols * 8));
+  HIPC(ensure(ctx->qmap, nb * 8));
+  HIPC(ensure(ctx->isync, icp_sync_words(P) * 4));
+  HIPC(ensure(ctx->active, active_list_bytes(total, P)));
+  HIPC(ensure(ctx->ctrs, kCtrWords * 4));
+  std::vector<float> pk(std::max<uint64_t>(total, total_ref) * 4);
+  auto upload4 = [&](const float* xyz, uint64_t n, void* dst) {  // xyz -> float4 (w = 1)
+    for (uint64_t i = 0; i < n; ++i) {
+      pk[4 * i] = xyz[3 * i];
+      pk[4 * i + 1] = xyz[3 * i + 1];
+      pk[4 * i + 2] = xyz[3 * i + 2];
+      pk[4 * i + 3] = 1.f;
+    }
+    return hipMemcpy(dst, pk.data(), n * 16, hipMemcpyHostToDevice);
+  };
+  HIPC(upload4(read_c, total, loc.read_c.p));
+  HIPC(upload4(ref_pts, total_ref, loc.bpts.p));
+  HIPC(upload4(ref_nrm, total_ref, loc.bnrm.p));
+  PairDesc* dDesc = ctx->desc.as<PairDesc>();
+  PairState* dState = ctx->state.as<PairState>();
+  uint32_t* sync = ctx->isync.as<uint32_t>();
+  ActiveList* al = ctx->active.as<ActiveList>();
+  double* slab = ctx->slab.as<double>();
+  HIPC(hipMemcpy(dDesc, desc.data(), P * sizeof(PairDesc), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(ctx->match.p, match, total * n_steps * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(ctx->d2.p, d2, total * n_steps * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(ctx->touch.p, touched, total * n_steps * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(ctx->qmap.p, md.pair.data(), nb * 4, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(ctx->qmap.as<uint32_t>() + nb, md.start.data(), nb * 4, hipMemcpyHostToDevice));
+  const BlockMap m{ctx->qmap.as<int32_t>(), ctx->qmap.as<uint32_t>() + nb, (uint32_t)nb};
+  HIPC(hipMemsetAsync(sync, 0, icp_sync_words(P) * 4, st_));
+  HIPC(hipMemsetAsync(ctx->ctrs.p, 0, kCtrWords * 4, st_));
+  HIPC(hipMemsetAsync(dState, 0, P * sizeof(PairState), st_));
+  launch_init_state(st_, (int)P, dDesc, dState);
+  for (size_t p = 0; p < P; ++p) {
+    if (init_T) HIPC(hipMemcpyAsync(dState[p].T, init_T + 16 * p, 64, hipMemcpyHostToDevice, st_));
+    if (active && !active[p]) HIPC(hipMemsetAsync(&dState[p].active, 0, sizeof(int32_t), st_));
+  }
+  IcpIterSync y = icp_sync_layout(sync, P, 0);
+  y.np = (int)P;
+  y.pd = dDesc;
+  y.st = dState;
+  y.al = al;
+  y.ctr = ctx->ctrs.as<uint32_t>();
+  IcpParams prm{};
+  prm.maxE2 = 1.f;
+  prm.maxR2 = INFINITY;
+  prm.max_iter = max_iter;
+  prm.smooth = smooth;
+  prm.min_rot = min_rot;
+  prm.min_trans = min_trans;
+  std::vector<PairState> hs(P);
+  constexpr uint32_t kSentinel = 0x7FF8DEADu;  // both halves: a NaN no sum produces
+  for (size_t s = 0; s < n_steps; ++s) {
+    for (size_t p = 0; p < P; ++p)
+      HIPC(hipMemcpyAsync(&dState[p].limit, limit + s * P + p, 4, hipMemcpyHostToDevice, st_));
+    HIPC(hipMemsetD32Async((hipDeviceptr_t)slab, (int)kSentinel, rows * kRedCols * 2, st_));
+    launch_active_list(st_, (int)P, dDesc, dState, al, y.ctr);
+    launch_icp_reduce_f(st_, m, dDesc, dState, loc.read_c.as<float4>(), ctx->match.as<int32_t>() + s * total,
+                        ctx->d2.as<float>() + s * total, ctx->touch.as<uint32_t>() + s * total,
+                        loc.bpts.as<float4>(), loc.bnrm.as<float4>(), slab, prm, y);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(out_slab + s * rows * kRedCols, slab, rows * kRedCols * 8, hipMemcpyDeviceToHost, st_));
+    HIPC(hipMemcpyAsync(hs.data(), dState, P * sizeof(PairState), hipMemcpyDeviceToHost, st_));
+    HIPC(hipStreamSynchronize(st_));
+    for (size_t p = 0; p < P; ++p) {
+      const size_t o = s * P + p;
+      const PairState& h = hs[p];
+      std::memcpy(out_T + 16 * o, h.T, 64);
+      int32_t* w = out_state + 6 * o;
+      w[0] = h.kept;
+      w[1] = h.iters;
+      w[2] = h.status;
+      w[3] = h.active;
+      w[4] = h.converged;
+      w[5] = h.hist_count;
+      out_inlier[o] = h.inlier_ratio;
+      out_touched[2 * o] = h.touched_pts;
+      out_touched[2 * o + 1] = h.touched_nodes;
+      const int last = (int)((uint32_t)(h.hist_count - 1) % (uint32_t)kHistRing);  // the entry just pushed
+      out_dqdt[2 * o] = h.dq[last];
+      out_dqdt[2 * o + 1] = h.dt[last];
+    }
+  }
+  // the arrival counters the iteration tail leaves for the next one: red | pairs, all zero
+  std::vector<uint32_t> w(P + 2);
+  HIPC(hipMemcpy(w.data(), y.red, (P + 2) * 4, hipMemcpyDeviceToHost));
+  uint64_t dirty = 0;
+  for (uint32_t v : w) dirty += v != 0;
+  *out_dirty = dirty;
+  return AICP_OK;
+}
+
 void aicp_hip_default_prefilter(aicp_prefilter_params* p) {
   if (!p) return;
   *p = aicp_prefilter_params{};

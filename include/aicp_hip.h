@@ -660,6 +660,35 @@ int aicp_hip_test_select(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* coun
                          float* out_limit, int32_t* out_status, int32_t* out_n_finite,
                          uint32_t* out_b1, uint32_t* out_miss /* each n_steps * n_pairs */,
                          uint64_t* out_dirty);
+/* Test surface: the tail of an ICP iteration, k_icp_reduce and k_icp_update_f as the loop launches
+ * them, on given matches. Runs n_steps steps, one after another on the same pair states; each is
+ * the active list followed by the production reduce + update launch. Pair p has n_read[p] centred
+ * readings (read_c, 3 floats each, the pairs one after another) and gathers reference points and
+ * normals at ref_off[p] + match from ref_pts / ref_nrm (3 * total_ref floats each; pairs may share
+ * a range). init_T (nullable): 16 floats per pair, column-major, T_iter before the first step
+ * (identity by default; the checker ring's entry 0 stays the identity's). Step s writes
+ * limit[s * n_pairs + p] into the pair's state (no select runs) and reads match, d2 and touched
+ * (low half: touched points, high half: touched nodes) at s * total + the pair's prefix offset,
+ * total = sum(n_read). Before every step the slab is filled with doubles of the bit pattern
+ * 0x7FF8DEAD7FF8DEAD, so a row nothing wrote is recognisable.
+ * Per step: out_slab gets all slab rows (pair p's ceil(n_read[p] / 1024) rows of 30 doubles at its
+ * prefix row offset); out_T 16 floats per pair; out_state 6 per pair: kept, iters, status, active,
+ * converged, hist_count; out_inlier 1; out_touched 2 (points, nodes; running totals); out_dqdt 2:
+ * dq and dt of the ring entry last pushed. out_dirty: non-zero words left in the reduce / pairs
+ * arrival counters after the last step (0 expected).
+ * AICP_ERR_INVALID, before any device work: a null pointer (init_T and active may be null), no
+ * pair or more than 4096, no step, a count of 0, ref_off + n_ref above total_ref, total_ref 0 or
+ * >= 2^28, smooth outside [1, 32), a non-finite limit, a match outside [0, n_ref) on a reading
+ * with d2 <= limit, sum(n_read) >= 2^31, n_steps * total >= 2^32. */
+int aicp_hip_test_step(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read, const uint32_t* n_ref,
+                       const uint32_t* ref_off, size_t total_ref, const float* read_c, const float* ref_pts,
+                       const float* ref_nrm, const float* init_T /* nullable */,
+                       const uint8_t* active /* nullable: 0 = pair starts inactive */, int32_t max_iter,
+                       int32_t smooth, float min_rot, float min_trans, size_t n_steps,
+                       const float* limit /* n_steps * n_pairs */, const int32_t* match, const float* d2,
+                       const uint32_t* touched /* each n_steps * total */, double* out_slab, float* out_T,
+                       int32_t* out_state, float* out_inlier, uint64_t* out_touched, double* out_dqdt,
+                       uint64_t* out_dirty);
 
 #ifdef __cplusplus
 }
