@@ -48,6 +48,8 @@ EXPORTS = [
     "aicp_hip_default_monitor_params", "aicp_hip_monitor", "aicp_hip_monitor_batch", "aicp_hip_last_monitor_stats",
     "aicp_hip_default_localization_params", "aicp_hip_localization_window", "aicp_hip_map_sequence_run",
     "aicp_hip_last_localization_timing",
+    "aicp_hip_map_align_batch", "aicp_hip_map_capacity", "aicp_hip_default_built_map_params",
+    "aicp_hip_built_map_window", "aicp_hip_built_map_sequence_run", "aicp_hip_last_built_map_timing",
 ]
 
 
@@ -60,7 +62,10 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_default_monitor_params", "aicp_hip_monitor", "aicp_hip_monitor_batch",
            "aicp_hip_last_monitor_stats",  # the registration quality monitor
            "aicp_hip_default_localization_params", "aicp_hip_localization_window", "aicp_hip_map_sequence_run",
-           "aicp_hip_last_localization_timing"}  # the localization stream
+           "aicp_hip_last_localization_timing",  # the localization stream
+           "aicp_hip_map_align_batch", "aicp_hip_map_capacity", "aicp_hip_default_built_map_params",
+           "aicp_hip_built_map_window", "aicp_hip_built_map_sequence_run",
+           "aicp_hip_last_built_map_timing"}  # the built-map localization stream
 
 
 class IcpConfig(C.Structure):
@@ -322,6 +327,47 @@ class LocalizationTiming(C.Structure):
     ]
 
 
+class BuiltMapParams(C.Structure):
+    """aicp_built_map_params: App's localization stream on the map it has built itself."""
+    _fields_ = [
+        ("reference_update_frequency", C.c_int32),
+        ("max_correction_magnitude", C.c_float),
+        ("crop_min", C.c_float),
+        ("crop_max", C.c_float),
+        ("resolution", C.c_double),
+        ("flags", C.c_int32),
+        ("pad", C.c_int32),
+    ]
+
+
+class BuiltMapResult(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32),
+        ("accepted", C.c_int32),
+        ("is_reference", C.c_int32),
+        ("pad", C.c_int32),
+        ("map_points", C.c_uint64),
+        ("crop_points", C.c_uint64),
+        ("corrected_origin", C.c_double * 3),
+        ("icp", IcpStats),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k in ("status", "accepted", "is_reference", "map_points", "crop_points")}
+        d["corrected_origin"] = [float(x) for x in self.corrected_origin]
+        d["icp"] = self.icp.as_dict()
+        return d
+
+
+class BuiltMapTiming(C.Structure):
+    _fields_ = [
+        ("windows", C.c_int32),
+        ("appends", C.c_int32),
+        ("wall_ms", C.c_double),
+        ("device_ms", C.c_double),
+    ]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -443,6 +489,18 @@ def _load():
         L.aicp_hip_map_sequence_run.argtypes = [vp, cfgp, lpp, C.POINTER(PrefilterParams), vp, C.POINTER(Cloud), fp, sz,
                                                 fp, C.POINTER(LocalizationResult), szp]
         L.aicp_hip_last_localization_timing.argtypes = [vp, C.POINTER(LocalizationTiming)]
+    if hasattr(L, "aicp_hip_built_map_sequence_run"):
+        bpp = C.POINTER(BuiltMapParams)
+        L.aicp_hip_map_align_batch.argtypes = [vp, cfgp, vp, C.c_float, C.c_float, C.POINTER(Cloud), fp, sz, C.c_double,
+                                               C.c_int, fp, stp]
+        L.aicp_hip_map_capacity.argtypes = [vp, szp]
+        L.aicp_hip_default_built_map_params.argtypes = [bpp]
+        L.aicp_hip_default_built_map_params.restype = None
+        L.aicp_hip_built_map_window.argtypes = [C.c_uint64, bpp, sz]
+        L.aicp_hip_built_map_window.restype = sz
+        L.aicp_hip_built_map_sequence_run.argtypes = [vp, cfgp, bpp, vp, C.POINTER(Cloud), fp, sz, fp,
+                                                      C.POINTER(BuiltMapResult), szp]
+        L.aicp_hip_last_built_map_timing.argtypes = [vp, C.POINTER(BuiltMapTiming)]
     if hasattr(L, "aicp_hip_test_select"):
         u32p = C.POINTER(C.c_uint32)
         L.aicp_hip_test_select.argtypes = [vp, sz, u32p, fp, C.POINTER(C.c_uint8), sz, ip, fp, fp, ip, ip, u32p, u32p,
@@ -613,6 +671,29 @@ def default_localization_params(**kw) -> LocalizationParams:
 def localization_window(n_clouds: int, params: LocalizationParams, remaining: int) -> int:
     """aicp_hip_localization_window (host only): the length of the next window of the stream."""
     return int(lib.aicp_hip_localization_window(int(n_clouds), C.byref(params), int(remaining)))
+
+
+def default_built_map_params(**kw) -> BuiltMapParams:
+    """App's settings for localization against the map it built (aicp_hip_default_built_map_params):
+    a reference every 5 accepted readings, max_correction_magnitude 1.0, crop -15..15, octomap
+    0.2 m, per-reading overlap auto-tune. Keyword overrides; overlap=/debug=/time_nn= set or clear
+    AICP_RUN_OVERLAP / AICP_SEQ_DEBUG / AICP_RUN_TIME_NN in flags."""
+    p = BuiltMapParams()
+    lib.aicp_hip_default_built_map_params(C.byref(p))
+    bits = {"overlap": AICP_RUN_OVERLAP, "debug": AICP_SEQ_DEBUG, "time_nn": AICP_RUN_TIME_NN}
+    for k, v in kw.items():
+        if k in bits:
+            p.flags = (p.flags | bits[k]) if v else (p.flags & ~bits[k])
+        elif not hasattr(p, k) or k == "pad":
+            raise AttributeError(f"aicp_built_map_params has no field {k}")
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def built_map_window(acc: int, params: BuiltMapParams, remaining: int) -> int:
+    """aicp_hip_built_map_window (host only): the length of the next window of the stream."""
+    return int(lib.aicp_hip_built_map_window(int(acc), C.byref(params), int(remaining)))
 
 
 def make_cloud(pts, origin=(0, 0, 0)):
@@ -839,6 +920,13 @@ class Context:
         t = LocalizationTiming()
         self.check(lib.aicp_hip_last_localization_timing(self.h, C.byref(t)))
         return {k: getattr(t, k) for k, _ in LocalizationTiming._fields_ if k != "pad"}
+
+    def last_built_map_timing(self):
+        """aicp_hip_last_built_map_timing: windows, appends, wall_ms, device_ms of the last
+        BuiltMap.sequence_run."""
+        t = BuiltMapTiming()
+        self.check(lib.aicp_hip_last_built_map_timing(self.h, C.byref(t)))
+        return {k: getattr(t, k) for k, _ in BuiltMapTiming._fields_}
 
     def last_nn_timing(self):
         n = C.c_int()

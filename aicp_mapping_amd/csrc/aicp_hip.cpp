@@ -1259,6 +1259,7 @@ void aicp_hip_destroy(aicp_hip_ctx* ctx) {
   delete ctx->pool;
   seq_state_free(ctx->seq);
   loc_bufs_free(ctx->loc);
+  bm_bufs_free(ctx->bm);
   for (PinBuf* b : {&ctx->pin_desc, &ctx->pin_state, &ctx->pin_out, &ctx->pin_io, &ctx->pin_ovl,
                     &ctx->pin_rdesc, &ctx->pin_gdesc, &ctx->pin_gstate, &ctx->pin_pf})
     release(*b);
@@ -2237,7 +2238,10 @@ int aicp_hip_map_create(aicp_hip_ctx* ctx, const float* pts, size_t n, size_t st
   HIPC(hipSetDevice(ctx->device));
   aicp_hip_map* m = new aicp_hip_map();
   if (n) {
-    const hipError_t e = ensure(m->pts, n * 16);
+    // exactly the cloud (ensure() would add a quarter): the first append grows by copy, to twice
+    const size_t nb = std::max<size_t>(256, n * 16);
+    const hipError_t e = hipMalloc(&m->pts.p, nb);
+    if (e == hipSuccess) m->pts.cap = nb;
     if (e != hipSuccess) {
       delete m;
       ctx->err = std::string("map allocation: ") + hipGetErrorString(e);
@@ -2292,6 +2296,25 @@ int aicp_hip_map_crop(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, floa
   return crop_device(ctx, map->pts.as<float4>(), map->n, inv, t, mn, mx, out, cap, out_n);
 }
 
+// A batch whose references are the map's crops around the readings' prior poses, written on the
+// device straight into the batch's reference array (map_crop_pairs), and its run
+static int map_batch(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_hip_map* map, float mn, float mx,
+                     const aicp_cloud* readings, const float* poses, size_t n, double resolution, int run_flags,
+                     float* out_T, aicp_icp_stats* stats) {
+  if (!map->n) FAIL(AICP_ERR_INVALID, "empty map");
+  if (n > (size_t)kMaxPairs) FAIL(AICP_ERR_UNSUPPORTED, "more than 4096 readings in one batch");
+  HIPC(hipSetDevice(ctx->device));
+  size_t n_ok = 0;
+  const uint32_t* counts = nullptr;
+  int rc = map_crop_pairs(ctx, map, mn, mx, readings, poses, n, nullptr, &n_ok, &counts);
+  if (rc) return rc;
+  if (n_ok < n) {
+    (void)hipStreamSynchronize(ctx->stream);  // (the scatter of the readings before it)
+    FAIL(AICP_ERR_INVALID, "reading " + std::to_string(n_ok) + ": empty map crop");
+  }
+  return run_batch(ctx, ctx->mapbatch, cfg, resolution, run_flags, out_T, stats, nullptr);
+}
+
 // Localization-only batch (localize_against_prior_map): every reading's reference is the map
 // cropped around its prior pose on the device (setReference, app.cpp:41-51), written straight
 // into the batch's reference array; the overlap is bypassed at 50 % (app.cpp:123-127), so the
@@ -2300,9 +2323,48 @@ int aicp_hip_map_register_batch(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, c
                                 float mx, const aicp_cloud* readings, const float* poses, size_t n, int flags,
                                 float* out_T, aicp_icp_stats* stats) {
   if (!ctx || !cfg || !map || !readings || !poses || !out_T || n == 0) return AICP_ERR_INVALID;
-  if (!map->n) FAIL(AICP_ERR_INVALID, "empty map");
-  if (n > (size_t)kMaxPairs) FAIL(AICP_ERR_UNSUPPORTED, "more than 4096 readings in one batch");
-  HIPC(hipSetDevice(ctx->device));
+  aicp_icp_config c = *cfg;
+  c.trimmed_ratio = aicp_hip_autotune_ratio(50.0f);  // octree_overlap_ = 50.0 (app.cpp:123-127)
+  return map_batch(ctx, &c, map, mn, mx, readings, poses, n, 0.0, AICP_RUN_ICP | (flags & AICP_RUN_TIME_NN), out_T,
+                   stats);
+}
+
+}  // extern "C"
+
+namespace aicp {
+namespace rt {
+
+// room for `add` more points behind the map's n: the copying growth of aicp_hip_map_merge (a
+// failed growth leaves the map as it was)
+int map_reserve(aicp_hip_ctx* ctx, aicp_hip_map* map, size_t add) {
+  if (map->n + add > (size_t)INT32_MAX) FAIL(AICP_ERR_INVALID, "map merge: more than 2^31 points");
+  const size_t need = (map->n + add) * 16;
+  if (need <= map->pts.cap && map->pts.p) return AICP_OK;
+  hipStream_t s = ctx->stream;
+  DevBuf nb;
+  HIPC(ensure(nb, std::max(need, 2 * map->pts.cap)));
+  hipError_t e = map->n ? hipMemcpyAsync(nb.p, map->pts.p, map->n * 16, hipMemcpyDeviceToDevice, s) : hipSuccess;
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(s);
+    release(nb);
+    FAIL(AICP_ERR_HIP, std::string("map merge: grow copy: ") + hipGetErrorString(e));
+  }
+  release(map->pts);
+  map->pts = nb;
+  return AICP_OK;
+}
+
+// The batch of aicp_hip_map_register_batch, without its run: reading i's reference is the map
+// cropped on the device to [mn, mx]^3 around poses[16 i ..], written straight into
+// ctx->mapbatch's reference array. Only the readings before the first empty crop enter the batch
+// (*n_ok of them; 0: nothing was uploaded). The reference's sensor origin is the pose's
+// translation; the reading's is read_origins[3 i ..] (null: the cloud's own). *counts: the n crop
+// sizes (pinned, valid until the next crop). The scatter is enqueued on ctx->stream, the stream
+// run_batch reads the reference points on (overlap) or orders its other streams behind (ev[14]).
+int map_crop_pairs(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float mx, const aicp_cloud* readings,
+                   const float* poses, size_t n, const double* read_origins, size_t* n_ok, const uint32_t** counts) {
+  *n_ok = 0;
   hipStream_t s = ctx->stream;
   const size_t ab = crop_args_bytes(), tiles = crop_tiles(map->n);
   const size_t o_args = 0, o_cnt = (n * ab + 255) & ~size_t(255), o_off = o_cnt + n * tiles * 4,
@@ -2311,23 +2373,27 @@ int aicp_hip_map_register_batch(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, c
   HIPC(ensure(ctx->pin_crop, n * ab + 2 * n * 4));
   char* ws = ctx->crop_ws.as<char>();
   char* h = ctx->pin_crop.as<char>();
+  uint32_t* htot = reinterpret_cast<uint32_t*>(h + n * ab);
+  *counts = htot;
   for (size_t i = 0; i < n; ++i) {
     float inv[9], t[3], rpy[3];
     crop_box_frame(poses + 16 * i, inv, t, rpy);
     pack_crop_args(inv, t, mn, mx, h + i * ab);
+    htot[i] = 0;
   }
+  if (!map->n) return AICP_OK;
   HIPC(hipMemcpyAsync(ws + o_args, h, n * ab, hipMemcpyHostToDevice, s));
   launch_crop_count_multi(s, (int)map->n, (int)n, ws + o_args, map->pts.as<float4>(), (uint32_t*)(ws + o_cnt),
                           (uint32_t*)(ws + o_off), (uint32_t*)(ws + o_tot));
   HIPC(hipGetLastError());
-  uint32_t* htot = reinterpret_cast<uint32_t*>(h + n * ab);
   HIPC(hipMemcpyAsync(htot, ws + o_tot, n * 4, hipMemcpyDeviceToHost, s));
   HIPC(hipStreamSynchronize(s));
-  // a batch whose references are the crops (pair i: reference i), readings from the host
-  std::vector<aicp_pair> pairs(n);
-  for (size_t i = 0; i < n; ++i) {
+  size_t m = 0;
+  while (m < n && htot[m] != 0) ++m;
+  if (!m) return AICP_OK;
+  std::vector<aicp_pair> pairs(m);
+  for (size_t i = 0; i < m; ++i) {
     const aicp_cloud& c = readings[i];
-    if (htot[i] == 0) FAIL(AICP_ERR_INVALID, "reading " + std::to_string(i) + ": empty map crop");
     aicp_pair& p = pairs[i];
     p = aicp_pair{};
     p.ref = c.pts;  // not read (references on the device)
@@ -2338,22 +2404,55 @@ int aicp_hip_map_register_batch(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, c
     p.read_stride = c.stride;
     for (int k = 0; k < 3; ++k) {
       p.ref_origin[k] = poses[16 * i + 12 + k];
-      p.read_origin[k] = c.origin[k];
+      p.read_origin[k] = read_origins ? read_origins[3 * i + k] : c.origin[k];
     }
   }
   if (!ctx->mapbatch) ctx->mapbatch = new aicp_hip_batch();
   aicp_hip_batch* B = ctx->mapbatch;
-  int rc = upload_pairs(ctx, pairs.data(), n, B, true);
+  int rc = upload_pairs(ctx, pairs.data(), m, B, true);
   if (rc) return rc;
   uint32_t* hbase = htot + n;
-  for (size_t i = 0; i < n; ++i) hbase[i] = B->rdesc[i].ref_off;
-  HIPC(hipMemcpyAsync(ws + o_base, hbase, n * 4, hipMemcpyHostToDevice, s));
-  launch_crop_scatter_multi(s, (int)map->n, (int)n, ws + o_args, map->pts.as<float4>(), (const uint32_t*)(ws + o_off),
+  for (size_t i = 0; i < m; ++i) hbase[i] = B->rdesc[i].ref_off;
+  HIPC(hipMemcpyAsync(ws + o_base, hbase, m * 4, hipMemcpyHostToDevice, s));
+  // (crops m .. n - 1 are not scattered: their bases are not set)
+  launch_crop_scatter_multi(s, (int)map->n, (int)m, ws + o_args, map->pts.as<float4>(), (const uint32_t*)(ws + o_off),
                             (const uint32_t*)(ws + o_base), B->ref_raw.as<float4>());
   HIPC(hipGetLastError());
-  aicp_icp_config c = *cfg;
-  c.trimmed_ratio = aicp_hip_autotune_ratio(50.0f);  // octree_overlap_ = 50.0 (app.cpp:123-127)
-  return run_batch(ctx, B, &c, 0.0, AICP_RUN_ICP | (flags & AICP_RUN_TIME_NN), out_T, stats, nullptr);
+  *n_ok = m;
+  return AICP_OK;
+}
+
+}  // namespace rt
+}  // namespace aicp
+
+extern "C" {
+
+// localize_against_built_map's batch (app.cpp:60-69, 123-135): as aicp_hip_map_register_batch, but
+// the overlap is not bypassed: with AICP_RUN_OVERLAP every reading's octree overlap against its
+// own device crop gives its ratio. run_batch marks and counts the reference side on ctx->stream,
+// behind the crop scatter in stream order, and the tree streams wait for ev[14], recorded on
+// ctx->stream behind the scatter too, so device-written references need no further ordering.
+int aicp_hip_map_align_batch(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_hip_map* map, float mn,
+                             float mx, const aicp_cloud* readings, const float* poses, size_t n, double resolution,
+                             int flags, float* out_T, aicp_icp_stats* stats) {
+  if (!ctx || !cfg || !map || !readings || !poses || !out_T || n == 0) return AICP_ERR_INVALID;
+  if (flags & ~(AICP_RUN_OVERLAP | AICP_RUN_ICP | AICP_RUN_TIME_NN)) FAIL(AICP_ERR_INVALID, "map align batch: flags");
+  const int run_flags = AICP_RUN_ICP | (flags & (AICP_RUN_OVERLAP | AICP_RUN_TIME_NN));
+  if ((run_flags & AICP_RUN_OVERLAP) && !(resolution > 0)) FAIL(AICP_ERR_INVALID, "resolution");
+  for (size_t i = 0; i < n; ++i) {
+    const aicp_cloud& c = readings[i];
+    if (!c.pts || c.n == 0 || c.stride < 12 || (c.stride % 4) || c.n > (uint64_t)INT32_MAX)
+      FAIL(AICP_ERR_INVALID, "invalid reading " + std::to_string(i));
+  }
+  const int rc = check_cfg(ctx, cfg, run_flags);
+  if (rc) return rc;
+  return map_batch(ctx, cfg, map, mn, mx, readings, poses, n, resolution, run_flags, out_T, stats);
+}
+
+int aicp_hip_map_capacity(const aicp_hip_map* map, size_t* n) {
+  if (!map || !n) return AICP_ERR_INVALID;
+  *n = map->pts.cap / 16;
+  return AICP_OK;
 }
 
 int aicp_hip_map_merge(aicp_hip_ctx* ctx, aicp_hip_map* map, const float* pts, size_t n, size_t stride,

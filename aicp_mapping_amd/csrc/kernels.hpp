@@ -305,13 +305,37 @@ struct LocRec {         // one reading's decisions (the host reads a window's re
 };
 // debug working mode (app.cpp:87-96): pts := initialT_ * pts in place (k_transform's expression)
 // and origin := translation of initialT_ * prior pose (k_debug_prep's)
-void launch_loc_move(hipStream_t s, int n, const LocState* S, double* origin, float4* pts);
+// (initT: 16 floats on the device, LocState::initT / BmState::initT)
+void launch_loc_move(hipStream_t s, int n, const float* initT, double* origin, float4* pts);
 // one thread walks the window's np readings in order (app.cpp:366-373, 414, 469-493): status,
 // drop test, count, corrected origin, initialT_ = correction * initialT_, merge / re-filter flags
 void launch_loc_commit(hipStream_t s, int np, const PairState* st, const float* T, const double* origin,
                        LocRules r, LocState* S, LocRec* rec);
 // out = T * in (the map's tail: transformPointCloud(reading, correction), k_transform's expression)
 void launch_loc_merge(hipStream_t s, int n, const float* T, const float4* in, float4* out);
+
+// ---- App's localization stream on the map it built (kernels_built_map.hip, built_map.cpp) ----
+struct BmState {        // the stream's state on the device
+  float initT[16];      // initialT_ (app.cpp:414), column-major
+  int32_t acc;          // readings accepted since the last reference (app.cpp:383-391)
+  int32_t append;       // the last window's append plan: the reading that goes to the map's tail, -1: none
+  int32_t pad[2];
+};
+struct BmRules {        // aicp_built_map_params as the commit kernel reads them
+  int32_t freq;
+  float max_corr;
+  int32_t overlap;      // the batch ran the overlap: an overlap error fails the reading
+};
+struct BmRec {          // one reading's decisions (the host reads a window's records once)
+  int32_t status;       // AICP_* of its registration; -1: after the reading that ended the stream
+  int32_t accepted, is_reference, pad;
+  double corrected_origin[3];
+};
+// one thread walks the window's np readings in order (app.cpp:366-391, 414): status, drop test
+// (from the first reading on), corrected origin, ++acc, acc == freq: reference (append plan) and
+// acc = 0, initialT_ = correction * initialT_
+void launch_bm_commit(hipStream_t s, int np, const PairState* st, const float* T, const double* origin, BmRules r,
+                      BmState* S, BmRec* rec);
 
 // ---- pre-filter (kernels_prefilter.hip): regionGrowingUniformPlaneSegmentationFilter -------
 constexpr int kPfMaxNbrs = 16;  // RegionGrowing neighbours per point (edge mask bits)

@@ -20,10 +20,10 @@ namespace aicp {
 // pcl::transformPointCloud's float order (apply4, as k_transform), in place; thread 0 of block 0
 // also makes the prior pose initialT_ * prior pose, of which only the translation is used
 // (fromMatrix4fToIsometry3d, common.cpp:4-23: corrected_origin's arithmetic, as k_debug_prep).
-__global__ __launch_bounds__(256) void k_loc_move(int n, const LocState* __restrict__ S, double* origin,
+__global__ __launch_bounds__(256) void k_loc_move(int n, const float* __restrict__ initT, double* origin,
                                                   float4* pts) {
   float Tl[16];
-  for (int k = 0; k < 16; ++k) Tl[k] = S->initT[k];
+  for (int k = 0; k < 16; ++k) Tl[k] = initT[k];
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     double o[3];
     corrected_origin(Tl, origin, o);
@@ -93,8 +93,8 @@ __global__ __launch_bounds__(256) void k_loc_merge(int n, const float* __restric
   out[i] = make_float4(q[0], q[1], q[2], 1.f);
 }
 
-void launch_loc_move(hipStream_t s, int n, const LocState* S, double* origin, float4* pts) {
-  k_loc_move<<<(unsigned)std::max(1, (n + 255) / 256), 256, 0, s>>>(n, S, origin, pts);
+void launch_loc_move(hipStream_t s, int n, const float* initT, double* origin, float4* pts) {
+  k_loc_move<<<(unsigned)std::max(1, (n + 255) / 256), 256, 0, s>>>(n, initT, origin, pts);
 }
 void launch_loc_commit(hipStream_t s, int np, const PairState* st, const float* T, const double* origin, LocRules r,
                        LocState* S, LocRec* rec) {

@@ -69,36 +69,6 @@ bool valid_params(const aicp_localization_params* p) {
          p->max_correction_magnitude == p->max_correction_magnitude;
 }
 
-// box frame of getPointsInOrientedBox (filteringUtils.cpp:619-637), as aicp_hip_map_register_batch
-void crop_frame(const float origin[16], float inv[9], float t[3]) {
-  float R[9], rpy[3];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) R[3 * r + c] = origin[c * 4 + r];
-  for (int q = 0; q < 3; ++q) t[q] = origin[12 + q];
-  crop_rotation_inverse(R, inv, rpy);
-}
-
-// room for `add` more points behind the map's n: the copying growth of aicp_hip_map_merge (a
-// failed growth leaves the map as it was)
-int map_reserve(aicp_hip_ctx* ctx, aicp_hip_map* map, size_t add) {
-  if (map->n + add > (size_t)INT32_MAX) FAIL(AICP_ERR_INVALID, "map merge: more than 2^31 points");
-  const size_t need = (map->n + add) * 16;
-  if (need <= map->pts.cap && map->pts.p) return AICP_OK;
-  hipStream_t s = ctx->stream;
-  DevBuf nb;
-  HIPC(ensure(nb, std::max(need, 2 * map->pts.cap)));
-  hipError_t e = map->n ? hipMemcpyAsync(nb.p, map->pts.p, map->n * 16, hipMemcpyDeviceToDevice, s) : hipSuccess;
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(s);
-    release(nb);
-    FAIL(AICP_ERR_HIP, std::string("map merge: grow copy: ") + hipGetErrorString(e));
-  }
-  release(map->pts);
-  map->pts = nb;
-  return AICP_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -183,10 +153,6 @@ int aicp_hip_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, con
     HIPC(hipMemcpyAsync(dS, hS, sizeof(LocState), hipMemcpyHostToDevice, s));
   }
   HIPC(hipEventRecord(L->ev_begin, s));
-  if (!ctx->mapbatch) ctx->mapbatch = new aicp_hip_batch();
-  aicp_hip_batch* B = ctx->mapbatch;
-  const size_t ab = crop_args_bytes();
-  std::vector<aicp_pair> pairs;
   std::vector<aicp_icp_stats> stats;
   int windows = 0, merges = 0, refilters = 0, status = AICP_OK;
   uint64_t n_clouds = 0;  // the host's mirror of LocState::n_clouds, from the records
@@ -195,61 +161,20 @@ int aicp_hip_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, con
   while (p < n && !status) {
     const size_t w = aicp_hip_localization_window(n_clouds, prm, n - p);
     const size_t map_n = map->n;
-    // every reading's crop size (one launch pair for the window)
-    const size_t tiles = crop_tiles(map_n);
-    const size_t o_cnt = (w * ab + 255) & ~size_t(255), o_off = o_cnt + w * tiles * 4, o_tot = o_off + w * tiles * 4,
-                 o_base = o_tot + w * 4, total_b = o_base + w * 4;
-    HIPC(ensure(ctx->crop_ws, total_b));
-    HIPC(ensure(ctx->pin_crop, w * ab + 2 * w * 4));
-    char* ws = ctx->crop_ws.as<char>();
-    char* h = ctx->pin_crop.as<char>();
-    uint32_t* htot = reinterpret_cast<uint32_t*>(h + w * ab);
-    for (size_t i = 0; i < w; ++i) {
-      float inv[9], t[3];
-      crop_frame(poses + 16 * (p + i), inv, t);
-      pack_crop_args(inv, t, prm->crop_min, prm->crop_max, h + i * ab);
-      htot[i] = 0;
-    }
-    if (map_n) {
-      HIPC(hipMemcpyAsync(ws, h, w * ab, hipMemcpyHostToDevice, s));
-      launch_crop_count_multi(s, (int)map_n, (int)w, ws, map->pts.as<float4>(), (uint32_t*)(ws + o_cnt),
-                              (uint32_t*)(ws + o_off), (uint32_t*)(ws + o_tot));
-      HIPC(hipGetLastError());
-      HIPC(hipMemcpyAsync(htot, ws + o_tot, w * 4, hipMemcpyDeviceToHost, s));
-      HIPC(hipStreamSynchronize(s));
-    }
-    // an empty crop ends the stream at its reading; the readings before it still run
+    // every reading's crop, straight into the batch's reference array (as the batch call). An
+    // empty crop ends the stream at its reading; the wr readings before it still run
     size_t wr = 0;
-    while (wr < w && htot[wr] != 0) ++wr;
+    const uint32_t* htot = nullptr;
+    rc = map_crop_pairs(ctx, map, prm->crop_min, prm->crop_max, readings + p, poses + 16 * p, w, nullptr, &wr, &htot);
+    if (rc) return rc;
     if (wr) {
-      pairs.assign(wr, aicp_pair{});
+      aicp_hip_batch* B = ctx->mapbatch;
       double* horg = reinterpret_cast<double*>(lp + o_org);
-      for (size_t i = 0; i < wr; ++i) {
-        const aicp_cloud& cl = readings[p + i];
-        aicp_pair& q = pairs[i];
-        q.ref = cl.pts;  // not read (references on the device)
-        q.n_ref = htot[i];
-        q.ref_stride = 16;
-        q.read = cl.pts;
-        q.n_read = cl.n;
-        q.read_stride = cl.stride;
-        for (int k = 0; k < 3; ++k) {
-          q.ref_origin[k] = poses[16 * (p + i) + 12 + k];
-          q.read_origin[k] = cl.origin[k];
-          horg[3 * i + k] = cl.origin[k];
-        }
-      }
-      rc = upload_pairs(ctx, pairs.data(), wr, B, true);
-      if (rc) return rc;
-      uint32_t* hbase = htot + w;
-      for (size_t i = 0; i < wr; ++i) hbase[i] = B->rdesc[i].ref_off;
-      HIPC(hipMemcpyAsync(ws + o_base, hbase, wr * 4, hipMemcpyHostToDevice, s));
+      for (size_t i = 0; i < wr; ++i)
+        for (int k = 0; k < 3; ++k) horg[3 * i + k] = readings[p + i].origin[k];
       HIPC(hipMemcpyAsync(L->origin.p, horg, wr * 24, hipMemcpyHostToDevice, s));
-      launch_crop_scatter_multi(s, (int)map_n, (int)wr, ws, map->pts.as<float4>(), (const uint32_t*)(ws + o_off),
-                                (const uint32_t*)(ws + o_base), B->ref_raw.as<float4>());
-      HIPC(hipGetLastError());
       if (debug) {  // (one reading per window) moved by the device's initialT_, its prior pose too
-        launch_loc_move(s, (int)B->desc[0].n_read, dS, L->origin.as<double>(),
+        launch_loc_move(s, (int)B->desc[0].n_read, dS->initT, L->origin.as<double>(),
                         B->read_raw.as<float4>() + B->desc[0].read_off);
         HIPC(hipGetLastError());
       }

@@ -257,12 +257,18 @@ struct SeqState;  // sequence.cpp
 void seq_state_free(SeqState* s);
 struct LocBufs;  // localization.cpp
 void loc_bufs_free(LocBufs* s);
+struct BmBufs;  // built_map.cpp
+void bm_bufs_free(BmBufs* s);
 
 // the batch pipeline (aicp_hip.cpp), for the entry points that compose a batch on the device
 int upload_pairs(aicp_hip_ctx* ctx, const aicp_pair* pairs, size_t n, aicp_hip_batch* B, bool refs_on_device,
                  bool skip_refs = false, bool skip_reads = false, bool nosync = false);
 int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, double res, int flags, float* outT,
               aicp_icp_stats* stats, float* out_overlap);
+// the device-resident map (aicp_hip.cpp), for the streams that grow it and crop it into a batch
+int map_reserve(aicp_hip_ctx* ctx, aicp_hip_map* map, size_t add);
+int map_crop_pairs(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float mx, const aicp_cloud* readings,
+                   const float* poses, size_t n, const double* read_origins, size_t* n_ok, const uint32_t** counts);
 
 }  // namespace rt
 }  // namespace aicp
@@ -309,6 +315,7 @@ struct aicp_hip_ctx {
   hipEvent_t pf_ev[8] = {};
   aicp::rt::SeqState* seq = nullptr;  // aicp_hip_sequence_run's buffers (sequence.cpp), kept across calls
   aicp::rt::LocBufs* loc = nullptr;    // aicp_hip_map_sequence_run's buffers (localization.cpp), kept across calls
+  aicp::rt::BmBufs* bm = nullptr;      // aicp_hip_built_map_sequence_run's buffers (built_map.cpp), kept across calls
   aicp_hip_batch* mapbatch = nullptr;  // aicp_hip_map_register_batch's batch buffers
   aicp::rt::DevBuf crop_ws;            // its crop work space
   aicp::rt::DevBuf ovl_sp, ovl_keys;   // sparse overlap: clouds, counts, offsets / key words

@@ -40,6 +40,13 @@ class PriorMap:
         L.lib.aicp_hip_map_size(self.h, C.byref(n))
         return n.value
 
+    @property
+    def capacity(self) -> int:
+        """Points the map's buffer holds before the next append has to grow it (aicp_hip_map_capacity)."""
+        n = C.c_size_t()
+        L.lib.aicp_hip_map_capacity(self.h, C.byref(n))
+        return n.value
+
     def getCloud(self) -> np.ndarray:
         """The map's points (AlignedCloud::getCloud), (N, 3) float32."""
         n = len(self)

@@ -532,6 +532,91 @@ int aicp_hip_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, con
                               aicp_localization_result* out /* n */, size_t* n_done);
 int aicp_hip_last_localization_timing(const aicp_hip_ctx* ctx, aicp_localization_timing* out);
 
+/* ---- localization against the map App has built itself (localize_against_built_map) ----------
+ * The batch: as aicp_hip_map_register_batch (crops straight into the batch's reference array, an
+ * empty crop is AICP_ERR_INVALID), but the overlap is not bypassed (app.cpp:123-135). flags:
+ * AICP_RUN_OVERLAP | AICP_RUN_TIME_NN (AICP_RUN_ICP is always on). With AICP_RUN_OVERLAP pair i's
+ * octree overlap at `resolution` is computed between its device crop (sensor origin
+ * poses[16 i + 12 .. 14]) and its reading (sensor origin readings[i].origin), its ratio is
+ * aicp_hip_autotune_ratio(overlap), and stats[i].overlap_percent / trimmed_ratio / overlap_keys are
+ * filled as aicp_hip_align_batch fills them. Without it the ratio is cfg->trimmed_ratio and
+ * overlap_percent is -1. */
+int aicp_hip_map_align_batch(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_hip_map* map, float min,
+                             float max, const aicp_cloud* readings, const float* poses /* 16*n */, size_t n,
+                             double resolution, int flags, float* out_T /* 16*n */,
+                             aicp_icp_stats* stats /* n, nullable */);
+/* points the map's buffer holds before the next append has to grow it (a map is created with
+ * room for its cloud only; a growth copies the map into a buffer of at least twice the size) */
+int aicp_hip_map_capacity(const aicp_hip_map* map, size_t* n);
+
+/* App's stream in this mode (processCloud app.cpp:282-414 with setReference app.cpp:60-69). The
+ * caller creates the map from App's first cloud, already pre-filtered (app.cpp:293-310:
+ * aligned_map_ = first cloud). State: the map, acc = 0 (readings accepted since the last
+ * reference), initialT_ = I. For reading i with prior pose P_i:
+ *   1. reference = getPointsInOrientedBox(map, crop_min, crop_max, P_i), reference pose P_i as
+ *      given (setReference runs before setAndFilterReading, app.cpp:333, 337: in debug mode the
+ *      crop and the reference's sensor origin use the unmoved pose). An empty crop is
+ *      AICP_ERR_INVALID for that reading;
+ *   2. AICP_SEQ_DEBUG only: reading = transformPointCloud(reading, initialT_) (float) and its
+ *      sensor origin becomes the translation of initialT_ * prior pose (app.cpp:87-96);
+ *   3. with AICP_RUN_OVERLAP the octree overlap at `resolution` between the crop (origin: the
+ *      translation of P_i as given) and the reading (origin: its, possibly moved, prior-pose
+ *      translation) and the auto-tuned ratio from it (app.cpp:132-135); without, cfg->trimmed_ratio.
+ *      Then ICP. A non-zero status ends the stream at that reading (app.cpp:210); everything before
+ *      it stays committed;
+ *   4. the reading is dropped when some |T(k,3)| > max_correction_magnitude (app.cpp:366-373, float
+ *      compare). getNbClouds() != 0 always holds (the graph holds the first cloud), so the first
+ *      reading can be dropped too. A dropped reading changes nothing;
+ *   5. accepted: corrected_origin as aicp_hip_sequence_run computes it, ++acc; when acc ==
+ *      reference_update_frequency the reading becomes a reference (app.cpp:383-391, 458-465):
+ *      map += transformPointCloud(reading, correction) (the moved reading in debug mode), acc = 0;
+ *      initialT_ = correction * initialT_ (app.cpp:414);
+ *   6. the map is never re-filtered (app.cpp:487 is guarded by localize_against_prior_map).
+ * Readings between two map changes are independent and run as one window through the batch above
+ * (aicp_hip_built_map_window); the decisions 4-5 are taken on the device, the reference reading
+ * is appended from the batch's device copy by the device's own correction, and the host reads one
+ * record per reading once per window. No reading crosses the bus a second time. */
+typedef struct {
+  int32_t reference_update_frequency; /* 5 */
+  float max_correction_magnitude;     /* 1.0 */
+  float crop_min, crop_max;           /* -15, 15: the crop cube around the prior pose */
+  double resolution;                  /* 0.2: the overlap's octree */
+  int32_t flags;                      /* AICP_RUN_OVERLAP | AICP_SEQ_DEBUG | AICP_RUN_TIME_NN; default AICP_RUN_OVERLAP */
+  int32_t pad;
+} aicp_built_map_params;
+/* 128 bytes, no implicit padding */
+typedef struct {
+  int32_t status;          /* AICP_* of this reading's registration */
+  int32_t accepted;        /* 0: dropped */
+  int32_t is_reference;    /* 1: appended to the map (the reference_update_frequency-th accepted) */
+  int32_t pad;
+  uint64_t map_points;     /* size of the map it was cropped from */
+  uint64_t crop_points;    /* size of its reference */
+  double corrected_origin[3]; /* as aicp_sequence_result (accepted readings) */
+  aicp_icp_stats icp;
+} aicp_built_map_result;
+typedef struct {
+  int32_t windows;         /* batches run */
+  int32_t appends;         /* references appended to the map */
+  double wall_ms;          /* the whole call */
+  double device_ms;        /* first crop enqueued -> last append done (HIP events) */
+} aicp_built_map_timing;
+void aicp_hip_default_built_map_params(aicp_built_map_params* out);
+/* Host-only: the length of the next window when acc readings have been accepted since the last
+ * reference and `remaining` are left: debug mode 1; else min(remaining, 4096,
+ * reference_update_frequency - acc). If every reading of the window is accepted the map changes
+ * exactly after its last one; if some are dropped it does not change and the next window is
+ * shorter; nothing is ever run twice. 0 for invalid parameters, acc >= reference_update_frequency
+ * or remaining = 0. */
+size_t aicp_hip_built_map_window(uint64_t acc, const aicp_built_map_params* prm, size_t remaining);
+/* readings / poses / out_T / out / n_done as aicp_hip_map_sequence_run. The map is updated in place
+ * (a failed growth leaves it as it was). */
+int aicp_hip_built_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_built_map_params* prm,
+                                    aicp_hip_map* map, const aicp_cloud* readings, const float* poses /* 16*n */,
+                                    size_t n, float* out_T /* 16*n */, aicp_built_map_result* out /* n */,
+                                    size_t* n_done);
+int aicp_hip_last_built_map_timing(const aicp_hip_ctx* ctx, aicp_built_map_timing* out);
+
 /* ---- device-resident batches (inputs uploaded once, run many times) ----------------------- */
 int aicp_hip_batch_upload(aicp_hip_ctx* ctx, const aicp_pair* pairs, size_t n_pairs,
                           aicp_hip_batch** out);

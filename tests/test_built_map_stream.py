@@ -1,0 +1,390 @@
+"""App's localization stream on the map it has built itself (aicp_hip_map_align_batch,
+aicp_hip_built_map_sequence_run; BuiltMap) against the host restatement of
+tests/built_map_reference.py (the oracle's crop, overlap, ratio, ICP, transform, corrected origin
+and Matrix4f product) and against the hand composition of the existing entry points (crop to the
+host, align_batch, merge), window by window. Fixture and expected patterns:
+tests/test_built_map_cpu.py pins them on the CPU."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import built_map_reference as br
+from aicp_mapping_amd import synthetic as sy
+
+pytestmark = pytest.mark.gpu
+
+MN, MX, RES = br.PARAMS["crop_min"], br.PARAMS["crop_max"], br.PARAMS["resolution"]
+
+
+@pytest.fixture(scope="module")
+def L():
+    import aicp_mapping_amd._lib as lib
+
+    return lib
+
+
+@pytest.fixture(scope="module")
+def ctx(L):
+    c = L.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def world(oracle):
+    first = br.make_first_cloud(oracle)
+    reads, poses, origins = br.make_stream()
+    return first, reads, poses, origins
+
+
+@pytest.fixture(scope="module")
+def free_robot(oracle, world):
+    """The free-running robot-mode replay of the fixture, computed once (read only)."""
+    first, reads, poses, origins = world
+    return br.replay(oracle, first, reads, poses, origins, **br.PARAMS)
+
+
+def params(L, **kw):
+    return L.default_built_map_params(**dict(br.PARAMS, **kw))
+
+
+def run(ctx, first, reads, poses, prm, cfg=None, raise_on_error=True):
+    from aicp_mapping_amd.built_map import BuiltMap
+
+    bm = BuiltMap(ctx, first)
+    T, res, done, rc = bm.sequence_run(reads, poses, cfg=cfg, params=prm, raise_on_error=raise_on_error)
+    final = bm.getCloud()
+    bm.free()
+    return T, res, done, rc, final
+
+
+def check_record(i, d_icp, r, T):
+    """One registration against the replay's record of it: the overlap's key counts, percentage
+    and ratio exactly, the same iterations and NN touch counts, T within 1e-6 rad / 1e-5 m."""
+    assert d_icp["overlap_keys"] == r["counts"], (i, d_icp["overlap_keys"], r["counts"])
+    assert d_icp["overlap_percent"] == np.float32(r["overlap"]), (i, d_icp["overlap_percent"], r["overlap"])
+    assert d_icp["trimmed_ratio"] == r["ratio"], (i, d_icp["trimmed_ratio"], r["ratio"])
+    assert d_icp["iterations"] == r["stats"].iterations, (i, d_icp["iterations"], r["stats"].iterations)
+    assert (d_icp["nn_points_touched"], d_icp["nn_nodes_touched"]) == (r["stats"].nn_points_touched,
+                                                                       r["stats"].nn_nodes_touched), i
+    rr, tt = sy.rot_err(r["T"], T)
+    print(f"reading {i}: drot {rr:.3e} rad dt {tt:.3e} m")
+    assert rr < 1e-6 and tt < 1e-5, (i, rr, tt)
+
+
+def check_against_replay(oracle, first, reads, poses, origins, prm, T, res, final, cfg=None, free=None):
+    """The free-running replay takes the same decisions; the forced replay (state from the
+    device's corrections) sees the same maps and crops, the same overlap keys and ratio, registers
+    in the same iterations with the same NN touch counts, and ends with the same map, bit for bit."""
+    n = len(res)
+    kw = dict(br.PARAMS, reference_update_frequency=prm.reference_update_frequency, debug=bool(prm.flags & 8),
+              overlap=bool(prm.flags & 1), cfg=cfg)
+    if free is None:
+        free, _ = br.replay(oracle, first, reads[:n], poses[:n], origins[:n], **kw)
+    for k in ("status", "accepted", "is_reference"):
+        assert [r[k] for r in res] == [r[k] for r in free[:n]], k
+    forced, fmap = br.replay(oracle, first, reads[:n], poses[:n], origins[:n], forced_T=T, **kw)
+    for i, (d, r) in enumerate(zip(res, forced)):
+        for k in ("status", "accepted", "is_reference", "map_points", "crop_points"):
+            assert d[k] == r[k], (i, k, d[k], r[k])
+        if r["status"]:
+            continue
+        check_record(i, d["icp"], r, T[i])
+        if r["accepted"]:
+            np.testing.assert_allclose(d["corrected_origin"], r["corrected_origin"], rtol=0, atol=1e-9)
+    np.testing.assert_array_equal(final, fmap)
+    return forced
+
+
+def host_pairs(bm, reads, poses):
+    """The batch from existing entry points: every crop to the host, then uploaded again."""
+    out = []
+    for r, P in zip(reads, poses):
+        crop = bm.crop(MN, MX, P)
+        out.append(dict(ref=crop, read=r, ref_origin=np.asarray(P, np.float32)[:3, 3].astype(np.float64),
+                        read_origin=np.asarray(P, np.float64)[:3, 3]))
+    return out
+
+
+# ---- the batch entry -------------------------------------------------------------------------
+@pytest.mark.parametrize("path", [0, 1], ids=["voxel-maps", "sorted-keys"])
+def test_batch_entry_equals_oracle(ctx, L, world, free_robot, path):
+    """Readings 0-2 against the first cloud (the robot-mode replay's first window): both overlap
+    paths count the device-written crops exactly as the oracle counts the host crop."""
+    from aicp_mapping_amd.built_map import BuiltMap
+
+    first, reads, poses, origins = world
+    bm = BuiltMap(ctx, first)
+    with ctx.options(overlap_path=path):
+        T, st, rc = bm.align_batch(reads[:3], poses[:3], MN, MX, resolution=RES,
+                                   flags=L.AICP_RUN_OVERLAP | L.AICP_RUN_TIME_NN)
+    bm.free()
+    assert rc == 0
+    for i in range(3):
+        r = free_robot[0][i]
+        assert r["map_points"] == len(first)
+        assert st[i]["status"] == 0
+        check_record(i, st[i], r, T[i])
+
+
+def test_batch_entry_equals_existing_entry_points(ctx, L, world):
+    """Bit for bit the composition crop-to-host + align_batch (results do not depend on how a
+    batch was put together), with the overlap and without it."""
+    from aicp_mapping_amd.built_map import BuiltMap
+
+    first, reads, poses, origins = world
+    bm = BuiltMap(ctx, first)
+    pairs = host_pairs(bm, reads[:3], poses[:3])
+    for path in (0, 1):
+        with ctx.options(overlap_path=path):
+            T, st, rc = bm.align_batch(reads[:3], poses[:3], MN, MX, resolution=RES, flags=L.AICP_RUN_OVERLAP)
+            Tc, stc, rcc = ctx.align_batch(pairs, resolution=RES, flags=L.AICP_RUN_OVERLAP | L.AICP_RUN_ICP)
+        assert rc == rcc == 0
+        np.testing.assert_array_equal(T, Tc)
+        assert st == stc, path
+        assert all(s["overlap_keys"][2] > 0 and 25.0 < s["overlap_percent"] < 70.0 for s in st)
+    # without the overlap: the chain's ratio, overlap_percent -1
+    cfg = L.default_config(trimmed_ratio=0.6)
+    T, st, rc = bm.align_batch(reads[:3], poses[:3], MN, MX, cfg=cfg, flags=0)
+    Tc, stc, rcc = ctx.align_batch(pairs, cfg=cfg, flags=L.AICP_RUN_ICP)
+    assert rc == rcc == 0
+    np.testing.assert_array_equal(T, Tc)
+    assert st == stc
+    assert all(s["trimmed_ratio"] == np.float32(0.6) and s["overlap_percent"] == -1.0 for s in st)
+    # and aicp_hip_map_register_batch is the same batch at the ratio of a 50 % overlap
+    Tr, strr, rcr = bm.register_batch(reads[:3], poses[:3], MN, MX)
+    T5, st5, rc5 = bm.align_batch(reads[:3], poses[:3], MN, MX, cfg=L.default_config(trimmed_ratio=0.5), flags=0)
+    np.testing.assert_array_equal(Tr, T5)
+    assert strr == st5
+    bm.free()
+
+
+def test_batch_entry_rejects_bad_arguments(ctx, L, world):
+    from aicp_mapping_amd.built_map import BuiltMap
+
+    first, reads, poses, origins = world
+    bm = BuiltMap(ctx, first)
+    far = np.array(poses[1], np.float64)
+    far[:3, 3] += (200.0, 0.0, 0.0)
+    T, st, rc = bm.align_batch(reads[:2], [poses[0], far], MN, MX, resolution=RES, raise_on_error=False)
+    assert rc == L.AICP_ERR_INVALID and "reading 1: empty map crop" in ctx.last_error()
+    for kw in (dict(flags=L.AICP_SEQ_DEBUG), dict(flags=16), dict(resolution=0.0), dict(resolution=float("nan"))):
+        T, st, rc = bm.align_batch(reads[:1], poses[:1], MN, MX, raise_on_error=False,
+                                   **dict(dict(resolution=RES, flags=L.AICP_RUN_OVERLAP), **kw))
+        assert rc == L.AICP_ERR_INVALID, kw
+    with pytest.raises(L.AicpError):
+        bm.align_batch(reads[:1], poses[:1], MN, MX, resolution=0.0)
+    np.testing.assert_array_equal(bm.getCloud(), first)
+    bm.free()
+
+
+# ---- the stream ------------------------------------------------------------------------------
+@pytest.mark.parametrize("debug", [False, True], ids=["robot", "debug"])
+def test_stream_equals_replay(ctx, oracle, L, world, free_robot, debug):
+    first, reads, poses, origins = world
+    prm = params(L, debug=debug)
+    T, res, done, rc, final = run(ctx, first, reads, poses, prm)
+    assert rc == 0 and done == 10
+    tm = ctx.last_built_map_timing()
+    check_against_replay(oracle, first, reads, poses, origins, prm, T, res, final,
+                         free=None if debug else free_robot[0])
+    if debug:
+        assert [r["accepted"] for r in res] == [1] * 10
+        assert [i for i, r in enumerate(res) if r["is_reference"]] == [2, 5, 8]
+    else:
+        assert [r["accepted"] for r in res] == [1, 1, 1, 1, 0, 1, 1, 1, 1, 1]
+        assert [i for i, r in enumerate(res) if r["is_reference"]] == [2, 6, 9]
+        assert [r["map_points"] for r in res] == [59522] * 3 + [62522] * 4 + [65522] * 3
+    assert len(final) == 68522
+    # windows of 3, 3, 1, 3 readings in robot mode, one reading each in debug mode
+    assert (tm["windows"], tm["appends"]) == (10 if debug else 4, 3)
+    assert tm["wall_ms"] >= tm["device_ms"] > 0
+
+
+def compose(ctx, L, first, reads, poses, prm, cfg=None):
+    """The stream from the existing entry points, one window at a time: every crop to the host and
+    up again inside align_batch, the drop test and the count on the host, every reference reading
+    uploaded a second time by merge."""
+    from aicp_mapping_amd.prior_map import PriorMap
+
+    pm = PriorMap(ctx, first)
+    n, p, acc = len(reads), 0, 0
+    Ts, stats, flags = [], [], []
+    mc = np.float32(prm.max_correction_magnitude)
+    while p < n:
+        w = L.built_map_window(acc, prm, n - p)
+        T, st, rc = ctx.align_batch(host_pairs(pm, reads[p:p + w], poses[p:p + w]), cfg=cfg, resolution=prm.resolution,
+                                    flags=L.AICP_RUN_OVERLAP | L.AICP_RUN_ICP)
+        assert rc == 0
+        for i in range(w):
+            Ts.append(T[i])
+            stats.append(st[i])
+            f = dict(accepted=0, is_reference=0)
+            flags.append(f)
+            if any(abs(T[i][k, 3]) > mc for k in range(3)):
+                continue
+            f["accepted"] = 1
+            acc += 1
+            if acc == prm.reference_update_frequency:
+                assert i == w - 1
+                pm.merge(reads[p + i], T[i])
+                f["is_reference"] = 1
+                acc = 0
+        p += w
+    final = pm.getCloud()
+    pm.free()
+    return np.stack(Ts), stats, flags, final
+
+
+def test_robot_mode_equals_hand_composition(ctx, L, world):
+    first, reads, poses, origins = world
+    prm = params(L)
+    T, res, done, rc, final = run(ctx, first, reads, poses, prm)
+    assert rc == 0 and done == 10
+    Tc, stc, fc, finalc = compose(ctx, L, first, reads, poses, prm)
+    np.testing.assert_array_equal(T, Tc)
+    for i in range(10):
+        assert res[i]["icp"] == stc[i], i
+        assert {k: res[i][k] for k in ("accepted", "is_reference")} == fc[i], i
+    np.testing.assert_array_equal(final, finalc)
+    T2, res2, done2, rc2, final2 = run(ctx, first, reads, poses, prm)  # repeatable
+    np.testing.assert_array_equal(T, T2)
+    assert res == res2 and done2 == 10
+    np.testing.assert_array_equal(final, final2)
+
+
+# ---- edge cases ------------------------------------------------------------------------------
+@pytest.mark.parametrize("debug", [False, True], ids=["robot", "debug"])
+def test_first_reading_can_be_dropped(ctx, oracle, L, world, debug):
+    first = world[0]
+    reads, poses, origins = br.make_stream(3, br.JUMP_ON_0)
+    prm = params(L, debug=debug)
+    T, res, done, rc, final = run(ctx, first, reads, poses, prm)
+    assert rc == 0 and done == 3
+    assert abs(T[0][1, 3]) > 0.4
+    assert [r["accepted"] for r in res] == [0, 1, 1] and not any(r["is_reference"] for r in res)
+    check_against_replay(oracle, first, reads, poses, origins, prm, T, res, final)
+    # the dropped reading postponed the reference: one window of 3 and, nothing appended, no more
+    assert ctx.last_built_map_timing()["windows"] == (3 if debug else 1)
+    np.testing.assert_array_equal(final, first)
+
+
+def test_frequency_1_appends_every_accepted_reading(ctx, oracle, L, world):
+    first, reads, poses, origins = world
+    prm = params(L, reference_update_frequency=1)
+    T, res, done, rc, final = run(ctx, first, reads[:6], poses[:6], prm)
+    assert rc == 0 and done == 6
+    assert [r["accepted"] for r in res] == [r["is_reference"] for r in res] == [1, 1, 1, 1, 0, 1]
+    assert [r["map_points"] for r in res] == [59522, 62522, 65522, 68522, 71522, 71522]
+    tm = ctx.last_built_map_timing()
+    assert (tm["windows"], tm["appends"]) == (6, 5) and len(final) == 74522
+    check_against_replay(oracle, first, reads[:6], poses[:6], origins[:6], prm, T, res, final)
+
+
+def test_frequency_beyond_the_stream_is_one_batch(ctx, L, world):
+    from aicp_mapping_amd.built_map import BuiltMap
+
+    first, reads, poses, origins = world
+    T, res, done, rc, final = run(ctx, first, reads, poses, params(L, reference_update_frequency=11))
+    assert rc == 0 and done == 10
+    tm = ctx.last_built_map_timing()
+    assert (tm["windows"], tm["appends"]) == (1, 0)
+    np.testing.assert_array_equal(final, first)
+    assert not any(r["is_reference"] for r in res) and all(r["map_points"] == len(first) for r in res)
+    bm = BuiltMap(ctx, first)
+    Tb, stb, rcb = bm.align_batch(reads, poses, MN, MX, resolution=RES, flags=L.AICP_RUN_OVERLAP)
+    bm.free()
+    assert rcb == 0
+    np.testing.assert_array_equal(T, Tb)
+    assert [r["icp"] for r in res] == stb
+    mc = np.float32(br.PARAMS["max_correction_magnitude"])
+    exp = [int(not any(abs(Tb[i][k, 3]) > mc for k in range(3))) for i in range(10)]
+    assert [r["accepted"] for r in res] == exp and exp[4] == 0
+
+
+def test_first_append_grows_the_map_by_copy(ctx, oracle, L, world):
+    """A map is created with room for its cloud only, so the first reference reading does not fit
+    behind it: the map moves to a larger buffer and its old points arrive there byte for byte."""
+    from aicp_mapping_amd.built_map import BuiltMap
+
+    first, reads, poses, origins = world
+    bm = BuiltMap(ctx, first)
+    assert len(bm) == bm.capacity == len(first)  # no spare capacity
+    T, res, done, rc = bm.sequence_run(reads[:3], poses[:3], params=params(L))
+    assert rc == 0 and done == 3 and res[2]["is_reference"] and ctx.last_built_map_timing()["appends"] == 1
+    assert len(bm) == len(first) + len(reads[2]) and bm.capacity >= 2 * len(first)  # grown, to at least twice
+    final = bm.getCloud()
+    assert final[:len(first)].tobytes() == first.tobytes()
+    np.testing.assert_array_equal(final[len(first):], oracle.transform_cloud(T[2], reads[2]))
+    # the next append fits: the buffer stays
+    cap = bm.capacity
+    T, res, done, rc = bm.sequence_run(reads[3:6], poses[3:6], params=params(L, max_correction_magnitude=10.0))
+    assert rc == 0 and res[2]["is_reference"] and bm.capacity == cap and len(bm) == len(first) + 6000
+    assert bm.getCloud()[:len(final)].tobytes() == final.tobytes()
+    bm.free()
+
+
+def test_invalid_parameters_touch_nothing(ctx, L, world):
+    from aicp_mapping_amd.built_map import BuiltMap
+
+    first, reads, poses, origins = world
+    bm = BuiltMap(ctx, first)
+    for kw in (dict(reference_update_frequency=0), dict(flags=16), dict(resolution=0.0),
+               dict(max_correction_magnitude=float("nan"))):
+        T, res, done, rc = bm.sequence_run(reads[:2], poses[:2], params=params(L, **kw), raise_on_error=False)
+        assert rc == L.AICP_ERR_INVALID and done == 0 and res == [], kw
+    with pytest.raises(L.AicpError):
+        bm.sequence_run(reads[:2], poses[:2], params=params(L, reference_update_frequency=0))
+    T, res, done, rc = bm.sequence_run([], [], params=params(L))
+    assert rc == 0 and done == 0
+    assert len(bm) == len(first)
+    bm.free()
+
+
+# ---- error handling --------------------------------------------------------------------------
+def test_stream_ends_at_the_failing_reading(ctx, oracle, L, world):
+    first, reads, poses, origins = world
+    prm = params(L)
+    # reading 1 sits inside the window of readings 0..2: reading 0 is committed, reading 2 is not
+    far = np.array(poses[1], np.float64)
+    far[:3, 3] += (200.0, 0.0, 0.0)
+    poses_far = poses[:1] + [far] + poses[2:]
+    T, res, done, rc, final = run(ctx, first, reads, poses_far, prm, raise_on_error=False)
+    assert rc == L.AICP_ERR_INVALID and done == 2 and len(res) == 2
+    assert [r["status"] for r in res] == [0, L.AICP_ERR_INVALID] and res[1]["crop_points"] == 0
+    assert res[0]["accepted"] == 1 and res[0]["icp"]["iterations"] > 0
+    check_against_replay(oracle, first, reads, poses_far, origins, prm, T, res, final)
+    np.testing.assert_array_equal(final, first)
+    with pytest.raises(L.AicpError) as e:
+        run(ctx, first, reads, poses_far, prm)
+    assert e.value.code == L.AICP_ERR_INVALID
+
+    cfg = L.default_config(nn_max_dist=5.0)
+    shifted = (reads[1] + np.float32([200.0, 0.0, 0.0])).astype(np.float32)
+    reads_bad = reads[:1] + [shifted] + reads[2:]
+    T, res, done, rc, final = run(ctx, first, reads_bad, poses, prm, cfg=cfg, raise_on_error=False)
+    assert rc == L.AICP_ERR_CONVERGENCE and done == 2 and len(res) == 2
+    assert [r["status"] for r in res] == [0, L.AICP_ERR_CONVERGENCE]
+    assert res[1]["crop_points"] > 0 and not res[1]["accepted"] and res[0]["accepted"] == 1
+    check_against_replay(oracle, first, reads_bad, poses, origins, prm, T, res, final,
+                         cfg=oracle.default_config(nn_max_dist=5.0))
+    np.testing.assert_array_equal(final, first)
+    with pytest.raises(L.ConvergenceError):
+        run(ctx, first, reads_bad, poses, prm, cfg=cfg)
+
+
+# ---- input layout ----------------------------------------------------------------------------
+def test_rows_of_16_bytes(ctx, L, world):
+    first, reads, poses, origins = world
+    prm = params(L)
+    T, res, done, rc, final = run(ctx, first, reads[:4], poses[:4], prm)
+    rows = [np.concatenate([r, np.full((len(r), 1), 7.0, np.float32)], 1) for r in reads[:4]]  # pcl::PointXYZ
+    first4 = np.concatenate([first, np.full((len(first), 1), 7.0, np.float32)], 1)
+    assert rows[0].shape[1] == 4 and first4.shape[1] == 4
+    T4, res4, done4, rc4, final4 = run(ctx, first4, rows, poses[:4], prm)
+    assert rc == rc4 == 0 and done == done4 == 4
+    np.testing.assert_array_equal(T, T4)
+    assert res == res4
+    np.testing.assert_array_equal(final, final4)
+    assert sum(r["is_reference"] for r in res) == 1 and len(final) == len(first) + 3000
