@@ -19,21 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .prior_map import PriorMap
-
-
-def _clouds_and_poses(readings, poses):
-    n = len(readings)
-    arr = (L.Cloud * max(n, 1))()
-    keep = []
-    pz = np.zeros((max(n, 1), 16), np.float32)
-    for i, r in enumerate(readings):
-        P = np.asarray(poses[i], np.float64).reshape(4, 4)
-        c, k = L.make_cloud(r, P[:3, 3])
-        arr[i] = c
-        keep.append(k)
-        pz[i] = np.asarray(poses[i], np.float32).reshape(4, 4).T.reshape(16)
-    return arr, pz, keep
+from .prior_map import PriorMap, _clouds_and_poses, _stream_results
 
 
 class BuiltMap(PriorMap):
@@ -76,7 +62,4 @@ class BuiltMap(PriorMap):
         done = C.c_size_t(0)
         rc = L.lib.aicp_hip_built_map_sequence_run(self.ctx.h, C.byref(cfg), C.byref(prm), self.h, arr, L._fptr(pz), n,
                                                    L._fptr(outT), res, C.byref(done))
-        if raise_on_error and rc != L.AICP_OK:
-            self.ctx.check(rc)
-        T = outT[:n].reshape(-1, 4, 4).transpose(0, 2, 1).copy()
-        return T, [res[i].as_dict() for i in range(done.value)], done.value, rc
+        return _stream_results(self.ctx, rc, raise_on_error, n, outT, res, done)

@@ -1258,8 +1258,7 @@ void aicp_hip_destroy(aicp_hip_ctx* ctx) {
   if (ctx->poll_host) (void)hipHostFree(ctx->poll_host);
   delete ctx->pool;
   seq_state_free(ctx->seq);
-  loc_bufs_free(ctx->loc);
-  bm_bufs_free(ctx->bm);
+  map_stream_bufs_free(ctx->ms);
   for (PinBuf* b : {&ctx->pin_desc, &ctx->pin_state, &ctx->pin_out, &ctx->pin_io, &ctx->pin_ovl,
                     &ctx->pin_rdesc, &ctx->pin_gdesc, &ctx->pin_gstate, &ctx->pin_pf})
     release(*b);
@@ -2334,8 +2333,8 @@ int aicp_hip_map_register_batch(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, c
 namespace aicp {
 namespace rt {
 
-// room for `add` more points behind the map's n: the copying growth of aicp_hip_map_merge (a
-// failed growth leaves the map as it was)
+// room for `add` more points behind the map's n, grown with a copy (ensure() would drop the
+// content; a failed growth leaves the map as it was: it keeps its old buffer)
 int map_reserve(aicp_hip_ctx* ctx, aicp_hip_map* map, size_t add) {
   if (map->n + add > (size_t)INT32_MAX) FAIL(AICP_ERR_INVALID, "map merge: more than 2^31 points");
   const size_t need = (map->n + add) * 16;
@@ -2439,11 +2438,8 @@ int aicp_hip_map_align_batch(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, cons
   if (flags & ~(AICP_RUN_OVERLAP | AICP_RUN_ICP | AICP_RUN_TIME_NN)) FAIL(AICP_ERR_INVALID, "map align batch: flags");
   const int run_flags = AICP_RUN_ICP | (flags & (AICP_RUN_OVERLAP | AICP_RUN_TIME_NN));
   if ((run_flags & AICP_RUN_OVERLAP) && !(resolution > 0)) FAIL(AICP_ERR_INVALID, "resolution");
-  for (size_t i = 0; i < n; ++i) {
-    const aicp_cloud& c = readings[i];
-    if (!c.pts || c.n == 0 || c.stride < 12 || (c.stride % 4) || c.n > (uint64_t)INT32_MAX)
-      FAIL(AICP_ERR_INVALID, "invalid reading " + std::to_string(i));
-  }
+  for (size_t i = 0; i < n; ++i)
+    if (!valid_cloud(readings[i])) FAIL(AICP_ERR_INVALID, "invalid reading " + std::to_string(i));
   const int rc = check_cfg(ctx, cfg, run_flags);
   if (rc) return rc;
   return map_batch(ctx, cfg, map, mn, mx, readings, poses, n, resolution, run_flags, out_T, stats);
@@ -2458,24 +2454,11 @@ int aicp_hip_map_capacity(const aicp_hip_map* map, size_t* n) {
 int aicp_hip_map_merge(aicp_hip_ctx* ctx, aicp_hip_map* map, const float* pts, size_t n, size_t stride,
                        const float T[16]) {
   if (!ctx || !map || !T || (n && !pts) || stride < 12 || (stride % 4)) return AICP_ERR_INVALID;
-  if (map->n + n > (size_t)INT32_MAX) FAIL(AICP_ERR_INVALID, "map merge: more than 2^31 points");
   if (!n) return AICP_OK;
   HIPC(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const size_t need = (map->n + n) * 16;
-  if (need > map->pts.cap) {  // grow with copy (ensure() would drop the content)
-    DevBuf nb;
-    HIPC(ensure(nb, std::max(need, 2 * map->pts.cap)));
-    hipError_t e = map->n ? hipMemcpyAsync(nb.p, map->pts.p, map->n * 16, hipMemcpyDeviceToDevice, s) : hipSuccess;
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {  // the map keeps its old buffer; the new one is released
-      (void)hipStreamSynchronize(s);
-      release(nb);
-      FAIL(AICP_ERR_HIP, std::string("map merge: grow copy: ") + hipGetErrorString(e));
-    }
-    release(map->pts);
-    map->pts = nb;
-  }
+  const int rc = map_reserve(ctx, map, n);
+  if (rc) return rc;
   HIPC(ensure(ctx->scratch, 64 + n * 16));
   HIPC(ensure(ctx->pin_io, n * 16 + 64));
   float* h = ctx->pin_io.as<float>();
@@ -2583,12 +2566,9 @@ int aicp_hip_sequence_run_raw(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, con
   if (doOvl && !(prm->resolution > 0)) FAIL(AICP_ERR_INVALID, "resolution");
   rc = check_cfg(ctx, cfg, AICP_RUN_ICP | (doOvl ? AICP_RUN_OVERLAP : 0));
   if (rc) return rc;
-  auto valid = [](const aicp_cloud& c) {
-    return c.pts && c.n >= 1 && c.n < (1ull << 31) && c.stride >= 12 && c.stride % 4 == 0;
-  };
-  if (!valid(*first)) FAIL(AICP_ERR_INVALID, "invalid first cloud");
+  if (!valid_cloud(*first)) FAIL(AICP_ERR_INVALID, "invalid first cloud");
   for (size_t i = 0; i < n; ++i)
-    if (!valid(readings[i])) FAIL(AICP_ERR_INVALID, "invalid reading " + std::to_string(i));
+    if (!valid_cloud(readings[i])) FAIL(AICP_ERR_INVALID, "invalid reading " + std::to_string(i));
   HIPC(hipSetDevice(ctx->device));
   // the first cloud: pre-filtered as given (processCloud, app.cpp:293-297)
   std::vector<float> ref;
@@ -2722,9 +2702,7 @@ struct RiskView {  // risk_core's results: host (pinned) and device
   const uint32_t *d_a_in_b, *d_b_in_a;  // device; null with zero clusters on a side
 };
 
-bool valid_cloud(const aicp_cloud* c) {
-  return c && c->pts && c->n >= 1 && c->n < (1ull << 31) && c->stride >= 12 && (c->stride % 4) == 0;
-}
+bool valid_cloud(const aicp_cloud* c) { return c && aicp::rt::valid_cloud(*c); }
 
 // the FOV filter of a cloud against `other` (column-major Isometry3d): the inverse in double as
 // R^T and -R^T t with explicit left-to-right sums, the pose itself as float for the way back

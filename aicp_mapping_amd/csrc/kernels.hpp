@@ -288,54 +288,38 @@ void launch_ovl_size(hipStream_t s, int n, PairState* st, OvlDesc* od, const uin
 // zero the n maps of od[] (device-side sizes, each at most max_bytes)
 void launch_ovl_clear(hipStream_t s, int n, const OvlDesc* od, uint8_t* maps, uint64_t max_bytes);
 
-// ---- App's localization stream on the prior map (kernels_localization.hip, localization.cpp) ----
-struct LocState {       // the stream's state on the device
+// ---- App's map localization streams (kernels_map_stream.hip, map_stream.cpp) -----------------
+// One window-stream serves the prior map (aicp_hip_map_sequence_run) and the map App builds
+// itself (aicp_hip_built_map_sequence_run); `built` selects the rules of the second.
+struct StreamState {    // the stream's state on the device
   float initT[16];      // initialT_ (app.cpp:414), column-major
-  int32_t n_clouds;     // aligned_clouds_graph_->getNbClouds()
+  int32_t count;        // prior map: aligned_clouds_graph_->getNbClouds(); built map: readings
+                        // accepted since the last reference (app.cpp:383-391)
   int32_t pad[3];
 };
-struct LocRules {       // aicp_localization_params as the commit kernel reads them
-  int32_t freq, refilter_every, merge;
+struct StreamRules {    // the stream's parameters as the commit kernel reads them
+  int32_t built;        // 0: prior map, 1: built map
+  int32_t freq;         // reference_update_frequency
+  int32_t refilter_every;  // prior map: map_refilter_every (0: never)
+  int32_t merge;        // prior map: AICP_LOC_MERGE
+  int32_t overlap;      // built map: the batch ran the overlap, an overlap error fails the reading
   float max_corr;
 };
-struct LocRec {         // one reading's decisions (the host reads a window's records once)
+struct StreamRec {      // one reading's decisions (the host reads a window's records once)
   int32_t status;       // AICP_* of its registration; -1: after the reading that ended the stream
-  int32_t accepted, merged, refiltered;
+  int32_t accepted;
+  int32_t append;       // the reading goes to the map's tail (merged / is_reference)
+  int32_t refilter;     // the map is pre-filtered after this reading (prior map)
   double corrected_origin[3];
 };
 // debug working mode (app.cpp:87-96): pts := initialT_ * pts in place (k_transform's expression)
 // and origin := translation of initialT_ * prior pose (k_debug_prep's)
-// (initT: 16 floats on the device, LocState::initT / BmState::initT)
+// (initT: 16 floats on the device, StreamState::initT)
 void launch_loc_move(hipStream_t s, int n, const float* initT, double* origin, float4* pts);
-// one thread walks the window's np readings in order (app.cpp:366-373, 414, 469-493): status,
-// drop test, count, corrected origin, initialT_ = correction * initialT_, merge / re-filter flags
-void launch_loc_commit(hipStream_t s, int np, const PairState* st, const float* T, const double* origin,
-                       LocRules r, LocState* S, LocRec* rec);
-// out = T * in (the map's tail: transformPointCloud(reading, correction), k_transform's expression)
-void launch_loc_merge(hipStream_t s, int n, const float* T, const float4* in, float4* out);
-
-// ---- App's localization stream on the map it built (kernels_built_map.hip, built_map.cpp) ----
-struct BmState {        // the stream's state on the device
-  float initT[16];      // initialT_ (app.cpp:414), column-major
-  int32_t acc;          // readings accepted since the last reference (app.cpp:383-391)
-  int32_t append;       // the last window's append plan: the reading that goes to the map's tail, -1: none
-  int32_t pad[2];
-};
-struct BmRules {        // aicp_built_map_params as the commit kernel reads them
-  int32_t freq;
-  float max_corr;
-  int32_t overlap;      // the batch ran the overlap: an overlap error fails the reading
-};
-struct BmRec {          // one reading's decisions (the host reads a window's records once)
-  int32_t status;       // AICP_* of its registration; -1: after the reading that ended the stream
-  int32_t accepted, is_reference, pad;
-  double corrected_origin[3];
-};
-// one thread walks the window's np readings in order (app.cpp:366-391, 414): status, drop test
-// (from the first reading on), corrected origin, ++acc, acc == freq: reference (append plan) and
-// acc = 0, initialT_ = correction * initialT_
-void launch_bm_commit(hipStream_t s, int np, const PairState* st, const float* T, const double* origin, BmRules r,
-                      BmState* S, BmRec* rec);
+// one thread walks the window's np readings in order (app.cpp:366-391, 414, 469-493): status, drop
+// test, count, corrected origin, initialT_ = correction * initialT_, append / re-filter flags
+void launch_stream_commit(hipStream_t s, int np, const PairState* st, const float* T, const double* origin,
+                          StreamRules r, StreamState* S, StreamRec* rec);
 
 // ---- pre-filter (kernels_prefilter.hip): regionGrowingUniformPlaneSegmentationFilter -------
 constexpr int kPfMaxNbrs = 16;  // RegionGrowing neighbours per point (edge mask bits)

@@ -1,0 +1,372 @@
+// map_stream.cpp — App's localization streams on a device-resident map (processCloud
+// app.cpp:282-414): on the prior map (aicp_hip_map_sequence_run; localize_against_prior_map,
+// setReference app.cpp:37-58, map maintenance app.cpp:469-493) and on the map App has built itself
+// (aicp_hip_built_map_sequence_run; localize_against_built_map, setReference app.cpp:60-69). Rules:
+// include/aicp_hip.h. One driver (run_stream) serves both; what differs comes in as a Stream value.
+//
+// The map changes only after an accepted reading (a merge, a re-filter, a new reference), and when
+// it does depends on a running count of accepted readings alone. Readings between two map changes
+// see the same map, so they are independent: they run as one batch (a window), cropped on the
+// device straight into the batch's reference array like aicp_hip_map_register_batch. The window
+// ends where the next map change would fall if every reading were accepted
+// (aicp_hip_localization_window, aicp_hip_built_map_window); a dropped reading only postpones the
+// change, so the map is still unchanged at the end of the window and the next, shorter window goes
+// on from the count reached. Nothing is run twice.
+//
+// Per window: [host] crop frames -> [device] crop counts -> [host] sizes the batch (one sync, as
+// the batch call) -> [device] crop scatter, (debug mode: the reading moved by initialT_), (built
+// map: overlap -> ratio beside the) trees, normals, ICP loop, finalize (run_batch) -> [device]
+// k_stream_commit: drop test, count, corrected origin, initialT_, append / re-filter flags ->
+// [host] reads the state and the records once -> [device] for the records that ask for it, in
+// order: k_transform from the batch's copy of the reading by the device's correction to the map's
+// tail, the map's pre-filter. No reading crosses the bus a second time.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/aicp_hip.h"
+#include "aicp_common.hpp"
+#include "icp_math.hpp"
+#include "kernels.hpp"
+#include "runtime.hpp"
+
+using namespace aicp;
+using namespace aicp::rt;
+
+namespace aicp {
+namespace rt {
+
+struct StreamTiming {
+  int windows = 0, appends = 0, refilters = 0;
+  double wall_ms = 0, device_ms = 0;
+};
+
+struct MapStreamBufs {
+  DevBuf win;     // StreamState, then (at kRecOff) a StreamRec per reading of the window
+  DevBuf origin;  // prior-pose translations of the window's readings, 3 doubles each
+  PinBuf pin;     // staging: win's mirror, then the origins
+  hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+  StreamTiming last[2];  // of the last call of each stream: [0] prior map, [1] built map
+};
+
+void map_stream_bufs_free(MapStreamBufs* L) {
+  if (!L) return;
+  release(L->win);
+  release(L->origin);
+  release(L->pin);
+  if (L->ev_begin) (void)hipEventDestroy(L->ev_begin);
+  if (L->ev_end) (void)hipEventDestroy(L->ev_end);
+  delete L;
+}
+
+}  // namespace rt
+}  // namespace aicp
+
+namespace {
+
+constexpr size_t kRecOff = 128;  // the records behind the state, in MapStreamBufs::win and its mirror
+static_assert(sizeof(StreamState) <= kRecOff && kRecOff % alignof(StreamRec) == 0, "win's layout");
+
+// run_stream writes both streams' results through aicp_localization_result: merged / refiltered
+// are is_reference / pad (always 0) of aicp_built_map_result
+#define SAME_FIELD(a, b) \
+  static_assert(offsetof(aicp_localization_result, a) == offsetof(aicp_built_map_result, b), "result layout")
+static_assert(sizeof(aicp_localization_result) == 128 && sizeof(aicp_built_map_result) == 128, "result layout");
+SAME_FIELD(status, status);
+SAME_FIELD(accepted, accepted);
+SAME_FIELD(merged, is_reference);
+SAME_FIELD(refiltered, pad);
+SAME_FIELD(map_points, map_points);
+SAME_FIELD(crop_points, crop_points);
+SAME_FIELD(corrected_origin, corrected_origin);
+SAME_FIELD(icp, icp);
+#undef SAME_FIELD
+
+constexpr int kLocFlags = AICP_LOC_MERGE | AICP_SEQ_DEBUG | AICP_RUN_TIME_NN;
+constexpr int kBmFlags = AICP_RUN_OVERLAP | AICP_SEQ_DEBUG | AICP_RUN_TIME_NN;
+
+bool valid_params(const aicp_localization_params* p) {
+  return p && p->reference_update_frequency >= 1 && p->map_refilter_every >= 0 && !(p->flags & ~kLocFlags) &&
+         p->max_correction_magnitude == p->max_correction_magnitude;
+}
+bool valid_params(const aicp_built_map_params* p) {
+  return p && p->reference_update_frequency >= 1 && !(p->flags & ~kBmFlags) &&
+         p->max_correction_magnitude == p->max_correction_magnitude && p->crop_min == p->crop_min &&
+         p->crop_max == p->crop_max && (!(p->flags & AICP_RUN_OVERLAP) || p->resolution > 0);
+}
+
+// What differs between the two streams (exactly one of loc / bm is set)
+struct Stream {
+  const aicp_localization_params* loc;
+  const aicp_built_map_params* bm;
+  const aicp_prefilter_params* pf;  // prior map: the re-filter's parameters
+  StreamRules rules;
+  float crop_min, crop_max;
+  bool debug;
+  int run_flags;      // run_batch's
+  double resolution;  // the overlap's (built map)
+};
+
+// the entry points' argument checks before their parameters'
+int stream_args(aicp_hip_ctx* ctx, const void* cfg, const void* prm, const aicp_hip_map* map,
+                const aicp_cloud* readings, const float* poses, size_t n, const float* out_T, const void* out,
+                size_t* n_done) {
+  if (!ctx || !n_done) return AICP_ERR_INVALID;
+  *n_done = 0;
+  if (!cfg || !prm || !map || (n && (!readings || !poses || !out_T || !out))) return AICP_ERR_INVALID;
+  return AICP_OK;
+}
+
+int run_stream(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, aicp_hip_map* map,
+               const aicp_cloud* readings, const float* poses, size_t n, float* out_T, aicp_localization_result* out,
+               size_t* n_done) {
+  for (size_t i = 0; i < n; ++i)
+    if (!valid_cloud(readings[i])) FAIL(AICP_ERR_INVALID, "invalid reading " + std::to_string(i));
+  int rc = check_cfg(ctx, cfg, P.run_flags);
+  if (rc) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  if (!ctx->ms) ctx->ms = new MapStreamBufs();
+  MapStreamBufs* L = ctx->ms;
+  StreamTiming& tm = L->last[P.bm ? 1 : 0];
+  tm = StreamTiming{};
+  if (!L->ev_begin) HIPC(hipEventCreate(&L->ev_begin));
+  if (!L->ev_end) HIPC(hipEventCreate(&L->ev_end));
+
+  // the stream's state: count = 0, initialT_ = I
+  const size_t wmax = std::min<size_t>(std::max<size_t>(n, 1), (size_t)kMaxPairs);
+  const size_t o_org = (kRecOff + wmax * sizeof(StreamRec) + 63) & ~size_t(63);
+  HIPC(ensure(L->win, kRecOff + wmax * sizeof(StreamRec)));
+  HIPC(ensure(L->origin, wmax * 24));
+  HIPC(ensure(L->pin, o_org + wmax * 24));
+  char* lp = L->pin.as<char>();
+  StreamState* dS = L->win.as<StreamState>();
+  StreamRec* dRec = reinterpret_cast<StreamRec*>(L->win.as<char>() + kRecOff);
+  StreamState* hS = reinterpret_cast<StreamState*>(lp);  // the host's mirror, read back with every window's records
+  const StreamRec* hrec = reinterpret_cast<const StreamRec*>(lp + kRecOff);
+  std::memset(hS, 0, sizeof(StreamState));
+  ident4(hS->initT);
+  HIPC(hipMemcpyAsync(dS, hS, sizeof(StreamState), hipMemcpyHostToDevice, s));
+  HIPC(hipEventRecord(L->ev_begin, s));
+  std::vector<aicp_icp_stats> stats;
+  int status = AICP_OK;
+  size_t p = 0;
+  bool empty_crop = false;
+  while (p < n && !status) {
+    const size_t w = P.bm ? aicp_hip_built_map_window((uint64_t)hS->count, P.bm, n - p)
+                          : aicp_hip_localization_window((uint64_t)hS->count, P.loc, n - p);
+    if (P.bm && w == 0) FAIL(AICP_ERR_HIP, "built-map stream: the device's count left its range");
+    const size_t map_n = map->n;
+    // built map, debug mode (one reading per window): the overlap's sensor origin of the moved
+    // reading, the translation of initialT_ * prior pose, from the mirror of the device's initialT_
+    // (k_loc_move computes the same for the commit, on the device)
+    double moved[3];
+    const bool use_moved = P.bm && P.debug;
+    if (use_moved) corrected_origin(hS->initT, readings[p].origin, moved);
+    // every reading's crop, straight into the batch's reference array (as the batch call). An
+    // empty crop ends the stream at its reading; the wr readings before it still run
+    size_t wr = 0;
+    const uint32_t* htot = nullptr;
+    rc = map_crop_pairs(ctx, map, P.crop_min, P.crop_max, readings + p, poses + 16 * p, w,
+                        use_moved ? moved : nullptr, &wr, &htot);
+    if (rc) return rc;
+    if (wr) {
+      aicp_hip_batch* B = ctx->mapbatch;
+      double* horg = reinterpret_cast<double*>(lp + o_org);
+      for (size_t i = 0; i < wr; ++i)
+        for (int k = 0; k < 3; ++k) horg[3 * i + k] = readings[p + i].origin[k];
+      HIPC(hipMemcpyAsync(L->origin.p, horg, wr * 24, hipMemcpyHostToDevice, s));
+      if (P.debug) {  // (one reading per window) moved by the device's initialT_, its prior pose too
+        launch_loc_move(s, (int)B->desc[0].n_read, dS->initT, L->origin.as<double>(),
+                        B->read_raw.as<float4>() + B->desc[0].read_off);
+        HIPC(hipGetLastError());
+      }
+      stats.assign(wr, aicp_icp_stats{});
+      for (auto& st : stats) st.status = -1;
+      rc = run_batch(ctx, B, cfg, P.resolution, P.run_flags, out_T + 16 * p, stats.data(), nullptr);
+      if (rc && stats[0].status == -1) return rc;  // the batch did not run to its end (not a reading's status)
+      ++tm.windows;
+      // App's bookkeeping for the window, on the device; one read-back of its state and records
+      launch_stream_commit(s, (int)wr, ctx->state.as<PairState>(), ctx->outT.as<float>(), L->origin.as<double>(),
+                           P.rules, dS, dRec);
+      HIPC(hipGetLastError());
+      HIPC(hipMemcpyAsync(lp, L->win.p, kRecOff + wr * sizeof(StreamRec), hipMemcpyDeviceToHost, s));
+      HIPC(hipStreamSynchronize(s));
+      // the map changes the records ask for, in order (by the window rule: after the last reading)
+      for (size_t i = 0; i < wr; ++i) {
+        const StreamRec& r = hrec[i];
+        aicp_localization_result& o = out[p + i];
+        std::memset(&o, 0, sizeof(o));
+        o.status = r.status;
+        o.accepted = r.accepted;
+        o.map_points = map_n;
+        o.crop_points = htot[i];
+        for (int k = 0; k < 3; ++k) o.corrected_origin[k] = r.corrected_origin[k];
+        o.icp = stats[i];
+        *n_done = p + i + 1;
+        if (r.status) {
+          status = r.status;
+          break;
+        }
+        if (r.append) {
+          const PairDesc& d = B->desc[i];
+          rc = map_reserve(ctx, map, d.n_read);
+          if (rc) return rc;
+          launch_transform(s, (int)d.n_read, ctx->outT.as<float>() + 16 * i, B->read_raw.as<float4>() + d.read_off,
+                           map->pts.as<float4>() + map->n);
+          HIPC(hipGetLastError());
+          map->n += d.n_read;
+          o.merged = 1;
+          ++tm.appends;
+        }
+        if (r.refilter) {
+          rc = aicp_hip_map_prefilter(ctx, map, P.pf);
+          if (rc) return rc;
+          o.refiltered = 1;
+          ++tm.refilters;
+        }
+      }
+    }
+    if (!status && wr < w) {  // the reading with the empty crop (libpointmatcher throws on an empty cloud)
+      aicp_localization_result& o = out[p + wr];
+      std::memset(&o, 0, sizeof(o));
+      o.status = o.icp.status = AICP_ERR_INVALID;
+      o.map_points = map_n;
+      o.icp.overlap_percent = -1.f;
+      ident4(out_T + 16 * (p + wr));
+      *n_done = p + wr + 1;
+      status = AICP_ERR_INVALID;
+      empty_crop = true;
+    }
+    p += wr;
+  }
+  HIPC(hipEventRecord(L->ev_end, s));
+  HIPC(hipStreamSynchronize(s));
+  tm.device_ms = ev_ms(L->ev_begin, L->ev_end);
+  tm.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (status)
+    ctx->err = "reading " + std::to_string(*n_done - 1) +
+               (empty_crop ? std::string(": empty map crop") : ": status " + std::to_string(status));
+  return status;
+}
+
+}  // namespace
+
+extern "C" {
+
+void aicp_hip_default_localization_params(aicp_localization_params* p) {
+  if (!p) return;
+  p->reference_update_frequency = 5;
+  p->map_refilter_every = 30;
+  p->max_correction_magnitude = 1.0f;
+  p->crop_min = -15.0f;
+  p->crop_max = 15.0f;
+  p->flags = AICP_LOC_MERGE;
+}
+
+void aicp_hip_default_built_map_params(aicp_built_map_params* p) {
+  if (!p) return;
+  p->reference_update_frequency = 5;
+  p->max_correction_magnitude = 1.0f;
+  p->crop_min = -15.0f;
+  p->crop_max = 15.0f;
+  p->resolution = 0.2;
+  p->flags = AICP_RUN_OVERLAP;
+  p->pad = 0;
+}
+
+size_t aicp_hip_localization_window(uint64_t n_clouds, const aicp_localization_params* prm, size_t remaining) {
+  if (!valid_params(prm) || remaining == 0) return 0;
+  if (prm->flags & AICP_SEQ_DEBUG) return 1;
+  size_t w = std::min<size_t>(remaining, (size_t)kMaxPairs);
+  if (!(prm->flags & AICP_LOC_MERGE)) return w;
+  // reading k of the window, if all before it are accepted too, is accepted as cloud n_clouds + k:
+  // the map changes after it when (n_clouds + k - 1) is a multiple of a period
+  auto to_next = [&](uint64_t period) -> uint64_t {
+    const uint64_t r = n_clouds % period;  // (n_clouds + k - 1) % period == 0, k >= 1
+    return r == 0 ? 1 : period - r + 1;
+  };
+  w = (size_t)std::min<uint64_t>(w, to_next((uint64_t)prm->reference_update_frequency));
+  if (prm->map_refilter_every > 0) w = (size_t)std::min<uint64_t>(w, to_next((uint64_t)prm->map_refilter_every));
+  return w;
+}
+
+size_t aicp_hip_built_map_window(uint64_t acc, const aicp_built_map_params* prm, size_t remaining) {
+  if (!valid_params(prm) || remaining == 0 || acc >= (uint64_t)prm->reference_update_frequency) return 0;
+  if (prm->flags & AICP_SEQ_DEBUG) return 1;
+  // reading k of the window (k >= 1), if all before it are accepted too, is the (acc + k)-th
+  // accepted since the last reference: the map changes after it when acc + k == frequency
+  const uint64_t to_ref = (uint64_t)prm->reference_update_frequency - acc;
+  return (size_t)std::min<uint64_t>(std::min<size_t>(remaining, (size_t)kMaxPairs), to_ref);
+}
+
+int aicp_hip_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* prm,
+                              const aicp_prefilter_params* pf, aicp_hip_map* map, const aicp_cloud* readings,
+                              const float* poses, size_t n, float* out_T, aicp_localization_result* out,
+                              size_t* n_done) {
+  const int rc = stream_args(ctx, cfg, prm, map, readings, poses, n, out_T, out, n_done);
+  if (rc) return rc;
+  if (!valid_params(prm)) FAIL(AICP_ERR_INVALID, "localization parameters");
+  aicp_prefilter_params pfd;
+  if (!pf) {
+    aicp_hip_default_prefilter(&pfd);
+    pf = &pfd;
+  }
+  aicp_icp_config c = *cfg;
+  c.trimmed_ratio = aicp_hip_autotune_ratio(50.0f);  // octree_overlap_ = 50.0 (app.cpp:123-127)
+  Stream P{};
+  P.loc = prm;
+  P.pf = pf;
+  P.rules.freq = prm->reference_update_frequency;
+  P.rules.refilter_every = prm->map_refilter_every;
+  P.rules.merge = (prm->flags & AICP_LOC_MERGE) ? 1 : 0;
+  P.rules.max_corr = prm->max_correction_magnitude;
+  P.crop_min = prm->crop_min;
+  P.crop_max = prm->crop_max;
+  P.debug = prm->flags & AICP_SEQ_DEBUG;
+  P.run_flags = AICP_RUN_ICP | (prm->flags & AICP_RUN_TIME_NN);
+  return run_stream(ctx, P, &c, map, readings, poses, n, out_T, out, n_done);
+}
+
+int aicp_hip_built_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_built_map_params* prm,
+                                    aicp_hip_map* map, const aicp_cloud* readings, const float* poses, size_t n,
+                                    float* out_T, aicp_built_map_result* out, size_t* n_done) {
+  const int rc = stream_args(ctx, cfg, prm, map, readings, poses, n, out_T, out, n_done);
+  if (rc) return rc;
+  if (!valid_params(prm)) FAIL(AICP_ERR_INVALID, "built-map parameters");
+  Stream P{};
+  P.bm = prm;
+  P.rules.built = 1;
+  P.rules.freq = prm->reference_update_frequency;
+  P.rules.overlap = (prm->flags & AICP_RUN_OVERLAP) ? 1 : 0;
+  P.rules.max_corr = prm->max_correction_magnitude;
+  P.crop_min = prm->crop_min;
+  P.crop_max = prm->crop_max;
+  P.debug = prm->flags & AICP_SEQ_DEBUG;
+  P.run_flags = AICP_RUN_ICP | (prm->flags & (AICP_RUN_OVERLAP | AICP_RUN_TIME_NN));
+  P.resolution = prm->resolution;
+  return run_stream(ctx, P, cfg, map, readings, poses, n, out_T, reinterpret_cast<aicp_localization_result*>(out),
+                    n_done);
+}
+
+int aicp_hip_last_localization_timing(const aicp_hip_ctx* ctx, aicp_localization_timing* out) {
+  if (!ctx || !out) return AICP_ERR_INVALID;
+  const StreamTiming t = ctx->ms ? ctx->ms->last[0] : StreamTiming{};
+  *out = aicp_localization_timing{t.windows, t.appends, t.refilters, 0, t.wall_ms, t.device_ms};
+  return AICP_OK;
+}
+
+int aicp_hip_last_built_map_timing(const aicp_hip_ctx* ctx, aicp_built_map_timing* out) {
+  if (!ctx || !out) return AICP_ERR_INVALID;
+  const StreamTiming t = ctx->ms ? ctx->ms->last[1] : StreamTiming{};
+  *out = aicp_built_map_timing{t.windows, t.appends, t.wall_ms, t.device_ms};
+  return AICP_OK;
+}
+
+}  // extern "C"

@@ -255,10 +255,13 @@ struct ReadCache {
 
 struct SeqState;  // sequence.cpp
 void seq_state_free(SeqState* s);
-struct LocBufs;  // localization.cpp
-void loc_bufs_free(LocBufs* s);
-struct BmBufs;  // built_map.cpp
-void bm_bufs_free(BmBufs* s);
+struct MapStreamBufs;  // map_stream.cpp
+void map_stream_bufs_free(MapStreamBufs* s);
+
+// a caller's cloud as the entry points that take aicp_cloud accept it
+inline bool valid_cloud(const aicp_cloud& c) {
+  return c.pts && c.n >= 1 && c.n <= (uint64_t)INT32_MAX && c.stride >= 12 && c.stride % 4 == 0;
+}
 
 // the batch pipeline (aicp_hip.cpp), for the entry points that compose a batch on the device
 int upload_pairs(aicp_hip_ctx* ctx, const aicp_pair* pairs, size_t n, aicp_hip_batch* B, bool refs_on_device,
@@ -314,8 +317,7 @@ struct aicp_hip_ctx {
   aicp_hip_batch* oneshot = nullptr;  // buffers of aicp_hip_align_batch, kept across calls
   hipEvent_t pf_ev[8] = {};
   aicp::rt::SeqState* seq = nullptr;  // aicp_hip_sequence_run's buffers (sequence.cpp), kept across calls
-  aicp::rt::LocBufs* loc = nullptr;    // aicp_hip_map_sequence_run's buffers (localization.cpp), kept across calls
-  aicp::rt::BmBufs* bm = nullptr;      // aicp_hip_built_map_sequence_run's buffers (built_map.cpp), kept across calls
+  aicp::rt::MapStreamBufs* ms = nullptr;  // the map localization streams' buffers (map_stream.cpp), kept across calls
   aicp_hip_batch* mapbatch = nullptr;  // aicp_hip_map_register_batch's batch buffers
   aicp::rt::DevBuf crop_ws;            // its crop work space
   aicp::rt::DevBuf ovl_sp, ovl_keys;   // sparse overlap: clouds, counts, offsets / key words

@@ -19,6 +19,30 @@ import numpy as np
 from . import _lib as L
 
 
+def _clouds_and_poses(readings, poses):
+    """The aicp_cloud array (origin: the prior pose's translation) and the column-major poses of a
+    batch or stream call (at least one slot each), and the arrays the clouds point into."""
+    n = len(readings)
+    arr = (L.Cloud * max(n, 1))()
+    keep = []
+    pz = np.zeros((max(n, 1), 16), np.float32)
+    for i, r in enumerate(readings):
+        P = np.asarray(poses[i], np.float64).reshape(4, 4)
+        c, k = L.make_cloud(r, P[:3, 3])
+        arr[i] = c
+        keep.append(k)
+        pz[i] = np.asarray(poses[i], np.float32).reshape(4, 4).T.reshape(16)
+    return arr, pz, keep
+
+
+def _stream_results(ctx, rc, raise_on_error, n, outT, res, done):
+    """The shared tail of the two sequence_run wrappers: (T, result dicts, n_done, rc)."""
+    if raise_on_error and rc != L.AICP_OK:
+        ctx.check(rc)
+    T = outT[:n].reshape(-1, 4, 4).transpose(0, 2, 1).copy()
+    return T, [res[i].as_dict() for i in range(done.value)], done.value, rc
+
+
 class PriorMap:
     def __init__(self, ctx: "L.Context", points):
         pts = L.as_points(points)
@@ -72,14 +96,7 @@ class PriorMap:
         Returns (T[n, 4, 4] row-major, list of stats dicts, rc)."""
         cfg = cfg or L.default_config()
         n = len(readings)
-        arr = (L.Cloud * n)()
-        keep = []
-        for i, r in enumerate(readings):
-            P = np.asarray(poses[i], np.float64).reshape(4, 4)
-            c, k = L.make_cloud(r, P[:3, 3])
-            arr[i] = c
-            keep.append(k)
-        pz = np.ascontiguousarray(np.stack([np.asarray(p, np.float32).reshape(4, 4).T.reshape(16) for p in poses]))
+        arr, pz, keep = _clouds_and_poses(readings, poses)
         outT = np.zeros((n, 16), np.float32)
         st = (L.IcpStats * n)()
         rc = L.lib.aicp_hip_map_register_batch(self.ctx.h, C.byref(cfg), self.h, float(mn), float(mx), arr, L._fptr(pz),
@@ -101,26 +118,14 @@ class PriorMap:
         cfg = cfg or L.default_config()
         prm = params or L.default_localization_params()
         n = len(readings)
-        arr = (L.Cloud * max(n, 1))()
-        keep = []
-        for i, r in enumerate(readings):
-            P = np.asarray(poses[i], np.float64).reshape(4, 4)
-            c, k = L.make_cloud(r, P[:3, 3])
-            arr[i] = c
-            keep.append(k)
-        pz = np.zeros((max(n, 1), 16), np.float32)
-        for i in range(n):
-            pz[i] = np.asarray(poses[i], np.float32).reshape(4, 4).T.reshape(16)
+        arr, pz, keep = _clouds_and_poses(readings, poses)
         outT = np.zeros((max(n, 1), 16), np.float32)
         res = (L.LocalizationResult * max(n, 1))()
         done = C.c_size_t(0)
         rc = L.lib.aicp_hip_map_sequence_run(self.ctx.h, C.byref(cfg), C.byref(prm),
                                              C.byref(prefilter) if prefilter is not None else None, self.h, arr,
                                              L._fptr(pz), n, L._fptr(outT), res, C.byref(done))
-        if raise_on_error and rc != L.AICP_OK:
-            self.ctx.check(rc)
-        T = outT[:n].reshape(-1, 4, 4).transpose(0, 2, 1).copy()
-        return T, [res[i].as_dict() for i in range(done.value)], done.value, rc
+        return _stream_results(self.ctx, rc, raise_on_error, n, outT, res, done)
 
     def merge(self, points, correction) -> None:
         """*map = *map + transformPointCloud(points, correction); correction a 4x4 (row-major)."""

@@ -388,3 +388,57 @@ def test_rows_of_16_bytes(ctx, L, world):
     assert res == res4
     np.testing.assert_array_equal(final, final4)
     assert sum(r["is_reference"] for r in res) == 1 and len(final) == len(first) + 3000
+
+
+# ---- both streams on one context -------------------------------------------------------------
+def test_streams_share_a_context(ctx, L, world):
+    """The two streams use one set of context buffers whose staging offsets depend on the call's n:
+    a prior-map stream of 4 readings, a built-map stream of 7 and the prior-map stream again on one
+    context give, bit for bit, what each gives on a context of its own, and each stream's last
+    timing survives a call of the other."""
+    from aicp_mapping_amd.prior_map import PriorMap
+
+    first, reads, poses, origins = world
+    assert all(len(r) == 3000 for r in reads[:7])
+    bprm, lprm = params(L), L.default_localization_params()
+
+    def prior(c):
+        pm = PriorMap(c, first)
+        T, res, done, rc = pm.sequence_run(reads[:4], poses[:4], params=lprm)
+        final = pm.getCloud()
+        pm.free()
+        tm = c.last_localization_timing()
+        return (T, res, done, rc, final), (tm["windows"], tm["merges"], tm["refilters"])
+
+    def built(c):
+        out = run(c, first, reads[:7], poses[:7], bprm)
+        tm = c.last_built_map_timing()
+        return out, (tm["windows"], tm["appends"])
+
+    def same(a, b):
+        np.testing.assert_array_equal(a[0], b[0])
+        assert a[1] == b[1] and a[2:4] == b[2:4]
+        np.testing.assert_array_equal(a[4], b[4])
+
+    p1, ptm1 = prior(ctx)
+    b2, btm2 = built(ctx)
+    tm = ctx.last_localization_timing()
+    assert (tm["windows"], tm["merges"], tm["refilters"]) == ptm1
+    p3, ptm3 = prior(ctx)
+    tm = ctx.last_built_map_timing()
+    assert (tm["windows"], tm["appends"]) == btm2
+    own = []
+    for f in (prior, built):
+        c = L.Context(0)
+        try:
+            own.append(f(c))
+        finally:
+            c.close()
+    assert p1[2:4] == (4, 0) and b2[2:4] == (7, 0)
+    same(p1, p3)
+    same(p1, own[0][0])
+    same(b2, own[1][0])
+    assert ptm1 == ptm3 == own[0][1] and btm2 == own[1][1]
+    # the first cloud is merged and the map re-filtered after it, then one window of 3; windows of
+    # 3, 3 and 1 readings with references at readings 2 and 6
+    assert ptm1 == (2, 1, 1) and btm2 == (3, 2)
