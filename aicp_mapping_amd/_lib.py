@@ -45,6 +45,7 @@ EXPORTS = [
     "aicp_hip_test_force_scan_stall", "aicp_hip_sequence_run_raw", "aicp_hip_build_info",
     "aicp_hip_fov_overlap", "aicp_hip_cluster_match", "aicp_hip_alignment_features",
     "aicp_hip_default_risk_params", "aicp_hip_last_risk_stats", "aicp_hip_test_select", "aicp_hip_test_step",
+    "aicp_hip_test_step_p2p",
     "aicp_hip_default_monitor_params", "aicp_hip_monitor", "aicp_hip_monitor_batch", "aicp_hip_last_monitor_stats",
     "aicp_hip_default_localization_params", "aicp_hip_localization_window", "aicp_hip_map_sequence_run",
     "aicp_hip_last_localization_timing",
@@ -65,7 +66,8 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_last_localization_timing",  # the localization stream
            "aicp_hip_map_align_batch", "aicp_hip_map_capacity", "aicp_hip_default_built_map_params",
            "aicp_hip_built_map_window", "aicp_hip_built_map_sequence_run",
-           "aicp_hip_last_built_map_timing"}  # the built-map localization stream
+           "aicp_hip_last_built_map_timing",  # the built-map localization stream
+           "aicp_hip_test_step_p2p"}  # the point-to-point chains
 
 
 class IcpConfig(C.Structure):
@@ -509,6 +511,10 @@ def _load():
         u32p, u8p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
         L.aicp_hip_test_step.argtypes = [vp, sz, u32p, u32p, u32p, sz, fp, fp, fp, fp, u8p, C.c_int32, C.c_int32,
                                          C.c_float, C.c_float, sz, fp, ip, fp, u32p, dp, fp, ip, fp, up, dp, up]
+    if hasattr(L, "aicp_hip_test_step_p2p"):  # (aicp_hip_test_step's without ref_nrm)
+        u32p, u8p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
+        L.aicp_hip_test_step_p2p.argtypes = [vp, sz, u32p, u32p, u32p, sz, fp, fp, fp, u8p, C.c_int32, C.c_int32,
+                                             C.c_float, C.c_float, sz, fp, ip, fp, u32p, dp, fp, ip, fp, up, dp, up]
     return L
 
 
@@ -581,9 +587,14 @@ def test_force_scan_stall(on: bool) -> int:
     return lib.aicp_hip_test_force_scan_stall(1 if on else 0)
 
 
-def default_config(**kw) -> IcpConfig:
+def default_config(point_to_point=False, **kw) -> IcpConfig:
+    """The default chain's parameters, with fields replaced by name. point_to_point=True asks for
+    PointToPointErrorMinimizer without SurfaceNormal on the reference (knn_normals = 0,
+    include/aicp_hip.h); every other element of the chain stays."""
     c = IcpConfig()
     lib.aicp_hip_default_config(C.byref(c))
+    if point_to_point:
+        c.knn_normals = 0
     for k, v in kw.items():
         setattr(c, k, v)
     return c
@@ -1015,12 +1026,28 @@ class Context:
         (n_steps, n_pairs); match, d2, touched (n_steps, total). Returns per step and pair: slab (a list
         over steps of (rows, 30) arrays), T (S, P, 16), kept, iters, status, active, converged,
         hist_count, inlier_ratio, touched_pts, touched_nodes, dq, dt as (S, P) arrays, and dirty."""
+        if ref_nrm is None:
+            raise ValueError("ref_nrm")
+        return Context._test_step(self, n_read, n_ref, ref_off, read_c, ref_pts, ref_nrm, limit, match, d2, touched,
+                                  init_T, active, max_iter, smooth, min_rot, min_trans)
+
+    def test_step_p2p(self, n_read, n_ref, ref_off, read_c, ref_pts, limit, match, d2, touched, init_T=None,
+                      active=None, max_iter=20, smooth=4, min_rot=1e-3, min_trans=1e-2, **unused):
+        """aicp_hip_test_step_p2p: test_step with the point-to-point kernels (no normals; a case's other
+        keys are ignored). Slab columns: 0..8 sum q_a p_b, 9..11 sum p, 12..14 sum q, 15..26 zero, 27
+        kept, 28 / 29 touched points / nodes."""
+        return Context._test_step(self, n_read, n_ref, ref_off, read_c, ref_pts, None, limit, match, d2, touched,
+                                  init_T, active, max_iter, smooth, min_rot, min_trans)
+
+    def _test_step(self, n_read, n_ref, ref_off, read_c, ref_pts, ref_nrm, limit, match, d2, touched, init_T,
+                   active, max_iter, smooth, min_rot, min_trans):
+        p2p = ref_nrm is None
         n_read = np.ascontiguousarray(n_read, np.uint32).ravel()
         n_ref = np.ascontiguousarray(n_ref, np.uint32).ravel()
         ref_off = np.ascontiguousarray(ref_off, np.uint32).ravel()
         read_c = np.ascontiguousarray(read_c, np.float32).reshape(-1, 3)
         ref_pts = np.ascontiguousarray(ref_pts, np.float32).reshape(-1, 3)
-        ref_nrm = np.ascontiguousarray(ref_nrm, np.float32).reshape(-1, 3)
+        ref_nrm = ref_pts if p2p else np.ascontiguousarray(ref_nrm, np.float32).reshape(-1, 3)
         P, total, total_ref = n_read.size, int(n_read.sum(dtype=np.uint64)), ref_pts.shape[0]
         limit = np.ascontiguousarray(limit, np.float32)
         S = limit.shape[0] if limit.ndim == 2 else 0
@@ -1048,9 +1075,10 @@ class Context:
         dirty = C.c_uint64()
         ip, u32p, dp = C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_double)
         u8p, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)
-        rc = lib.aicp_hip_test_step(
+        fn = lib.aicp_hip_test_step_p2p if p2p else lib.aicp_hip_test_step
+        rc = fn(
             self.h, P, n_read.ctypes.data_as(u32p), n_ref.ctypes.data_as(u32p), ref_off.ctypes.data_as(u32p), total_ref,
-            _fptr(read_c), _fptr(ref_pts), _fptr(ref_nrm), _fptr(T0) if T0 is not None else None,
+            _fptr(read_c), _fptr(ref_pts), *(() if p2p else (_fptr(ref_nrm),)), _fptr(T0) if T0 is not None else None,
             act.ctypes.data_as(u8p) if act is not None else None, int(max_iter), int(smooth), float(min_rot),
             float(min_trans), S, _fptr(limit), match.ctypes.data_as(ip), _fptr(d2), touched.ctypes.data_as(u32p),
             slab.ctypes.data_as(dp), _fptr(T), state.ctypes.data_as(ip), _fptr(inl), tch.ctypes.data_as(u64p),

@@ -262,7 +262,7 @@ struct IcpParams {
   int32_t max_iter;
   int32_t smooth;
   float min_rot, min_trans;
-  int32_t knn_normals;
+  int32_t knn_normals;  // 0: PointToPointErrorMinimizer (launch_icp_reduce_f picks the kernels by it)
   int32_t prof_slot;  // diagnostic builds (AICP_XCD_PROF): the launch's record slot
 };
 

@@ -112,8 +112,9 @@ int check_cfg(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, int flags) {
   if (!cfg) FAIL(AICP_ERR_INVALID, "null config");
   if (cfg->knn_match != 1) FAIL(AICP_ERR_UNSUPPORTED, "KDTreeMatcher.knn != 1");
   if (flags & AICP_RUN_ICP) {
-    if (cfg->knn_normals != 10 && cfg->knn_normals != 20 && cfg->knn_normals != 30)
-      FAIL(AICP_ERR_UNSUPPORTED, "SurfaceNormal knn must be 10, 20 or 30");
+    // 0: no SurfaceNormal on the reference, PointToPointErrorMinimizer
+    if (cfg->knn_normals != 0 && cfg->knn_normals != 10 && cfg->knn_normals != 20 && cfg->knn_normals != 30)
+      FAIL(AICP_ERR_UNSUPPORTED, "SurfaceNormal knn must be 10, 20 or 30 (0: point-to-point)");
     if (cfg->max_iter < 1 || cfg->max_iter > 1000) FAIL(AICP_ERR_INVALID, "maxIterationCount");
     if (cfg->smooth_length < 1 || cfg->smooth_length >= kHistRing) FAIL(AICP_ERR_UNSUPPORTED, "smoothLength");
     if (cfg->bucket_size < 1) FAIL(AICP_ERR_INVALID, "bucketSize");
@@ -687,6 +688,9 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
   if (!read_hit) ctx->rdc.valid = false;  // (read_s is rewritten below; oneshot() re-validates)
   const bool hit_trees = rcache.use && rcache.hit_trees && doIcp;
   const bool hit_ovl = rcache.use && rcache.hit_ovl && doOvl;
+  // PointToPointErrorMinimizer: no SurfaceNormal on the reference, so no raw-coordinate tree, no
+  // normals kNN and no normals scatter; the matcher tree alone serves the loop
+  const bool p2p = doIcp && cfg->knn_normals == 0;
   hipStream_t s = ctx->stream;
   // the events that order this context's streams release at device scope; ev[1], which the host
   // waits on before it reads the key boxes copied to pinned memory, keeps the system-scope fence
@@ -852,49 +856,57 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
         if (ctx->pin_rdesc.as<PairDesc>()[r].n_ref > 4000000u) ctx->tl_total = 0;
       if (ctx->opt.nn_engine == 1) ctx->tl_total = 0;
     }
-    HIPC(ensure(ctx->rdesc_raw, R * sizeof(PairDesc)));
     HIPC(hipStreamWaitEvent(s2, ctx->ev[14], 0));  // the reference points (not the readings) are on the device
     HIPC(hipEventRecord(ctx->ev[8], s2));
-    HIPC(hipMemcpyAsync(ctx->rdesc_raw.p, ctx->pin_rdesc.p, R * sizeof(PairDesc), hipMemcpyHostToDevice, s2));
-    launch_init_state(s2, (int)R, ctx->rdesc_raw.as<PairDesc>(), dRstate);
     uint64_t n_ref_max = 0;
     for (const PairDesc& r : B->rdesc) n_ref_max = std::max<uint64_t>(n_ref_max, r.n_ref);
     // s3 (worker thread; it still polls its levels in a polled redo): centroid, centred
     // reference, matcher tree, pair frames
     const int plan1 = plan_levels(n_ref_max, ctx->tb[1], ctx->opt.tree_plan);
-    // Large batches build the raw tree first and the matcher tree beside the normals' kNN
-    // (raw_tree_first()): the raw tree gates the kNN, which gates the loop, while the matcher
-    // tree is needed only by the loop; built together, the two trees' latency-bound subtree
-    // kernels share the CUs' wave slots and both finish late.
-    const bool raw_first = raw_tree_first(B->total_ref, ctx->opt);
-    if (!raw_first)
+    if (p2p) {
+      // the matcher tree alone. s2 has no work of its own before the loop's set-up; it still
+      // records the events that the later code and the phase times read (ev[13] is waited on only
+      // by a matcher worker that is given it, below)
       worker = std::thread([&, plan1] { wrc = matcher_trees(ctx, B, cfg->bucket_size, dDesc, dRdesc, plan1, werr); });
-    // SurfaceNormal runs on the reference as given, before the centring (ICP::compute,
-    // SURVEY A.1 steps 1-2): its own libnabo tree over the raw coordinates first
-    rc = device_trees_begin(ctx->tb[0], ctx->err, s2, R, B->total_ref, ctx->rdesc_raw.as<PairDesc>(),
-                            B->ref_raw.as<float4>(), 0, kNormalsBucket, ctx->bpts_raw, ctx->nodes_raw);
-    if (rc) return join_worker(rc);
-    // s2: raw tree levels + subtrees, SurfaceNormal, all enqueued before the host waits for
-    // the overlap's key boxes
-    const int rf = ctx->opt.raw_first_at;
-    rc = device_trees_end(ctx->tb[0], ctx->err, s2, R, B->total_ref, ctx->rdesc_raw.as<PairDesc>(), kNormalsBucket,
-                          ctx->bpts_raw, ctx->nodes_raw, plan_levels(n_ref_max, ctx->tb[0], ctx->opt.tree_plan, true), nullptr, true,
-                          raw_first && rf == 2 ? ctx->ev[13] : nullptr);
-    if (rc) return join_worker(rc);
-    if (raw_first) {
-      if (rf != 2) HIPC(hipEventRecord(ctx->ev[13], s2));
-      worker = std::thread(
-          [&, plan1] { wrc = matcher_trees(ctx, B, cfg->bucket_size, dDesc, dRdesc, plan1, werr, ctx->ev[13]); });
+      HIPC(hipEventRecord(ctx->ev[10], s2));
+    } else {
+      HIPC(ensure(ctx->rdesc_raw, R * sizeof(PairDesc)));
+      HIPC(hipMemcpyAsync(ctx->rdesc_raw.p, ctx->pin_rdesc.p, R * sizeof(PairDesc), hipMemcpyHostToDevice, s2));
+      launch_init_state(s2, (int)R, ctx->rdesc_raw.as<PairDesc>(), dRstate);
+      // Large batches build the raw tree first and the matcher tree beside the normals' kNN
+      // (raw_tree_first()): the raw tree gates the kNN, which gates the loop, while the matcher
+      // tree is needed only by the loop; built together, the two trees' latency-bound subtree
+      // kernels share the CUs' wave slots and both finish late.
+      const bool raw_first = raw_tree_first(B->total_ref, ctx->opt);
+      if (!raw_first)
+        worker = std::thread([&, plan1] { wrc = matcher_trees(ctx, B, cfg->bucket_size, dDesc, dRdesc, plan1, werr); });
+      // SurfaceNormal runs on the reference as given, before the centring (ICP::compute,
+      // SURVEY A.1 steps 1-2): its own libnabo tree over the raw coordinates first
+      rc = device_trees_begin(ctx->tb[0], ctx->err, s2, R, B->total_ref, ctx->rdesc_raw.as<PairDesc>(),
+                              B->ref_raw.as<float4>(), 0, kNormalsBucket, ctx->bpts_raw, ctx->nodes_raw);
+      if (rc) return join_worker(rc);
+      // s2: raw tree levels + subtrees, SurfaceNormal, all enqueued before the host waits for
+      // the overlap's key boxes
+      const int rf = ctx->opt.raw_first_at;
+      rc = device_trees_end(ctx->tb[0], ctx->err, s2, R, B->total_ref, ctx->rdesc_raw.as<PairDesc>(), kNormalsBucket,
+                            ctx->bpts_raw, ctx->nodes_raw, plan_levels(n_ref_max, ctx->tb[0], ctx->opt.tree_plan, true), nullptr, true,
+                            raw_first && rf == 2 ? ctx->ev[13] : nullptr);
+      if (rc) return join_worker(rc);
+      if (raw_first) {
+        if (rf != 2) HIPC(hipEventRecord(ctx->ev[13], s2));
+        worker = std::thread(
+            [&, plan1] { wrc = matcher_trees(ctx, B, cfg->bucket_size, dDesc, dRdesc, plan1, werr, ctx->ev[13]); });
+      }
+      // normals on the raw tree (bucket order of that tree)
+      HIPC(ensure(ctx->nrm_raw, B->total_ref * 16));
+      HIPC(ensure(ctx->nbids, B->total_ref * 4 * (size_t)cfg->knn_normals));
+      uint32_t* nCtr = dCtr + kKnnCtrOff;
+      if (!launch_normals(s2, (int)R, (uint32_t)B->total_ref, ctx->rdesc_raw.as<PairDesc>(), dRstate,
+                          ctx->nodes_raw.as<uint4>(), nullptr, ctx->bpts_raw.as<float4>(), ctx->nrm_raw.as<float4>(),
+                          cfg->knn_normals, ctx->nbids.as<int32_t>(), nCtr, ctx->opt.normals_knn_engine))
+        FAIL(AICP_ERR_UNSUPPORTED, "normals knn");
+      HIPC(hipEventRecord(ctx->ev[10], s2));
     }
-    // normals on the raw tree (bucket order of that tree)
-    HIPC(ensure(ctx->nrm_raw, B->total_ref * 16));
-    HIPC(ensure(ctx->nbids, B->total_ref * 4 * (size_t)cfg->knn_normals));
-    uint32_t* nCtr = dCtr + kKnnCtrOff;
-    if (!launch_normals(s2, (int)R, (uint32_t)B->total_ref, ctx->rdesc_raw.as<PairDesc>(), dRstate,
-                        ctx->nodes_raw.as<uint4>(), nullptr, ctx->bpts_raw.as<float4>(), ctx->nrm_raw.as<float4>(),
-                        cfg->knn_normals, ctx->nbids.as<int32_t>(), nCtr, ctx->opt.normals_knn_engine))
-      FAIL(AICP_ERR_UNSUPPORTED, "normals knn");
-    HIPC(hipEventRecord(ctx->ev[10], s2));
   }
   if (doOvl) {
     rc = join_ovl(doIcp ? AICP_OK : overlap_maps(ctx, B, P, G, dDesc, dState, dG, dGst, readS, res, false, oerr));
@@ -911,7 +923,7 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
     HIPC(hipStreamWaitEvent(s2, ctx->ev[3], 0));
     HIPC(ensure(ctx->read_c, B->total_read * 16));
     HIPC(ensure(ctx->bpts, B->total_ref * 16));
-    HIPC(ensure(ctx->bnrm, B->total_ref * 16));
+    if (!p2p) HIPC(ensure(ctx->bnrm, B->total_ref * 16));
     HIPC(ensure(ctx->match, B->total_read * 4));
     HIPC(ensure(ctx->d2, B->total_read * 4));
     HIPC(ensure(ctx->touch, B->total_read * 4));
@@ -924,7 +936,7 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
     HIPC(ensure(ctx->isync, icp_sync_words(P) * 4));
     HIPC(hipMemsetAsync(ctx->isync.p, 0, icp_sync_words(P) * 4, s));
     float4* bpts = ctx->bpts.as<float4>();
-    float4* bnrm = ctx->bnrm.as<float4>();
+    float4* bnrm = p2p ? nullptr : ctx->bnrm.as<float4>();
     float4* readc = ctx->read_c.as<float4>();
     const uint4* nodes = ctx->nodes.as<uint4>();
     HIPC(hipStreamWaitEvent(s2, ctx->ev[11], 0));
@@ -932,11 +944,13 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
     launch_prepare_read(s2, B->m_read, dDesc, readS, readc);
     // normals from the raw tree's bucket order into the matcher tree's bucket order (a cached
     // reference's are there already)
-    HIPC(ensure(ctx->inv, B->total_ref * 4));
-    if (!hit_trees)
-      launch_normals_to_matcher(s2, (int)R, (uint32_t)B->total_ref, dRdesc, bpts, ctx->bpts_raw.as<float4>(),
-                                ctx->nrm_raw.as<float4>(), ctx->inv.as<uint32_t>(), bnrm);
-    launch_pairs_degenerate(s2, (int)P, dDesc, dState, dRstate);
+    if (!p2p) {
+      HIPC(ensure(ctx->inv, B->total_ref * 4));
+      if (!hit_trees)
+        launch_normals_to_matcher(s2, (int)R, (uint32_t)B->total_ref, dRdesc, bpts, ctx->bpts_raw.as<float4>(),
+                                  ctx->nrm_raw.as<float4>(), ctx->inv.as<uint32_t>(), bnrm);
+      launch_pairs_degenerate(s2, (int)P, dDesc, dState, dRstate);
+    }
     HIPC(hipEventRecord(ctx->ev[4], s2));
     HIPC(hipStreamWaitEvent(s, ctx->ev[4], 0));
     HIPC(hipEventRecord(ctx->ev[9], s));
@@ -1058,7 +1072,7 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
   HIPC(hipStreamSynchronize(s));
   if (doIcp && !hit_trees) {  // planned tree builds: errors recorded on the device
     rcache.trees = false;
-    rc = device_trees_check(ctx->tb[0], ctx->err);
+    rc = p2p ? AICP_OK : device_trees_check(ctx->tb[0], ctx->err);  // (no raw tree was built)
     if (!rc) rc = device_trees_check(ctx->tb[1], ctx->err);
     if (rc) return rc;
     if (ctx->tl_total && (ctx->tb[1].pin_ctl.as<TreeCtl>()->error & 4))
@@ -1819,14 +1833,15 @@ int aicp_hip_test_select(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* coun
 // red_blk_off / n_red_blk, states, the kReduceBlock-reading block map, zeroed work space,
 // IcpIterSync). Every argument is checked before the device is touched. The readings, reference
 // points and normals live in buffers of this call (the context's hold the resident reference).
-int aicp_hip_test_step(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read, const uint32_t* n_ref,
+// ref_nrm null: the point-to-point kernels (aicp_hip_test_step_p2p), which read no normals.
+static int test_step_run(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read, const uint32_t* n_ref,
                        const uint32_t* ref_off, size_t total_ref, const float* read_c, const float* ref_pts,
                        const float* ref_nrm, const float* init_T, const uint8_t* active, int32_t max_iter,
                        int32_t smooth, float min_rot, float min_trans, size_t n_steps, const float* limit,
                        const int32_t* match, const float* d2, const uint32_t* touched, double* out_slab,
                        float* out_T, int32_t* out_state, float* out_inlier, uint64_t* out_touched,
                        double* out_dqdt, uint64_t* out_dirty) {
-  if (!ctx || !n_read || !n_ref || !ref_off || !read_c || !ref_pts || !ref_nrm || !limit || !match || !d2 ||
+  if (!ctx || !n_read || !n_ref || !ref_off || !read_c || !ref_pts || !limit || !match || !d2 ||
       !touched || !out_slab || !out_T || !out_state || !out_inlier || !out_touched || !out_dqdt || !out_dirty)
     return AICP_ERR_INVALID;
   if (n_pairs == 0 || n_pairs > (size_t)kMaxPairs || n_steps == 0 || total_ref == 0) return AICP_ERR_INVALID;
@@ -1881,7 +1896,7 @@ int aicp_hip_test_step(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read
   } loc;
   HIPC(ensure(loc.read_c, total * 16));
   HIPC(ensure(loc.bpts, total_ref * 16));
-  HIPC(ensure(loc.bnrm, total_ref * 16));
+  if (ref_nrm) HIPC(ensure(loc.bnrm, total_ref * 16));
   HIPC(ensure(ctx->desc, P * sizeof(PairDesc)));
   HIPC(ensure(ctx->state, P * sizeof(PairState)));
   HIPC(ensure(ctx->match, total * n_steps * 4));
@@ -1904,7 +1919,7 @@ int aicp_hip_test_step(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read
   };
   HIPC(upload4(read_c, total, loc.read_c.p));
   HIPC(upload4(ref_pts, total_ref, loc.bpts.p));
-  HIPC(upload4(ref_nrm, total_ref, loc.bnrm.p));
+  if (ref_nrm) HIPC(upload4(ref_nrm, total_ref, loc.bnrm.p));
   PairDesc* dDesc = ctx->desc.as<PairDesc>();
   PairState* dState = ctx->state.as<PairState>();
   uint32_t* sync = ctx->isync.as<uint32_t>();
@@ -1938,6 +1953,7 @@ int aicp_hip_test_step(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read
   prm.smooth = smooth;
   prm.min_rot = min_rot;
   prm.min_trans = min_trans;
+  prm.knn_normals = ref_nrm ? 20 : 0;  // (which pair of kernels launch_icp_reduce_f launches)
   std::vector<PairState> hs(P);
   constexpr uint32_t kSentinel = 0x7FF8DEADu;  // both halves: a NaN no sum produces
   for (size_t s = 0; s < n_steps; ++s) {
@@ -1978,6 +1994,31 @@ int aicp_hip_test_step(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read
   for (uint32_t v : w) dirty += v != 0;
   *out_dirty = dirty;
   return AICP_OK;
+}
+
+int aicp_hip_test_step(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read, const uint32_t* n_ref,
+                       const uint32_t* ref_off, size_t total_ref, const float* read_c, const float* ref_pts,
+                       const float* ref_nrm, const float* init_T, const uint8_t* active, int32_t max_iter,
+                       int32_t smooth, float min_rot, float min_trans, size_t n_steps, const float* limit,
+                       const int32_t* match, const float* d2, const uint32_t* touched, double* out_slab,
+                       float* out_T, int32_t* out_state, float* out_inlier, uint64_t* out_touched,
+                       double* out_dqdt, uint64_t* out_dirty) {
+  if (!ref_nrm) return AICP_ERR_INVALID;
+  return test_step_run(ctx, n_pairs, n_read, n_ref, ref_off, total_ref, read_c, ref_pts, ref_nrm, init_T, active,
+                       max_iter, smooth, min_rot, min_trans, n_steps, limit, match, d2, touched, out_slab, out_T,
+                       out_state, out_inlier, out_touched, out_dqdt, out_dirty);
+}
+
+int aicp_hip_test_step_p2p(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read, const uint32_t* n_ref,
+                           const uint32_t* ref_off, size_t total_ref, const float* read_c, const float* ref_pts,
+                           const float* init_T, const uint8_t* active, int32_t max_iter, int32_t smooth,
+                           float min_rot, float min_trans, size_t n_steps, const float* limit, const int32_t* match,
+                           const float* d2, const uint32_t* touched, double* out_slab, float* out_T,
+                           int32_t* out_state, float* out_inlier, uint64_t* out_touched, double* out_dqdt,
+                           uint64_t* out_dirty) {
+  return test_step_run(ctx, n_pairs, n_read, n_ref, ref_off, total_ref, read_c, ref_pts, nullptr, init_T, active,
+                       max_iter, smooth, min_rot, min_trans, n_steps, limit, match, d2, touched, out_slab, out_T,
+                       out_state, out_inlier, out_touched, out_dqdt, out_dirty);
 }
 
 void aicp_hip_default_prefilter(aicp_prefilter_params* p) {
@@ -2566,6 +2607,7 @@ int aicp_hip_sequence_run_raw(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, con
   if (doOvl && !(prm->resolution > 0)) FAIL(AICP_ERR_INVALID, "resolution");
   rc = check_cfg(ctx, cfg, AICP_RUN_ICP | (doOvl ? AICP_RUN_OVERLAP : 0));
   if (rc) return rc;
+  if (cfg->knn_normals == 0) FAIL(AICP_ERR_UNSUPPORTED, "point-to-point chain in the frame-to-reference stream");
   if (!valid_cloud(*first)) FAIL(AICP_ERR_INVALID, "invalid first cloud");
   for (size_t i = 0; i < n; ++i)
     if (!valid_cloud(readings[i])) FAIL(AICP_ERR_INVALID, "invalid reading " + std::to_string(i));

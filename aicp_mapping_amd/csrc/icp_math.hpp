@@ -446,6 +446,120 @@ AICP_HD int solve6(const double* A, const double* b, double* x) {
   return 2;
 }
 
+// ---- 3x3 SVD, one-sided (Hestenes) Jacobi -------------------------------------------------
+// M = U diag(sig) V^T (all row-major), sig descending with ties by index. The columns of a copy of
+// M are rotated against each other in the fixed order (0,1), (0,2), (1,2) until a sweep rotates
+// nothing (two columns count as orthogonal when (a_p . a_q)^2 <= eps^2 |a_p|^2 |a_q|^2) or
+// kSvd3Sweeps sweeps have run; V accumulates the rotations. Working on M itself, not on M^T M,
+// keeps the condition number unsquared: a column's direction is accurate relative to its own
+// norm. Only + - * / sqrt and comparisons in double, no dynamic index: tests/p2p_reference.py
+// restates it operation for operation. A column of U whose sig is 0 (or not finite) is not
+// normalised: its entries are those of the rotated column.
+constexpr int kSvd3Sweeps = 30;
+
+#define AICP_SVD3_ROT(p, q)                                                      \
+  {                                                                              \
+    const double al = (a[p] * a[p] + a[3 + p] * a[3 + p]) + a[6 + p] * a[6 + p]; \
+    const double be = (a[q] * a[q] + a[3 + q] * a[3 + q]) + a[6 + q] * a[6 + q]; \
+    const double ga = (a[p] * a[q] + a[3 + p] * a[3 + q]) + a[6 + p] * a[6 + q]; \
+    if (ga * ga > (kDblEps * kDblEps) * (al * be)) {                             \
+      rotated = true;                                                            \
+      const double ze = (be - al) / (2.0 * ga);                                  \
+      const double az = ze < 0 ? -ze : ze;                                       \
+      const double tt = (ze < 0 ? -1.0 : 1.0) / (az + sqrt(ze * ze + 1.0));      \
+      const double cc = 1.0 / sqrt(tt * tt + 1.0), ss = tt * cc;                 \
+      AICP_UNROLL for (int k = 0; k < 3; ++k) {                                  \
+        const double ap = a[3 * k + p], aq = a[3 * k + q];                       \
+        a[3 * k + p] = cc * ap - ss * aq;                                        \
+        a[3 * k + q] = ss * ap + cc * aq;                                        \
+        const double vp = V[3 * k + p], vq = V[3 * k + q];                       \
+        V[3 * k + p] = cc * vp - ss * vq;                                        \
+        V[3 * k + q] = ss * vp + cc * vq;                                        \
+      }                                                                          \
+    }                                                                            \
+  }
+
+// columns j and j + 1 of a and V and their sig swapped when sig[j] < sig[j + 1]
+#define AICP_SVD3_ORDER(j)                             \
+  if (sig[j] < sig[j + 1]) {                           \
+    double t_ = sig[j];                                \
+    sig[j] = sig[j + 1];                               \
+    sig[j + 1] = t_;                                   \
+    AICP_UNROLL for (int k = 0; k < 3; ++k) {          \
+      t_ = a[3 * k + j];                               \
+      a[3 * k + j] = a[3 * k + j + 1];                 \
+      a[3 * k + j + 1] = t_;                           \
+      t_ = V[3 * k + j];                               \
+      V[3 * k + j] = V[3 * k + j + 1];                 \
+      V[3 * k + j + 1] = t_;                           \
+    }                                                  \
+  }
+
+AICP_HD void svd3(const double* M, double* U, double* sig, double* V) {
+  double a[9];
+  AICP_UNROLL for (int i = 0; i < 9; ++i) {
+    a[i] = M[i];
+    V[i] = (i % 4 == 0) ? 1.0 : 0.0;
+  }
+  for (int sweep = 0; sweep < kSvd3Sweeps; ++sweep) {
+    bool rotated = false;
+    AICP_SVD3_ROT(0, 1)
+    AICP_SVD3_ROT(0, 2)
+    AICP_SVD3_ROT(1, 2)
+    if (!rotated) break;
+  }
+  AICP_UNROLL for (int j = 0; j < 3; ++j) sig[j] = sqrt((a[j] * a[j] + a[3 + j] * a[3 + j]) + a[6 + j] * a[6 + j]);
+  AICP_SVD3_ORDER(0)
+  AICP_SVD3_ORDER(1)
+  AICP_SVD3_ORDER(0)
+  AICP_UNROLL for (int j = 0; j < 3; ++j)
+    AICP_UNROLL for (int k = 0; k < 3; ++k) U[3 * k + j] = sig[j] > 0 ? a[3 * k + j] / sig[j] : a[3 * k + j];
+}
+#undef AICP_SVD3_ROT
+#undef AICP_SVD3_ORDER
+
+AICP_HD double det3(const double* R) {
+  const double d0 = R[0] * (R[4] * R[8] - R[5] * R[7]);
+  const double d1 = R[3] * (R[1] * R[8] - R[2] * R[7]);
+  const double d2 = R[6] * (R[1] * R[5] - R[2] * R[4]);
+  return (d0 - d1) + d2;
+}
+
+// The proper rotation R (row-major) that maximises tr(R^T M), M = sum (q - qm)(p - pm)^T:
+// PointToPointErrorMinimizer's R = U V^T with the row of V^T of the smallest singular value
+// negated when det(U V^T) < 0. A singular value counts when sig_i > sig_0 * 3 FLT_EPSILON (the
+// rank rule in solve6's form). Rank 3: as stated. Rank 2: the third columns of U and V are the
+// cross products of the first two, which is what the determinant rule yields. Rank < 2 (one point,
+// collinear points): the data do not fix R; R = I. Returns the rank.
+AICP_HD int p2p_rotation(const double* M, double* R) {
+  double U[9], sig[3], V[9];
+  svd3(M, U, sig, V);
+  const double thr = sig[0] * (3.0 * (double)kFltEps);
+  int rank = 0;
+  AICP_UNROLL for (int j = 0; j < 3; ++j) rank += sig[j] > thr ? 1 : 0;
+  if (rank < 2) {
+    AICP_UNROLL for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    return rank;
+  }
+  if (rank == 2) {
+    U[2] = U[3] * U[7] - U[6] * U[4];
+    U[5] = U[6] * U[1] - U[0] * U[7];
+    U[8] = U[0] * U[4] - U[3] * U[1];
+    V[2] = V[3] * V[7] - V[6] * V[4];
+    V[5] = V[6] * V[1] - V[0] * V[7];
+    V[8] = V[0] * V[4] - V[3] * V[1];
+  }
+  AICP_UNROLL for (int r = 0; r < 3; ++r)
+    AICP_UNROLL for (int c = 0; c < 3; ++c)
+      R[3 * r + c] = (U[3 * r] * V[3 * c] + U[3 * r + 1] * V[3 * c + 1]) + U[3 * r + 2] * V[3 * c + 2];
+  if (rank == 3 && det3(R) < 0) {
+    AICP_UNROLL for (int r = 0; r < 3; ++r)
+      AICP_UNROLL for (int c = 0; c < 3; ++c)
+        R[3 * r + c] = (U[3 * r] * V[3 * c] + U[3 * r + 1] * V[3 * c + 1]) - U[3 * r + 2] * V[3 * c + 2];
+  }
+  return rank;
+}
+
 // SurfaceNormal: rank(fullPivQR(C)) + 1 >= 3 -> smallest eigenvector, else e_y.
 AICP_HD bool normal_from_cov(const double* C, float* nrm) {
   PivQR<3> qr;

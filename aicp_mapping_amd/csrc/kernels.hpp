@@ -86,6 +86,8 @@ constexpr uint32_t kFinalLds = 8192;  // candidates the final select of a pair c
 void launch_icp_select_fused(hipStream_t s, BlockMap m, const PairDesc* pd, PairState* st, const float* d2,
                              uint32_t* hist1, uint32_t* cand, uint32_t* cand_cnt, const IcpIterSync& y,
                              uint32_t force_cl = 0);
+// prm.knn_normals == 0: the point-to-point pair of kernels (k_icp_reduce_p2p / k_icp_update_p2p;
+// bnrm is not read and may be null), else k_icp_reduce / k_icp_update_f
 void launch_icp_reduce_f(hipStream_t s, BlockMap m, const PairDesc* pd, PairState* st, const float4* read_c,
                          const int32_t* match, const float* d2, const uint32_t* touched, const float4* bpts,
                          const float4* bnrm, double* slab, const IcpParams& prm, const IcpIterSync& y);

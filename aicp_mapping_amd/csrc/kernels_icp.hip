@@ -14,6 +14,9 @@
 //                  sums + LDS, one deterministic partial row per workgroup (no atomics)
 //   k_icp_update_f fixed-order sum of the partial rows, 6x6 solve, AngleAxis update of T_iter,
 //                  Counter + Differential checkers, per-pair active flag
+//   k_icp_reduce_p2p / k_icp_update_p2p  the last two for PointToPointErrorMinimizer
+//                  (IcpParams::knn_normals == 0): sums of q p^T, p and q without a normal
+//                  gather; means, 3x3 SVD rotation, translation, the same checkers
 // SurfaceNormal: k_knn_ids (persistent kNN, eps 0, ids only) + k_normals_from_ids (uniform
 // covariance / eigen work per point).
 #include <hip/hip_ext.h>
@@ -2339,33 +2342,9 @@ __device__ __forceinline__ void normal_system(const double* tot, double* A, doub
   for (int a = 0; a < 6; ++a) b[a] = -tot[21 + a];
 }
 
-// the serial part of an ICP update (one lane): solve, compose, checkers
-// x_full: the LLT solution when the pivoted-QR rank is full (solve6's first path, computed by
-// two waves side by side in icp_update_body), or nullptr: solve6 here
-__device__ void update_serial(const PairDesc& d, PairState& s, const double* tot, const IcpParams& prm,
-                              const double* x_full) {
-  s.touched_pts += (uint64_t)tot[28];
-  s.touched_nodes += (uint64_t)tot[29];
-  const int32_t kept = (int32_t)tot[27];
-  s.kept = kept;
-  if (kept == 0) {  // ConvergenceError("no point to minimize")
-    s.status = 1;
-    s.active = 0;
-    return;
-  }
-  double xd[6];
-  if (x_full) {
-    for (int a = 0; a < 6; ++a) xd[a] = x_full[a];
-  } else {
-    double A[36], b[6];
-    normal_system(tot, A, b);
-    solve6(A, b, xd);
-  }
-  float x[6];
-  for (int a = 0; a < 6; ++a) x[a] = (float)xd[a];
-  float dT[16];
-  delta_transform(x, dT);
-  mul4(dT, s.T, s.T);
+// what follows the composition of T_iter in every update, whichever the error minimizer: the
+// inlier ratio and the checkers
+__device__ __forceinline__ void update_tail(const PairDesc& d, PairState& s, int32_t kept, const IcpParams& prm) {
   s.inlier_ratio = (float)((double)(float)kept / (double)d.n_read);
   // checkers (YAML order): Counter, then Differential. The new T_iter is applied to the reading
   // at the start of the next iteration (or, inside the final T, to the output reading), where
@@ -2412,6 +2391,36 @@ __device__ void update_serial(const PairDesc& d, PairState& s, const double* tot
     }
   }
   s.active = iterate ? 1 : 0;
+}
+
+// the serial part of an ICP update (one lane): solve, compose, checkers
+// x_full: the LLT solution when the pivoted-QR rank is full (solve6's first path, computed by
+// two waves side by side in icp_update_body), or nullptr: solve6 here
+__device__ void update_serial(const PairDesc& d, PairState& s, const double* tot, const IcpParams& prm,
+                              const double* x_full) {
+  s.touched_pts += (uint64_t)tot[28];
+  s.touched_nodes += (uint64_t)tot[29];
+  const int32_t kept = (int32_t)tot[27];
+  s.kept = kept;
+  if (kept == 0) {  // ConvergenceError("no point to minimize")
+    s.status = 1;
+    s.active = 0;
+    return;
+  }
+  double xd[6];
+  if (x_full) {
+    for (int a = 0; a < 6; ++a) xd[a] = x_full[a];
+  } else {
+    double A[36], b[6];
+    normal_system(tot, A, b);
+    solve6(A, b, xd);
+  }
+  float x[6];
+  for (int a = 0; a < 6; ++a) x[a] = (float)xd[a];
+  float dT[16];
+  delta_transform(x, dT);
+  mul4(dT, s.T, s.T);
+  update_tail(d, s, kept, prm);
 }
 
 // one pair's update by a 256-thread workgroup: its slab rows summed (thread t sums column
@@ -2487,6 +2496,180 @@ __global__ __launch_bounds__(256) void k_icp_update_f(const PairDesc* __restrict
   PairState& s = st[pair];
   if (!s.active) return;
   icp_update_body(pd[pair], s, slab, prm);
+  AICP_IP_BODY(3);
+  AICP_IP_TAIL0;
+  pair_done(y);
+  AICP_IP_TAIL(3);
+}
+
+// ---- PointToPointErrorMinimizer: the same two launches without the reference normals ----------
+// Slab row of a reduce workgroup (kRedCols columns, so the slab, red_blk_off and the update's row
+// sum keep their shape): 0..8 sum q_a p_b (index 3a + b; a product of two floats is exact in
+// double), 9..11 sum p, 12..14 sum q, 15..26 0.0, 27 kept, 28 / 29 touched points / nodes.
+// p = apply4(T_iter, r) in float, q = bpts[ref_off + match]; kept: d2 <= limit.
+constexpr int kP2pAcc = 18;  // the columns that are summed: 0..14, then 27..29
+
+__global__ __launch_bounds__(kNNBlock) void k_icp_reduce_p2p(
+    BlockMap m, const PairDesc* __restrict__ pd, const PairState* __restrict__ st,
+    const float4* __restrict__ read_c, const int32_t* __restrict__ match, const float* __restrict__ d2,
+    const uint32_t* __restrict__ touched, const float4* __restrict__ bpts, double* __restrict__ slab) {
+  AICP_IP_T0;
+  const int pair = m.pair[blockIdx.x];
+  const PairState& s = st[pair];
+  if (!s.active) return;
+  const PairDesc& d = pd[pair];
+  float T[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) T[i] = s.T[i];
+  const float limit = s.limit;
+  double acc[kP2pAcc];
+#pragma unroll
+  for (int i = 0; i < kP2pAcc; ++i) acc[i] = 0.0;
+  uint32_t tpts = 0, tnod = 0;
+  // as icp_reduce_body: the thread's four readings loaded first, then the gathers of the kept
+  // ones (16 B each, no normal), then the arithmetic
+  const uint32_t base = m.start[blockIdx.x];
+  bool keep[kReducePerThread];
+  int32_t pos[kReducePerThread];
+  float4 r[kReducePerThread];
+#pragma unroll
+  for (int it = 0; it < kReducePerThread; ++it) {
+    const uint32_t j = base + it * kNNBlock + threadIdx.x;
+    keep[it] = false;
+    pos[it] = 0;
+    if (j < d.n_read) {
+      const uint32_t tc = touched[d.read_off + j];
+      tpts += tc & 0xFFFFu;
+      tnod += tc >> 16;
+      keep[it] = d2[d.read_off + j] <= limit;
+      pos[it] = match[d.read_off + j];
+      r[it] = read_c[d.read_off + j];
+    }
+  }
+  float4 q[kReducePerThread];
+#pragma unroll
+  for (int it = 0; it < kReducePerThread; ++it)
+    if (keep[it]) q[it] = bpts[d.ref_off + pos[it]];
+#pragma unroll
+  for (int it = 0; it < kReducePerThread; ++it) {
+    if (!keep[it]) continue;
+    float p[3];
+    apply4(T, r[it].x, r[it].y, r[it].z, p);
+    const float qv[3] = {q[it].x, q[it].y, q[it].z};
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) acc[3 * a + b] += (double)qv[a] * (double)p[b];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      acc[9 + a] += (double)p[a];
+      acc[12 + a] += (double)qv[a];
+    }
+    acc[15] += 1.0;
+  }
+  acc[16] = (double)tpts;
+  acc[17] = (double)tnod;
+  constexpr int kRows = kNNBlock / 16;
+  __shared__ double part[kRows][kP2pAcc];
+  const int lane = threadIdx.x & 63;
+  const int row = threadIdx.x >> 4;
+#pragma unroll
+  for (int i = 0; i < kP2pAcc; ++i) {
+    const double v = row_sum_d(acc[i]);
+    if ((lane & 15) == 0) part[row][i] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kRedCols) {
+    const int c = threadIdx.x;
+    const int src = c < 15 ? c : c - 12;  // (columns 27..29 are sums 15..17)
+    double v = 0.0;
+    if (c < 15 || c >= 27) {
+#pragma unroll
+      for (int w = 0; w < kRows; ++w) v += part[w][src];
+    }
+    const uint32_t srow = d.red_blk_off + m.start[blockIdx.x] / kReduceBlock;
+    slab[(size_t)srow * kRedCols + c] = v;
+  }
+  AICP_IP_BODY(2);
+}
+
+// the serial part of a point-to-point update (one lane): means, M, R = U V^T, t, compose, checkers
+__device__ void update_serial_p2p(const PairDesc& d, PairState& s, const double* tot, const IcpParams& prm) {
+  s.touched_pts += (uint64_t)tot[28];
+  s.touched_nodes += (uint64_t)tot[29];
+  const int32_t kept = (int32_t)tot[27];
+  s.kept = kept;
+  if (kept == 0) {  // ConvergenceError("no point to minimize")
+    s.status = 1;
+    s.active = 0;
+    return;
+  }
+  const double n = (double)kept;
+  double pm[3], qm[3], M[9], R[9];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    pm[a] = tot[9 + a] / n;
+    qm[a] = tot[12 + a] / n;
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) M[3 * a + b] = tot[3 * a + b] - (tot[12 + a] * tot[9 + b]) / n;
+  p2p_rotation(M, R);
+  float dT[16];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double t = qm[a] - ((R[3 * a] * pm[0] + R[3 * a + 1] * pm[1]) + R[3 * a + 2] * pm[2]);
+#pragma unroll
+    for (int b = 0; b < 3; ++b) dT[b * 4 + a] = (float)R[3 * a + b];
+    dT[12 + a] = (float)t;
+    dT[a * 4 + 3] = 0.f;
+  }
+  dT[15] = 1.f;
+  mul4(dT, s.T, s.T);
+  update_tail(d, s, kept, prm);
+}
+
+// k_icp_update_f's row sum (thread t: column t % kRedCols over rows t / kRedCols + 8 k in order,
+// then the 8 groups in order), then update_serial_p2p on lane 0
+__global__ __launch_bounds__(256) void k_icp_update_p2p(const PairDesc* __restrict__ pd, PairState* st,
+                                                        const double* __restrict__ slab, IcpParams prm,
+                                                        IcpIterSync y) {
+  AICP_IP_T0;
+  const int pair = blockIdx.x;
+  PairState& s = st[pair];
+  if (!s.active) return;
+  const PairDesc& d = pd[pair];
+  constexpr int kGroups = 256 / kRedCols;
+  __shared__ double part[kGroups][kRedCols];
+  __shared__ double tot[kRedCols];
+  const int t = threadIdx.x;
+  if (t < kGroups * kRedCols) {
+    const int g = t / kRedCols, c = t - g * kRedCols;
+    const double* col = slab + (size_t)d.red_blk_off * kRedCols + c;
+    double v = 0.0;
+    for (uint32_t r0 = g; r0 < d.n_red_blk; r0 += 16u * kGroups) {
+      double x[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const uint32_t r = r0 + (uint32_t)u * kGroups;
+        x[u] = r < d.n_red_blk ? col[(size_t)r * kRedCols] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u)
+        if (r0 + (uint32_t)u * kGroups < d.n_red_blk) v += x[u];
+    }
+    part[g][c] = v;
+  }
+  __syncthreads();
+  if (t < kRedCols) {
+    double v = part[0][t];
+#pragma unroll
+    for (int g = 1; g < kGroups; ++g) v += part[g][t];
+    tot[t] = v;
+  }
+  __syncthreads();
+  if (t == 0) update_serial_p2p(d, s, tot, prm);
   AICP_IP_BODY(3);
   AICP_IP_TAIL0;
   pair_done(y);
@@ -2915,6 +3098,11 @@ void launch_icp_reduce_f(hipStream_t s, BlockMap m, const PairDesc* pd, PairStat
                          const int32_t* match, const float* d2, const uint32_t* touched, const float4* bpts,
                          const float4* bnrm, double* slab, const IcpParams& prm, const IcpIterSync& y) {
   if (!m.n_blocks) return;
+  if (prm.knn_normals == 0) {  // PointToPointErrorMinimizer (no reference normals: bnrm is not read)
+    k_icp_reduce_p2p<<<m.n_blocks, kNNBlock, 0, s>>>(m, pd, st, read_c, match, d2, touched, bpts, slab);
+    k_icp_update_p2p<<<y.np, 256, 0, s>>>(y.pd, y.st, slab, prm, y);
+    return;
+  }
   k_icp_reduce<<<m.n_blocks, kNNBlock, 0, s>>>(m, pd, st, read_c, match, d2, touched, bpts, bnrm, slab);
   k_icp_update_f<<<y.np, 256, 0, s>>>(y.pd, y.st, slab, prm, y);
 }

@@ -258,6 +258,7 @@ int aicp_hip_parse_pm_yaml(const char* path, aicp_icp_config* out) {
   c.bucket_size = 8;
   c.knn_match = 1;
   bool haveRefNormals = false, haveCounter = false, haveDifferential = false;
+  bool pointToPoint = false, refNormalsDropped = false;
   std::vector<std::pair<std::string, const Y*>> items;
 
   for (auto& kv : root.map) {
@@ -272,7 +273,7 @@ int aicp_hip_parse_pm_yaml(const char* path, aicp_icp_config* out) {
         int32_t keepNormals = 1;
         to_int(param(it.second, "keepNormals"), keepNormals);
         if (key == "referenceDataPointsFilters") {
-          if (!keepNormals) return AICP_ERR_UNSUPPORTED;
+          if (!keepNormals) refNormalsDropped = true;  // (refused below unless the minimizer ignores them)
           int32_t knn = 5;
           to_int(param(it.second, "knn"), knn);
           c.knn_normals = knn;
@@ -301,9 +302,16 @@ int aicp_hip_parse_pm_yaml(const char* path, aicp_icp_config* out) {
       std::string name;
       const Y* p;
       if (!single(v, name, p)) return AICP_ERR_INVALID;
-      if (name != "PointToPlaneErrorMinimizer") return AICP_ERR_UNSUPPORTED;
-      int32_t f2d = 0;
-      if (to_int(param(p, "force2D"), f2d) && f2d) return AICP_ERR_UNSUPPORTED;
+      if (name == "PointToPointErrorMinimizer") {
+        // the bare name, as the reference's chain files write it. The map form
+        // ("PointToPointErrorMinimizer:", with or without parameters) stays unsupported, as before
+        if (p) return AICP_ERR_UNSUPPORTED;
+        pointToPoint = true;
+      } else {
+        if (name != "PointToPlaneErrorMinimizer") return AICP_ERR_UNSUPPORTED;
+        int32_t f2d = 0;
+        if (to_int(param(p, "force2D"), f2d) && f2d) return AICP_ERR_UNSUPPORTED;
+      }
     } else if (key == "transformationCheckers") {
       if (!list_items(v, items)) return AICP_ERR_INVALID;
       for (auto& it : items) {
@@ -329,7 +337,14 @@ int aicp_hip_parse_pm_yaml(const char* path, aicp_icp_config* out) {
       return AICP_ERR_UNSUPPORTED;
     }
   }
-  if (!haveRefNormals || !haveCounter) return AICP_ERR_UNSUPPORTED;
+  if (pointToPoint) {
+    // the reference's SurfaceNormal output is unused, as the reading's is: the filter is optional
+    // and ignored; knn_normals = 0 selects the minimizer (include/aicp_hip.h)
+    c.knn_normals = 0;
+  } else if (!haveRefNormals || refNormalsDropped) {
+    return AICP_ERR_UNSUPPORTED;
+  }
+  if (!haveCounter) return AICP_ERR_UNSUPPORTED;
   if (!haveDifferential) {
     c.min_diff_rot = -1.f;  // never fires
     c.min_diff_trans = -1.f;

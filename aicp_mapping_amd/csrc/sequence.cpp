@@ -1302,6 +1302,8 @@ int aicp_hip_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const a
   if (doOvl && !(prm->resolution > 0)) FAIL(AICP_ERR_INVALID, "resolution");
   int rc = check_cfg(ctx, cfg, AICP_RUN_ICP | (doOvl ? AICP_RUN_OVERLAP : 0));
   if (rc) return rc;
+  // this stream owns its reference chain (raw tree, SurfaceNormal, scatter): point-to-plane only
+  if (cfg->knn_normals == 0) FAIL(AICP_ERR_UNSUPPORTED, "point-to-point chain in the frame-to-reference stream");
   auto valid = [](const aicp_cloud& c) {
     return c.pts && c.n >= 1 && c.n < (1ull << 28) && c.stride >= 12 && c.stride % 4 == 0;
   };

@@ -50,9 +50,16 @@ extern "C" {
 typedef struct aicp_hip_ctx aicp_hip_ctx;
 typedef struct aicp_hip_batch aicp_hip_batch;
 
-/* The libpointmatcher chain subset of icp_autotuned_default.yaml:9-51. */
+/* The libpointmatcher chain subset of icp_autotuned_default.yaml:9-51, and its point-to-point
+ * variant (icp_2Dtesting_cfg.yaml).
+ * knn_normals: 10, 20 or 30 run SurfaceNormal on the reference and PointToPlaneErrorMinimizer;
+ * 0 means no SurfaceNormal on the reference and PointToPointErrorMinimizer (point-to-plane cannot
+ * run without normals, so the value is unambiguous). aicp_hip_parse_pm_yaml sets 0 for a chain
+ * whose errorMinimizer is the bare name PointToPointErrorMinimizer, as the reference's chain files
+ * write it (the map form "PointToPointErrorMinimizer:" stays AICP_ERR_UNSUPPORTED, as it was). Served by the register / batch / multi /
+ * localization-stream calls; aicp_hip_sequence_run and _run_raw return AICP_ERR_UNSUPPORTED. */
 typedef struct {
-  int32_t knn_normals;    /* SurfaceNormalDataPointsFilter.knn            (20)   */
+  int32_t knn_normals;    /* SurfaceNormalDataPointsFilter.knn; 0: point-to-point (20) */
   float nn_epsilon;       /* KDTreeMatcher.epsilon                        (3.16) */
   float nn_max_dist;      /* KDTreeMatcher.maxDist                        (inf)  */
   float trimmed_ratio;    /* TrimmedDistOutlierFilter.ratio               (0.70) */
@@ -774,6 +781,18 @@ int aicp_hip_test_step(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read
                        const uint32_t* touched /* each n_steps * total */, double* out_slab, float* out_T,
                        int32_t* out_state, float* out_inlier, uint64_t* out_touched, double* out_dqdt,
                        uint64_t* out_dirty);
+/* The same for the PointToPointErrorMinimizer's kernels, k_icp_reduce_p2p and k_icp_update_p2p:
+ * aicp_hip_test_step without ref_nrm (no normals are read). Slab columns: 0..8 sum q_a p_b (3a + b),
+ * 9..11 sum p, 12..14 sum q, 15..26 0.0, 27 kept, 28 / 29 touched points / nodes. */
+int aicp_hip_test_step_p2p(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read, const uint32_t* n_ref,
+                           const uint32_t* ref_off, size_t total_ref, const float* read_c, const float* ref_pts,
+                           const float* init_T /* nullable */,
+                           const uint8_t* active /* nullable: 0 = pair starts inactive */, int32_t max_iter,
+                           int32_t smooth, float min_rot, float min_trans, size_t n_steps,
+                           const float* limit /* n_steps * n_pairs */, const int32_t* match, const float* d2,
+                           const uint32_t* touched /* each n_steps * total */, double* out_slab, float* out_T,
+                           int32_t* out_state, float* out_inlier, uint64_t* out_touched, double* out_dqdt,
+                           uint64_t* out_dirty);
 
 #ifdef __cplusplus
 }
