@@ -51,6 +51,7 @@ EXPORTS = [
     "aicp_hip_last_localization_timing",
     "aicp_hip_map_align_batch", "aicp_hip_map_capacity", "aicp_hip_default_built_map_params",
     "aicp_hip_built_map_window", "aicp_hip_built_map_sequence_run", "aicp_hip_last_built_map_timing",
+    "aicp_hip_map_sequence_run_raw", "aicp_hip_built_map_sequence_run_raw", "aicp_hip_test_ingest",
 ]
 
 
@@ -67,7 +68,9 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_map_align_batch", "aicp_hip_map_capacity", "aicp_hip_default_built_map_params",
            "aicp_hip_built_map_window", "aicp_hip_built_map_sequence_run",
            "aicp_hip_last_built_map_timing",  # the built-map localization stream
-           "aicp_hip_test_step_p2p"}  # the point-to-point chains
+           "aicp_hip_test_step_p2p",  # the point-to-point chains
+           "aicp_hip_map_sequence_run_raw", "aicp_hip_built_map_sequence_run_raw",
+           "aicp_hip_test_ingest"}  # raw readings in the two map streams
 
 
 class IcpConfig(C.Structure):
@@ -515,6 +518,13 @@ def _load():
         u32p, u8p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
         L.aicp_hip_test_step_p2p.argtypes = [vp, sz, u32p, u32p, u32p, sz, fp, fp, fp, u8p, C.c_int32, C.c_int32,
                                              C.c_float, C.c_float, sz, fp, ip, fp, u32p, dp, fp, ip, fp, up, dp, up]
+    if hasattr(L, "aicp_hip_map_sequence_run_raw"):  # (the pre-filtered streams' plus pf_read and out_kept)
+        u32p, pfp, clp = C.POINTER(C.c_uint32), C.POINTER(PrefilterParams), C.POINTER(Cloud)
+        L.aicp_hip_map_sequence_run_raw.argtypes = [vp, cfgp, C.POINTER(LocalizationParams), pfp, pfp, vp, clp, fp, sz,
+                                                    fp, C.POINTER(LocalizationResult), u32p, szp]
+        L.aicp_hip_built_map_sequence_run_raw.argtypes = [vp, cfgp, C.POINTER(BuiltMapParams), pfp, vp, clp, fp, sz, fp,
+                                                          C.POINTER(BuiltMapResult), u32p, szp]
+        L.aicp_hip_test_ingest.argtypes = [vp, fp, sz, sz, fp, fp]
     return L
 
 
@@ -1108,6 +1118,18 @@ class Context:
         rc = lib.aicp_hip_transform(self.h, _fptr(t), _fptr(pts), pts.shape[0], pts.shape[1] * 4, _fptr(out))
         self.check(rc)
         return out
+
+    def test_ingest(self, rows, T=None, download=True):
+        """aicp_hip_test_ingest: the raw streams' upload and k_stream_ingest alone. rows: (N, 3|4|8|12)
+        float32; T: 4x4 row-major (None: no move). Returns (N, 4) float32 rows (x, y, z, 1), or
+        None with download=False (the timing tool's)."""
+        a = as_points(rows)
+        t = None if T is None else np.ascontiguousarray(np.asarray(T, np.float32).reshape(4, 4).T.reshape(16))
+        out = np.zeros((max(a.shape[0], 1), 4), np.float32) if download else None
+        rc = lib.aicp_hip_test_ingest(self.h, _fptr(a), a.shape[0], a.shape[1] * 4, None if t is None else _fptr(t),
+                                      _fptr(out) if download else None)
+        self.check(rc)
+        return out[:a.shape[0]] if download else None
 
     def crop_box(self, pts, mn, mx, origin):
         """getPointsInOrientedBox (filteringUtils.cpp:619-637) on device: returns (kept xyz in

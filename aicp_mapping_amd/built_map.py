@@ -45,14 +45,19 @@ class BuiltMap(PriorMap):
             self.ctx.check(rc)
         return outT[:n].reshape(-1, 4, 4).transpose(0, 2, 1).copy(), [st[i].as_dict() for i in range(n)], rc
 
-    def sequence_run(self, readings, poses, cfg=None, params=None, raise_on_error=True):
+    def sequence_run(self, readings, poses, cfg=None, params=None, raise_on_error=True, raw=False,
+                     read_prefilter=None):
         """App's stream in this mode (aicp_hip_built_map_sequence_run): reading i is registered
         against the map cropped around poses[i] with its own overlap and ratio, dropped on a large
         correction (the first reading too), and every reference_update_frequency-th accepted
         reading is appended to the map, in place. params: BuiltMapParams
         (default_built_map_params). Returns (T[n, 4, 4] row-major corrections, list of result dicts
         of the readings processed, n_done, rc); a registration error ends the stream at reading
-        n_done - 1 and raises unless raise_on_error is False."""
+        n_done - 1 and raises unless raise_on_error is False.
+        raw=True (aicp_hip_built_map_sequence_run_raw): the readings are RAW clouds, pre-filtered
+        inside the stream in App's order (debug mode: moved by initialT_ first) with read_prefilter
+        (PrefilterParams; None: the defaults); the return value gains a fifth element, the (n,)
+        uint32 counts of the points each reading kept."""
         cfg = cfg or L.default_config()
         prm = params or L.default_built_map_params()
         n = len(readings)
@@ -60,6 +65,13 @@ class BuiltMap(PriorMap):
         outT = np.zeros((max(n, 1), 16), np.float32)
         res = (L.BuiltMapResult * max(n, 1))()
         done = C.c_size_t(0)
-        rc = L.lib.aicp_hip_built_map_sequence_run(self.ctx.h, C.byref(cfg), C.byref(prm), self.h, arr, L._fptr(pz), n,
-                                                   L._fptr(outT), res, C.byref(done))
-        return _stream_results(self.ctx, rc, raise_on_error, n, outT, res, done)
+        if not raw:
+            rc = L.lib.aicp_hip_built_map_sequence_run(self.ctx.h, C.byref(cfg), C.byref(prm), self.h, arr, L._fptr(pz),
+                                                       n, L._fptr(outT), res, C.byref(done))
+            return _stream_results(self.ctx, rc, raise_on_error, n, outT, res, done)
+        pfr = read_prefilter if read_prefilter is not None else L.default_prefilter()
+        kept = np.zeros(max(n, 1), np.uint32)
+        rc = L.lib.aicp_hip_built_map_sequence_run_raw(self.ctx.h, C.byref(cfg), C.byref(prm), C.byref(pfr), self.h, arr,
+                                                       L._fptr(pz), n, L._fptr(outT), res,
+                                                       kept.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(done))
+        return _stream_results(self.ctx, rc, raise_on_error, n, outT, res, done) + (kept[:n],)

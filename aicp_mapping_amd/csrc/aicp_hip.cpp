@@ -2402,8 +2402,12 @@ int map_reserve(aicp_hip_ctx* ctx, aicp_hip_map* map, size_t add) {
 // translation; the reading's is read_origins[3 i ..] (null: the cloud's own). *counts: the n crop
 // sizes (pinned, valid until the next crop). The scatter is enqueued on ctx->stream, the stream
 // run_batch reads the reference points on (overlap) or orders its other streams behind (ev[14]).
+// dev_read_n (nullable): the readings are on the device already, dev_read_n[i] points each; the
+// batch is sized for them, nothing of them is packed or uploaded, and the caller writes them into
+// the batch's read_raw at desc[i].read_off (the raw streams: the pre-filter's kept points).
 int map_crop_pairs(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float mx, const aicp_cloud* readings,
-                   const float* poses, size_t n, const double* read_origins, size_t* n_ok, const uint32_t** counts) {
+                   const float* poses, size_t n, const double* read_origins, size_t* n_ok, const uint32_t** counts,
+                   const uint32_t* dev_read_n) {
   *n_ok = 0;
   hipStream_t s = ctx->stream;
   const size_t ab = crop_args_bytes(), tiles = crop_tiles(map->n);
@@ -2440,7 +2444,7 @@ int map_crop_pairs(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float m
     p.n_ref = htot[i];
     p.ref_stride = 16;
     p.read = c.pts;
-    p.n_read = c.n;
+    p.n_read = dev_read_n ? dev_read_n[i] : c.n;
     p.read_stride = c.stride;
     for (int k = 0; k < 3; ++k) {
       p.ref_origin[k] = poses[16 * i + 12 + k];
@@ -2449,7 +2453,7 @@ int map_crop_pairs(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float m
   }
   if (!ctx->mapbatch) ctx->mapbatch = new aicp_hip_batch();
   aicp_hip_batch* B = ctx->mapbatch;
-  int rc = upload_pairs(ctx, pairs.data(), m, B, true);
+  int rc = upload_pairs(ctx, pairs.data(), m, B, true, false, dev_read_n != nullptr);
   if (rc) return rc;
   uint32_t* hbase = htot + n;
   for (size_t i = 0; i < m; ++i) hbase[i] = B->rdesc[i].ref_off;
@@ -2459,6 +2463,65 @@ int map_crop_pairs(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float m
                             (const uint32_t*)(ws + o_base), B->ref_raw.as<float4>());
   HIPC(hipGetLastError());
   *n_ok = m;
+  return AICP_OK;
+}
+
+// A caller's raw rows onto the device, behind everything enqueued on ctx->stream: rows of at most
+// 16 bytes travel as they are (no more bytes than the packed form), wider rows are packed to
+// float4 on the host first. The rows land in ctx->scratch at `off` (a multiple of 16); *drows /
+// *dstride: where, and their stride there. The stream is synchronised first (pin_io is free).
+static int ingest_upload(aicp_hip_ctx* ctx, const float* pts, size_t n, size_t stride, size_t off, const void** drows,
+                         size_t* dstride) {
+  hipStream_t s = ctx->stream;
+  const bool verbatim = stride <= 16;
+  const size_t ds = verbatim ? stride : 16;
+  HIPC(hipStreamSynchronize(s));
+  HIPC(ensure(ctx->scratch, off + n * ds));
+  HIPC(ensure(ctx->pin_io, n * ds + 64));
+  char* h = ctx->pin_io.as<char>();
+  if (verbatim) {
+    const size_t bytes = (n - 1) * stride + 12;  // (the caller's last row may end with its z)
+    const size_t nt = bytes < (1u << 20) ? 1 : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    const char* src = reinterpret_cast<const char*>(pts);
+    if (nt == 1)
+      std::memcpy(h, src, bytes);
+    else
+      ctx_pool(ctx)->run(nt, [&](size_t t) {
+        const size_t a = bytes * t / nt, b = bytes * (t + 1) / nt;
+        std::memcpy(h + a, src + a, b - a);
+      });
+    HIPC(hipMemcpyAsync(ctx->scratch.as<char>() + off, h, bytes, hipMemcpyHostToDevice, s));
+  } else {
+    pack_many({PackSeg{pts, n, stride, reinterpret_cast<float*>(h)}}, ctx_pool(ctx));
+    HIPC(hipMemcpyAsync(ctx->scratch.as<char>() + off, h, n * 16, hipMemcpyHostToDevice, s));
+  }
+  *drows = ctx->scratch.as<char>() + off;
+  *dstride = ds;
+  return AICP_OK;
+}
+
+int stream_prefilter_check(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf) { return pf_check(ctx, pf); }
+
+// setAndFilterReading (app.cpp:77-100) for one raw reading of a map stream, all on the device
+int stream_prefilter_raw(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf, const aicp_cloud& c, const float* d_initT,
+                         double* d_origin, float4* dst, uint32_t* kept) {
+  *kept = 0;
+  hipStream_t s = ctx->stream;
+  PfLayout Lo;
+  int rc = pf_layout(ctx, c.n, &Lo);
+  if (rc) return rc;
+  const void* drows = nullptr;
+  size_t dstride = 0;
+  rc = ingest_upload(ctx, c.pts, c.n, c.stride, 0, &drows, &dstride);
+  if (rc) return rc;
+  launch_stream_ingest(s, (int)c.n, drows, dstride, d_initT, d_origin, Lo.pts4);
+  HIPC(hipGetLastError());
+  PfRun o;
+  rc = pf_core(ctx, pf, c.n, Lo, &o);  // (returns with the stream idle)
+  if (rc) return rc;
+  if (!o.V || !o.n_out) return AICP_OK;
+  HIPC(hipMemcpyAsync(dst, o.out4, (size_t)o.n_out * 16, hipMemcpyDeviceToDevice, s));
+  *kept = o.n_out;
   return AICP_OK;
 }
 
@@ -2484,6 +2547,28 @@ int aicp_hip_map_align_batch(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, cons
   const int rc = check_cfg(ctx, cfg, run_flags);
   if (rc) return rc;
   return map_batch(ctx, cfg, map, mn, mx, readings, poses, n, resolution, run_flags, out_T, stats);
+}
+
+// Test surface: the raw streams' ingest alone (the upload policy of ingest_upload, k_stream_ingest)
+int aicp_hip_test_ingest(aicp_hip_ctx* ctx, const float* rows, size_t n, size_t stride, const float* T, float* out4) {
+  if (!ctx || (n && !rows) || stride < 12 || (stride % 4) || n > (size_t)INT32_MAX) return AICP_ERR_INVALID;
+  if (n == 0) return AICP_OK;
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  // scratch: T | the rows (ingest_upload) | the output
+  const size_t o_rows = 256, o_out = (o_rows + n * std::min<size_t>(stride, 16) + 255) & ~size_t(255);
+  HIPC(ensure(ctx->scratch, o_out + n * 16));
+  const void* drows = nullptr;
+  size_t dstride = 0;
+  const int rc = ingest_upload(ctx, rows, n, stride, o_rows, &drows, &dstride);
+  if (rc) return rc;
+  char* d = ctx->scratch.as<char>();
+  if (T) HIPC(hipMemcpyAsync(d, T, 64, hipMemcpyHostToDevice, s));
+  launch_stream_ingest(s, (int)n, drows, dstride, T ? (const float*)d : nullptr, nullptr, (float4*)(d + o_out));
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(s));
+  if (out4) HIPC(hipMemcpy(out4, d + o_out, n * 16, hipMemcpyDeviceToHost));
+  return AICP_OK;
 }
 
 int aicp_hip_map_capacity(const aicp_hip_map* map, size_t* n) {

@@ -318,6 +318,12 @@ struct StreamRec {      // one reading's decisions (the host reads a window's re
 // and origin := translation of initialT_ * prior pose (k_debug_prep's)
 // (initT: 16 floats on the device, StreamState::initT)
 void launch_loc_move(hipStream_t s, int n, const float* initT, double* origin, float4* pts);
+// a raw reading's rows (n rows of `stride` bytes on the device, 16-byte aligned, stride >= 12 and a
+// multiple of 4) -> out[i] = float4(x, y, z, 1); initT (nullable, 16 floats on the device): each
+// point moved by it (k_transform's expression) and, with origin (nullable), origin := translation
+// of initT * prior pose (k_loc_move's)
+void launch_stream_ingest(hipStream_t s, int n, const void* rows, size_t stride, const float* initT, double* origin,
+                          float4* out);
 // one thread walks the window's np readings in order (app.cpp:366-391, 414, 469-493): status, drop
 // test, count, corrected origin, initialT_ = correction * initialT_, append / re-filter flags
 void launch_stream_commit(hipStream_t s, int np, const PairState* st, const float* T, const double* origin,

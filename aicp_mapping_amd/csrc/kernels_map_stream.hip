@@ -7,7 +7,8 @@
 // origin, initialT_, which reading goes to the map's tail, re-filter); the host appends from the
 // batch's copy of the reading by the device's own correction (launch_transform). In the debug
 // working mode k_loc_move moves the reading by the device-resident initialT_ before it is
-// registered.
+// registered. Raw readings (the *_run_raw entry points) enter through k_stream_ingest, which
+// unpacks the caller's rows into the pre-filter's input and, in debug mode, moves them first.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +38,48 @@ __global__ __launch_bounds__(256) void k_loc_move(int n, const float* __restrict
   float q[3];
   apply4(Tl, p.x, p.y, p.z, q);
   pts[i] = make_float4(q[0], q[1], q[2], 1.f);
+}
+
+// A raw reading as the caller's rows were uploaded (n rows of stride_w 32-bit words, xyz first)
+// into the pre-filter's input: float4(x, y, z, 1). With initT (debug mode, setAndFilterReading
+// app.cpp:90-99: the RAW reading is moved, then pre-filtered) every point goes through apply4, the
+// float expression of k_transform / k_loc_move, and thread 0 of block 0 makes origin the
+// translation of initialT_ * prior pose as k_loc_move does. One thread per point; a row of 16
+// bytes is one 128-bit load, any other stride three 32-bit loads.
+__global__ __launch_bounds__(256) void k_stream_ingest(int n, const float* __restrict__ rows, int stride_w,
+                                                       const float* __restrict__ initT, double* origin,
+                                                       float4* __restrict__ out) {
+  float Tl[16];
+  if (initT) {
+    for (int k = 0; k < 16; ++k) Tl[k] = initT[k];
+    if (origin && blockIdx.x == 0 && threadIdx.x == 0) {
+      double o[3];
+      corrected_origin(Tl, origin, o);
+      for (int k = 0; k < 3; ++k) origin[k] = o[k];
+    }
+  }
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float x, y, z;
+  if (stride_w == 4) {
+    const float4 p = reinterpret_cast<const float4*>(rows)[i];
+    x = p.x;
+    y = p.y;
+    z = p.z;
+  } else {
+    const float* p = rows + (size_t)i * (size_t)stride_w;
+    x = p[0];
+    y = p[1];
+    z = p[2];
+  }
+  if (initT) {
+    float q[3];
+    apply4(Tl, x, y, z, q);
+    x = q[0];
+    y = q[1];
+    z = q[2];
+  }
+  out[i] = make_float4(x, y, z, 1.f);
 }
 
 // The window's readings in order, one thread (a window holds at most kMaxPairs readings and the
@@ -94,7 +137,13 @@ __global__ void k_stream_commit(int np, const PairState* __restrict__ st, const 
 void launch_loc_move(hipStream_t s, int n, const float* initT, double* origin, float4* pts) {
   k_loc_move<<<(unsigned)std::max(1, (n + 255) / 256), 256, 0, s>>>(n, initT, origin, pts);
 }
-void launch_stream_commit(hipStream_t s, int np, const PairState* st, const float* T, const double* origin,
+void launch_stream_ingest(hipStream_t s, int n, const void* rows, size_t stride, const float* initT, double* origin,
+                          float4* out) {
+  if (n > 0)
+    k_stream_ingest<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, static_cast<const float*>(rows), (int)(stride / 4),
+                                                                initT, origin, out);
+}
+void launch_stream_commit(hipStream_t s, int np,const PairState* st, const float* T, const double* origin,
                           StreamRules r, StreamState* S, StreamRec* rec) {
   if (np > 0) k_stream_commit<<<1, 64, 0, s>>>(np, st, T, origin, r, S, rec);
 }

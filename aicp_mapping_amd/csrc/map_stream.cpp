@@ -20,6 +20,11 @@
 // [host] reads the state and the records once -> [device] for the records that ask for it, in
 // order: k_transform from the batch's copy of the reading by the device's correction to the map's
 // tail, the map's pre-filter. No reading crosses the bus a second time.
+//
+// Raw readings (the *_run_raw entry points; setAndFilterReading, app.cpp:77-100): before the
+// window's crop every raw reading is uploaded, unpacked and (debug mode) moved by the device's
+// initialT_ (k_stream_ingest), pre-filtered (stream_prefilter_raw, aicp_hip.cpp), and its kept
+// points wait on the device for the batch; the rest of the window is the same.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -50,6 +55,7 @@ struct MapStreamBufs {
   DevBuf win;     // StreamState, then (at kRecOff) a StreamRec per reading of the window
   DevBuf origin;  // prior-pose translations of the window's readings, 3 doubles each
   PinBuf pin;     // staging: win's mirror, then the origins
+  DevBuf stage;   // raw streams: the window's pre-filtered readings, one after another
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   StreamTiming last[2];  // of the last call of each stream: [0] prior map, [1] built map
 };
@@ -59,6 +65,7 @@ void map_stream_bufs_free(MapStreamBufs* L) {
   release(L->win);
   release(L->origin);
   release(L->pin);
+  release(L->stage);
   if (L->ev_begin) (void)hipEventDestroy(L->ev_begin);
   if (L->ev_end) (void)hipEventDestroy(L->ev_end);
   delete L;
@@ -105,6 +112,7 @@ struct Stream {
   const aicp_localization_params* loc;
   const aicp_built_map_params* bm;
   const aicp_prefilter_params* pf;  // prior map: the re-filter's parameters
+  const aicp_prefilter_params* pf_read;  // raw streams: the readings' pre-filter (null: pre-filtered readings)
   StreamRules rules;
   float crop_min, crop_max;
   bool debug;
@@ -124,7 +132,9 @@ int stream_args(aicp_hip_ctx* ctx, const void* cfg, const void* prm, const aicp_
 
 int run_stream(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, aicp_hip_map* map,
                const aicp_cloud* readings, const float* poses, size_t n, float* out_T, aicp_localization_result* out,
-               size_t* n_done) {
+               uint32_t* out_kept, size_t* n_done) {
+  const bool raw = P.pf_read != nullptr;
+  if (out_kept) std::fill(out_kept, out_kept + n, 0u);
   for (size_t i = 0; i < n; ++i)
     if (!valid_cloud(readings[i])) FAIL(AICP_ERR_INVALID, "invalid reading " + std::to_string(i));
   int rc = check_cfg(ctx, cfg, P.run_flags);
@@ -157,7 +167,8 @@ int run_stream(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, a
   std::vector<aicp_icp_stats> stats;
   int status = AICP_OK;
   size_t p = 0;
-  bool empty_crop = false;
+  bool empty_crop = false, empty_read = false;
+  std::vector<uint32_t> kept;  // raw streams: what the pre-filter kept of the window's readings
   while (p < n && !status) {
     const size_t w = P.bm ? aicp_hip_built_map_window((uint64_t)hS->count, P.bm, n - p)
                           : aicp_hip_localization_window((uint64_t)hS->count, P.loc, n - p);
@@ -173,16 +184,56 @@ int run_stream(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, a
     // empty crop ends the stream at its reading; the wr readings before it still run
     size_t wr = 0;
     const uint32_t* htot = nullptr;
-    rc = map_crop_pairs(ctx, map, P.crop_min, P.crop_max, readings + p, poses + 16 * p, w,
-                        use_moved ? moved : nullptr, &wr, &htot);
-    if (rc) return rc;
+    double* horg = reinterpret_cast<double*>(lp + o_org);
+    // raw streams: setAndFilterReading (app.cpp:77-100) for every reading of the window, before the
+    // crop (the pre-filter and the crop share work space with the batch, not with each other: each
+    // is done before the next starts). The kept points wait in L->stage, sized once for the window
+    // (the voxel grid never adds a point). Debug mode (one reading per window): the ingest kernel
+    // moves the raw points and the prior origin by the device's initialT_. A reading the pre-filter
+    // empties ends the window before it, as an empty crop does
+    size_t wp = w;  // readings that reach the crop
+    if (raw) {
+      uint64_t sum = 0;
+      for (size_t i = 0; i < w; ++i) sum += readings[p + i].n;
+      HIPC(ensure(L->stage, sum * 16));
+      kept.assign(w, 0u);
+      if (P.debug) {
+        for (int k = 0; k < 3; ++k) horg[k] = readings[p].origin[k];
+        HIPC(hipMemcpyAsync(L->origin.p, horg, 24, hipMemcpyHostToDevice, s));
+      }
+      uint64_t off = 0;
+      for (size_t i = 0; i < w; ++i) {
+        rc = stream_prefilter_raw(ctx, P.pf_read, readings[p + i], P.debug ? dS->initT : nullptr,
+                                  P.debug ? L->origin.as<double>() : nullptr, L->stage.as<float4>() + off, &kept[i]);
+        if (rc) return rc;
+        if (!kept[i]) {
+          wp = i;
+          break;
+        }
+        off += kept[i];
+      }
+    }
+    if (wp) {
+      rc = map_crop_pairs(ctx, map, P.crop_min, P.crop_max, readings + p, poses + 16 * p, wp,
+                          use_moved ? moved : nullptr, &wr, &htot, raw ? kept.data() : nullptr);
+      if (rc) return rc;
+    }
     if (wr) {
       aicp_hip_batch* B = ctx->mapbatch;
-      double* horg = reinterpret_cast<double*>(lp + o_org);
-      for (size_t i = 0; i < wr; ++i)
-        for (int k = 0; k < 3; ++k) horg[3 * i + k] = readings[p + i].origin[k];
-      HIPC(hipMemcpyAsync(L->origin.p, horg, wr * 24, hipMemcpyHostToDevice, s));
-      if (P.debug) {  // (one reading per window) moved by the device's initialT_, its prior pose too
+      if (raw) {  // the staged readings into the batch (its sizes are known only after the crop)
+        uint64_t off = 0;
+        for (size_t i = 0; i < wr; ++i) {
+          HIPC(hipMemcpyAsync(B->read_raw.as<float4>() + B->desc[i].read_off, L->stage.as<float4>() + off,
+                              (size_t)kept[i] * 16, hipMemcpyDeviceToDevice, s));
+          off += kept[i];
+        }
+      }
+      if (!(raw && P.debug)) {  // (raw debug mode: up already, and moved by the ingest kernel)
+        for (size_t i = 0; i < wr; ++i)
+          for (int k = 0; k < 3; ++k) horg[3 * i + k] = readings[p + i].origin[k];
+        HIPC(hipMemcpyAsync(L->origin.p, horg, wr * 24, hipMemcpyHostToDevice, s));
+      }
+      if (P.debug && !raw) {  // (one reading per window) moved by the device's initialT_, its prior pose too
         launch_loc_move(s, (int)B->desc[0].n_read, dS->initT, L->origin.as<double>(),
                         B->read_raw.as<float4>() + B->desc[0].read_off);
         HIPC(hipGetLastError());
@@ -233,7 +284,9 @@ int run_stream(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, a
         }
       }
     }
-    if (!status && wr < w) {  // the reading with the empty crop (libpointmatcher throws on an empty cloud)
+    // the reading with the empty crop, or the one the pre-filter emptied (libpointmatcher throws on
+    // an empty cloud); the lower index ends the stream (wr <= wp: the crop saw the readings before wp)
+    if (!status && wr < w) {
       aicp_localization_result& o = out[p + wr];
       std::memset(&o, 0, sizeof(o));
       o.status = o.icp.status = AICP_ERR_INVALID;
@@ -242,8 +295,10 @@ int run_stream(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, a
       ident4(out_T + 16 * (p + wr));
       *n_done = p + wr + 1;
       status = AICP_ERR_INVALID;
-      empty_crop = true;
+      (wr < wp ? empty_crop : empty_read) = true;
     }
+    if (raw && out_kept)
+      for (size_t i = 0; i < w && p + i < *n_done; ++i) out_kept[p + i] = kept[i];
     p += wr;
   }
   HIPC(hipEventRecord(L->ev_end, s));
@@ -252,7 +307,9 @@ int run_stream(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, a
   tm.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (status)
     ctx->err = "reading " + std::to_string(*n_done - 1) +
-               (empty_crop ? std::string(": empty map crop") : ": status " + std::to_string(status));
+               (empty_crop   ? std::string(": empty map crop")
+                : empty_read ? std::string(": keeps no point after the pre-filter")
+                             : ": status " + std::to_string(status));
   return status;
 }
 
@@ -306,11 +363,19 @@ size_t aicp_hip_built_map_window(uint64_t acc, const aicp_built_map_params* prm,
   return (size_t)std::min<uint64_t>(std::min<size_t>(remaining, (size_t)kMaxPairs), to_ref);
 }
 
-int aicp_hip_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* prm,
-                              const aicp_prefilter_params* pf, aicp_hip_map* map, const aicp_cloud* readings,
-                              const float* poses, size_t n, float* out_T, aicp_localization_result* out,
-                              size_t* n_done) {
-  const int rc = stream_args(ctx, cfg, prm, map, readings, poses, n, out_T, out, n_done);
+// the raw entry points' further checks (after stream_args): the readings' pre-filter
+static int raw_args(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf_read) {
+  if (!pf_read) return AICP_ERR_INVALID;
+  return stream_prefilter_check(ctx, pf_read);
+}
+
+// raw: readings as App receives them, pre-filtered by pf_read inside the stream
+static int loc_stream(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* prm,
+                      const aicp_prefilter_params* pf, bool raw, const aicp_prefilter_params* pf_read,
+                      aicp_hip_map* map, const aicp_cloud* readings, const float* poses, size_t n, float* out_T,
+                      aicp_localization_result* out, uint32_t* out_kept, size_t* n_done) {
+  int rc = stream_args(ctx, cfg, prm, map, readings, poses, n, out_T, out, n_done);
+  if (!rc && raw) rc = raw_args(ctx, pf_read);
   if (rc) return rc;
   if (!valid_params(prm)) FAIL(AICP_ERR_INVALID, "localization parameters");
   aicp_prefilter_params pfd;
@@ -323,6 +388,7 @@ int aicp_hip_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, con
   Stream P{};
   P.loc = prm;
   P.pf = pf;
+  P.pf_read = raw ? pf_read : nullptr;
   P.rules.freq = prm->reference_update_frequency;
   P.rules.refilter_every = prm->map_refilter_every;
   P.rules.merge = (prm->flags & AICP_LOC_MERGE) ? 1 : 0;
@@ -331,17 +397,20 @@ int aicp_hip_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, con
   P.crop_max = prm->crop_max;
   P.debug = prm->flags & AICP_SEQ_DEBUG;
   P.run_flags = AICP_RUN_ICP | (prm->flags & AICP_RUN_TIME_NN);
-  return run_stream(ctx, P, &c, map, readings, poses, n, out_T, out, n_done);
+  return run_stream(ctx, P, &c, map, readings, poses, n, out_T, out, out_kept, n_done);
 }
 
-int aicp_hip_built_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_built_map_params* prm,
-                                    aicp_hip_map* map, const aicp_cloud* readings, const float* poses, size_t n,
-                                    float* out_T, aicp_built_map_result* out, size_t* n_done) {
-  const int rc = stream_args(ctx, cfg, prm, map, readings, poses, n, out_T, out, n_done);
+static int bm_stream(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_built_map_params* prm, bool raw,
+                     const aicp_prefilter_params* pf_read, aicp_hip_map* map, const aicp_cloud* readings,
+                     const float* poses, size_t n, float* out_T, aicp_built_map_result* out, uint32_t* out_kept,
+                     size_t* n_done) {
+  int rc = stream_args(ctx, cfg, prm, map, readings, poses, n, out_T, out, n_done);
+  if (!rc && raw) rc = raw_args(ctx, pf_read);
   if (rc) return rc;
   if (!valid_params(prm)) FAIL(AICP_ERR_INVALID, "built-map parameters");
   Stream P{};
   P.bm = prm;
+  P.pf_read = raw ? pf_read : nullptr;
   P.rules.built = 1;
   P.rules.freq = prm->reference_update_frequency;
   P.rules.overlap = (prm->flags & AICP_RUN_OVERLAP) ? 1 : 0;
@@ -352,7 +421,35 @@ int aicp_hip_built_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cf
   P.run_flags = AICP_RUN_ICP | (prm->flags & (AICP_RUN_OVERLAP | AICP_RUN_TIME_NN));
   P.resolution = prm->resolution;
   return run_stream(ctx, P, cfg, map, readings, poses, n, out_T, reinterpret_cast<aicp_localization_result*>(out),
-                    n_done);
+                    out_kept, n_done);
+}
+
+int aicp_hip_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* prm,
+                              const aicp_prefilter_params* pf, aicp_hip_map* map, const aicp_cloud* readings,
+                              const float* poses, size_t n, float* out_T, aicp_localization_result* out,
+                              size_t* n_done) {
+  return loc_stream(ctx, cfg, prm, pf, false, nullptr, map, readings, poses, n, out_T, out, nullptr, n_done);
+}
+
+int aicp_hip_map_sequence_run_raw(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* prm,
+                                  const aicp_prefilter_params* pf_map, const aicp_prefilter_params* pf_read,
+                                  aicp_hip_map* map, const aicp_cloud* readings, const float* poses, size_t n,
+                                  float* out_T, aicp_localization_result* out, uint32_t* out_kept, size_t* n_done) {
+  return loc_stream(ctx, cfg, prm, pf_map, true, pf_read, map, readings, poses, n, out_T, out, out_kept, n_done);
+}
+
+int aicp_hip_built_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_built_map_params* prm,
+                                    aicp_hip_map* map, const aicp_cloud* readings, const float* poses, size_t n,
+                                    float* out_T, aicp_built_map_result* out, size_t* n_done) {
+  return bm_stream(ctx, cfg, prm, false, nullptr, map, readings, poses, n, out_T, out, nullptr, n_done);
+}
+
+int aicp_hip_built_map_sequence_run_raw(aicp_hip_ctx* ctx, const aicp_icp_config* cfg,
+                                        const aicp_built_map_params* prm, const aicp_prefilter_params* pf_read,
+                                        aicp_hip_map* map, const aicp_cloud* readings, const float* poses, size_t n,
+                                        float* out_T, aicp_built_map_result* out, uint32_t* out_kept,
+                                        size_t* n_done) {
+  return bm_stream(ctx, cfg, prm, true, pf_read, map, readings, poses, n, out_T, out, out_kept, n_done);
 }
 
 int aicp_hip_last_localization_timing(const aicp_hip_ctx* ctx, aicp_localization_timing* out) {

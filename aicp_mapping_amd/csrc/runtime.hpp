@@ -271,7 +271,15 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
 // the device-resident map (aicp_hip.cpp), for the streams that grow it and crop it into a batch
 int map_reserve(aicp_hip_ctx* ctx, aicp_hip_map* map, size_t add);
 int map_crop_pairs(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float mx, const aicp_cloud* readings,
-                   const float* poses, size_t n, const double* read_origins, size_t* n_ok, const uint32_t** counts);
+                   const float* poses, size_t n, const double* read_origins, size_t* n_ok, const uint32_t** counts,
+                   const uint32_t* dev_read_n = nullptr);
+// a raw reading for the raw streams (map_stream.cpp): its rows uploaded, k_stream_ingest into the
+// pre-filter's input (d_initT / d_origin: debug mode, nullable), the pre-filter, and the kept
+// points copied device-to-device to dst (room for c.n points). Returns with ctx->stream idle up to
+// that copy and *kept known.
+int stream_prefilter_raw(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf, const aicp_cloud& c, const float* d_initT,
+                         double* d_origin, float4* dst, uint32_t* kept);
+int stream_prefilter_check(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf);  // pf_check
 
 }  // namespace rt
 }  // namespace aicp

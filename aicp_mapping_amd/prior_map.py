@@ -105,7 +105,8 @@ class PriorMap:
             self.ctx.check(rc)
         return outT.reshape(-1, 4, 4).transpose(0, 2, 1).copy(), [x.as_dict() for x in st], rc
 
-    def sequence_run(self, readings, poses, cfg=None, params=None, prefilter=None, raise_on_error=True):
+    def sequence_run(self, readings, poses, cfg=None, params=None, prefilter=None, raise_on_error=True, raw=False,
+                     read_prefilter=None):
         """App's localization stream on this map (aicp_hip_map_sequence_run, app.cpp:282-414 with
         app.cpp:41-58, 469-493): reading i is registered against the map cropped around poses[i]
         (4x4 row-major prior pose; its translation is the reading's origin), dropped on a large
@@ -114,7 +115,11 @@ class PriorMap:
         LocalizationParams (default_localization_params); prefilter: the re-filter's
         PrefilterParams (None: the defaults). Returns (T[n, 4, 4] row-major corrections, list of
         result dicts of the readings processed, n_done, rc); a registration error ends the stream
-        at reading n_done - 1 and raises unless raise_on_error is False."""
+        at reading n_done - 1 and raises unless raise_on_error is False.
+        raw=True (aicp_hip_map_sequence_run_raw): the readings are RAW clouds, pre-filtered inside
+        the stream in App's order (debug mode: moved by initialT_ first) with read_prefilter
+        (PrefilterParams; None: the defaults); the return value gains a fifth element, the (n,)
+        uint32 counts of the points each reading kept."""
         cfg = cfg or L.default_config()
         prm = params or L.default_localization_params()
         n = len(readings)
@@ -122,10 +127,17 @@ class PriorMap:
         outT = np.zeros((max(n, 1), 16), np.float32)
         res = (L.LocalizationResult * max(n, 1))()
         done = C.c_size_t(0)
-        rc = L.lib.aicp_hip_map_sequence_run(self.ctx.h, C.byref(cfg), C.byref(prm),
-                                             C.byref(prefilter) if prefilter is not None else None, self.h, arr,
-                                             L._fptr(pz), n, L._fptr(outT), res, C.byref(done))
-        return _stream_results(self.ctx, rc, raise_on_error, n, outT, res, done)
+        pf_map = C.byref(prefilter) if prefilter is not None else None
+        if not raw:
+            rc = L.lib.aicp_hip_map_sequence_run(self.ctx.h, C.byref(cfg), C.byref(prm), pf_map, self.h, arr,
+                                                 L._fptr(pz), n, L._fptr(outT), res, C.byref(done))
+            return _stream_results(self.ctx, rc, raise_on_error, n, outT, res, done)
+        pfr = read_prefilter if read_prefilter is not None else L.default_prefilter()
+        kept = np.zeros(max(n, 1), np.uint32)
+        rc = L.lib.aicp_hip_map_sequence_run_raw(self.ctx.h, C.byref(cfg), C.byref(prm), pf_map, C.byref(pfr), self.h,
+                                                 arr, L._fptr(pz), n, L._fptr(outT), res,
+                                                 kept.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(done))
+        return _stream_results(self.ctx, rc, raise_on_error, n, outT, res, done) + (kept[:n],)
 
     def merge(self, points, correction) -> None:
         """*map = *map + transformPointCloud(points, correction); correction a 4x4 (row-major)."""

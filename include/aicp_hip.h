@@ -624,6 +624,39 @@ int aicp_hip_built_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cf
                                     size_t* n_done);
 int aicp_hip_last_built_map_timing(const aicp_hip_ctx* ctx, aicp_built_map_timing* out);
 
+/* Both streams from RAW readings, in App's own order (processCloud calls setAndFilterReading,
+ * app.cpp:77-100, for every reading). Every rule of aicp_hip_map_sequence_run /
+ * aicp_hip_built_map_sequence_run holds unchanged (the crop by the pose as given, overlap and ratio,
+ * the drop test, counts, merge / append, re-filter, the windows, an error ending the stream); only
+ * the reading differs:
+ *   robot mode:     reading = prefilter(raw);
+ *   AICP_SEQ_DEBUG: reading = prefilter(transformPointCloud(raw, initialT_)) with prior pose
+ *                   initialT_ * prior pose (app.cpp:87-99). The filtered reading is not moved again.
+ * The map append (T * reading) takes this filtered reading (App's read_prefiltered), in debug mode
+ * the moved one. pf_read (required) is used as given, viewpoint included, as
+ * aicp_hip_sequence_run_raw uses its pf; an unsupported pf_read is refused before anything runs.
+ * pf_map: the prior map's re-filter (nullable: the defaults). Per window every raw reading is
+ * uploaded (rows of at most 16 bytes as they are, wider rows packed on the host), unpacked and, in
+ * debug mode, moved by the device's initialT_ (k_stream_ingest), pre-filtered, and its kept points
+ * are handed to the batch on the device: they never come back to the host.
+ * A reading the pre-filter empties has status AICP_ERR_INVALID and an identity out_T and ends the
+ * stream there, exactly as an empty crop does (the readings before it in the window still run); of
+ * an empty crop and an emptied reading in one window the lower reading index ends the stream (at
+ * the same reading: the pre-filter's). out_kept (nullable): n counts, the points reading i kept;
+ * 0 for the readings behind *n_done. Point-to-point chains as in the pre-filtered streams. */
+int aicp_hip_map_sequence_run_raw(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* prm,
+                                  const aicp_prefilter_params* pf_map, const aicp_prefilter_params* pf_read,
+                                  aicp_hip_map* map, const aicp_cloud* readings /* RAW */,
+                                  const float* poses /* 16*n */, size_t n, float* out_T /* 16*n */,
+                                  aicp_localization_result* out /* n */, uint32_t* out_kept /* n, nullable */,
+                                  size_t* n_done);
+int aicp_hip_built_map_sequence_run_raw(aicp_hip_ctx* ctx, const aicp_icp_config* cfg,
+                                        const aicp_built_map_params* prm, const aicp_prefilter_params* pf_read,
+                                        aicp_hip_map* map, const aicp_cloud* readings /* RAW */,
+                                        const float* poses /* 16*n */, size_t n, float* out_T /* 16*n */,
+                                        aicp_built_map_result* out /* n */, uint32_t* out_kept /* n, nullable */,
+                                        size_t* n_done);
+
 /* ---- device-resident batches (inputs uploaded once, run many times) ----------------------- */
 int aicp_hip_batch_upload(aicp_hip_ctx* ctx, const aicp_pair* pairs, size_t n_pairs,
                           aicp_hip_batch** out);
@@ -662,7 +695,9 @@ int aicp_hip_last_phase_ms(const aicp_hip_ctx* ctx, double out_ms[5]);
  * initialT_ afterwards. App moves the RAW reading first and pre-filters the moved cloud
  * (setAndFilterReading, app.cpp:87-99); the 0.08 m VoxelGrid is aligned to the world frame, so the
  * two orders keep different points unless initialT_ is the identity. App's exact order is
- * aicp_hip_sequence_run_raw below; this entry point is the robot-mode fast path. */
+ * aicp_hip_sequence_run_raw below (and aicp_hip_map_sequence_run_raw /
+ * aicp_hip_built_map_sequence_run_raw above for the two map streams, whose pre-filtered entry
+ * points share this caveat); this entry point is the robot-mode fast path. */
 #define AICP_SEQ_DEBUG 8
 
 typedef struct {
@@ -793,6 +828,12 @@ int aicp_hip_test_step_p2p(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_
                            const uint32_t* touched /* each n_steps * total */, double* out_slab, float* out_T,
                            int32_t* out_state, float* out_inlier, uint64_t* out_touched, double* out_dqdt,
                            uint64_t* out_dirty);
+/* Test surface: the raw streams' ingest alone. rows: n rows of `stride` bytes (>= 12, a multiple of
+ * 4), xyz first, uploaded as the raw streams upload them (at most 16 bytes: verbatim; wider: packed
+ * on the host), then k_stream_ingest: out4[4 i ..] = (x, y, z, 1), moved by T (nullable, column-major
+ * float[16]) in aicp_hip_transform's float expression. out4 (nullable: nothing is downloaded). */
+int aicp_hip_test_ingest(aicp_hip_ctx* ctx, const float* rows, size_t n, size_t stride,
+                         const float* T /* nullable */, float* out4 /* 4*n, nullable */);
 
 #ifdef __cplusplus
 }
