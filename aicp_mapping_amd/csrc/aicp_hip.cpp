@@ -954,13 +954,7 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
     HIPC(hipEventRecord(ctx->ev[4], s2));
     HIPC(hipStreamWaitEvent(s, ctx->ev[4], 0));
     HIPC(hipEventRecord(ctx->ev[9], s));
-    prm.maxE2 = (1 + cfg->nn_epsilon) * (1 + cfg->nn_epsilon);
-    prm.maxR2 = cfg->nn_max_dist * cfg->nn_max_dist;
-    prm.max_iter = cfg->max_iter;
-    prm.smooth = cfg->smooth_length;
-    prm.min_rot = cfg->min_diff_rot;
-    prm.min_trans = cfg->min_diff_trans;
-    prm.knn_normals = cfg->knn_normals;
+    prm = icp_params(cfg);
     // The ICP loop on s: per iteration the NN, then select + reduce with the per-pair steps and
     // the next active list inside (launch_icp_select_f / _reduce_f)
     uint32_t reads = 0, max_read = 0;
@@ -1028,12 +1022,7 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
                     timeNN ? ctx->nn_ev[2 * nn_launches] : nullptr, timeNN ? ctx->nn_ev[2 * nn_launches + 1] : nullptr);
       HIPC(hipGetLastError());
       ++nn_launches;
-      IcpIterSync y = icp_sync_layout(ctx->isync.as<uint32_t>(), P, 0);
-      y.np = (int)P;
-      y.pd = dDesc;
-      y.st = dState;
-      y.al = al;
-      y.ctr = dCtr;
+      IcpIterSync y = icp_iter_sync(ctx->isync.as<uint32_t>(), P, (int)P, dDesc, dState, al, dCtr);
       if (written(it + 1)) {
         ctx->poll_host[it + 1] = 0xffffffffu;  // (before the launch that writes it)
         y.host_n = ctx->poll_dev + it + 1;
@@ -1785,12 +1774,7 @@ int aicp_hip_test_select(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* coun
   launch_init_state(st_, (int)P, dDesc, dState);
   for (size_t p = 0; p < P && active; ++p)
     if (!active[p]) HIPC(hipMemsetAsync(&dState[p].active, 0, sizeof(int32_t), st_));
-  IcpIterSync y = icp_sync_layout(sync, P, 0);
-  y.np = (int)P;
-  y.pd = dDesc;
-  y.st = dState;
-  y.al = al;
-  y.ctr = ctx->ctrs.as<uint32_t>();
+  IcpIterSync y = icp_iter_sync(sync, P, (int)P, dDesc, dState, al, ctx->ctrs.as<uint32_t>());
   std::vector<PairState> hs(P);
   for (size_t s = 0; s < n_steps; ++s) {
     HIPC(hipMemsetAsync(y.pairs, 0, 4, st_));  // (stopped pairs arrived there; the update kernel's arrivals complete it)
@@ -1940,20 +1924,15 @@ static int test_step_run(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_re
     if (init_T) HIPC(hipMemcpyAsync(dState[p].T, init_T + 16 * p, 64, hipMemcpyHostToDevice, st_));
     if (active && !active[p]) HIPC(hipMemsetAsync(&dState[p].active, 0, sizeof(int32_t), st_));
   }
-  IcpIterSync y = icp_sync_layout(sync, P, 0);
-  y.np = (int)P;
-  y.pd = dDesc;
-  y.st = dState;
-  y.al = al;
-  y.ctr = ctx->ctrs.as<uint32_t>();
-  IcpParams prm{};
-  prm.maxE2 = 1.f;
-  prm.maxR2 = INFINITY;
-  prm.max_iter = max_iter;
-  prm.smooth = smooth;
-  prm.min_rot = min_rot;
-  prm.min_trans = min_trans;
-  prm.knn_normals = ref_nrm ? 20 : 0;  // (which pair of kernels launch_icp_reduce_f launches)
+  IcpIterSync y = icp_iter_sync(sync, P, (int)P, dDesc, dState, al, ctx->ctrs.as<uint32_t>());
+  aicp_icp_config tc{};  // (nn_epsilon 0: every match is exact)
+  tc.knn_normals = ref_nrm ? 20 : 0;  // (which pair of kernels launch_icp_reduce_f launches)
+  tc.nn_max_dist = INFINITY;
+  tc.max_iter = max_iter;
+  tc.smooth_length = smooth;
+  tc.min_diff_rot = min_rot;
+  tc.min_diff_trans = min_trans;
+  const IcpParams prm = icp_params(&tc);
   std::vector<PairState> hs(P);
   constexpr uint32_t kSentinel = 0x7FF8DEADu;  // both halves: a NaN no sum produces
   for (size_t s = 0; s < n_steps; ++s) {

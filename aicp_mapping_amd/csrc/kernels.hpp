@@ -68,8 +68,11 @@ struct IcpIterSync {
 void tree_prof_dump();  // diagnostic builds (AICP_ITER_PROF): k_tr_mid phase times to stderr
 void iter_prof_dump();  // diagnostic builds (AICP_ITER_PROF): per-kernel body / tail times to stderr
 inline size_t icp_sync_words(size_t n_pairs) { return 3 * n_pairs + 2; }
-// sync words laid out for pairs [0, n_pairs): sel1 | sel2 | red | pairs (2: one per group)
-IcpIterSync icp_sync_layout(uint32_t* words, size_t n_pairs, int group);
+// an iteration's IcpIterSync: the sync words laid out for pairs [0, n_pairs) (sel1 | sel2 | red |
+// pairs, of whose 2 words the first is used) and the group that iterates, np pairs from pd / st.
+// host_n, done_sig / ticket / outT and src_pair are the caller's to set.
+IcpIterSync icp_iter_sync(uint32_t* words, size_t n_pairs, int np, const PairDesc* pd, PairState* st, ActiveList* al,
+                          uint32_t* ctr);
 void launch_icp_select_f(hipStream_t s, BlockMap m, const PairDesc* pd, PairState* st, const float* d2,
                          uint32_t* hist1, uint32_t* cand, uint32_t* cand_cnt, const IcpIterSync& y);
 // from the second iteration on: the select in one launch, its compaction on the previous

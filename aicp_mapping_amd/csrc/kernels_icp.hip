@@ -1448,6 +1448,113 @@ __device__ void block_find_rank(const uint32_t* h, int nb, uint32_t k, uint32_t*
 
 constexpr uint32_t kInfBits = 0x7f800000u;
 
+// the distances [j0, j0 + kT * kPer) of a pair (bits: its d2 as words) into v, kT threads with
+// kPer each; kInfBits, which no phase counts, past n_read
+template <int kT, int kPer>
+__device__ __forceinline__ void sel_load(uint32_t (&v)[kPer], const uint32_t* __restrict__ bits, uint32_t j0,
+                                         uint32_t n_read) {
+#pragma unroll
+  for (int u = 0; u < kPer; ++u) {
+    const uint32_t j = j0 + threadIdx.x + (uint32_t)kT * u;
+    v[u] = j < n_read ? bits[j] : kInfBits;
+  }
+}
+
+// digit 1 (bits 31..21) of v counted into two LDS sub-histograms, one per half of the workgroup
+// (LDS atomic conflicts); complete on return
+template <int kT, int kPer>
+__device__ __forceinline__ void sel_count1(const uint32_t (&v)[kPer], uint32_t (*h)[kHistBins]) {
+  const int t = threadIdx.x;
+  for (int i = t; i < 2 * kHistBins; i += kT) (&h[0][0])[i] = 0;
+  __syncthreads();
+  uint32_t* mine = h[t / (kT / 2)];
+#pragma unroll
+  for (int u = 0; u < kPer; ++u)
+    if (v[u] != kInfBits) atomicAdd(&mine[v[u] >> 21], 1u);
+  __syncthreads();
+}
+
+// the two sub-histograms added into the pair's global histogram g
+template <int kT>
+__device__ __forceinline__ void sel_flush1(const uint32_t (*h)[kHistBins], uint32_t* __restrict__ g) {
+  for (int b = threadIdx.x; b < kHistBins; b += kT) {
+    const uint32_t c = h[0][b] + h[1][b];
+    if (c) atomicAdd(&g[b], c);
+  }
+}
+
+// the values of v[0, kPer) (one block-map entry of the pair, kT threads) whose digit 1 is b into
+// the pair's candidate list: per-wave ballot counts, one atomic per workgroup on cand_cnt (the
+// per-pair counter is shared by ~30 workgroups). A caller that calls again puts a barrier in
+// between: wcount / base are rewritten by the next call.
+template <int kT, int kPer>
+__device__ __forceinline__ void sel_compact_bin(const uint32_t (&v)[kPer], uint32_t b, uint32_t* __restrict__ cv,
+                                                uint32_t* cnt) {
+  constexpr int kW = kT / 64;
+  __shared__ uint32_t wcount[kW];
+  __shared__ uint32_t base;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  uint32_t mine = 0;  // this wave's hits
+#pragma unroll
+  for (int u = 0; u < kPer; ++u) mine += (uint32_t)__popcll(__ballot(v[u] != kInfBits && (v[u] >> 21) == b));
+  if (lane == 0) wcount[w] = mine;
+  __syncthreads();
+  if (t == 0) {
+    uint32_t tot = 0;
+#pragma unroll
+    for (int k = 0; k < kW; ++k) tot += wcount[k];
+    base = tot ? atomicAdd(cnt, tot) : 0u;
+  }
+  __syncthreads();
+  if (wcount[w]) {
+    uint32_t o = base;
+    for (int k = 0; k < w; ++k) o += wcount[k];
+    const uint64_t below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+      const bool hit = v[u] != kInfBits && (v[u] >> 21) == b;
+      const uint64_t mk = __ballot(hit);
+      if (hit) cv[o + (uint32_t)__popcll(mk & below)] = v[u];
+      o += (uint32_t)__popcll(mk);
+    }
+  }
+}
+
+// the rank of the trimmed limit among n finite distances: getDistsQuantile's
+// (size_t)(float(n) * ratio), ratio == 1 giving the last, clamped
+__device__ __forceinline__ uint32_t sel_rank(uint32_t n, float ratio) {
+  if (ratio == 1.0f) return n - 1;
+  const float kf = (float)n * ratio;
+  const uint32_t k = (uint32_t)kf;
+  return k >= n ? n - 1 : k;
+}
+
+// digits 2 (bits 20..10) and 3 (bits 9..0) over the candidates src[0, c) of digit-1 bin b1 (the
+// workgroup's writes to src fenced by the caller; the barrier is here): the bits of the value of
+// rank r1 among them, on every thread. nt: the workgroup's threads; h: kHistBins words, wsum: 16,
+// res: 2, all rewritten.
+__device__ __forceinline__ uint32_t sel_digits23(const uint32_t* src, uint32_t c, uint32_t b1, uint32_t r1, int nt,
+                                                 uint32_t* h, uint32_t* wsum, uint32_t* res) {
+  const int t = threadIdx.x;
+  for (int i = t; i < kHistBins; i += nt) h[i] = 0;
+  __syncthreads();
+  for (uint32_t i = t; i < c; i += nt) atomicAdd(&h[(src[i] >> 10) & 2047u], 1u);
+  __syncthreads();
+  block_find_rank(h, kHistBins, r1, res, wsum);
+  const uint32_t b2 = res[0], r2 = res[1];
+  __syncthreads();
+  for (int i = t; i < kHistBins; i += nt) h[i] = 0;
+  __syncthreads();
+  const uint32_t hi21 = (b1 << 11) | b2;
+  for (uint32_t i = t; i < c; i += nt) {
+    const uint32_t v = src[i];
+    if ((v >> 10) == hi21) atomicAdd(&h[v & 1023u], 1u);
+  }
+  __syncthreads();
+  block_find_rank(h, kHist3Bins, r2, res, wsum);
+  return (hi21 << 10) | res[0];
+}
+
 // ---- TrimmedDist limit = exact k-th smallest finite d2, k = (size_t)(float(n) * ratio)
 // (getDistsQuantile), as a radix select on the float bits (non-negative floats
 // order like their bit patterns) spread over the whole chip:
@@ -1460,32 +1567,12 @@ __global__ __launch_bounds__(256) void k_sel_hist(BlockMap m, const PairDesc* __
                                                   uint32_t* __restrict__ hist1) {
   const int pair = m.pair[blockIdx.x];
   if (!st[pair].active) return;
-  __shared__ uint32_t h[2][kHistBins];  // one sub-histogram per wave pair (LDS atomic conflicts)
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int i = 0; i < 2 * kHistBins / 256; ++i) (&h[0][0])[t + 256 * i] = 0;
+  __shared__ uint32_t h[2][kHistBins];
   const PairDesc& d = pd[pair];
-  const uint32_t* bits = (const uint32_t*)(d2 + d.read_off);
-  const uint32_t j0 = m.start[blockIdx.x];
   uint32_t v[kSelPerThread];
-#pragma unroll
-  for (int u = 0; u < kSelPerThread; ++u) {
-    const uint32_t j = j0 + t + 256u * u;
-    v[u] = j < d.n_read ? bits[j] : kInfBits;
-  }
-  __syncthreads();
-  uint32_t* mine = h[t >> 7];
-#pragma unroll
-  for (int u = 0; u < kSelPerThread; ++u)
-    if (v[u] != kInfBits) atomicAdd(&mine[v[u] >> 21], 1u);
-  __syncthreads();
-  uint32_t* g = hist1 + (size_t)pair * kHistBins;
-#pragma unroll
-  for (int i = 0; i < kHistBins / 256; ++i) {
-    const int b = t + 256 * i;
-    const uint32_t c = h[0][b] + h[1][b];
-    if (c) atomicAdd(&g[b], c);
-  }
+  sel_load<256>(v, (const uint32_t*)(d2 + d.read_off), m.start[blockIdx.x], d.n_read);
+  sel_count1<256>(v, h);
+  sel_flush1<256>(h, hist1 + (size_t)pair * kHistBins);
 }
 
 // per pair (one workgroup, any size): n = #finite, k, bin b1 holding rank k, rank r1 inside it;
@@ -1545,16 +1632,7 @@ __device__ bool sel_find1_body(PairState& s, uint32_t* __restrict__ g, const Sel
     }
     return false;
   }
-  const float ratio = s.ratio;
-  uint32_t k;
-  if (ratio == 1.0f) {
-    k = n - 1;
-  } else {
-    const float kf = (float)n * ratio;
-    k = (uint32_t)kf;
-    if (k >= n) k = n - 1;
-  }
-  block_find_rank(h, kHistBins, k, res, wsum);
+  block_find_rank(h, kHistBins, sel_rank(n, s.ratio), res, wsum);
   if (t == 0) {
     s.sel_b1 = res[0];
     s.sel_r1 = res[1];
@@ -1590,30 +1668,14 @@ __global__ __launch_bounds__(kT) void k_sel_hist_f(BlockMap m, const PairDesc* _
   AICP_IP_T0;
   const int pair = m.pair[blockIdx.x];
   if (!st[pair].active) return;
-  __shared__ uint32_t h[2][kHistBins];  // one sub-histogram per half workgroup (LDS atomic conflicts)
+  __shared__ uint32_t h[2][kHistBins];
   __shared__ uint32_t wsum[16], res[2];
-  const int t = threadIdx.x;
-  for (int i = t; i < 2 * kHistBins; i += kT) (&h[0][0])[i] = 0;
   const PairDesc& d = pd[pair];
-  const uint32_t* bits = (const uint32_t*)(d2 + d.read_off);
-  const uint32_t j0 = m.start[blockIdx.x];
   uint32_t v[kPer];
-#pragma unroll
-  for (int u = 0; u < kPer; ++u) {
-    const uint32_t j = j0 + t + (uint32_t)kT * u;
-    v[u] = j < d.n_read ? bits[j] : kInfBits;
-  }
-  __syncthreads();
-  uint32_t* mine = h[t / (kT / 2)];
-#pragma unroll
-  for (int u = 0; u < kPer; ++u)
-    if (v[u] != kInfBits) atomicAdd(&mine[v[u] >> 21], 1u);
-  __syncthreads();
+  sel_load<kT>(v, (const uint32_t*)(d2 + d.read_off), m.start[blockIdx.x], d.n_read);
+  sel_count1<kT>(v, h);
   uint32_t* g = hist1 + (size_t)pair * kHistBins;
-  for (int b = t; b < kHistBins; b += kT) {
-    const uint32_t c = h[0][b] + h[1][b];
-    if (c) atomicAdd(&g[b], c);
-  }
+  sel_flush1<kT>(h, g);
   const uint32_t nblk = (d.n_read + 256u * kSelPerThread - 1) / (256u * kSelPerThread);
   AICP_IP_BODY(0);
   if (!last_arrival(&y.sel1[pair], nblk)) return;
@@ -1633,42 +1695,10 @@ __global__ __launch_bounds__(256) void k_sel_compact(BlockMap m, const PairDesc*
   const int pair = m.pair[blockIdx.x];
   const PairState& s = st[pair];
   if (!s.active) return;
-  __shared__ uint32_t wcount[4];
-  __shared__ uint32_t base;
   const PairDesc& d = pd[pair];
-  const uint32_t b1 = s.sel_b1;
-  const uint32_t* bits = (const uint32_t*)(d2 + d.read_off);
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const uint32_t j0 = m.start[blockIdx.x];
   uint32_t v[kSelPerThread];
-#pragma unroll
-  for (int u = 0; u < kSelPerThread; ++u) {
-    const uint32_t j = j0 + t + 256u * u;
-    v[u] = j < d.n_read ? bits[j] : kInfBits;
-  }
-  uint32_t mine = 0;  // this wave's hits
-#pragma unroll
-  for (int u = 0; u < kSelPerThread; ++u)
-    mine += (uint32_t)__popcll(__ballot(v[u] != kInfBits && (v[u] >> 21) == b1));
-  // one atomic per block (the per-pair counter is shared by ~30 blocks)
-  if (lane == 0) wcount[w] = mine;
-  __syncthreads();
-  if (t == 0) {
-    const uint32_t tot = wcount[0] + wcount[1] + wcount[2] + wcount[3];
-    base = tot ? atomicAdd(&cand_cnt[pair], tot) : 0u;
-  }
-  __syncthreads();
-  if (!wcount[w]) return;
-  uint32_t o = base;
-  for (int k = 0; k < w; ++k) o += wcount[k];
-  const uint64_t below = (1ull << lane) - 1ull;
-#pragma unroll
-  for (int u = 0; u < kSelPerThread; ++u) {
-    const bool hit = v[u] != kInfBits && (v[u] >> 21) == b1;
-    const uint64_t mk = __ballot(hit);
-    if (hit) cand[d.read_off + o + (uint32_t)__popcll(mk & below)] = v[u];
-    o += (uint32_t)__popcll(mk);
-  }
+  sel_load<256>(v, (const uint32_t*)(d2 + d.read_off), m.start[blockIdx.x], d.n_read);
+  sel_compact_bin<256>(v, s.sel_b1, cand + d.read_off, cand_cnt + pair);
 }
 
 // per pair (one workgroup, any size): digits 2 (bits 20..10) and 3 (bits 9..0) over the candidates.
@@ -1680,9 +1710,6 @@ __global__ __launch_bounds__(256) void k_sel_compact(BlockMap m, const PairDesc*
 // they were just written by another thread of the workgroup)
 __device__ void sel_final_body(PairState& s, uint32_t b1, uint32_t r1, const uint32_t* __restrict__ cv,
                                uint32_t* cand_cnt, const SelLds& L) {
-  uint32_t* h = L.h;
-  uint32_t* wsum = L.wsum;
-  uint32_t* res = L.res;
   uint32_t* cl = L.cl;
   const int t = threadIdx.x, nt = (int)blockDim.x;
   const uint32_t c = __hip_atomic_load(cand_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1703,24 +1730,9 @@ __device__ void sel_final_body(PairState& s, uint32_t b1, uint32_t r1, const uin
       }
     }
   }
-  for (int i = t; i < kHistBins; i += nt) h[i] = 0;
-  __syncthreads();
-  for (uint32_t i = t; i < c; i += nt) atomicAdd(&h[(src[i] >> 10) & 2047u], 1u);
-  __syncthreads();
-  block_find_rank(h, kHistBins, r1, res, wsum);
-  const uint32_t b2 = res[0], r2 = res[1];
-  __syncthreads();
-  for (int i = t; i < kHistBins; i += nt) h[i] = 0;
-  __syncthreads();
-  const uint32_t hi21 = (b1 << 11) | b2;
-  for (uint32_t i = t; i < c; i += nt) {
-    const uint32_t v = src[i];
-    if ((v >> 10) == hi21) atomicAdd(&h[v & 1023u], 1u);
-  }
-  __syncthreads();
-  block_find_rank(h, kHist3Bins, r2, res, wsum);
+  const uint32_t limit = sel_digits23(src, c, b1, r1, nt, L.h, L.wsum, L.res);
   if (t == 0) {
-    s.limit = __uint_as_float((hi21 << 10) | res[0]);
+    s.limit = __uint_as_float(limit);
     *cand_cnt = 0;  // ready for the next iteration
   }
 }
@@ -1742,49 +1754,15 @@ template <int kT>
 __global__ __launch_bounds__(kT) void k_sel_compact_f(BlockMap m, const PairDesc* __restrict__ pd, PairState* st,
                                                       const float* __restrict__ d2, uint32_t* __restrict__ cand,
                                                       uint32_t* __restrict__ cand_cnt, IcpIterSync y) {
-  constexpr int kPer = kNNBlock * kSelPerThread / kT, kW = kT / 64;
+  constexpr int kPer = kNNBlock * kSelPerThread / kT;
   AICP_IP_T0;
   const int pair = m.pair[blockIdx.x];
   PairState& s = st[pair];
   if (!s.active) return;
-  __shared__ uint32_t wcount[kW];
-  __shared__ uint32_t base;
   const PairDesc& d = pd[pair];
-  const uint32_t b1 = s.sel_b1;
-  const uint32_t* bits = (const uint32_t*)(d2 + d.read_off);
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const uint32_t j0 = m.start[blockIdx.x];
   uint32_t v[kPer];
-#pragma unroll
-  for (int u = 0; u < kPer; ++u) {
-    const uint32_t j = j0 + t + (uint32_t)kT * u;
-    v[u] = j < d.n_read ? bits[j] : kInfBits;
-  }
-  uint32_t mine = 0;  // this wave's hits
-#pragma unroll
-  for (int u = 0; u < kPer; ++u)
-    mine += (uint32_t)__popcll(__ballot(v[u] != kInfBits && (v[u] >> 21) == b1));
-  if (lane == 0) wcount[w] = mine;
-  __syncthreads();
-  if (t == 0) {
-    uint32_t tot = 0;
-#pragma unroll
-    for (int k = 0; k < kW; ++k) tot += wcount[k];
-    base = tot ? atomicAdd(&cand_cnt[pair], tot) : 0u;
-  }
-  __syncthreads();
-  if (wcount[w]) {
-    uint32_t o = base;
-    for (int k = 0; k < w; ++k) o += wcount[k];
-    const uint64_t below = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-      const bool hit = v[u] != kInfBits && (v[u] >> 21) == b1;
-      const uint64_t mk = __ballot(hit);
-      if (hit) cand[d.read_off + o + (uint32_t)__popcll(mk & below)] = v[u];
-      o += (uint32_t)__popcll(mk);
-    }
-  }
+  sel_load<kT>(v, (const uint32_t*)(d2 + d.read_off), m.start[blockIdx.x], d.n_read);
+  sel_compact_bin<kT>(v, s.sel_b1, cand + d.read_off, cand_cnt + pair);
   const uint32_t nblk = (d.n_read + 256u * kSelPerThread - 1) / (256u * kSelPerThread);
   AICP_IP_BODY(1);
   if (!last_arrival(&y.sel2[pair], nblk)) return;
@@ -1792,41 +1770,6 @@ __global__ __launch_bounds__(kT) void k_sel_compact_f(BlockMap m, const PairDesc
   __shared__ uint32_t h[kHistBins], wsum[16], res[2], cl[kFinalLds];
   sel_final_body(s, s.sel_b1, s.sel_r1, cand + d.read_off, cand_cnt + pair, SelLds{h, wsum, res, cl, kFinalLds});
   AICP_IP_TAIL(1);
-}
-// the values of v[0, kPer) (one block-map entry of the pair, kT threads) whose digit 1 is b into
-// the pair's candidate list: per-wave ballot counts, one atomic per workgroup on cand_cnt
-template <int kT, int kPer>
-__device__ __forceinline__ void sel_compact_bin(const uint32_t (&v)[kPer], uint32_t b, uint32_t* __restrict__ cv,
-                                                uint32_t* cnt) {
-  constexpr int kW = kT / 64;
-  __shared__ uint32_t wcount[kW];
-  __shared__ uint32_t base;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  uint32_t mine = 0;
-#pragma unroll
-  for (int u = 0; u < kPer; ++u) mine += (uint32_t)__popcll(__ballot(v[u] != kInfBits && (v[u] >> 21) == b));
-  if (lane == 0) wcount[w] = mine;
-  __syncthreads();
-  if (t == 0) {
-    uint32_t tot = 0;
-#pragma unroll
-    for (int k = 0; k < kW; ++k) tot += wcount[k];
-    base = tot ? atomicAdd(cnt, tot) : 0u;
-  }
-  __syncthreads();
-  if (wcount[w]) {
-    uint32_t o = base;
-    for (int k = 0; k < w; ++k) o += wcount[k];
-    const uint64_t below = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-      const bool hit = v[u] != kInfBits && (v[u] >> 21) == b;
-      const uint64_t mk = __ballot(hit);
-      if (hit) cv[o + (uint32_t)__popcll(mk & below)] = v[u];
-      o += (uint32_t)__popcll(mk);
-    }
-  }
-  __syncthreads();  // (wcount / base are rewritten by the next call)
 }
 
 // The whole select in one launch from the second ICP iteration on: k_sel_hist_f's histogram, and
@@ -1854,30 +1797,16 @@ __global__ __launch_bounds__(kT) void k_sel_fused(BlockMap m, const PairDesc* __
   __shared__ uint32_t wsum[16], res[2];
   uint32_t(*h)[kHistBins] = reinterpret_cast<uint32_t(*)[kHistBins]>(lds);
   const int t = threadIdx.x;
-  for (int i = t; i < 2 * kHistBins; i += kT) (&h[0][0])[i] = 0;
   const PairDesc& d = pd[pair];
   const uint32_t* bits = (const uint32_t*)(d2 + d.read_off);
-  const uint32_t j0 = m.start[blockIdx.x];
   const uint32_t guess = s.sel_b1;  // the previous iteration's bin (find1 rewrites it after every block arrived)
   uint32_t v[kPer];
-#pragma unroll
-  for (int u = 0; u < kPer; ++u) {
-    const uint32_t j = j0 + t + (uint32_t)kT * u;
-    v[u] = j < d.n_read ? bits[j] : kInfBits;
-  }
-  __syncthreads();
-  uint32_t* mine = h[t / (kT / 2)];
-#pragma unroll
-  for (int u = 0; u < kPer; ++u)
-    if (v[u] != kInfBits) atomicAdd(&mine[v[u] >> 21], 1u);
-  __syncthreads();
+  sel_load<kT>(v, bits, m.start[blockIdx.x], d.n_read);
+  sel_count1<kT>(v, h);
   uint32_t* g = hist1 + (size_t)pair * kHistBins;
-  for (int b = t; b < kHistBins; b += kT) {
-    const uint32_t c = h[0][b] + h[1][b];
-    if (c) atomicAdd(&g[b], c);
-  }
+  sel_flush1<kT>(h, g);
   uint32_t* cv = cand + d.read_off;
-  sel_compact_bin<kT, kPer>(v, guess, cv, cand_cnt + pair);
+  sel_compact_bin<kT>(v, guess, cv, cand_cnt + pair);
   const uint32_t nblk = (d.n_read + 256u * kSelPerThread - 1) / (256u * kSelPerThread);
   if (!last_arrival(&y.sel1[pair], nblk)) return;
   __syncthreads();  // (every thread's reads of the sub-histograms precede the tails' writes)
@@ -1900,12 +1829,9 @@ __global__ __launch_bounds__(kT) void k_sel_fused(BlockMap m, const PairDesc* __
     if (t == 0) __hip_atomic_store(cand_cnt + pair, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     for (uint32_t jb = 0; jb < d.n_read; jb += (uint32_t)kT * kPer) {
-#pragma unroll
-      for (int u = 0; u < kPer; ++u) {
-        const uint32_t j = jb + t + (uint32_t)kT * u;
-        v[u] = j < d.n_read ? bits[j] : kInfBits;
-      }
-      sel_compact_bin<kT, kPer>(v, b1, cv, cand_cnt + pair);
+      sel_load<kT>(v, bits, jb, d.n_read);
+      sel_compact_bin<kT>(v, b1, cv, cand_cnt + pair);
+      __syncthreads();  // (sel_compact_bin's LDS words are rewritten by the next round)
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __threadfence();
@@ -1936,21 +1862,9 @@ __global__ __launch_bounds__(kSelPairThreads) void k_sel_pair(const PairDesc* __
   __shared__ uint32_t wsum[16], res[2];
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const PairDesc& d = pd[pair];
-  const uint32_t n_read = d.n_read;
-  const uint32_t* bits = (const uint32_t*)(d2 + d.read_off);
-  for (int i = t; i < 2 * kHistBins; i += kT) (&h[0][0])[i] = 0;
   uint32_t v[kSelPairPer];
-#pragma unroll
-  for (int u = 0; u < kSelPairPer; ++u) {
-    const uint32_t j = (uint32_t)t + (uint32_t)kT * u;
-    v[u] = j < n_read ? bits[j] : kInfBits;
-  }
-  __syncthreads();
-  uint32_t* mine = h[t / (kT / 2)];
-#pragma unroll
-  for (int u = 0; u < kSelPairPer; ++u)
-    if (v[u] != kInfBits) atomicAdd(&mine[v[u] >> 21], 1u);
-  __syncthreads();
+  sel_load<kT>(v, (const uint32_t*)(d2 + d.read_off), 0u, d.n_read);
+  sel_count1<kT>(v, h);
   uint32_t cnt = 0;
   for (int b = t; b < kHistBins; b += kT) {
     const uint32_t c = h[0][b] + h[1][b];
@@ -1964,7 +1878,7 @@ __global__ __launch_bounds__(kSelPairThreads) void k_sel_pair(const PairDesc* __
   uint32_t n = 0;
   for (int k = 0; k < kT / 64; ++k) n += wsum[k];
   __syncthreads();  // (wsum is reused by block_find_rank)
-  if (n == 0) {  // ConvergenceError("no outlier to filter"), as sel_find1_body
+  if (n == 0) {  // ConvergenceError("no outlier to filter")
     if (t == 0) {
       s.status = 1;
       s.active = 0;
@@ -1972,16 +1886,7 @@ __global__ __launch_bounds__(kSelPairThreads) void k_sel_pair(const PairDesc* __
     pair_done(y);
     return;
   }
-  const float ratio = s.ratio;
-  uint32_t k;
-  if (ratio == 1.0f) {
-    k = n - 1;
-  } else {
-    const float kf = (float)n * ratio;
-    k = (uint32_t)kf;
-    if (k >= n) k = n - 1;
-  }
-  block_find_rank(h[0], kHistBins, k, res, wsum);
+  block_find_rank(h[0], kHistBins, sel_rank(n, s.ratio), res, wsum);
   const uint32_t b1 = res[0], r1 = res[1];
   if (t == 0) {
     s.sel_b1 = b1;
@@ -2013,24 +1918,8 @@ __global__ __launch_bounds__(kSelPairThreads) void k_sel_pair(const PairDesc* __
   }
   if (!lds) __threadfence_block();
   __syncthreads();
-  // digits 2 (bits 20..10) and 3 (bits 9..0) over the candidates
-  for (int i = t; i < kHistBins; i += kT) h[0][i] = 0;
-  __syncthreads();
-  for (uint32_t i = t; i < c; i += kT) atomicAdd(&h[0][(dst[i] >> 10) & 2047u], 1u);
-  __syncthreads();
-  block_find_rank(h[0], kHistBins, r1, res, wsum);
-  const uint32_t b2 = res[0], r2 = res[1];
-  __syncthreads();
-  for (int i = t; i < kHistBins; i += kT) h[0][i] = 0;
-  __syncthreads();
-  const uint32_t hi21 = (b1 << 11) | b2;
-  for (uint32_t i = t; i < c; i += kT) {
-    const uint32_t x = dst[i];
-    if ((x >> 10) == hi21) atomicAdd(&h[0][x & 1023u], 1u);
-  }
-  __syncthreads();
-  block_find_rank(h[0], kHist3Bins, r2, res, wsum);
-  if (t == 0) s.limit = __uint_as_float((hi21 << 10) | res[0]);
+  const uint32_t limit = sel_digits23(dst, c, b1, r1, kT, h[0], wsum, res);
+  if (t == 0) s.limit = __uint_as_float(limit);
 }
 
 #ifndef AICP_SEL_COMPACT_THREADS
@@ -2058,6 +1947,63 @@ __device__ __forceinline__ double row_sum_d(double v) {
   return v;
 }
 
+// The load stage of a reduce workgroup: kReducePerThread readings per thread (the block's
+// reduction is paid once per kReduceBlock readings), all loads of the thread's readings first
+// (independent), so that with the gathers of the kept ones and then the arithmetic a reading
+// costs two round trips instead of three. keep: d2 <= limit (inclusive); pos:
+// the match; r: the reading; tpts / tnod: the thread's sums of the touch word's two halves.
+__device__ __forceinline__ void reduce_load(const BlockMap& m, const PairDesc& d, float limit,
+                                            const float4* __restrict__ read_c, const int32_t* __restrict__ match,
+                                            const float* __restrict__ d2, const uint32_t* __restrict__ touched,
+                                            bool (&keep)[kReducePerThread], int32_t (&pos)[kReducePerThread],
+                                            float4 (&r)[kReducePerThread], uint32_t& tpts, uint32_t& tnod) {
+  tpts = tnod = 0;
+  const uint32_t base = m.start[blockIdx.x], off = d.read_off, n_read = d.n_read;
+#pragma unroll
+  for (int it = 0; it < kReducePerThread; ++it) {
+    const uint32_t j = base + it * kNNBlock + threadIdx.x;
+    keep[it] = false;
+    pos[it] = 0;
+    if (j < n_read) {
+      const uint32_t tc = touched[off + j];
+      tpts += tc & 0xFFFFu;
+      tnod += tc >> 16;
+      keep[it] = d2[off + j] <= limit;
+      pos[it] = match[off + j];
+      r[it] = read_c[off + j];
+    }
+  }
+}
+
+// A reduce workgroup's N sums into its slab row: row sums (DPP) -> one partial per row of 16
+// lanes in LDS -> a fixed-order sum of the block's rows (no cross-row shuffles). col(c): the sum
+// that slab column c holds, or -1 for a column written as +0.0.
+template <int N, class Col>
+__device__ __forceinline__ void reduce_block_sum(const double (&acc)[N], const BlockMap& m, const PairDesc& d,
+                                                 double* __restrict__ slab, Col col) {
+  constexpr int kRows = kNNBlock / 16;
+  __shared__ double part[kRows][N];
+  const int lane = threadIdx.x & 63;
+  const int row = threadIdx.x >> 4;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const double v = row_sum_d(acc[i]);
+    if ((lane & 15) == 0) part[row][i] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kRedCols) {
+    const int src = col((int)threadIdx.x);
+    double v = 0.0;
+    if (src >= 0) {
+#pragma unroll
+      for (int w = 0; w < kRows; ++w) v += part[w][src];
+    }
+    // the pair's partial rows start at red_blk_off (m may cover a subset of the pairs)
+    const uint32_t srow = d.red_blk_off + m.start[blockIdx.x] / kReduceBlock;
+    slab[(size_t)srow * kRedCols + threadIdx.x] = v;
+  }
+}
+
 // one reduce workgroup's partial sums (kRedCols) into its slab row
 __device__ __forceinline__ void icp_reduce_body(BlockMap m, const PairDesc& d, const PairState& s,
                                                 const float4* __restrict__ read_c, const int32_t* __restrict__ match,
@@ -2067,32 +2013,14 @@ __device__ __forceinline__ void icp_reduce_body(BlockMap m, const PairDesc& d, c
   float T[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) T[i] = s.T[i];
-  const float limit = s.limit;
   double acc[kRedCols];
 #pragma unroll
   for (int i = 0; i < kRedCols; ++i) acc[i] = 0.0;
-  uint32_t tpts = 0, tnod = 0;
-  // kReducePerThread readings per thread (the block's reduction below is paid once per
-  // kReduceBlock readings): all loads of the thread's readings first (independent), then the
-  // gathers of the kept ones, then the arithmetic: two round trips instead of three per reading.
-  const uint32_t base = m.start[blockIdx.x];
+  uint32_t tpts, tnod;
   bool keep[kReducePerThread];
   int32_t pos[kReducePerThread];
   float4 r[kReducePerThread];
-#pragma unroll
-  for (int it = 0; it < kReducePerThread; ++it) {
-    const uint32_t j = base + it * kNNBlock + threadIdx.x;
-    keep[it] = false;
-    pos[it] = 0;
-    if (j < d.n_read) {
-      const uint32_t tc = touched[d.read_off + j];
-      tpts += tc & 0xFFFFu;
-      tnod += tc >> 16;
-      keep[it] = d2[d.read_off + j] <= limit;
-      pos[it] = match[d.read_off + j];
-      r[it] = read_c[d.read_off + j];
-    }
-  }
+  reduce_load(m, d, s.limit, read_c, match, d2, touched, keep, pos, r, tpts, tnod);
   float4 q[kReducePerThread], nr[kReducePerThread];
 #pragma unroll
   for (int it = 0; it < kReducePerThread; ++it)
@@ -2128,26 +2056,7 @@ __device__ __forceinline__ void icp_reduce_body(BlockMap m, const PairDesc& d, c
   }
   acc[28] = (double)tpts;
   acc[29] = (double)tnod;
-  // row sums (DPP) -> one partial per row of 16 lanes in LDS -> a fixed-order sum of the
-  // block's rows (no cross-row shuffles)
-  constexpr int kRows = kNNBlock / 16;
-  __shared__ double part[kRows][kRedCols];
-  const int lane = threadIdx.x & 63;
-  const int row = threadIdx.x >> 4;
-#pragma unroll
-  for (int i = 0; i < kRedCols; ++i) {
-    const double v = row_sum_d(acc[i]);
-    if ((lane & 15) == 0) part[row][i] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kRedCols) {
-    double v = 0.0;
-#pragma unroll
-    for (int w = 0; w < kRows; ++w) v += part[w][threadIdx.x];
-    // the pair's partial rows start at red_blk_off (m may cover a subset of the pairs)
-    const uint32_t row = d.red_blk_off + m.start[blockIdx.x] / kReduceBlock;
-    slab[(size_t)row * kRedCols + threadIdx.x] = v;
-  }
+  reduce_block_sum(acc, m, d, slab, [](int c) { return c; });
 }
 
 __global__ __launch_bounds__(kNNBlock) void k_icp_reduce(
@@ -2393,11 +2302,9 @@ __device__ __forceinline__ void update_tail(const PairDesc& d, PairState& s, int
   s.active = iterate ? 1 : 0;
 }
 
-// the serial part of an ICP update (one lane): solve, compose, checkers
-// x_full: the LLT solution when the pivoted-QR rank is full (solve6's first path, computed by
-// two waves side by side in icp_update_body), or nullptr: solve6 here
-__device__ void update_serial(const PairDesc& d, PairState& s, const double* tot, const IcpParams& prm,
-                              const double* x_full) {
+// what precedes the solve in every update, whichever the error minimizer: the touch totals and
+// the kept count of the pair's sums; returns it, 0 when the pair stopped for it
+__device__ __forceinline__ int32_t update_head(PairState& s, const double* tot) {
   s.touched_pts += (uint64_t)tot[28];
   s.touched_nodes += (uint64_t)tot[29];
   const int32_t kept = (int32_t)tot[27];
@@ -2405,8 +2312,17 @@ __device__ void update_serial(const PairDesc& d, PairState& s, const double* tot
   if (kept == 0) {  // ConvergenceError("no point to minimize")
     s.status = 1;
     s.active = 0;
-    return;
   }
+  return kept;
+}
+
+// the serial part of an ICP update (one lane): solve, compose, checkers
+// x_full: the LLT solution when the pivoted-QR rank is full (solve6's first path, computed by
+// two waves side by side in icp_update_body), or nullptr: solve6 here
+__device__ void update_serial(const PairDesc& d, PairState& s, const double* tot, const IcpParams& prm,
+                              const double* x_full) {
+  const int32_t kept = update_head(s, tot);
+  if (kept == 0) return;
   double xd[6];
   if (x_full) {
     for (int a = 0; a < 6; ++a) xd[a] = x_full[a];
@@ -2423,14 +2339,14 @@ __device__ void update_serial(const PairDesc& d, PairState& s, const double* tot
   update_tail(d, s, kept, prm);
 }
 
-// one pair's update by a 256-thread workgroup: its slab rows summed (thread t sums column
+// a pair's slab rows summed into tot[kRedCols] by a 256-thread workgroup: thread t sums column
 // t % kRedCols over rows t / kRedCols + 8 k -- independent loads, contiguous across the block --
-// then a fixed-order sum of the 8 groups), then update_serial on lane 0
-__device__ void icp_update_body(const PairDesc& d, PairState& s, const double* __restrict__ slab,
-                                const IcpParams& prm) {
-  constexpr int kGroups = 256 / kRedCols;
-  __shared__ double part[kGroups][kRedCols];
-  __shared__ double tot[kRedCols];
+// then a fixed-order sum of the 8 groups; tot is complete on return. part, tot: the kernel's LDS
+// (as SelLds: one allocation per kernel).
+constexpr int kSlabGroups = 256 / kRedCols;
+__device__ __forceinline__ void slab_total(const PairDesc& d, const double* __restrict__ slab,
+                                           double (*part)[kRedCols], double* tot) {
+  constexpr int kGroups = kSlabGroups;
   const int t = threadIdx.x;
   if (t < kGroups * kRedCols) {
     const int g = t / kRedCols, c = t - g * kRedCols;
@@ -2459,6 +2375,15 @@ __device__ void icp_update_body(const PairDesc& d, PairState& s, const double* _
     tot[t] = v;
   }
   __syncthreads();
+}
+
+// one pair's update by a 256-thread workgroup: slab_total, then update_serial on lane 0
+__device__ void icp_update_body(const PairDesc& d, PairState& s, const double* __restrict__ slab,
+                                const IcpParams& prm) {
+  __shared__ double part[kSlabGroups][kRedCols];
+  __shared__ double tot[kRedCols];
+  const int t = threadIdx.x;
+  slab_total(d, slab, part, tot);
   // solve6's full-rank path with its two halves side by side: wave 0 the pivoted-QR rank, wave 1
   // the LLT solve (each ~half of the serial solve); a rank below 6 or a failed LLT falls back
   // to solve6 on lane 0
@@ -2521,31 +2446,15 @@ __global__ __launch_bounds__(kNNBlock) void k_icp_reduce_p2p(
   float T[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) T[i] = s.T[i];
-  const float limit = s.limit;
   double acc[kP2pAcc];
 #pragma unroll
   for (int i = 0; i < kP2pAcc; ++i) acc[i] = 0.0;
-  uint32_t tpts = 0, tnod = 0;
-  // as icp_reduce_body: the thread's four readings loaded first, then the gathers of the kept
-  // ones (16 B each, no normal), then the arithmetic
-  const uint32_t base = m.start[blockIdx.x];
+  uint32_t tpts, tnod;
   bool keep[kReducePerThread];
   int32_t pos[kReducePerThread];
   float4 r[kReducePerThread];
-#pragma unroll
-  for (int it = 0; it < kReducePerThread; ++it) {
-    const uint32_t j = base + it * kNNBlock + threadIdx.x;
-    keep[it] = false;
-    pos[it] = 0;
-    if (j < d.n_read) {
-      const uint32_t tc = touched[d.read_off + j];
-      tpts += tc & 0xFFFFu;
-      tnod += tc >> 16;
-      keep[it] = d2[d.read_off + j] <= limit;
-      pos[it] = match[d.read_off + j];
-      r[it] = read_c[d.read_off + j];
-    }
-  }
+  reduce_load(m, d, s.limit, read_c, match, d2, touched, keep, pos, r, tpts, tnod);
+  // the gathers of the kept ones are 16 B each (no normal)
   float4 q[kReducePerThread];
 #pragma unroll
   for (int it = 0; it < kReducePerThread; ++it)
@@ -2569,41 +2478,15 @@ __global__ __launch_bounds__(kNNBlock) void k_icp_reduce_p2p(
   }
   acc[16] = (double)tpts;
   acc[17] = (double)tnod;
-  constexpr int kRows = kNNBlock / 16;
-  __shared__ double part[kRows][kP2pAcc];
-  const int lane = threadIdx.x & 63;
-  const int row = threadIdx.x >> 4;
-#pragma unroll
-  for (int i = 0; i < kP2pAcc; ++i) {
-    const double v = row_sum_d(acc[i]);
-    if ((lane & 15) == 0) part[row][i] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kRedCols) {
-    const int c = threadIdx.x;
-    const int src = c < 15 ? c : c - 12;  // (columns 27..29 are sums 15..17)
-    double v = 0.0;
-    if (c < 15 || c >= 27) {
-#pragma unroll
-      for (int w = 0; w < kRows; ++w) v += part[w][src];
-    }
-    const uint32_t srow = d.red_blk_off + m.start[blockIdx.x] / kReduceBlock;
-    slab[(size_t)srow * kRedCols + c] = v;
-  }
+  // (columns 27..29 are sums 15..17)
+  reduce_block_sum(acc, m, d, slab, [](int c) { return c < 15 ? c : c >= 27 ? c - 12 : -1; });
   AICP_IP_BODY(2);
 }
 
 // the serial part of a point-to-point update (one lane): means, M, R = U V^T, t, compose, checkers
 __device__ void update_serial_p2p(const PairDesc& d, PairState& s, const double* tot, const IcpParams& prm) {
-  s.touched_pts += (uint64_t)tot[28];
-  s.touched_nodes += (uint64_t)tot[29];
-  const int32_t kept = (int32_t)tot[27];
-  s.kept = kept;
-  if (kept == 0) {  // ConvergenceError("no point to minimize")
-    s.status = 1;
-    s.active = 0;
-    return;
-  }
+  const int32_t kept = update_head(s, tot);
+  if (kept == 0) return;
   const double n = (double)kept;
   double pm[3], qm[3], M[9], R[9];
 #pragma unroll
@@ -2630,8 +2513,7 @@ __device__ void update_serial_p2p(const PairDesc& d, PairState& s, const double*
   update_tail(d, s, kept, prm);
 }
 
-// k_icp_update_f's row sum (thread t: column t % kRedCols over rows t / kRedCols + 8 k in order,
-// then the 8 groups in order), then update_serial_p2p on lane 0
+// slab_total, then update_serial_p2p on lane 0
 __global__ __launch_bounds__(256) void k_icp_update_p2p(const PairDesc* __restrict__ pd, PairState* st,
                                                         const double* __restrict__ slab, IcpParams prm,
                                                         IcpIterSync y) {
@@ -2640,36 +2522,10 @@ __global__ __launch_bounds__(256) void k_icp_update_p2p(const PairDesc* __restri
   PairState& s = st[pair];
   if (!s.active) return;
   const PairDesc& d = pd[pair];
-  constexpr int kGroups = 256 / kRedCols;
-  __shared__ double part[kGroups][kRedCols];
+  __shared__ double part[kSlabGroups][kRedCols];
   __shared__ double tot[kRedCols];
-  const int t = threadIdx.x;
-  if (t < kGroups * kRedCols) {
-    const int g = t / kRedCols, c = t - g * kRedCols;
-    const double* col = slab + (size_t)d.red_blk_off * kRedCols + c;
-    double v = 0.0;
-    for (uint32_t r0 = g; r0 < d.n_red_blk; r0 += 16u * kGroups) {
-      double x[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const uint32_t r = r0 + (uint32_t)u * kGroups;
-        x[u] = r < d.n_red_blk ? col[(size_t)r * kRedCols] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < 16; ++u)
-        if (r0 + (uint32_t)u * kGroups < d.n_red_blk) v += x[u];
-    }
-    part[g][c] = v;
-  }
-  __syncthreads();
-  if (t < kRedCols) {
-    double v = part[0][t];
-#pragma unroll
-    for (int g = 1; g < kGroups; ++g) v += part[g][t];
-    tot[t] = v;
-  }
-  __syncthreads();
-  if (t == 0) update_serial_p2p(d, s, tot, prm);
+  slab_total(d, slab, part, tot);
+  if (threadIdx.x == 0) update_serial_p2p(d, s, tot, prm);
   AICP_IP_BODY(3);
   AICP_IP_TAIL0;
   pair_done(y);
@@ -3061,12 +2917,18 @@ void launch_icp_select(hipStream_t s, BlockMap m, int n_pairs, const PairDesc* p
   k_sel_compact<<<m.n_blocks, 256, 0, s>>>(m, pd, st, d2, cand, cand_cnt);
   k_sel_final<<<n_pairs, 1024, 0, s>>>(pd + p0, st + p0, cand, cand_cnt + p0);
 }
-IcpIterSync icp_sync_layout(uint32_t* words, size_t n_pairs, int group) {
+IcpIterSync icp_iter_sync(uint32_t* words, size_t n_pairs, int np, const PairDesc* pd, PairState* st, ActiveList* al,
+                          uint32_t* ctr) {
   IcpIterSync y{};
   y.sel1 = words;
   y.sel2 = words + n_pairs;
   y.red = words + 2 * n_pairs;
-  y.pairs = words + 3 * n_pairs + group;
+  y.pairs = words + 3 * n_pairs;
+  y.np = np;
+  y.pd = pd;
+  y.st = st;
+  y.al = al;
+  y.ctr = ctr;
   return y;
 }
 void launch_icp_select_f(hipStream_t s, BlockMap m, const PairDesc* pd, PairState* st, const float* d2,

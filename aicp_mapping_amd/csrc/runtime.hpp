@@ -206,6 +206,18 @@ int device_trees_check(TreeBufs& T, std::string& err);
 // force: aicp_hip_options::tree_plan
 int plan_levels(uint64_t n_max, const TreeBufs& T, int force, bool lean = false);
 int check_cfg(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, int flags);
+// what the ICP kernels take of a chain (prof_slot 0: the NN launches' callers number it)
+inline IcpParams icp_params(const aicp_icp_config* cfg) {
+  IcpParams ip{};
+  ip.maxE2 = (1 + cfg->nn_epsilon) * (1 + cfg->nn_epsilon);
+  ip.maxR2 = cfg->nn_max_dist * cfg->nn_max_dist;
+  ip.max_iter = cfg->max_iter;
+  ip.smooth = cfg->smooth_length;
+  ip.min_rot = cfg->min_diff_rot;
+  ip.min_trans = cfg->min_diff_trans;
+  ip.knn_normals = cfg->knn_normals;
+  return ip;
+}
 WorkerPool* ctx_pool(aicp_hip_ctx* ctx);  // the context's packing threads, created on first use
 
 // The drop-in path's reference cache. App registers reading after reading against one reference

@@ -1007,19 +1007,6 @@ static BlockMap map_sub(const BlockMap& m, uint32_t off, uint32_t cnt) {
   return r;
 }
 
-static IcpParams icp_params(const aicp_icp_config* cfg) {
-  IcpParams ip;
-  std::memset(&ip, 0, sizeof(ip));
-  ip.maxE2 = (1 + cfg->nn_epsilon) * (1 + cfg->nn_epsilon);
-  ip.maxR2 = cfg->nn_max_dist * cfg->nn_max_dist;
-  ip.max_iter = cfg->max_iter;
-  ip.smooth = cfg->smooth_length;
-  ip.min_rot = cfg->min_diff_rot;
-  ip.min_trans = cfg->min_diff_trans;
-  ip.knn_normals = cfg->knn_normals;
-  return ip;
-}
-
 // whether the host waits for poll word k, the active count at the start of iteration k, before
 // it enqueues the rest of that iteration (from smoothLength on: no pair can stop earlier except on
 // an error)
@@ -1090,12 +1077,7 @@ static int loop_part(aicp_hip_ctx* ctx, SeqState* S, const aicp_icp_config* cfg,
     poll_host[it + 1] = 0xffffffffu;
     hn_next = poll_dev + it + 1;
   }
-  IcpIterSync y = icp_sync_layout(sl.isync.as<uint32_t>(), np, 0);
-  y.np = lp.np_l;
-  y.pd = lp.gd;
-  y.st = lp.gs;
-  y.al = al;
-  y.ctr = ctr;
+  IcpIterSync y = icp_iter_sync(sl.isync.as<uint32_t>(), np, lp.np_l, lp.gd, lp.gs, al, ctr);
   y.host_n = hn_next;
   y.src_pair = R.next_src;
   const int ff = S->opt.select_fused_from;

@@ -7,12 +7,14 @@ directory. Per kernel, the assembly text and the resource entries of its metadat
 for equality after removing what differs between two compiles of one source or moves when another
 function of the file is removed: trailing `;` comments, the function ordinal in local labels and the
 __hip_cuid_ symbol. Prints one line per kernel; exits 1 unless every kernel present in both trees is
-the same (kernels whose demangled name contains an --allow NAME may differ). Needs no GPU.
+the same (kernels whose demangled name contains an --allow NAME may differ; for those that do, both
+sides' resource entries and spill counts are printed). Needs no GPU.
 """
 import argparse, collections, concurrent.futures, os, re, shlex, subprocess, sys, tempfile
 
 META = (".vgpr_count", ".sgpr_count", ".agpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size",
         ".kernarg_segment_size", ".max_flat_workgroup_size")
+SHOWN = (".vgpr_spill_count",)  # printed with META for an allowed kernel that differs, not compared
 
 
 def device_compiles(csrc):
@@ -55,8 +57,13 @@ def kernels(text):
     for item in re.split(r"\n  - ", text[text.find("amdhsa.kernels:"):])[1:]:
         sym = re.search(r"\.name:\s+(\S+)", item)
         if sym:
-            meta[sym.group(1)] = sorted(l.strip() for l in item.splitlines() if l.strip().split(":")[0] in META)
+            meta[sym.group(1)] = sorted(l.strip() for l in item.splitlines() if l.strip().split(":")[0] in META + SHOWN)
     return {k: ("\n".join(body[k]), meta.get(k)) for k in body}  # device functions too: no metadata
+
+
+def compared(kernel):
+    text, meta = kernel
+    return text, meta and [l for l in meta if l.split(":")[0] in META]
 
 
 def main():
@@ -78,7 +85,7 @@ def main():
         print(f"{src}: {len(old)} kernels in OLD, {len(new)} in NEW")
         for sym, name in zip(names, demangled):
             if sym in old and sym in new:
-                state = "same" if old[sym] == new[sym] else "DIFFERENT"
+                state = "same" if compared(old[sym]) == compared(new[sym]) else "DIFFERENT"
                 if state != "same":
                     allowed = any(x in name for x in a.allow)
                     bad += not allowed
@@ -86,6 +93,9 @@ def main():
             else:
                 state = "only in OLD" if sym in old else "only in NEW"
             print(f"  {state:12s} {name.split('(')[0][:160]}")
+            if state.endswith("(allowed)"):
+                for side, k in (("OLD", old[sym]), ("NEW", new[sym])):
+                    print(f"    {side} " + "  ".join(k[1] or []))
     return 1 if bad else 0
 
 
