@@ -52,6 +52,7 @@ EXPORTS = [
     "aicp_hip_map_align_batch", "aicp_hip_map_capacity", "aicp_hip_default_built_map_params",
     "aicp_hip_built_map_window", "aicp_hip_built_map_sequence_run", "aicp_hip_last_built_map_timing",
     "aicp_hip_map_sequence_run_raw", "aicp_hip_built_map_sequence_run_raw", "aicp_hip_test_ingest",
+    "aicp_hip_test_tree",
 ]
 
 
@@ -70,7 +71,8 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_last_built_map_timing",  # the built-map localization stream
            "aicp_hip_test_step_p2p",  # the point-to-point chains
            "aicp_hip_map_sequence_run_raw", "aicp_hip_built_map_sequence_run_raw",
-           "aicp_hip_test_ingest"}  # raw readings in the two map streams
+           "aicp_hip_test_ingest",  # raw readings in the two map streams
+           "aicp_hip_test_tree"}  # the kd-tree build, node for node
 
 
 class IcpConfig(C.Structure):
@@ -525,6 +527,9 @@ def _load():
         L.aicp_hip_built_map_sequence_run_raw.argtypes = [vp, cfgp, C.POINTER(BuiltMapParams), pfp, vp, clp, fp, sz, fp,
                                                           C.POINTER(BuiltMapResult), u32p, szp]
         L.aicp_hip_test_ingest.argtypes = [vp, fp, sz, sz, fp, fp]
+    if hasattr(L, "aicp_hip_test_tree"):
+        u32p = C.POINTER(C.c_uint32)
+        L.aicp_hip_test_tree.argtypes = [vp, sz, u32p, fp, C.c_int32, C.c_int32, u32p, u32p, ip, fp, u32p, fp, u32p]
     return L
 
 
@@ -1130,6 +1135,56 @@ class Context:
                                       _fptr(out) if download else None)
         self.check(rc)
         return out[:a.shape[0]] if download else None
+
+    def test_tree(self, clouds, center=0, bucket=8):
+        """aicp_hip_test_tree: the matcher's batched kd-tree build on `clouds` (a list of (n, 3)
+        float32 arrays, one batch) and what it wrote. Returns dict(rc, error (the last error text for
+        rc != 0), ctl=dict(nseg (50,), n_small, n_mid, n_big, error), trees=[...]); a tree is
+        dict(node_off, n_nodes, tree_depth, mean (3,) float32, bpts (n, 3) float32 and ids (n,)
+        int32 in bucket order, and per node cd (3: leaf), cut (float32, 0 at a leaf), cut_bits,
+        right_or_count (right child, or the leaf's point count), bucket_start (-1 at an inner node),
+        parent (-1 at the root), depth). rc is AICP_ERR_UNSUPPORTED / AICP_ERR_HIP for a build
+        that reports a depth error / another error bit; the outputs are filled all the same. Any
+        other failure raises."""
+        clouds = [np.ascontiguousarray(c, np.float32).reshape(-1, 3) for c in clouds]
+        counts = np.array([c.shape[0] for c in clouds], np.uint32)
+        P, total = counts.size, int(counts.sum(dtype=np.uint64))
+        pts = np.ascontiguousarray(np.concatenate(clouds, axis=0)) if P else np.zeros((0, 3), np.float32)
+        node_off, n_nodes = np.zeros(P, np.uint32), np.zeros(P, np.uint32)
+        depth, mean = np.zeros(P, np.int32), np.zeros((P, 3), np.float32)
+        nodes = np.zeros((2 * total + 2, 4), np.uint32)
+        bpts = np.zeros((total, 4), np.float32)
+        ctl = np.zeros(54, np.uint32)  # AICP_TEST_TREE_CTL_WORDS
+        u32p, ip = C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+        rc = lib.aicp_hip_test_tree(self.h, P, counts.ctypes.data_as(u32p), _fptr(pts), int(center), int(bucket),
+                                    node_off.ctypes.data_as(u32p), n_nodes.ctypes.data_as(u32p),
+                                    depth.ctypes.data_as(ip), _fptr(mean), nodes.ctypes.data_as(u32p), _fptr(bpts),
+                                    ctl.ctypes.data_as(u32p))
+        err = int(ctl[53])
+        if rc != AICP_OK and not (rc in (AICP_ERR_HIP, AICP_ERR_UNSUPPORTED) and err):
+            self.check(rc)
+        out = dict(rc=rc, error=self.last_error() if rc else "",
+                   ctl=dict(nseg=ctl[:50].copy(), n_small=int(ctl[50]), n_mid=int(ctl[51]), n_big=int(ctl[52]),
+                            error=err),
+                   trees=[])
+        off = 0
+        for p in range(P):
+            n = int(counts[p])
+            no = min(int(node_off[p]), nodes.shape[0])
+            rec = nodes[no:min(no + int(n_nodes[p]), nodes.shape[0])]
+            leaf = (rec[:, 1] & 3) == 3
+            b = bpts[off:off + n]
+            out["trees"].append(dict(
+                node_off=int(node_off[p]), n_nodes=int(n_nodes[p]), tree_depth=int(depth[p]), mean=mean[p].copy(),
+                bpts=b[:, :3].copy(), ids=b[:, 3].copy().view(np.int32),
+                cd=(rec[:, 1] & 3).astype(np.int32),
+                cut=np.where(leaf, np.uint32(0), rec[:, 0]).astype(np.uint32).view(np.float32),
+                cut_bits=rec[:, 0].copy(),
+                right_or_count=np.where(leaf, rec[:, 0], rec[:, 1] >> 2).astype(np.int32),
+                bucket_start=np.where(leaf, (rec[:, 1] >> 2).astype(np.int64), -1).astype(np.int32),
+                parent=rec[:, 2].copy().view(np.int32), depth=rec[:, 3].astype(np.int32)))
+            off += n
+        return out
 
     def crop_box(self, pts, mn, mx, origin):
         """getPointsInOrientedBox (filteringUtils.cpp:619-637) on device: returns (kept xyz in

@@ -2000,6 +2000,68 @@ int aicp_hip_test_step_p2p(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_
                        out_state, out_inlier, out_touched, out_dqdt, out_dirty);
 }
 
+// The matcher's batched build (matcher_trees: device_trees_begin / device_trees_end on tb[1] with
+// run_batch's plan, then device_trees_check) on given clouds, and everything it wrote, verbatim.
+// A build that reports through the control block (a depth beyond the device stack, a scan that
+// took its slow path) still ran to its end, so the outputs are downloaded whatever it reports.
+int aicp_hip_test_tree(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* counts, const float* pts, int32_t center,
+                       int32_t bucket, uint32_t* out_node_off, uint32_t* out_n_nodes, int32_t* out_depth,
+                       float* out_mean, uint32_t* out_nodes, float* out_bpts, uint32_t* out_ctl) {
+  static_assert(sizeof(TreeCtl) == 4 * AICP_TEST_TREE_CTL_WORDS, "aicp_hip.h: the control block's words");
+  if (!ctx || !counts || !pts || !out_node_off || !out_n_nodes || !out_depth || !out_mean || !out_nodes ||
+      !out_bpts || !out_ctl)
+    return AICP_ERR_INVALID;
+  if (n_refs == 0 || n_refs > (size_t)kMaxPairs || center < 0 || center > 1 || bucket < 1 || bucket > 4096)
+    return AICP_ERR_INVALID;
+  const size_t P = n_refs;
+  uint64_t total = 0, n_max = 0;
+  for (size_t p = 0; p < P; ++p) {
+    if (counts[p] == 0) return AICP_ERR_INVALID;
+    total += counts[p];
+    n_max = std::max<uint64_t>(n_max, counts[p]);
+  }
+  if (total >= (1ull << 28)) return AICP_ERR_INVALID;
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  ctx->refc.invalidate();  // (ctx->bpts / nodes are rewritten)
+  std::vector<PairDesc> desc(P, PairDesc{});
+  uint32_t off = 0;
+  for (size_t p = 0; p < P; ++p) {
+    desc[p].ref_off = off;
+    desc[p].n_ref = counts[p];
+    desc[p].ratio = 0.5f;
+    desc[p].ref_id = (int32_t)p;
+    ident4(desc[p].Tin);
+    off += counts[p];
+  }
+  std::vector<float> raw4(4 * (size_t)total);
+  pack_xyz4(pts, total, 12, raw4.data());
+  HIPC(ensure(ctx->ref1, total * 16));
+  HIPC(ensure(ctx->desc, P * sizeof(PairDesc)));
+  PairDesc* dDesc = ctx->desc.as<PairDesc>();
+  HIPC(hipMemcpy(ctx->ref1.p, raw4.data(), total * 16, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(dDesc, desc.data(), P * sizeof(PairDesc), hipMemcpyHostToDevice));
+  TreeBufs& T = ctx->tb[1];
+  int rc = device_trees_begin(T, ctx->err, s, P, total, dDesc, ctx->ref1.as<float4>(), center, bucket, ctx->bpts,
+                              ctx->nodes);
+  if (rc) return rc;
+  rc = device_trees_end(T, ctx->err, s, P, total, dDesc, bucket, ctx->bpts, ctx->nodes,
+                        plan_levels(n_max, T, ctx->opt.tree_plan));
+  HIPC(hipStreamSynchronize(s));
+  if (!rc) rc = device_trees_check(T, ctx->err);
+  HIPC(hipMemcpy(desc.data(), dDesc, P * sizeof(PairDesc), hipMemcpyDeviceToHost));
+  for (size_t p = 0; p < P; ++p) {
+    out_node_off[p] = desc[p].node_off;
+    out_n_nodes[p] = desc[p].n_nodes;
+    out_depth[p] = desc[p].tree_depth;
+    for (int k = 0; k < 3; ++k) out_mean[3 * p + k] = desc[p].mean[k];
+  }
+  HIPC(hipMemcpy(out_nodes, ctx->nodes.p, (2 * (size_t)total + 2) * 16, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(out_bpts, ctx->bpts.p, (size_t)total * 16, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(out_ctl, T.tw.ctl, sizeof(TreeCtl), hipMemcpyDeviceToHost));
+  return rc;
+}
+
 void aicp_hip_default_prefilter(aicp_prefilter_params* p) {
   if (!p) return;
   *p = aicp_prefilter_params{};

@@ -577,7 +577,12 @@ __global__ __launch_bounds__(kLbThreads) void k_tr_scan1(uint32_t total, const i
       [&](uint32_t i) -> uint32_t {
         if (i >= total) return 0u;
         const int s = segof[i];
-        return (s >= 0 && coord(W[i], seg[s].cd) < seg_cut(seg[s])) ? 1u : 0u;
+        if (s < 0) return 0u;
+        // the coordinate by its offset, one load whatever cd is: with coord()'s three-way choice the
+        // compiler's copy of this predicate in lookback_scan's slow path took the coordinate of a
+        // cd = 2 segment from the wrong address (a stalled build then scanned wrong counts)
+        const float v = reinterpret_cast<const float*>(W + i)[seg[s].cd];
+        return v < seg_cut(seg[s]) ? 1u : 0u;
       },
       X, st, ctl);
 }

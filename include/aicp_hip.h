@@ -828,6 +828,33 @@ int aicp_hip_test_step_p2p(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_
                            const uint32_t* touched /* each n_steps * total */, double* out_slab, float* out_T,
                            int32_t* out_state, float* out_inlier, uint64_t* out_touched, double* out_dqdt,
                            uint64_t* out_dirty);
+/* Test surface: the batched kd-tree build as a registration batch runs it for its matcher trees,
+ * on given clouds, and everything it wrote. pts: the n_refs clouds one after another, 3 floats per
+ * point, counts[r] points each; they are built as one batch (one launch sequence for all clouds),
+ * with the global levels planned from the largest cloud, the context's tree_plan / tree_lvl_min
+ * options and what the context's previous build used. center 0: trees on the points as given
+ * (mean 0); 1: the exact centroid of each cloud and trees on the centred points. bucket: the leaf
+ * size (1..4096).
+ * Per cloud: out_node_off (its first record in out_nodes), out_n_nodes, out_depth, out_mean (3).
+ * out_nodes: 2 * total + 2 records of 4 words, total = sum(counts): an inner node {cut (float
+ * bits), cd | right child << 2, parent, depth}, a leaf {point count, 3 | bucket start << 2, parent,
+ * depth}; child, parent (0xFFFFFFFF at the root) and bucket start are local to the cloud, the left
+ * child is the next record. Records past the last cloud's are not written. out_bpts: total rows
+ * (x, y, z, input id within the cloud as integer bits) in bucket order, cloud r's at its prefix
+ * offset. out_ctl: AICP_TEST_TREE_CTL_WORDS words of the build's control block: segments per global
+ * level [0, 50), then n_small (segments given to the subtree builders), n_mid (to the mid-size
+ * builder), n_big (segments above the mid-size limit left over by a plan that was too shallow) and
+ * the error bits (1: deeper than 47 levels, 16: a scan took its slow path).
+ * The outputs are filled whatever the build reports: AICP_ERR_UNSUPPORTED for a tree deeper than the
+ * device stack, AICP_ERR_HIP for any other error bit. Invalidates the context's reference cache.
+ * AICP_ERR_INVALID, before any device work: a null pointer, no cloud or more than 4096, a count of
+ * 0, total >= 2^28, center outside {0, 1}, bucket outside [1, 4096]. */
+#define AICP_TEST_TREE_CTL_WORDS 54
+int aicp_hip_test_tree(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* counts, const float* pts,
+                       int32_t center, int32_t bucket, uint32_t* out_node_off, uint32_t* out_n_nodes,
+                       int32_t* out_depth, float* out_mean /* 3 * n_refs */,
+                       uint32_t* out_nodes /* 4 * (2 * total + 2) */, float* out_bpts /* 4 * total */,
+                       uint32_t* out_ctl /* AICP_TEST_TREE_CTL_WORDS */);
 /* Test surface: the raw streams' ingest alone. rows: n rows of `stride` bytes (>= 12, a multiple of
  * 4), xyz first, uploaded as the raw streams upload them (at most 16 bytes: verbatim; wider: packed
  * on the host), then k_stream_ingest: out4[4 i ..] = (x, y, z, 1), moved by T (nullable, column-major
