@@ -232,7 +232,7 @@ struct NodeEvent {
 #ifndef AICP_SUBMAX
 #define AICP_SUBMAX 1024
 #endif
-constexpr int kSubMax = AICP_SUBMAX;  // largest segment one wave finishes in LDS (k_tr_subtree)
+constexpr int kSubMax = AICP_SUBMAX;
 struct SubSeg {
   uint32_t f, c;
   int32_t pair, depth;

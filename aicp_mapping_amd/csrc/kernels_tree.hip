@@ -182,9 +182,102 @@ __device__ __forceinline__ void split_dim(const float* mn, const float* mx, int&
   ideal = (a + b) / 2;
 }
 
-__device__ __forceinline__ float seg_cut(const TreeSeg& s) {
-  const float lo = ord_dec(s.lo), hi = ord_dec(s.hi);
-  return s.ideal < lo ? lo : (s.ideal > hi ? hi : s.ideal);
+// ---- the node rule (header comment), shared by every builder -----------------------------------
+// (lo, hi) = min and max of the points' cd coordinate; br1 / br2 = the two Hoare boundaries
+__device__ __forceinline__ float clamp_cut(float ideal, float lo, float hi) {
+  return ideal < lo ? lo : (ideal > hi ? hi : ideal);
+}
+
+__device__ __forceinline__ float seg_cut(const TreeSeg& s) { return clamp_cut(s.ideal, ord_dec(s.lo), ord_dec(s.hi)); }
+
+__device__ __forceinline__ uint32_t left_count(float ideal, float lo, float hi, uint32_t br1, uint32_t br2,
+                                               uint32_t count) {
+  if (ideal < lo) return 1;
+  if (ideal > hi) return count - 1;
+  if (br1 > count / 2) return br1;
+  if (br2 < count / 2) return br2;
+  return count / 2;
+}
+
+__device__ __forceinline__ NodeEvent inner_event(uint32_t f, uint32_t c, int depth, int pair, float cut, int cd,
+                                                 uint32_t left, uint32_t pf, int pdepth) {
+  NodeEvent e{};
+  e.f = f;
+  e.c = c;
+  e.depth = depth;
+  e.pair = pair;
+  e.cut_bits = __float_as_uint(cut);
+  e.cd = cd;
+  e.left = left;
+  e.parent_f = pf;
+  e.parent_depth = pdepth;
+  return e;
+}
+
+// A child's box: the parent's, with the child's side of cd at the cut (left child: mx[cd], right
+// child: mn[cd]). Selects, not a store through cd: a dynamic index would put the box in scratch.
+__device__ __forceinline__ void child_box(const float* mn, const float* mx, int side, int cd, float cut, float* cmn,
+                                          float* cmx) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    cmn[k] = (side && k == cd) ? cut : mn[k];
+    cmx[k] = (!side && k == cd) ? cut : mx[k];
+  }
+}
+
+__device__ __forceinline__ SubSeg sub_seg(uint32_t f, uint32_t c, int pair, int depth, const float* mn,
+                                          const float* mx, uint32_t pf, int pdepth) {
+  SubSeg g;
+  g.f = f;
+  g.c = c;
+  g.pair = pair;
+  g.depth = depth;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    g.mn[k] = mn[k];
+    g.mx[k] = mx[k];
+  }
+  g.parent_f = pf;
+  g.parent_depth = pdepth;
+  return g;
+}
+
+// A node of a segment's subtree in the builders that work on the segment's own copy of the points
+// (wave, block, mid-size): positions local to the segment, the parent's global.
+struct SubNode {
+  uint32_t lf, lc;  // local first / count
+  int32_t depth;
+  float mn[3], mx[3];
+  uint32_t pf;      // parent first (global)
+  int32_t pdepth;
+};
+
+__device__ __forceinline__ SubNode sub_root(const SubSeg& g) {
+  SubNode r;
+  r.lf = 0;
+  r.lc = g.c;
+  r.depth = g.depth;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    r.mn[k] = g.mn[k];
+    r.mx[k] = g.mx[k];
+  }
+  r.pf = g.parent_f;
+  r.pdepth = g.parent_depth;
+  return r;
+}
+
+// child `side` of nd (a node of the segment at global position gf) split at `left` points
+__device__ __forceinline__ SubNode sub_child(const SubNode& nd, int side, uint32_t left, int cd, float cut,
+                                             uint32_t gf) {
+  SubNode c;
+  c.lf = side ? nd.lf + left : nd.lf;
+  c.lc = side ? nd.lc - left : left;
+  c.depth = nd.depth + 1;
+  c.pf = gf + nd.lf;
+  c.pdepth = nd.depth;
+  child_box(nd.mn, nd.mx, side, cd, cut, c.mn, c.mx);
+  return c;
 }
 
 // ---- single-pass scan (decoupled look-back) ---------------------------------------------------
@@ -549,24 +642,13 @@ __global__ void k_tr_roots(int n_pairs, uint32_t total, const PairDesc* __restri
       emit_event(ev, valid, ecnt, total, leaf_event(d.ref_off, d.n_ref, 0, p, 0, -1));
     } else {
       const uint32_t si = atomicAdd(d.n_ref <= (uint32_t)kSubMax ? &ctl->n_small : &ctl->n_mid, 1u);
-      SubSeg& g = (d.n_ref <= (uint32_t)kSubMax ? subs : mids)[si];
-      g.f = d.ref_off;
-      g.c = d.n_ref;
-      g.pair = p;
-      g.depth = 0;
-      for (int k = 0; k < 3; ++k) {
-        g.mn[k] = s.mn[k];
-        g.mx[k] = s.mx[k];
-      }
-      g.parent_f = 0;
-      g.parent_depth = -1;
+      (d.n_ref <= (uint32_t)kSubMax ? subs : mids)[si] = sub_seg(d.ref_off, d.n_ref, p, 0, s.mn, s.mx, 0, -1);
     }
     s.count = 0;  // not split by the global levels
   }
   if (p == 0) ctl->nseg[0] = (uint32_t)n_pairs;
 }
 
-// ---- one global level ------------------------------------------------------------------------
 // ---- one global level ------------------------------------------------------------------------
 // X1 = exclusive scan of the pass-1 predicate (v < cut) over positions [0, total]
 __global__ __launch_bounds__(kLbThreads) void k_tr_scan1(uint32_t total, const int32_t* __restrict__ segof,
@@ -667,38 +749,19 @@ __device__ void tr_split_seg(uint32_t si, int level, int last, uint32_t total, T
   const float lo = ord_dec(g.lo), hi = ord_dec(g.hi);
   const float cut = seg_cut(g);
   const uint32_t br1 = g.br1, br2 = br1 + (X2[f + count] - X2[f]);
-  uint32_t left;
-  if (g.ideal < lo) left = 1;
-  else if (g.ideal > hi) left = count - 1;
-  else if (br1 > count / 2) left = br1;
-  else if (br2 < count / 2) left = br2;
-  else left = count / 2;
+  const uint32_t left = left_count(g.ideal, lo, hi, br1, br2, count);
+  // read once: the stores below may alias the segment, which would load them again per child
+  const int cd = g.cd, depth = g.depth, pair = g.pair, cdepth = depth + 1;
   g.br2 = br2;
   g.left = left;
-  NodeEvent e{};
-  e.f = f;
-  e.c = count;
-  e.depth = g.depth;
-  e.pair = g.pair;
-  e.cut_bits = __float_as_uint(cut);
-  e.cd = g.cd;
-  e.left = left;
-  e.parent_f = g.parent_f;
-  e.parent_depth = g.parent_depth;
-  emit_event(ev, valid, ecnt, total, e);
-  const int cdepth = g.depth + 1;
-  if (pair_depth[g.pair] < cdepth) atomicMax(&pair_depth[g.pair], cdepth);
+  emit_event(ev, valid, ecnt, total, inner_event(f, count, depth, pair, cut, cd, left, g.parent_f, g.parent_depth));
+  if (pair_depth[pair] < cdepth) atomicMax(&pair_depth[pair], cdepth);
   for (int side = 0; side < 2; ++side) {
     const uint32_t cf = side ? f + left : f, cc = side ? count - left : left;
     float mn[3], mx[3];
-    for (int k = 0; k < 3; ++k) {
-      mn[k] = g.mn[k];
-      mx[k] = g.mx[k];
-    }
-    if (side) mn[g.cd] = cut;
-    else mx[g.cd] = cut;
+    child_box(g.mn, g.mx, side, cd, cut, mn, mx);
     if (cc <= (uint32_t)bucket) {
-      emit_event(ev, valid, ecnt, total, leaf_event(cf, cc, cdepth, g.pair, f, g.depth));
+      emit_event(ev, valid, ecnt, total, leaf_event(cf, cc, cdepth, pair, f, depth));
       g.child[side] = -1;
       continue;
     }
@@ -711,17 +774,7 @@ __device__ void tr_split_seg(uint32_t si, int level, int last, uint32_t total, T
         g.child[side] = -1;
         continue;
       }
-      SubSeg& c = (mid ? mids : subs)[ni];
-      c.f = cf;
-      c.c = cc;
-      c.pair = g.pair;
-      c.depth = cdepth;
-      for (int k = 0; k < 3; ++k) {
-        c.mn[k] = mn[k];
-        c.mx[k] = mx[k];
-      }
-      c.parent_f = f;
-      c.parent_depth = g.depth;
+      (mid ? mids : subs)[ni] = sub_seg(cf, cc, pair, cdepth, mn, mx, f, depth);
       g.child[side] = -2;
       continue;
     }
@@ -734,10 +787,10 @@ __device__ void tr_split_seg(uint32_t si, int level, int last, uint32_t total, T
     TreeSeg& c = next[ni];
     c.first = cf;
     c.count = cc;
-    c.pair = g.pair;
+    c.pair = pair;
     c.depth = cdepth;
     c.parent_f = f;
-    c.parent_depth = g.depth;
+    c.parent_depth = depth;
     for (int k = 0; k < 3; ++k) {
       c.mn[k] = mn[k];
       c.mx[k] = mx[k];
@@ -852,14 +905,6 @@ __global__ __launch_bounds__(256) void k_tr_move2(uint32_t total, const int32_t*
 // One wave finishes the whole subtree of a segment of <= kSubMax points in LDS, depth first,
 // with the same node rule; the Hoare passes use ballot/popcount ranks and swap each
 // misplaced pair in place (the pairs are disjoint). All control flow is wave-uniform.
-struct SubNode {
-  uint32_t lf, lc;  // local first / count
-  int32_t depth;
-  float mn[3], mx[3];
-  uint32_t pf;      // parent first (global)
-  int32_t pdepth;
-};
-
 __device__ __forceinline__ uint32_t popc_lt(uint64_t m) {
   const int lane = threadIdx.x & 63;
   return (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
@@ -869,8 +914,22 @@ __device__ __forceinline__ uint32_t wave_sum_u(uint32_t v) {
   return wave_reduce_dpp(v, [](uint32_t a, uint32_t b) { return a + b; });
 }
 
+// What orders a wave's writes to the points and position arrays before its reads of them: the
+// workgroup barrier where the wave is the workgroup (k_tr_subtree, LDS or global memory), the
+// wavefront fence and wave barrier where the other waves of the block work on other nodes
+// (k_tr_subtree_blk, LDS).
+struct SyncBlock {
+  static __device__ __forceinline__ void sync() { __syncthreads(); }
+};
+struct SyncWave {
+  static __device__ __forceinline__ void sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+};
+
 // one Hoare pass over local [lo_b, end) with boundary br: elements with pred in [lo_b, br)
-template <class PosT, class Pred>
+template <class Sync, class PosT, class Pred>
 __device__ __forceinline__ void wave_hoare(float4* pts, PosT* posA, PosT* posB, uint32_t lo_b, uint32_t br,
                                            uint32_t end, Pred pred) {
   const int lane = threadIdx.x & 63;
@@ -886,7 +945,7 @@ __device__ __forceinline__ void wave_hoare(float4* pts, PosT* posA, PosT* posB, 
     ra += (uint32_t)__popcll(ma);
     rb += (uint32_t)__popcll(mb);
   }
-  __syncthreads();
+  Sync::sync();
   // the k-th misplaced element from the left swaps with the k-th misplaced from the right
   for (uint32_t k = lane; k < ra; k += 64) {
     const uint32_t a = posA[k], b = posB[rb - 1 - k];
@@ -894,7 +953,44 @@ __device__ __forceinline__ void wave_hoare(float4* pts, PosT* posA, PosT* posB, 
     pts[a] = pts[b];
     pts[b] = t;
   }
-  __syncthreads();
+  Sync::sync();
+}
+
+// What one wave does to one node above the bucket: the cut dimension and the cut from the points'
+// extent, the two partition counts, the Hoare pass on (v < cut), the tie pass on (v == cut) if any
+// point ties, and the left count. posA / posB = partition scratch for the node's points.
+struct WaveSplit {
+  int cd;
+  float cut;
+  uint32_t left;
+};
+template <class Sync, class PosT>
+__device__ __forceinline__ WaveSplit wave_split(const SubNode& nd, float4* pts, PosT* posA, PosT* posB) {
+  const int lane = threadIdx.x & 63;
+  int cd;
+  float ideal;
+  split_dim(nd.mn, nd.mx, cd, ideal);
+  const uint32_t a0 = nd.lf, end = nd.lf + nd.lc;
+  float mn = __builtin_inff(), mx = -__builtin_inff();
+  for (uint32_t j = a0 + lane; j < end; j += 64) {
+    const float v = coord(pts[j], cd);
+    mn = fminf(mn, v);
+    mx = fmaxf(mx, v);
+  }
+  const float lo = wave_min(mn), hi = wave_max(mx);
+  const float cut = clamp_cut(ideal, lo, hi);
+  uint32_t nl = 0, ne = 0;
+  for (uint32_t j = a0 + lane; j < end; j += 64) {
+    const float v = coord(pts[j], cd);
+    nl += v < cut ? 1u : 0u;
+    ne += v == cut ? 1u : 0u;
+  }
+  nl = wave_sum_u(nl);
+  ne = wave_sum_u(ne);
+  const uint32_t br1 = nl, br2 = nl + ne;
+  wave_hoare<Sync>(pts, posA, posB, a0, a0 + br1, end, [&](const float4& p) { return coord(p, cd) < cut; });
+  if (ne) wave_hoare<Sync>(pts, posA, posB, a0 + br1, a0 + br2, end, [&](const float4& p) { return coord(p, cd) == cut; });
+  return {cd, cut, left_count(ideal, lo, hi, br1, br2, nd.lc)};
 }
 
 // One segment's whole subtree, depth first, by one wave. pts = the segment's points (LDS copy,
@@ -905,16 +1001,7 @@ __device__ void subtree_build(const SubSeg& g, uint32_t total, float4* pts, PosT
                               NodeEvent* ev, uint8_t* valid, uint32_t* ecnt, int32_t* pair_depth, int bucket) {
   const int lane = threadIdx.x;
   const uint32_t gf = g.f;
-  SubNode nd;
-  nd.lf = 0;
-  nd.lc = g.c;
-  nd.depth = g.depth;
-  for (int k = 0; k < 3; ++k) {
-    nd.mn[k] = g.mn[k];
-    nd.mx[k] = g.mx[k];
-  }
-  nd.pf = g.parent_f;
-  nd.pdepth = g.parent_depth;
+  SubNode nd = sub_root(g);
   int sp = 0;
   int maxd = g.depth;
   for (;;) {
@@ -924,63 +1011,12 @@ __device__ void subtree_build(const SubSeg& g, uint32_t total, float4* pts, PosT
       nd = stk[--sp];
       continue;
     }
-    int cd;
-    float ideal;
-    split_dim(nd.mn, nd.mx, cd, ideal);
-    const uint32_t a0 = nd.lf, end = nd.lf + nd.lc;
-    float mn = __builtin_inff(), mx = -__builtin_inff();
-    for (uint32_t j = a0 + lane; j < end; j += 64) {
-      const float v = coord(pts[j], cd);
-      mn = fminf(mn, v);
-      mx = fmaxf(mx, v);
-    }
-    const float lo = wave_min(mn), hi = wave_max(mx);
-    const float cut = ideal < lo ? lo : (ideal > hi ? hi : ideal);
-    uint32_t nl = 0, ne = 0;
-    for (uint32_t j = a0 + lane; j < end; j += 64) {
-      const float v = coord(pts[j], cd);
-      nl += v < cut ? 1u : 0u;
-      ne += v == cut ? 1u : 0u;
-    }
-    nl = wave_sum_u(nl);
-    ne = wave_sum_u(ne);
-    const uint32_t br1 = nl, br2 = nl + ne, count = nd.lc;
-    wave_hoare(pts, posA, posB, a0, a0 + br1, end, [&](const float4& p) { return coord(p, cd) < cut; });
-    if (ne) wave_hoare(pts, posA, posB, a0 + br1, a0 + br2, end, [&](const float4& p) { return coord(p, cd) == cut; });
-    uint32_t left;
-    if (ideal < lo) left = 1;
-    else if (ideal > hi) left = count - 1;
-    else if (br1 > count / 2) left = br1;
-    else if (br2 < count / 2) left = br2;
-    else left = count / 2;
-    if (lane == 0) {
-      NodeEvent e{};
-      e.f = gf + nd.lf;
-      e.c = count;
-      e.depth = nd.depth;
-      e.pair = g.pair;
-      e.cut_bits = __float_as_uint(cut);
-      e.cd = cd;
-      e.left = left;
-      e.parent_f = nd.pf;
-      e.parent_depth = nd.pdepth;
-      emit_event(ev, valid, ecnt, total, e);
-    }
-    SubNode L, R;
-    L.lf = nd.lf;
-    L.lc = left;
-    R.lf = nd.lf + left;
-    R.lc = count - left;
-    L.depth = R.depth = nd.depth + 1;
-    L.pf = R.pf = gf + nd.lf;
-    L.pdepth = R.pdepth = nd.depth;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {  // selects, not a dynamic store (keeps the node in registers)
-      L.mn[k] = nd.mn[k];
-      R.mx[k] = nd.mx[k];
-      L.mx[k] = k == cd ? cut : nd.mx[k];
-      R.mn[k] = k == cd ? cut : nd.mn[k];
-    }
+    const WaveSplit s = wave_split<SyncBlock>(nd, pts, posA, posB);
+    if (lane == 0)
+      emit_event(ev, valid, ecnt, total,
+                 inner_event(gf + nd.lf, nd.lc, nd.depth, g.pair, s.cut, s.cd, s.left, nd.pf, nd.pdepth));
+    // (the nodes stay in registers: child_box)
+    const SubNode L = sub_child(nd, 0, s.left, s.cd, s.cut, gf), R = sub_child(nd, 1, s.left, s.cd, s.cut, gf);
     if (L.depth > maxd) maxd = L.depth;
     if (sp >= kFarStack) break;  // deeper than the device stack: k_tr_emit reports it
     if (lane == 0) stk[sp] = R;
@@ -1007,41 +1043,6 @@ __device__ void subtree_build(const SubSeg& g, uint32_t total, float4* pts, PosT
 constexpr int kSubWaves = AICP_SUBWAVES;
 constexpr int kSubLevelCap = 256;  // nodes above bucket per level (<= kSubMax / (bucket + 1))
 
-__device__ __forceinline__ void wave_sync_lds() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// wave_hoare with wave-local synchronisation (the other waves of the block work on other nodes)
-__device__ __forceinline__ void wave_hoare_w(float4* pts, uint16_t* posA, uint16_t* posB, uint32_t lo_b, uint32_t br,
-                                             uint32_t end, int cd, float cut, bool eq) {
-  const int lane = threadIdx.x & 63;
-  uint32_t ra = 0, rb = 0;
-  for (uint32_t jb = lo_b; jb < end; jb += 64) {
-    const uint32_t j = jb + lane;
-    const bool ok = j < end;
-    bool pr = false;
-    if (ok) {
-      const float v = coord(pts[j], cd);
-      pr = eq ? (v == cut) : (v < cut);
-    }
-    const bool ml = ok && j < br && !pr, mr = ok && j >= br && pr;
-    const uint64_t ma = __ballot(ml), mb = __ballot(mr);
-    if (ml) posA[ra + popc_lt(ma)] = (uint16_t)j;
-    if (mr) posB[rb + popc_lt(mb)] = (uint16_t)j;
-    ra += (uint32_t)__popcll(ma);
-    rb += (uint32_t)__popcll(mb);
-  }
-  wave_sync_lds();
-  for (uint32_t k = lane; k < ra; k += 64) {
-    const uint32_t a = posA[k], b = posB[rb - 1 - k];
-    const float4 t = pts[a];
-    pts[a] = pts[b];
-    pts[b] = t;
-  }
-  wave_sync_lds();
-}
-
 __global__ __launch_bounds__(64 * kSubWaves) void k_tr_subtree_blk(uint32_t total, const TreeCtl* __restrict__ ctl,
                                                                    const SubSeg* __restrict__ subs,
                                                                    const float4* __restrict__ W,
@@ -1062,16 +1063,7 @@ __global__ __launch_bounds__(64 * kSubWaves) void k_tr_subtree_blk(uint32_t tota
     const uint32_t gf = g.f;
     for (uint32_t j = threadIdx.x; j < g.c; j += blockDim.x) pts[j] = W[gf + j];
     if (threadIdx.x == 0) {
-      SubNode& r = lvl[0][0];
-      r.lf = 0;
-      r.lc = g.c;
-      r.depth = g.depth;
-      for (int k = 0; k < 3; ++k) {
-        r.mn[k] = g.mn[k];
-        r.mx[k] = g.mx[k];
-      }
-      r.pf = g.parent_f;
-      r.pdepth = g.parent_depth;
+      lvl[0][0] = sub_root(g);
       n_lvl[0] = 1;
       n_lvl[1] = 0;
       maxd = g.depth;
@@ -1083,60 +1075,13 @@ __global__ __launch_bounds__(64 * kSubWaves) void k_tr_subtree_blk(uint32_t tota
       if (n == 0) break;
       for (uint32_t i = wv; i < n; i += kSubWaves) {
         const SubNode nd = lvl[cur][i];  // count > bucket (leaves are emitted when created)
-        int cd;
-        float ideal;
-        split_dim(nd.mn, nd.mx, cd, ideal);
-        const uint32_t a0 = nd.lf, end = nd.lf + nd.lc;
-        float mn = __builtin_inff(), mx = -__builtin_inff();
-        for (uint32_t j = a0 + lane; j < end; j += 64) {
-          const float v = coord(pts[j], cd);
-          mn = fminf(mn, v);
-          mx = fmaxf(mx, v);
-        }
-        const float lo = wave_min(mn), hi = wave_max(mx);
-        const float cut = ideal < lo ? lo : (ideal > hi ? hi : ideal);
-        uint32_t nl = 0, ne = 0;
-        for (uint32_t j = a0 + lane; j < end; j += 64) {
-          const float v = coord(pts[j], cd);
-          nl += v < cut ? 1u : 0u;
-          ne += v == cut ? 1u : 0u;
-        }
-        nl = wave_sum_u(nl);
-        ne = wave_sum_u(ne);
-        const uint32_t br1 = nl, br2 = nl + ne, count = nd.lc;
-        wave_hoare_w(pts, posA[wv], posB[wv], a0, a0 + br1, end, cd, cut, false);
-        if (ne) wave_hoare_w(pts, posA[wv], posB[wv], a0 + br1, a0 + br2, end, cd, cut, true);
-        uint32_t left;
-        if (ideal < lo) left = 1;
-        else if (ideal > hi) left = count - 1;
-        else if (br1 > count / 2) left = br1;
-        else if (br2 < count / 2) left = br2;
-        else left = count / 2;
+        const WaveSplit s = wave_split<SyncWave>(nd, pts, posA[wv], posB[wv]);
         if (lane == 0) {
-          NodeEvent e{};
-          e.f = gf + nd.lf;
-          e.c = count;
-          e.depth = nd.depth;
-          e.pair = g.pair;
-          e.cut_bits = __float_as_uint(cut);
-          e.cd = cd;
-          e.left = left;
-          e.parent_f = nd.pf;
-          e.parent_depth = nd.pdepth;
-          emit_event(ev, valid, ecnt, total, e);
+          emit_event(ev, valid, ecnt, total,
+                     inner_event(gf + nd.lf, nd.lc, nd.depth, g.pair, s.cut, s.cd, s.left, nd.pf, nd.pdepth));
           atomicMax(&maxd, nd.depth + 1);
           for (int side = 0; side < 2; ++side) {
-            SubNode c;
-            c.lf = side ? nd.lf + left : nd.lf;
-            c.lc = side ? count - left : left;
-            c.depth = nd.depth + 1;
-            c.pf = gf + nd.lf;
-            c.pdepth = nd.depth;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-              c.mn[k] = (side && k == cd) ? cut : nd.mn[k];
-              c.mx[k] = (!side && k == cd) ? cut : nd.mx[k];
-            }
+            const SubNode c = sub_child(nd, side, s.left, s.cd, s.cut, gf);
             if (c.lc <= (uint32_t)bucket) {
               emit_event(ev, valid, ecnt, total, leaf_event(gf + c.lf, c.lc, c.depth, g.pair, c.pf, c.pdepth));
             } else {
@@ -1345,7 +1290,7 @@ __global__ __launch_bounds__(kLvlThreads, 8) void k_tr_subtree_lvl(uint32_t tota
         cut[u] = 0.f;
         if (key[u] >= 0) {
           const float lo = ord_dec(nlo[key[u]]), hi = ord_dec(nhi[key[u]]), id = nideal[key[u]];
-          cut[u] = id < lo ? lo : (id > hi ? hi : id);
+          cut[u] = clamp_cut(id, lo, hi);
           x = v[u] < cut[u] ? 1u : (v[u] == cut[u] ? 0x10000u : 0u);
         }
         if (wave_seg_sum(key[u], x) && key[u] >= 0 && x) {
@@ -1400,29 +1345,14 @@ __global__ __launch_bounds__(kLvlThreads, 8) void k_tr_subtree_lvl(uint32_t tota
       if ((uint32_t)t < nn) {
         const uint32_t count = N.c[t], nl = ncnt[t] & 0xFFFFu, ne = ncnt[t] >> 16;
         const float lo = ord_dec(nlo[t]), hi = ord_dec(nhi[t]), ideal = nideal[t];
-        const float ct = ideal < lo ? lo : (ideal > hi ? hi : ideal);
+        const float ct = clamp_cut(ideal, lo, hi);
         const int cd = ncd[t];
-        const uint32_t br1 = nl, br2 = nl + ne;
-        uint32_t left;
-        if (ideal < lo) left = 1;
-        else if (ideal > hi) left = count - 1;
-        else if (br1 > count / 2) left = br1;
-        else if (br2 < count / 2) left = br2;
-        else left = count / 2;
+        const uint32_t left = left_count(ideal, lo, hi, nl, nl + ne, count);
         nleft[t] = (uint16_t)left;
         const uint32_t f0 = N.f[t];
         const int pdepth = depth == g.depth ? g.parent_depth : depth - 1;
-        NodeEvent e{};
-        e.f = gf + f0;
-        e.c = count;
-        e.depth = depth;
-        e.pair = g.pair;
-        e.cut_bits = __float_as_uint(ct);
-        e.cd = cd;
-        e.left = left;
-        e.parent_f = N.pf[t];
-        e.parent_depth = pdepth;
-        emit_event(ev, valid, ecnt, total, e);
+        emit_event(ev, valid, ecnt, total, inner_event(gf + f0, count, depth, g.pair, ct, cd, left, N.pf[t], pdepth));
+        const float mn[3] = {N.mn[0][t], N.mn[1][t], N.mn[2][t]}, mx[3] = {N.mx[0][t], N.mx[1][t], N.mx[2][t]};
         for (int side = 0; side < 2; ++side) {
           const uint32_t cf = side ? f0 + left : f0, cc = side ? count - left : left;
           if (cc <= (uint32_t)bucket) {
@@ -1432,10 +1362,12 @@ __global__ __launch_bounds__(kLvlThreads, 8) void k_tr_subtree_lvl(uint32_t tota
             const uint32_t q = atomicAdd(&n_next, 1u);
             M.f[q] = (uint16_t)cf;
             M.c[q] = (uint16_t)cc;
+            float cmn[3], cmx[3];
+            child_box(mn, mx, side, cd, ct, cmn, cmx);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-              M.mn[k][q] = (side && k == cd) ? ct : N.mn[k][t];
-              M.mx[k][q] = (!side && k == cd) ? ct : N.mx[k][t];
+              M.mn[k][q] = cmn[k];
+              M.mx[k][q] = cmx[k];
             }
             M.pf[q] = gf + f0;
             nch[side][t] = (uint16_t)q;
@@ -1587,16 +1519,7 @@ __global__ __launch_bounds__(kMidThreads) void k_tr_mid(uint32_t total, TreeCtl*
 #endif
     for (uint32_t j = t; j < g.c; j += kMidThreads) pts[j] = W[gf + j];
     if (t == 0) {
-      SubNode& r = stk[0];
-      r.lf = 0;
-      r.lc = g.c;
-      r.depth = g.depth;
-      for (int k = 0; k < 3; ++k) {
-        r.mn[k] = g.mn[k];
-        r.mx[k] = g.mx[k];
-      }
-      r.pf = g.parent_f;
-      r.pdepth = g.parent_depth;
+      stk[0] = sub_root(g);
       sp_s = 1;
       nout_s = 0;
       maxd_s = g.depth;
@@ -1638,7 +1561,7 @@ __global__ __launch_bounds__(kMidThreads) void k_tr_mid(uint32_t total, TreeCtl*
         lo = fminf(lo, sMn[i]);
         hi = fmaxf(hi, sMx[i]);
       }
-      const float cut = ideal < lo ? lo : (ideal > hi ? hi : ideal);
+      const float cut = clamp_cut(ideal, lo, hi);
       uint32_t nle = 0;
       for (uint32_t j = a0 + t; j < end; j += kMidThreads) {
         const float v = coord(pts[j], cd);
@@ -1654,37 +1577,14 @@ __global__ __launch_bounds__(kMidThreads) void k_tr_mid(uint32_t total, TreeCtl*
       const uint32_t br1 = nl, br2 = nl + ne;
       mid_hoare(pts, posA, posB, sAB, a0, a0 + br1, end, cd, cut, false);
       if (ne) mid_hoare(pts, posA, posB, sAB, a0 + br1, a0 + br2, end, cd, cut, true);
-      uint32_t left;
-      if (ideal < lo) left = 1;
-      else if (ideal > hi) left = count - 1;
-      else if (br1 > count / 2) left = br1;
-      else if (br2 < count / 2) left = br2;
-      else left = count / 2;
+      const uint32_t left = left_count(ideal, lo, hi, br1, br2, count);
       if (t == 0) {
-        NodeEvent e{};
-        e.f = gf + nd.lf;
-        e.c = count;
-        e.depth = nd.depth;
-        e.pair = g.pair;
-        e.cut_bits = __float_as_uint(cut);
-        e.cd = cd;
-        e.left = left;
-        e.parent_f = nd.pf;
-        e.parent_depth = nd.pdepth;
-        emit_event(ev, valid, ecnt, total, e);
+        emit_event(ev, valid, ecnt, total,
+                   inner_event(gf + nd.lf, count, nd.depth, g.pair, cut, cd, left, nd.pf, nd.pdepth));
         if (nd.depth + 1 > maxd_s) maxd_s = nd.depth + 1;
         int spn = sp - 1;
         for (int side = 0; side < 2; ++side) {
-          SubNode c;
-          c.lf = side ? nd.lf + left : nd.lf;
-          c.lc = side ? count - left : left;
-          c.depth = nd.depth + 1;
-          c.pf = gf + nd.lf;
-          c.pdepth = nd.depth;
-          for (int k = 0; k < 3; ++k) {
-            c.mn[k] = (side && k == cd) ? cut : nd.mn[k];
-            c.mx[k] = (!side && k == cd) ? cut : nd.mx[k];
-          }
+          const SubNode c = sub_child(nd, side, left, cd, cut, gf);
           if (c.lc <= (uint32_t)bucket) {
             emit_event(ev, valid, ecnt, total, leaf_event(gf + c.lf, c.lc, c.depth, g.pair, c.pf, c.pdepth));
           } else if (c.lc <= (uint32_t)kSubMax) {
@@ -1694,17 +1594,7 @@ __global__ __launch_bounds__(kMidThreads) void k_tr_mid(uint32_t total, TreeCtl*
               atomicOr(&ctl->error, 8);
               continue;
             }
-            SubSeg& o = outq[nout_s++];
-            o.f = gf + c.lf;
-            o.c = c.lc;
-            o.pair = g.pair;
-            o.depth = c.depth;
-            for (int k = 0; k < 3; ++k) {
-              o.mn[k] = c.mn[k];
-              o.mx[k] = c.mx[k];
-            }
-            o.parent_f = c.pf;
-            o.parent_depth = c.pdepth;
+            outq[nout_s++] = sub_seg(gf + c.lf, c.lc, g.pair, c.depth, c.mn, c.mx, c.pf, c.pdepth);
           } else if (spn < kMidStack) {
             stk[spn++] = c;
           } else {
@@ -1941,8 +1831,14 @@ __device__ __forceinline__ uint32_t tl_slot(const uint4& a) {
   return (a.y & 3u) == kLeaf ? (a.x << 28) | (a.y >> 2) : a.x;
 }
 
+// treelets used per reference within its allotment and addressable by the 26-bit base field;
+// leaf slots need count < 16 and bucket starts < 2^28
 __device__ __forceinline__ void tl_check_ref(const PairDesc& r, const uint32_t* __restrict__ rank, int bucket,
-                                             TreeCtl* ctl);
+                                             TreeCtl* ctl) {
+  const uint32_t used = 1u + 4u * (rank[r.node_off + r.n_nodes] - rank[r.node_off]);
+  if (used > r.tl_cap || used >= (1u << 26) || bucket > 15 || r.n_ref >= (1u << 28)) atomicOr(&ctl->error, 4);
+}
+
 // the records; threads < n_refs also run k_tl_check's test for reference g
 __global__ __launch_bounds__(256) void k_tl_build(int n_refs, uint32_t cap, const PairDesc* __restrict__ rd,
                                                   const uint4* __restrict__ nodes, const uint32_t* __restrict__ rank,
@@ -1990,14 +1886,6 @@ __global__ __launch_bounds__(256) void k_tl_build(int n_refs, uint32_t cap, cons
   tl[r.tl_off + id] = rec;
 }
 
-// treelets used per reference within its allotment and addressable by the 26-bit base field;
-// leaf slots need count < 16 and bucket starts < 2^28
-__device__ __forceinline__ void tl_check_ref(const PairDesc& r, const uint32_t* __restrict__ rank, int bucket,
-                                             TreeCtl* ctl) {
-  const uint32_t used = 1u + 4u * (rank[r.node_off + r.n_nodes] - rank[r.node_off]);
-  if (used > r.tl_cap || used >= (1u << 26) || bucket > 15 || r.n_ref >= (1u << 28)) atomicOr(&ctl->error, 4);
-}
-
 hipError_t launch_treelets(hipStream_t s, int n_refs, uint32_t cap, const PairDesc* rd, const uint4* nodes,
                            int bucket, uint32_t* rank, uint4* tl, uint2* link, const TreeWork& w) {
   if (n_refs <= 0 || cap == 0) return hipSuccess;
@@ -2033,10 +1921,6 @@ void launch_pairs_degenerate_part(hipStream_t s, int n_pairs, const PairDesc* pd
 size_t lb_stride_words(uint32_t total) { return lb_words(total + 2); }
 uint32_t tree_mid_max() { return (uint32_t)kMidMax; }
 size_t tree_sum_tiles(size_t n) { return tiles_of(n); }
-// k_tr_subtree_lvl from this many points of a build (C5: 61 M); smaller builds are latency-bound
-// and keep k_tr_subtree_blk (r04: C2 2620 against 2479 clouds/s with the level builder).
-// aicp_hip_options::tree_lvl_min sets it (TreeWork::lvl_min; the equivalence test builds small
-// trees both ways).
 hipError_t set_lb_force_stall(int on) {
   const int v = on ? 1 : 0;
   return hipMemcpyToSymbol(HIP_SYMBOL(g_lb_force_stall), &v, sizeof(v));
@@ -2097,7 +1981,11 @@ hipError_t launch_tree_level(hipStream_t s, int level, uint32_t total, const Tre
 }
 
 // grid: an upper bound of the small-segment count (<= total / (bucket + 1) + pairs), capped;
-// the kernel strides over the device-side count
+// the kernel strides over the device-side count.
+// k_tr_subtree_lvl from TreeWork::lvl_min points of a build (C5: 61 M); smaller builds are
+// latency-bound and keep k_tr_subtree_blk (r04: C2 2620 against 2479 clouds/s with the level
+// builder). aicp_hip_options::tree_lvl_min sets it (the equivalence test builds small trees both
+// ways).
 hipError_t launch_tree_subtrees(hipStream_t s, uint32_t total, const TreeWork& w, float4* bpts, int bucket) {
   const size_t bound = std::min<size_t>(w.max_seg, (size_t)total / (size_t)(bucket + 1) + (size_t)w.n_pairs + 1);
   const bool blk = bucket >= 4;  // level widths fit kSubLevelCap

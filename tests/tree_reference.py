@@ -407,6 +407,15 @@ def _cases():
                     path=("deep_levels", "no_big"), cond=(("depth", 40, 47),)))
     # more than 64 scan tiles: the look-back goes round its window
     out.append(case("long_lookback", ("two", 70000, 51), path=("levels",)))
+    # ties (the second Hoare pass, on v == cut) where only k_tr_mid and the block builder met them:
+    # the level builder's any_eq pass, the wave builder in place in global memory (32-bit
+    # positions) and the global levels' pass-2 partner search (k_tr_move2)
+    out.append(case("lvl_builder_lattice", ("lattice", 5000, 33), opts=dict(tree_lvl_min=1), path=("root_mid",),
+                    cond=(("depth", 16, 16),)))
+    out.append(case("lvl_builder_identical", ("identical", 3000), opts=dict(tree_lvl_min=1), path=("root_mid",),
+                    cond=(("depth", 9, 9),)))
+    out.append(case("plan_1_lattice", ("lattice", 20000, 33), opts=dict(tree_plan=1), path=("big",)))
+    out.append(case("levels_lattice", ("lattice", 20000, 33), path=("levels",), cond=(("depth", 18, 18),)))
     return out
 
 

@@ -92,7 +92,7 @@ def main():
                     state += " (allowed)" if allowed else ""
             else:
                 state = "only in OLD" if sym in old else "only in NEW"
-            print(f"  {state:12s} {name.split('(')[0][:160]}")
+            print(f"  {state:12s} {name.replace('(anonymous namespace)::', '').split('(')[0][:160]}")
             if state.endswith("(allowed)"):
                 for side, k in (("OLD", old[sym]), ("NEW", new[sym])):
                     print(f"    {side} " + "  ".join(k[1] or []))
