@@ -53,6 +53,8 @@ EXPORTS = [
     "aicp_hip_built_map_window", "aicp_hip_built_map_sequence_run", "aicp_hip_last_built_map_timing",
     "aicp_hip_map_sequence_run_raw", "aicp_hip_built_map_sequence_run_raw", "aicp_hip_test_ingest",
     "aicp_hip_test_tree",
+    "aicp_hip_svm_load", "aicp_hip_svm_free", "aicp_hip_svm_info", "aicp_hip_svm_predict", "aicp_hip_pipeline",
+    "aicp_hip_sequence_run_risk",
 ]
 
 
@@ -72,7 +74,9 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_test_step_p2p",  # the point-to-point chains
            "aicp_hip_map_sequence_run_raw", "aicp_hip_built_map_sequence_run_raw",
            "aicp_hip_test_ingest",  # raw readings in the two map streams
-           "aicp_hip_test_tree"}  # the kd-tree build, node for node
+           "aicp_hip_test_tree",  # the kd-tree build, node for node
+           "aicp_hip_svm_load", "aicp_hip_svm_free", "aicp_hip_svm_info", "aicp_hip_svm_predict",
+           "aicp_hip_pipeline", "aicp_hip_sequence_run_risk"}  # the classifier and the risk gate
 
 
 class IcpConfig(C.Structure):
@@ -257,6 +261,39 @@ class SequenceResult(C.Structure):
         d["corrected_origin"] = [float(x) for x in self.corrected_origin]
         d["icp"] = self.icp.as_dict()
         return d
+
+
+class SvmInfo(C.Structure):
+    """aicp_svm_info (include/aicp_hip.h)."""
+    _fields_ = [
+        ("format", C.c_int32),
+        ("var_count", C.c_int32),
+        ("class_count", C.c_int32),
+        ("sv_total", C.c_int32),
+        ("sv_count", C.c_int32),
+        ("has_index", C.c_int32),
+        ("degree", C.c_double),
+        ("gamma", C.c_double),
+        ("coef0", C.c_double),
+        ("rho", C.c_double),
+    ]
+
+
+class PipelineRecord(C.Structure):
+    """aicp_pipeline_record (include/aicp_hip.h)."""
+    _fields_ = [
+        ("n_read", C.c_uint64),
+        ("fov_overlap", C.c_float),
+        ("octree_overlap", C.c_float),
+        ("alignability", C.c_float),
+        ("raw", C.c_float),
+        ("risk", C.c_double),
+        ("registered", C.c_int32),
+        ("trimmed_ratio", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Options(C.Structure):
@@ -530,6 +567,17 @@ def _load():
     if hasattr(L, "aicp_hip_test_tree"):
         u32p = C.POINTER(C.c_uint32)
         L.aicp_hip_test_tree.argtypes = [vp, sz, u32p, fp, C.c_int32, C.c_int32, u32p, u32p, ip, fp, u32p, fp, u32p]
+    if hasattr(L, "aicp_hip_svm_load"):
+        dp, clp, pfp = C.POINTER(C.c_double), C.POINTER(Cloud), C.POINTER(PrefilterParams)
+        rpp, prp = C.POINTER(RiskParams), C.POINTER(PipelineRecord)
+        L.aicp_hip_svm_load.argtypes = [C.c_char_p, C.POINTER(vp)]
+        L.aicp_hip_svm_free.argtypes = [vp]
+        L.aicp_hip_svm_free.restype = None
+        L.aicp_hip_svm_info.argtypes = [vp, C.POINTER(SvmInfo), fp, dp, ip]
+        L.aicp_hip_svm_predict.argtypes = [vp, vp, fp, sz, fp, dp]
+        L.aicp_hip_pipeline.argtypes = [vp, cfgp, rpp, vp, C.c_double, pp, dp, dp, C.c_double, fp, prp, stp]
+        L.aicp_hip_sequence_run_risk.argtypes = [vp, cfgp, C.POINTER(SequenceParams), pfp, rpp, vp, C.c_double, clp, dp,
+                                                 clp, dp, sz, fp, C.POINTER(SequenceResult), prp, szp]
     return L
 
 
@@ -783,6 +831,42 @@ def _pose16(pose):
 
 def _dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+class SvmModel:
+    """One aicp_hip_svm: the classifier's OpenCV model XML, parsed on the host (no device needed).
+    Raises AicpError with AICP_ERR_UNSUPPORTED / AICP_ERR_INVALID as aicp_hip_svm_load returns them."""
+
+    def __init__(self, path: str):
+        self.h = None
+        h = C.c_void_p()
+        rc = lib.aicp_hip_svm_load(os.fsencode(path), C.byref(h))
+        if rc != AICP_OK:
+            raise AicpError(rc, f"aicp_hip_svm_load({path}) failed")
+        self.h = h
+
+    def info(self) -> dict:
+        """aicp_hip_svm_info: the scalar fields, support_vectors (sv_total, 2) float32, alpha
+        float64[sv_count], index int32[sv_count]."""
+        i = SvmInfo()
+        rc = lib.aicp_hip_svm_info(self.h, C.byref(i), None, None, None)
+        if rc != AICP_OK:
+            raise AicpError(rc, "aicp_hip_svm_info failed")
+        sv = np.zeros((i.sv_total, 2), np.float32)
+        alpha = np.zeros(i.sv_count, np.float64)
+        index = np.zeros(i.sv_count, np.int32)
+        lib.aicp_hip_svm_info(self.h, C.byref(i), _fptr(sv), _dptr(alpha), index.ctypes.data_as(C.POINTER(C.c_int32)))
+        d = {k: getattr(i, k) for k, _ in SvmInfo._fields_}
+        d.update(support_vectors=sv, alpha=alpha, index=index)
+        return d
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.aicp_hip_svm_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
 
 
 # aicp_hip_options overrides every new Context starts with (bench.py --opt k=v); empty: the
@@ -1314,6 +1398,63 @@ class Context:
         st = RiskStats()
         self.check(lib.aicp_hip_last_risk_stats(self.h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in RiskStats._fields_}
+
+    # -------------------------------------------------------------- classifier and gate -----
+    def svm_predict(self, model: "SvmModel", samples):
+        """aicp_hip_svm_predict: samples (n, 2) = (overlap percent, alignability) in one launch.
+        Returns (raw float32[n], risk float64[n])."""
+        x = np.ascontiguousarray(np.asarray(samples, np.float32).reshape(-1, 2))
+        n = x.shape[0]
+        raw, risk = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float64)
+        self.check(lib.aicp_hip_svm_predict(self.h, model.h, _fptr(x), n, _fptr(raw), _dptr(risk)))
+        return raw[:n], risk[:n]
+
+    def pipeline(self, model: "SvmModel", threshold, ref, read, ref_pose, read_pose, cfg=None, risk_params=None,
+                 resolution=0.2, init_T=None):
+        """aicp_hip_pipeline (runAicpPipeline with failure_prediction_mode) for one pair of
+        pre-filtered clouds: returns (T 4x4 row-major, record dict, stats dict)."""
+        cfg = cfg or default_config()
+        prm = risk_params or default_risk_params()
+        p, keep = make_pair(ref, read, init_T=init_T)
+        pa, pb = _pose16(ref_pose), _pose16(read_pose)
+        outT = np.zeros(16, np.float32)
+        rec, st = PipelineRecord(), IcpStats()
+        self.check(lib.aicp_hip_pipeline(self.h, C.byref(cfg), C.byref(prm), model.h, float(threshold), C.byref(p),
+                                         _dptr(pa), _dptr(pb), float(resolution), _fptr(outT), C.byref(rec),
+                                         C.byref(st)))
+        return outT.reshape(4, 4).T.copy(), rec.as_dict(), st.as_dict()
+
+    def sequence_run_risk(self, model: "SvmModel", threshold, first, first_pose, readings, poses, cfg=None,
+                          params=None, prefilter=None, risk_params=None, raise_on_error=True):
+        """aicp_hip_sequence_run_risk: App's stream from RAW clouds with the risk gate. poses: 4x4
+        row-major prior poses. Returns (T[n, 4, 4], list of result dicts, list of record dicts,
+        n_done, rc)."""
+        cfg = cfg or default_config()
+        prm = params or default_sequence_params()
+        pf = prefilter or default_prefilter()
+        rp = risk_params or default_risk_params()
+        n = len(readings)
+        fc, keep0 = make_cloud(first, np.asarray(first_pose, np.float64)[:3, 3])
+        arr = (Cloud * max(n, 1))()
+        keep = [keep0]
+        for i, r in enumerate(readings):
+            c, k = make_cloud(r, np.asarray(poses[i], np.float64)[:3, 3])
+            arr[i] = c
+            keep.append(k)
+        p0 = _pose16(first_pose)
+        pn = np.ascontiguousarray(np.concatenate([_pose16(P) for P in poses]) if n else np.zeros(16))
+        outT = np.zeros((max(n, 1), 16), np.float32)
+        res = (SequenceResult * max(n, 1))()
+        rec = (PipelineRecord * max(n, 1))()
+        done = C.c_size_t(0)
+        rc = lib.aicp_hip_sequence_run_risk(self.h, C.byref(cfg), C.byref(prm), C.byref(pf), C.byref(rp), model.h,
+                                            float(threshold), C.byref(fc), _dptr(p0), arr, _dptr(pn), n, _fptr(outT),
+                                            res, rec, C.byref(done))
+        if raise_on_error and rc != AICP_OK:
+            self.check(rc)
+        T = outT[:n].reshape(-1, 4, 4).transpose(0, 2, 1).copy()
+        k = done.value
+        return T, [res[i].as_dict() for i in range(k)], [rec[i].as_dict() for i in range(k)], k, rc
 
 
     # -------------------------------------------------------------- quality monitor ---------

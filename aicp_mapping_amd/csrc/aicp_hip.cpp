@@ -31,6 +31,7 @@
 #include "icp_math.hpp"
 #include "kernels.hpp"
 #include "runtime.hpp"
+#include "svm_model.hpp"
 
 using namespace aicp;
 using namespace aicp::rt;
@@ -1251,6 +1252,9 @@ void aicp_hip_destroy(aicp_hip_ctx* ctx) {
   release(ctx->pin_risk);
   for (auto e : ctx->risk_ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto& m : ctx->svm_models) release(m.entries);
+  release(ctx->svm_io);
+  release(ctx->pin_svm);
   for (DevBuf* b : {&ctx->mon_bpts, &ctx->mon_nodes, &ctx->mon_bpts2, &ctx->mon_nodes2, &ctx->mon_ws}) release(*b);
   release(ctx->pin_mon);
   for (auto e : ctx->mon_ev)
@@ -2868,6 +2872,7 @@ struct RiskView {  // risk_core's results: host (pinned) and device
   const int32_t* m_idx;
   const float *m_ov, *m_dist;
   const uint32_t *d_a_in_b, *d_b_in_a;  // device; null with zero clusters on a side
+  const RiskOut* d_out;                 // device; null with zero clusters on a side (the result is all zero)
 };
 
 bool valid_cloud(const aicp_cloud* c) { return c && aicp::rt::valid_cloud(*c); }
@@ -2965,7 +2970,8 @@ int risk_core(aicp_hip_ctx* ctx, const RiskSide& A, const RiskSide& B, float max
       h_dist[j] = -1.f;
     }
   }
-  *view = RiskView{&H->out, h_idx, h_ov, h_dist, both ? a_in_b : nullptr, both ? b_in_a : nullptr};
+  *view = RiskView{&H->out, h_idx, h_ov, h_dist, both ? a_in_b : nullptr, both ? b_in_a : nullptr,
+                   both ? dout : nullptr};
   return AICP_OK;
 }
 
@@ -3094,10 +3100,12 @@ int aicp_hip_cluster_match(aicp_hip_ctx* ctx, const float* sampled_a, const int3
   return AICP_OK;
 }
 
-int aicp_hip_alignment_features(aicp_hip_ctx* ctx, const aicp_risk_params* prm, const aicp_cloud* cloud_a,
-                                const aicp_cloud* cloud_b, const double pose_a[16], const double pose_b[16],
-                                aicp_risk_result* out, float* planes_a, size_t* n_planes_a, float* planes_b,
-                                size_t* n_planes_b, size_t planes_cap) {
+// d_align (nullable, device): receives the alignability from the device's own result, enqueued on
+// ctx->stream (the pipeline's classifier reads it there)
+static int alignment_features(aicp_hip_ctx* ctx, const aicp_risk_params* prm, const aicp_cloud* cloud_a,
+                              const aicp_cloud* cloud_b, const double pose_a[16], const double pose_b[16],
+                              aicp_risk_result* out, float* planes_a, size_t* n_planes_a, float* planes_b,
+                              size_t* n_planes_b, size_t planes_cap, float* d_align) {
   if (!ctx || !prm || !pose_a || !pose_b || !out || !valid_cloud(cloud_a) || !valid_cloud(cloud_b))
     return AICP_ERR_INVALID;
   int rc = pf_check(ctx, &prm->prefilter);
@@ -3193,6 +3201,12 @@ int aicp_hip_alignment_features(aicp_hip_ctx* ctx, const aicp_risk_params* prm, 
   RiskView v;
   rc = risk_core(ctx, S[0], S[1], prm->max_angle_deg, prm->box_scale, E + 4, &v);
   if (rc) return rc;
+  if (d_align) {
+    if (v.d_out)
+      HIPC(hipMemcpyAsync(d_align, &v.d_out->alignability, 4, hipMemcpyDeviceToDevice, s));
+    else
+      HIPC(hipMemsetAsync(d_align, 0, 4, s));  // no matching planes: alignability 0 (:344-348)
+  }
   out->alignability = v.out->alignability;
   out->n_matches = v.out->n_matches;
   for (int k = 0; k < 3; ++k) {
@@ -3239,9 +3253,428 @@ int aicp_hip_alignment_features(aicp_hip_ctx* ctx, const aicp_risk_params* prm, 
   return AICP_OK;
 }
 
+int aicp_hip_alignment_features(aicp_hip_ctx* ctx, const aicp_risk_params* prm, const aicp_cloud* cloud_a,
+                                const aicp_cloud* cloud_b, const double pose_a[16], const double pose_b[16],
+                                aicp_risk_result* out, float* planes_a, size_t* n_planes_a, float* planes_b,
+                                size_t* n_planes_b, size_t planes_cap) {
+  return alignment_features(ctx, prm, cloud_a, cloud_b, pose_a, pose_b, out, planes_a, n_planes_a, planes_b,
+                            n_planes_b, planes_cap, nullptr);
+}
+
 int aicp_hip_last_risk_stats(const aicp_hip_ctx* ctx, aicp_risk_stats* out) {
   if (!ctx || !out) return AICP_ERR_INVALID;
   *out = ctx->last_risk;
+  return AICP_OK;
+}
+
+}  // extern "C"
+
+// ---- the classifier, the gated pipeline and the gated stream (failure_prediction_mode) ----------
+namespace {
+
+constexpr size_t kSvmModelsKept = 8;  // device copies a context keeps (the oldest goes first)
+
+struct GateRec {  // the pipeline's record in device memory: the classifier's sample, then its outputs
+  float overlap, alignability;
+  float raw, ratio;
+  double risk;
+  int32_t gate, pad;
+};
+
+// the model's device copy in this context: uploaded on first use, found by the model's id afterwards
+int svm_device(aicp_hip_ctx* ctx, const aicp_hip_svm* m, const SvmEntry** entries, SvmParams* prm) {
+  if (m->var_count != 2 || m->sv_count < 1 || m->sv_count > kSvmMaxEntries ||
+      m->alpha.size() != (size_t)m->sv_count || m->index.size() != (size_t)m->sv_count ||
+      m->sv.size() != 2 * (size_t)m->sv_total)
+    FAIL(AICP_ERR_INVALID, "svm model");
+  *prm = SvmParams{};
+  prm->degree = m->degree;
+  prm->gamma = m->gamma;
+  prm->coef0 = m->coef0;
+  prm->rho = m->rho;
+  prm->threshold = 0.0;
+  prm->count = (uint32_t)m->sv_count;
+  for (auto& d : ctx->svm_models)
+    if (d.id == m->id && d.count == prm->count) {
+      *entries = d.entries.as<SvmEntry>();
+      return AICP_OK;
+    }
+  std::vector<SvmEntry> h((size_t)m->sv_count);
+  for (int32_t j = 0; j < m->sv_count; ++j) {
+    const int32_t k = m->index[j];
+    if (k < 0 || k >= m->sv_total) FAIL(AICP_ERR_INVALID, "svm model: index out of range");
+    h[j] = SvmEntry{m->sv[2 * (size_t)k], m->sv[2 * (size_t)k + 1], m->alpha[j]};
+  }
+  if (ctx->svm_models.size() >= kSvmModelsKept) {
+    HIPC(hipStreamSynchronize(ctx->stream));
+    release(ctx->svm_models.front().entries);
+    ctx->svm_models.erase(ctx->svm_models.begin());
+  }
+  aicp_hip_ctx::SvmDev d;
+  HIPC(ensure(d.entries, h.size() * sizeof(SvmEntry)));
+  const hipError_t e = hipMemcpy(d.entries.p, h.data(), h.size() * sizeof(SvmEntry), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    release(d.entries);
+    HIPC(e);
+  }
+  d.id = m->id;
+  d.count = prm->count;
+  ctx->svm_models.push_back(d);
+  *entries = d.entries.as<SvmEntry>();
+  return AICP_OK;
+}
+
+// Poses are column-major double[16] (Eigen::Isometry3d::data()); every sum below runs left to right
+// in double with no contraction, the library functions are libm's.
+inline double pose_at(const double* P, int r, int c) { return P[c * 4 + r]; }
+
+// Eigen::Quaterniond(rotation matrix): the trace / largest-diagonal branches; q = x, y, z, w
+void quat_from_rotation(const double* P, double q[4]) {
+  auto m = [&](int r, int c) { return pose_at(P, r, c); };
+  double t = (m(0, 0) + m(1, 1)) + m(2, 2);
+  if (t > 0.0) {
+    t = std::sqrt(t + 1.0);
+    q[3] = 0.5 * t;
+    t = 0.5 / t;
+    q[0] = (m(2, 1) - m(1, 2)) * t;
+    q[1] = (m(0, 2) - m(2, 0)) * t;
+    q[2] = (m(1, 0) - m(0, 1)) * t;
+  } else {
+    int i = 0;
+    if (m(1, 1) > m(0, 0)) i = 1;
+    if (m(2, 2) > m(i, i)) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    t = std::sqrt(((m(i, i) - m(j, j)) - m(k, k)) + 1.0);
+    q[i] = 0.5 * t;
+    t = 0.5 / t;
+    q[3] = (m(k, j) - m(j, k)) * t;
+    q[j] = (m(j, i) + m(i, j)) * t;
+    q[k] = (m(k, i) + m(i, k)) * t;
+  }
+}
+
+// Quaterniond::toRotationMatrix (corrected_origin's expressions), R row-major
+void rotation_from_quat(const double q[4], double R[9]) {
+  const double x = q[0], y = q[1], z = q[2], w = q[3];
+  const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
+  const double twx = tx * w, twy = ty * w, twz = tz * w;
+  const double txx = tx * x, txy = ty * x, txz = tz * x;
+  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  R[0] = 1.0 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
+  R[3] = txy + twz, R[4] = 1.0 - (txx + tzz), R[5] = tyz - twx;
+  R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1.0 - (txx + tyy);
+}
+
+// quat_to_euler (common.cpp:70-78)
+void euler_from_quat(const double q[4], double* roll, double* pitch, double* yaw) {
+  const double q0 = q[3], q1 = q[0], q2 = q[1], q3 = q[2];
+  *roll = std::atan2(2 * (q0 * q1 + q2 * q3), 1 - 2 * (q1 * q1 + q2 * q2));
+  *pitch = std::asin(2 * (q0 * q2 - q3 * q1));
+  *yaw = std::atan2(2 * (q0 * q3 + q1 * q2), 1 - 2 * (q2 * q2 + q3 * q3));
+}
+
+// euler_to_quat (common.cpp:81-105), q = x, y, z, w
+void quat_from_euler(double roll, double pitch, double yaw, double q[4]) {
+  if (roll == M_PI && pitch == 0 && yaw == 0) {
+    q[0] = 1, q[1] = 0, q[2] = 0, q[3] = 0;
+    return;
+  }
+  if (pitch == M_PI && roll == 0 && yaw == 0) {
+    q[0] = 0, q[1] = 1, q[2] = 0, q[3] = 0;
+    return;
+  }
+  if (yaw == M_PI && roll == 0 && pitch == 0) {
+    q[0] = 0, q[1] = 0, q[2] = 1, q[3] = 0;
+    return;
+  }
+  const double sy = std::sin(yaw * 0.5), cy = std::cos(yaw * 0.5), sp = std::sin(pitch * 0.5),
+               cp = std::cos(pitch * 0.5), sr = std::sin(roll * 0.5), cr = std::cos(roll * 0.5);
+  q[3] = cr * cp * cy + sr * sp * sy;
+  q[0] = sr * cp * cy - cr * sp * sy;
+  q[1] = cr * sp * cy + sr * cp * sy;
+  q[2] = cr * cp * sy - sr * sp * cy;
+}
+
+// fromMatrix4fToIsometry3d(T) * prior (common.cpp:4-23; corrected_origin's arithmetic for the
+// translation, the same row sums for the rotation)
+void moved_pose(const float* T, const double* prior, double* out) {
+  float m[3][3];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) m[r][c] = T[c * 4 + r];
+  float q[4];
+  float t = (m[0][0] + m[1][1]) + m[2][2];
+  if (t > 0.f) {
+    t = (float)std::sqrt((double)(t + 1.f));
+    q[3] = 0.5f * t;
+    t = 0.5f / t;
+    q[0] = (m[2][1] - m[1][2]) * t;
+    q[1] = (m[0][2] - m[2][0]) * t;
+    q[2] = (m[1][0] - m[0][1]) * t;
+  } else {
+    int i = 0;
+    if (m[1][1] > m[0][0]) i = 1;
+    if (m[2][2] > m[i][i]) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    t = (float)std::sqrt((double)(((m[i][i] - m[j][j]) - m[k][k]) + 1.f));
+    q[i] = 0.5f * t;
+    t = 0.5f / t;
+    q[3] = (m[k][j] - m[j][k]) * t;
+    q[j] = (m[j][i] + m[i][j]) * t;
+    q[k] = (m[k][i] + m[i][k]) * t;
+  }
+  const double qd[4] = {q[0], q[1], q[2], q[3]};
+  double R[9];
+  rotation_from_quat(qd, R);
+  for (int k = 0; k < 16; ++k) out[k] = (k == 15) ? 1.0 : 0.0;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c)
+      out[c * 4 + r] = (R[3 * r] * pose_at(prior, 0, c) + R[3 * r + 1] * pose_at(prior, 1, c)) +
+                       R[3 * r + 2] * pose_at(prior, 2, c);
+    out[12 + r] = ((R[3 * r] * prior[12] + R[3 * r + 1] * prior[13]) + R[3 * r + 2] * prior[14]) + (double)T[12 + r];
+  }
+}
+
+// AlignedCloud::removePitchRollCorrection (aligned_cloud.cpp:31-52): the corrected pose keeps its
+// translation and yaw and takes roll and pitch from the odometry pose
+void fix_pitch_roll(const double* corrected, const double* odom, double* out) {
+  double qo[4], qc[4], ro, po, yo, rc, pc, yc, qf[4], R[9];
+  quat_from_rotation(odom, qo);
+  euler_from_quat(qo, &ro, &po, &yo);
+  quat_from_rotation(corrected, qc);
+  euler_from_quat(qc, &rc, &pc, &yc);
+  quat_from_euler(ro, po, yc, qf);
+  rotation_from_quat(qf, R);
+  for (int k = 0; k < 16; ++k) out[k] = (k == 15) ? 1.0 : 0.0;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) out[c * 4 + r] = R[3 * r + c];
+    out[12 + r] = corrected[12 + r];
+  }
+}
+
+// runAicpPipeline with failure_prediction_mode for one pair (include/aicp_hip.h). icp_flags:
+// AICP_RUN_TIME_NN or 0. *risk_rc: the features' result for the callers that want it (nullable).
+int pipeline_core(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_risk_params* risk_prm,
+                  const aicp_hip_svm* model, double threshold, const aicp_pair* pair, const double* ref_pose,
+                  const double* read_pose, double resolution, int icp_flags, float* out_T,
+                  aicp_pipeline_record* rec, aicp_icp_stats* stats) {
+  hipStream_t s = ctx->stream;
+  ident4(out_T);
+  *rec = aicp_pipeline_record{};
+  rec->n_read = pair->n_read;
+  aicp_icp_stats st{};
+  st.overlap_percent = -1.f;
+  if (stats) *stats = st;
+  HIPC(ensure(ctx->svm_io, sizeof(GateRec)));
+  HIPC(ensure(ctx->pin_svm, sizeof(GateRec)));
+  GateRec* dg = ctx->svm_io.as<GateRec>();
+  const SvmEntry* entries = nullptr;
+  SvmParams sp;
+  int rc = svm_device(ctx, model, &entries, &sp);
+  if (rc) return rc;
+  sp.threshold = threshold;
+  // 1. computeOverlap: the poses' translations are the sensor origins (app.cpp:229)
+  aicp_pair p = *pair;
+  for (int k = 0; k < 3; ++k) {
+    p.ref_origin[k] = ref_pose[12 + k];
+    p.read_origin[k] = read_pose[12 + k];
+  }
+  aicp_icp_stats ost{};
+  rc = oneshot(ctx, cfg, &p, 1, resolution, AICP_RUN_OVERLAP, nullptr, &ost, nullptr);
+  if (!rc) rc = ost.status;
+  if (rc) return rc;
+  HIPC(hipMemcpyAsync(&dg->overlap, &ctx->state.as<PairState>()[0].overlap, 4, hipMemcpyDeviceToDevice, s));
+  // 2. computeAlignmentRisk's features on the same clouds and poses (app.cpp:153-167)
+  aicp_cloud ca{}, cb{};
+  ca.pts = pair->ref, ca.n = pair->n_ref, ca.stride = pair->ref_stride;
+  cb.pts = pair->read, cb.n = pair->n_read, cb.stride = pair->read_stride;
+  aicp_risk_result rr{};
+  rc = alignment_features(ctx, risk_prm, &ca, &cb, ref_pose, read_pose, &rr, nullptr, nullptr, nullptr, nullptr, 0,
+                          &dg->alignability);
+  if (rc) return rc;
+  // 3. the classifier, the gate and the ratio, from the device's own features
+  launch_svm_predict(s, 1, sp, entries, &dg->overlap, &dg->raw, &dg->risk, &dg->gate, &dg->ratio);
+  HIPC(hipGetLastError());
+  GateRec* hg = ctx->pin_svm.as<GateRec>();
+  HIPC(hipMemcpyAsync(hg, dg, sizeof(GateRec), hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  rec->fov_overlap = rr.fov_overlap;
+  rec->octree_overlap = hg->overlap;
+  rec->alignability = hg->alignability;
+  rec->raw = hg->raw;
+  rec->risk = hg->risk;
+  rec->trimmed_ratio = hg->ratio;
+  rec->registered = hg->gate ? 0 : 1;
+  st.overlap_percent = hg->overlap;
+  st.trimmed_ratio = hg->ratio;
+  for (int k = 0; k < 3; ++k) st.overlap_keys[k] = ost.overlap_keys[k];
+  // 4. computeRegistration at the device's ratio, unless gated (app.cpp:243-245)
+  if (rec->registered) {
+    aicp_icp_config c2 = *cfg;
+    c2.trimmed_ratio = hg->ratio;
+    aicp_icp_stats ist{};
+    rc = oneshot(ctx, &c2, &p, 1, 0.0, AICP_RUN_ICP | icp_flags, out_T, &ist, nullptr);
+    if (!rc) rc = ist.status;
+    ist.overlap_percent = st.overlap_percent;
+    for (int k = 0; k < 3; ++k) ist.overlap_keys[k] = st.overlap_keys[k];
+    st = ist;
+    st.status = rc;
+  }
+  if (stats) *stats = st;
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int aicp_hip_svm_predict(aicp_hip_ctx* ctx, const aicp_hip_svm* model, const float* samples, size_t n, float* raw,
+                         double* risk) {
+  if (!ctx || !model || (n && (!samples || !risk))) return AICP_ERR_INVALID;
+  if (n == 0) return AICP_OK;
+  if (n > (1ull << 28)) FAIL(AICP_ERR_UNSUPPORTED, "more than 2^28 samples in a call");
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const SvmEntry* entries = nullptr;
+  SvmParams sp;
+  const int rc = svm_device(ctx, model, &entries, &sp);
+  if (rc) return rc;
+  // samples (2 n floats) | risk (n doubles) | raw (n floats), the same layout in pinned memory
+  HIPC(hipStreamSynchronize(s));  // (pin_svm and svm_io are free)
+  HIPC(ensure(ctx->svm_io, 20 * n));
+  HIPC(ensure(ctx->pin_svm, 20 * n));
+  char* d = ctx->svm_io.as<char>();
+  char* h = ctx->pin_svm.as<char>();
+  std::memcpy(h, samples, 8 * n);
+  HIPC(hipMemcpyAsync(d, h, 8 * n, hipMemcpyHostToDevice, s));
+  launch_svm_predict(s, (uint32_t)n, sp, entries, (const float*)d, (float*)(d + 16 * n), (double*)(d + 8 * n), nullptr,
+                     nullptr);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(h + 8 * n, d + 8 * n, 12 * n, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  std::memcpy(risk, h + 8 * n, 8 * n);
+  if (raw) std::memcpy(raw, h + 16 * n, 4 * n);
+  return AICP_OK;
+}
+
+int aicp_hip_pipeline(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_risk_params* risk_prm,
+                      const aicp_hip_svm* model, double threshold, const aicp_pair* pair, const double ref_pose[16],
+                      const double read_pose[16], double resolution, float out_T[16], aicp_pipeline_record* rec,
+                      aicp_icp_stats* stats) {
+  if (!ctx || !cfg || !risk_prm || !model || !pair || !ref_pose || !read_pose || !out_T || !rec)
+    return AICP_ERR_INVALID;
+  if (!valid_pair(*pair)) FAIL(AICP_ERR_INVALID, "invalid pair");
+  if (!(resolution > 0)) FAIL(AICP_ERR_INVALID, "resolution");
+  int rc = check_cfg(ctx, cfg, AICP_RUN_ICP | AICP_RUN_OVERLAP);
+  if (rc) return rc;
+  rc = pf_check(ctx, &risk_prm->prefilter);
+  if (rc) return rc;
+  HIPC(hipSetDevice(ctx->device));
+  return pipeline_core(ctx, cfg, risk_prm, model, threshold, pair, ref_pose, read_pose, resolution, 0, out_T, rec,
+                       stats);
+}
+
+// App's stream from raw clouds with the risk gate (app.cpp:282-414): see include/aicp_hip.h.
+int aicp_hip_sequence_run_risk(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_sequence_params* prm,
+                               const aicp_prefilter_params* pf, const aicp_risk_params* risk_prm,
+                               const aicp_hip_svm* model, double threshold, const aicp_cloud* first,
+                               const double first_pose[16], const aicp_cloud* readings, const double* poses, size_t n,
+                               float* out_T, aicp_sequence_result* out, aicp_pipeline_record* rec, size_t* n_done) {
+  if (!ctx || !cfg || !prm || !pf || !risk_prm || !model || !first || !first_pose ||
+      (n && (!readings || !poses || !out_T || !out || !rec)) || !n_done)
+    return AICP_ERR_INVALID;
+  *n_done = 0;
+  int rc = pf_check(ctx, pf);
+  if (rc) return rc;
+  rc = pf_check(ctx, &risk_prm->prefilter);
+  if (rc) return rc;
+  const int F = prm->reference_update_frequency;
+  if (F < 1) FAIL(AICP_ERR_INVALID, "reference_update_frequency must be >= 1");
+  const bool debug = prm->flags & AICP_SEQ_DEBUG;
+  if (!(prm->resolution > 0)) FAIL(AICP_ERR_INVALID, "resolution");
+  rc = check_cfg(ctx, cfg, AICP_RUN_ICP | AICP_RUN_OVERLAP);
+  if (rc) return rc;
+  if (cfg->knn_normals == 0) FAIL(AICP_ERR_UNSUPPORTED, "point-to-point chain in the frame-to-reference stream");
+  if (!valid_cloud(first)) FAIL(AICP_ERR_INVALID, "invalid first cloud");
+  for (size_t i = 0; i < n; ++i)
+    if (!valid_cloud(&readings[i])) FAIL(AICP_ERR_INVALID, "invalid reading " + std::to_string(i));
+  HIPC(hipSetDevice(ctx->device));
+  // the first cloud: pre-filtered as given, its pose through updateCloud (app.cpp:293-299)
+  std::vector<float> ref;
+  rc = pf_cloud(ctx, pf, *first, nullptr, ref);
+  if (rc) return rc;
+  if (ref.empty()) FAIL(AICP_ERR_INVALID, "the first cloud keeps no point after the pre-filter");
+  double ref_pose[16];
+  fix_pitch_roll(first_pose, first_pose, ref_pose);
+  float initT[16];
+  ident4(initT);
+  int ref_id = -1, acc = 0;
+  const int icp_flags = prm->flags & AICP_RUN_TIME_NN;
+  std::vector<float> rd;
+  for (size_t i = 0; i < n; ++i) {
+    // setAndFilterReading (app.cpp:77-100): robot mode filters the reading as given; debug mode
+    // moves the raw reading by initialT_ first and its prior pose becomes initialT_iso * prior pose
+    const double* odom = poses + 16 * i;
+    double prior[16];
+    if (debug)
+      moved_pose(initT, odom, prior);
+    else
+      std::memcpy(prior, odom, sizeof(prior));
+    aicp_sequence_result& r = out[i];
+    r = aicp_sequence_result{};
+    r.reference = ref_id;
+    float* T = out_T + 16 * i;
+    ident4(T);
+    rec[i] = aicp_pipeline_record{};
+    rc = pf_cloud(ctx, pf, readings[i], debug ? initT : nullptr, rd);
+    if (rc) return rc;
+    if (rd.empty()) {  // libpointmatcher throws on an empty cloud: the worker ends (app.cpp:210)
+      r.status = r.icp.status = AICP_ERR_INVALID;
+      *n_done = i + 1;
+      FAIL(AICP_ERR_INVALID, "reading " + std::to_string(i) + " keeps no point after the pre-filter");
+    }
+    aicp_pair p{};
+    p.ref = ref.data();
+    p.n_ref = ref.size() / 3;
+    p.ref_stride = 12;
+    p.read = rd.data();
+    p.n_read = rd.size() / 3;
+    p.read_stride = 12;
+    rc = pipeline_core(ctx, cfg, risk_prm, model, threshold, &p, ref_pose, prior, prm->resolution, icp_flags, T,
+                       &rec[i], &r.icp);
+    r.status = r.icp.status = rc;
+    *n_done = i + 1;
+    if (rc) {
+      ctx->err = "reading " + std::to_string(i) + ": status " + std::to_string(rc) + ": " + ctx->err;
+      return rc;
+    }
+    if (!rec[i].registered) {
+      // app.cpp:401-411: the unmoved reading joins the graph with its prior pose and is the
+      // reference at once; the count restarts; the correction stays the identity
+      r.accepted = 1;
+      r.is_reference = 1;
+      for (int k = 0; k < 3; ++k) r.corrected_origin[k] = prior[12 + k];
+      ref.swap(rd);
+      fix_pitch_roll(prior, odom, ref_pose);
+      ref_id = (int)i;
+      acc = 0;
+      continue;
+    }
+    if (correction_rejected(T, prm->max_correction_magnitude)) continue;  // app.cpp:366-373
+    r.accepted = 1;
+    corrected_origin(T, prior + 12, r.corrected_origin);
+    if (++acc == F) {  // the corrected reading is the next reference (app.cpp:375-391)
+      std::vector<float> next(rd.size());
+      for (size_t j = 0; j < rd.size(); j += 3) apply4(T, rd[j], rd[j + 1], rd[j + 2], &next[j]);
+      ref.swap(next);
+      double corrected[16];
+      moved_pose(T, prior, corrected);
+      fix_pitch_roll(corrected, odom, ref_pose);
+      ref_id = (int)i;
+      r.is_reference = 1;
+      acc = 0;
+    }
+    mul4(T, initT, initT);  // initialT_ = correction * initialT_ (app.cpp:414)
+  }
   return AICP_OK;
 }
 

@@ -432,6 +432,22 @@ void launch_risk_match(hipStream_t s, uint32_t nca, uint32_t ncb, const RiskClus
                        const uint32_t* a_in_b, const uint32_t* b_in_a, float max_angle, int32_t* best_j,
                        float* best_ov, float* best_d, int32_t* m_idx, float* m_ov, float* m_dist, RiskOut* out);
 
+// ---- the failure-prediction classifier (kernels_svm.hip): svm.cpp's SVM and App's gate ---------
+struct SvmEntry {  // one decision-function entry: its support vector (by the file's index), its alpha
+  float v0, v1;
+  double alpha;
+};
+struct SvmParams {
+  double degree, gamma, coef0, rho;
+  double threshold;  // the gate's (read only when a gate is written)
+  uint32_t count;    // entries (<= kSvmMaxEntries: staged in LDS)
+  uint32_t pad;
+};
+// sample i = samples[2 i], samples[2 i + 1] (device memory): raw (nullable), risk; gate and ratio
+// (nullable): !(risk <= threshold) and autotune_ratio_fast(samples[2 i])
+void launch_svm_predict(hipStream_t s, uint32_t n, const SvmParams& prm, const SvmEntry* entries,
+                        const float* samples, float* raw, double* risk, int32_t* gate, float* ratio);
+
 // ---- registration quality monitor (kernels_monitor.hip): icpMonitor.cpp's metrics -------------
 struct MonSeg {       // one tree/query segment of a 1-NN launch (32 bytes)
   uint32_t slot_off;  // its first slot in the launch's slot space (whole 64-slot chunks per segment)

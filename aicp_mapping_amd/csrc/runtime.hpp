@@ -356,6 +356,16 @@ struct aicp_hip_ctx {
   aicp::rt::PinBuf pin_risk;
   hipEvent_t risk_ev[7] = {};
   aicp_risk_stats last_risk{};
+  // the classifier (kernels_svm.hip): the models this context has seen, uploaded once each (keyed
+  // by aicp_hip_svm::id), samples / results of a predict call, and the pipeline's gate record
+  struct SvmDev {
+    uint64_t id = 0;
+    aicp::rt::DevBuf entries;
+    uint32_t count = 0;
+  };
+  std::vector<SvmDev> svm_models;
+  aicp::rt::DevBuf svm_io;
+  aicp::rt::PinBuf pin_svm;
   // registration quality monitor (monitor.cpp): trees and work space of its own (the reference
   // cache keeps bpts / nodes; mon_*2: the chain matcher's trees when its bucket size is not 8)
   aicp::rt::DevBuf mon_bpts, mon_nodes, mon_bpts2, mon_nodes2, mon_ws;

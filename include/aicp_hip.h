@@ -15,6 +15,10 @@
  *                                            -> aicp_hip_autotune_ratio,
  *                                               aicp_hip_replace_ratio_config_file,
  *                                               aicp_hip_align_batch (overlap -> ratio -> ICP on device)
+ *   SVM::test (failure_prediction_mode)    aicp_core/src/classification/svm.cpp:48-110
+ *                                            -> aicp_hip_svm_load, aicp_hip_svm_predict
+ *   App::runAicpPipeline with the risk gate  aicp_core/src/registration/app.cpp:218-247, 362-411
+ *                                            -> aicp_hip_pipeline, aicp_hip_sequence_run_risk
  *
  * Conventions
  *   - Plain C, no exceptions cross this boundary; every entry point returns an AICP_* code.
@@ -286,7 +290,8 @@ int aicp_hip_last_prefilter_stats(const aicp_hip_ctx* ctx, aicp_prefilter_stats*
 
 /* ---- alignment risk (failure_prediction_mode, App::computeAlignmentRisk, app.cpp:143-185) ------
  * The two features App feeds its classifier (app.cpp:179: octree_overlap_, alignability_) and
- * fov_overlap_. The SVM itself (two floats in, an OpenCV model file) stays with the caller.
+ * fov_overlap_. The classifier itself, the gate it drives and the gated stream follow below
+ * (aicp_hip_svm_*, aicp_hip_pipeline, aicp_hip_sequence_run_risk).
  * Poses are column-major double[16] (Eigen::Isometry3d::data()). Rules and the one deliberate
  * deviation (the clamped cosine): DESIGN.md §4.5. */
 
@@ -372,6 +377,69 @@ typedef struct {
   double wall_ms;           /* the whole call */
 } aicp_risk_stats;
 int aicp_hip_last_risk_stats(const aicp_hip_ctx* ctx, aicp_risk_stats* out);
+
+/* ---- the classifier of failure_prediction_mode (aicp_core/src/classification/svm.cpp) ------------
+ * App's SVM: an OpenCV model file (two classes, two variables: octree overlap in percent and
+ * alignability, POLY kernel), evaluated as cv::ml::SVM::predict(..., RAW_OUTPUT) and mapped to a
+ * risk in [0, 1] (svm.cpp:82). Per sample x and support vector v, in this order:
+ *   s = (double)(v0 * x0) + (double)(v1 * x1), the products in float;
+ *   base = (float)(s * gamma + coef0);  K = (float)pow((double)base, degree);
+ *   sum = -rho + sum_j alpha[j] * K[index[j]] in double;  raw = (float)sum;
+ *   risk = 1.0 - 1.0 / (1.0 + exp(-(double)raw)).
+ * The double sum runs in a fixed order (lane l of a wave takes entries l, l + 64, ..., a shuffle
+ * tree joins the lanes, -rho is added last): a result depends on its input alone. */
+typedef struct aicp_hip_svm aicp_hip_svm;
+typedef struct {
+  int32_t format;      /* 3: <opencv_ml_svm> with <format>3</format>; 0: the older <my_svm> root */
+  int32_t var_count, class_count;
+  int32_t sv_total;    /* support vectors in the file */
+  int32_t sv_count;    /* entries of the one decision function */
+  int32_t has_index;   /* 0: the file has no <index>, which means the identity */
+  double degree, gamma, coef0, rho;
+} aicp_svm_info;
+/* Host only (no device needed), the project's own small reader of the model XML. Read: svmType (or
+ * svm_type), kernel/type, degree, gamma, coef0, var_count, class_count, sv_total, support_vectors and
+ * of the one decision function sv_count, rho, alpha, index; class_labels and everything else is read
+ * past. AICP_ERR_UNSUPPORTED: anything but C_SVC / POLY / 2 classes / var_count 2, or more than 2048
+ * decision-function entries; AICP_ERR_INVALID: a file that cannot be read or does not parse, a
+ * support-vector count that is not sv_total, sv_count != len(alpha), len(index) != sv_count, an
+ * index entry outside [0, sv_total). */
+int aicp_hip_svm_load(const char* path, aicp_hip_svm** out);
+void aicp_hip_svm_free(aicp_hip_svm* model);
+/* the parsed model: support_vectors 2 * sv_total floats, alpha and index sv_count each (nullable) */
+int aicp_hip_svm_info(const aicp_hip_svm* model, aicp_svm_info* out, float* support_vectors, double* alpha,
+                      int32_t* index);
+/* n samples (overlap percent, alignability) in one launch, one wave per sample. The model's arrays
+ * are uploaded on a context's first call with that model and stay there (a freed model's copy is
+ * dropped with the context). raw (nullable): n floats; risk: n doubles. n = 0 is AICP_OK. */
+int aicp_hip_svm_predict(aicp_hip_ctx* ctx, const aicp_hip_svm* model, const float* samples /* 2*n */, size_t n,
+                         float* raw /* n, nullable */, double* risk /* n */);
+
+/* App::runAicpPipeline with failure_prediction_mode (app.cpp:218-247) for one pair of pre-filtered
+ * clouds: (1) the octree overlap at `resolution` with the poses' translations as sensor origins
+ * (App hands the same Isometry3d to both steps: pair->ref_origin / read_origin are not read);
+ * (2) aicp_hip_alignment_features on (reference, reading) with (ref_pose, read_pose);
+ * (3) the classifier on ((float)overlap, (float)alignability); (4) registerClouds at the auto-tuned
+ * ratio when risk <= threshold. Overlap and alignability stay in device memory; one launch of the
+ * classifier's kernel reads them there and writes raw, risk, the gate !(risk <= threshold) (a NaN
+ * risk gates, as in C++) and the ratio aicp_hip_autotune_ratio(overlap): no host arithmetic stands
+ * between the features and the decision, the host reads the record back and enqueues the ICP with the
+ * device's ratio, or does not. A gated pair leaves out_T the identity, stats->iterations 0 and
+ * stats->status AICP_OK. rec + out_T are aicp_test's result line (aicp_test.cpp:187-198). */
+typedef struct {
+  uint64_t n_read;        /* points of the (pre-filtered) reading */
+  float fov_overlap;      /* overlapFilter's value */
+  float octree_overlap;   /* percent */
+  float alignability;
+  float raw;              /* the decision function's value */
+  double risk;
+  int32_t registered;     /* 1: risk <= threshold, the ICP ran; 0: gated */
+  float trimmed_ratio;    /* aicp_hip_autotune_ratio(octree_overlap), computed on the device */
+} aicp_pipeline_record;
+int aicp_hip_pipeline(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_risk_params* risk_prm,
+                      const aicp_hip_svm* model, double threshold, const aicp_pair* pair, const double ref_pose[16],
+                      const double read_pose[16], double resolution, float out_T[16], aicp_pipeline_record* rec,
+                      aicp_icp_stats* stats /* nullable */);
 
 /* ---- registration quality monitor (aicp_core/src/utils/icpMonitor.cpp) -------------------------
  * What PointmatcherRegistration would print with pointmatcher.printOutputStatistics
@@ -751,6 +819,31 @@ int aicp_hip_sequence_run_raw(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, con
                               const aicp_prefilter_params* pf, const aicp_cloud* first, const aicp_cloud* readings,
                               size_t n_readings, float* out_T /* 16*n */, aicp_sequence_result* out /* n */,
                               size_t* n_done);
+
+/* App's stream from RAW clouds with failure_prediction_mode (processCloud, app.cpp:282-414 with both
+ * branches of the `if` at app.cpp:362): aicp_hip_sequence_run_raw's rules, reading by reading in
+ * robot and in debug mode (the features take host round trips per pair), with the pair going through
+ * aicp_hip_pipeline against the current reference and its pose:
+ *   risk <= threshold: the drop test, the correction, the frequency update and initialT_ =
+ *     correction * initialT_ as in aicp_hip_sequence_run_raw;
+ *   otherwise (app.cpp:401-411): the unmoved pre-filtered reading joins the graph with its prior pose
+ *     (debug mode: initialT_ * prior pose) and at once becomes the reference; the count towards
+ *     reference_update_frequency restarts; the correction is the identity, so initialT_ stays. It is
+ *     reported with status AICP_OK, accepted 1, is_reference 1, corrected_origin = that pose's
+ *     translation, out_T the identity and rec[i].registered 0.
+ * poses: 16 doubles per reading, column-major (Eigen::Isometry3d::data()); the readings' sensor
+ * origins are their translations (readings[i].origin is not read), first_pose the first cloud's.
+ * The pose of a reference that is a corrected reading is App's corrected pose, in double on the
+ * host: fromMatrix4fToIsometry3d(correction) * prior pose, then removePitchRollCorrection
+ * (aligned_cloud.cpp:31-74, common.cpp:4-23, 70-105); its translation is corrected_origin. prm->flags:
+ * AICP_SEQ_DEBUG | AICP_RUN_TIME_NN (the overlap always runs: the classifier needs it). rec: n
+ * records. The windowed aicp_hip_sequence_run is not involved. */
+int aicp_hip_sequence_run_risk(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_sequence_params* prm,
+                               const aicp_prefilter_params* pf, const aicp_risk_params* risk_prm,
+                               const aicp_hip_svm* model, double threshold, const aicp_cloud* first,
+                               const double first_pose[16], const aicp_cloud* readings /* RAW */,
+                               const double* poses /* 16*n */, size_t n_readings, float* out_T /* 16*n */,
+                               aicp_sequence_result* out /* n */, aicp_pipeline_record* rec /* n */, size_t* n_done);
 
 /* ---- kernel-level entry points (parity tests and diagnostics) --------------------------- */
 /* kd-tree over pts (as given, no centring) + k-NN of queries: libnabo
