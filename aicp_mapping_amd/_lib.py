@@ -55,6 +55,9 @@ EXPORTS = [
     "aicp_hip_test_tree",
     "aicp_hip_svm_load", "aicp_hip_svm_free", "aicp_hip_svm_info", "aicp_hip_svm_predict", "aicp_hip_pipeline",
     "aicp_hip_sequence_run_risk",
+    "aicp_hip_default_accum_params", "aicp_hip_accum_create", "aicp_hip_accum_free", "aicp_hip_accum_push",
+    "aicp_hip_accum_state", "aicp_hip_accum_clear", "aicp_hip_accum_download", "aicp_hip_accum_prefilter",
+    "aicp_hip_accum_pose_matrix", "aicp_hip_motion_gate",
 ]
 
 
@@ -76,7 +79,10 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_test_ingest",  # raw readings in the two map streams
            "aicp_hip_test_tree",  # the kd-tree build, node for node
            "aicp_hip_svm_load", "aicp_hip_svm_free", "aicp_hip_svm_info", "aicp_hip_svm_predict",
-           "aicp_hip_pipeline", "aicp_hip_sequence_run_risk"}  # the classifier and the risk gate
+           "aicp_hip_pipeline", "aicp_hip_sequence_run_risk",  # the classifier and the risk gate
+           "aicp_hip_default_accum_params", "aicp_hip_accum_create", "aicp_hip_accum_free", "aicp_hip_accum_push",
+           "aicp_hip_accum_state", "aicp_hip_accum_clear", "aicp_hip_accum_download", "aicp_hip_accum_prefilter",
+           "aicp_hip_accum_pose_matrix", "aicp_hip_motion_gate"}  # the sweep accumulator
 
 
 class IcpConfig(C.Structure):
@@ -412,6 +418,14 @@ class BuiltMapTiming(C.Structure):
     ]
 
 
+class AccumParams(C.Structure):
+    _fields_ = [
+        ("batch_size", C.c_int32),
+        ("crop_min", C.c_float),
+        ("crop_max", C.c_float),
+    ]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -578,6 +592,21 @@ def _load():
         L.aicp_hip_pipeline.argtypes = [vp, cfgp, rpp, vp, C.c_double, pp, dp, dp, C.c_double, fp, prp, stp]
         L.aicp_hip_sequence_run_risk.argtypes = [vp, cfgp, C.POINTER(SequenceParams), pfp, rpp, vp, C.c_double, clp, dp,
                                                  clp, dp, sz, fp, C.POINTER(SequenceResult), prp, szp]
+    if hasattr(L, "aicp_hip_accum_create"):
+        u32p, dp, pfp = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(PrefilterParams)
+        L.aicp_hip_default_accum_params.argtypes = [C.POINTER(AccumParams)]
+        L.aicp_hip_default_accum_params.restype = None
+        L.aicp_hip_accum_create.argtypes = [vp, C.POINTER(AccumParams), sz, C.POINTER(vp)]
+        L.aicp_hip_accum_free.argtypes = [vp, vp]
+        L.aicp_hip_accum_free.restype = None
+        L.aicp_hip_accum_push.argtypes = [vp, vp, fp, sz, sz, dp]
+        L.aicp_hip_accum_state.argtypes = [vp, vp, ip, ip, szp, u32p]
+        L.aicp_hip_accum_clear.argtypes = [vp, vp]
+        L.aicp_hip_accum_download.argtypes = [vp, vp, fp, sz, szp]
+        L.aicp_hip_accum_prefilter.argtypes = [vp, vp, pfp, fp, fp, sz, szp]
+        L.aicp_hip_accum_pose_matrix.argtypes = [dp, fp]
+        L.aicp_hip_accum_pose_matrix.restype = None
+        L.aicp_hip_motion_gate.argtypes = [dp, dp, C.c_double, C.c_double]
     return L
 
 

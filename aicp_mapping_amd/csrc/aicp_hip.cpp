@@ -2570,6 +2570,46 @@ int stream_prefilter_raw(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf, con
   return AICP_OK;
 }
 
+// aicp_hip_prefilter on n points that already lie on the device (float4, w = 1; the sweep
+// accumulator's cloud), which stay as they are: copied, or with T (nullable, host) moved by
+// launch_transform as aicp_hip_transform moves them, into the pre-filter's input.
+int prefilter_resident(aicp_hip_ctx* ctx, const aicp_prefilter_params* prm, const float4* dpts, size_t n,
+                       const float* T, float* out, size_t cap, size_t* out_n) {
+  int rc = pf_check(ctx, prm);
+  if (rc) return rc;
+  *out_n = 0;
+  ctx->last_pf = aicp_prefilter_stats{};
+  if (n == 0) return AICP_OK;
+  const auto t_wall = std::chrono::steady_clock::now();
+  hipStream_t s = ctx->stream;
+  PfLayout Lo;
+  rc = pf_layout(ctx, n, &Lo);
+  if (rc) return rc;
+  if (T) {
+    HIPC(hipStreamSynchronize(s));  // (scratch is free)
+    HIPC(ensure(ctx->scratch, 64));
+    HIPC(hipMemcpy(ctx->scratch.p, T, 64, hipMemcpyHostToDevice));
+    launch_transform(s, (int)n, ctx->scratch.as<float>(), dpts, Lo.pts4);
+    HIPC(hipGetLastError());
+  } else {
+    HIPC(hipMemcpyAsync(Lo.pts4, dpts, n * 16, hipMemcpyDeviceToDevice, s));
+  }
+  PfRun o;
+  rc = pf_core(ctx, prm, n, Lo, &o);  // (returns with the stream idle)
+  if (rc) return rc;
+  if (o.V && o.n_out) {
+    if (o.n_out > cap) FAIL(AICP_ERR_INVALID, "pre-filter: output capacity too small");
+    HIPC(ensure(ctx->pin_io, (size_t)o.n_out * 16));
+    float* h = ctx->pin_io.as<float>();
+    HIPC(hipMemcpy(h, o.out4, (size_t)o.n_out * 16, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < o.n_out; ++i)
+      for (int k = 0; k < 3; ++k) out[3 * i + k] = h[4 * i + k];
+    *out_n = o.n_out;
+  }
+  ctx->last_pf.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wall).count();
+  return AICP_OK;
+}
+
 }  // namespace rt
 }  // namespace aicp
 
@@ -3328,14 +3368,17 @@ int svm_device(aicp_hip_ctx* ctx, const aicp_hip_svm* m, const SvmEntry** entrie
 // in double with no contraction, the library functions are libm's.
 inline double pose_at(const double* P, int r, int c) { return P[c * 4 + r]; }
 
-// Eigen::Quaterniond(rotation matrix): the trace / largest-diagonal branches; q = x, y, z, w
-void quat_from_rotation(const double* P, double q[4]) {
-  auto m = [&](int r, int c) { return pose_at(P, r, c); };
-  double t = (m(0, 0) + m(1, 1)) + m(2, 2);
-  if (t > 0.0) {
-    t = std::sqrt(t + 1.0);
-    q[3] = 0.5 * t;
-    t = 0.5 / t;
+// Eigen::Quaternion<S>(rotation matrix): the trace / largest-diagonal branches; q = x, y, z, w.
+// P: a column-major 4x4 of S (a pose, or a correction). S = float: Eigen's float evaluation (sqrtf
+// is correctly rounded, as (float)sqrt((double)x) is for a float x).
+template <class S>
+void quat_from_rotation(const S* P, S q[4]) {
+  auto m = [&](int r, int c) { return P[c * 4 + r]; };
+  S t = (m(0, 0) + m(1, 1)) + m(2, 2);
+  if (t > S(0)) {
+    t = std::sqrt(t + S(1));
+    q[3] = S(0.5) * t;
+    t = S(0.5) / t;
     q[0] = (m(2, 1) - m(1, 2)) * t;
     q[1] = (m(0, 2) - m(2, 0)) * t;
     q[2] = (m(1, 0) - m(0, 1)) * t;
@@ -3344,25 +3387,26 @@ void quat_from_rotation(const double* P, double q[4]) {
     if (m(1, 1) > m(0, 0)) i = 1;
     if (m(2, 2) > m(i, i)) i = 2;
     const int j = (i + 1) % 3, k = (j + 1) % 3;
-    t = std::sqrt(((m(i, i) - m(j, j)) - m(k, k)) + 1.0);
-    q[i] = 0.5 * t;
-    t = 0.5 / t;
+    t = std::sqrt(((m(i, i) - m(j, j)) - m(k, k)) + S(1));
+    q[i] = S(0.5) * t;
+    t = S(0.5) / t;
     q[3] = (m(k, j) - m(j, k)) * t;
     q[j] = (m(j, i) + m(i, j)) * t;
     q[k] = (m(k, i) + m(i, k)) * t;
   }
 }
 
-// Quaterniond::toRotationMatrix (corrected_origin's expressions), R row-major
-void rotation_from_quat(const double q[4], double R[9]) {
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w;
-  const double txx = tx * x, txy = ty * x, txz = tz * x;
-  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  R[0] = 1.0 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
-  R[3] = txy + twz, R[4] = 1.0 - (txx + tzz), R[5] = tyz - twx;
-  R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1.0 - (txx + tyy);
+// Quaternion<S>::toRotationMatrix (corrected_origin's expressions), R row-major
+template <class S>
+void rotation_from_quat(const S q[4], S R[9]) {
+  const S x = q[0], y = q[1], z = q[2], w = q[3];
+  const S tx = S(2) * x, ty = S(2) * y, tz = S(2) * z;
+  const S twx = tx * w, twy = ty * w, twz = tz * w;
+  const S txx = tx * x, txy = ty * x, txz = tz * x;
+  const S tyy = ty * y, tyz = tz * y, tzz = tz * z;
+  R[0] = S(1) - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
+  R[3] = txy + twz, R[4] = S(1) - (txx + tzz), R[5] = tyz - twx;
+  R[6] = txz - twy, R[7] = tyz + twx, R[8] = S(1) - (txx + tyy);
 }
 
 // quat_to_euler (common.cpp:70-78)
@@ -3398,30 +3442,8 @@ void quat_from_euler(double roll, double pitch, double yaw, double q[4]) {
 // fromMatrix4fToIsometry3d(T) * prior (common.cpp:4-23; corrected_origin's arithmetic for the
 // translation, the same row sums for the rotation)
 void moved_pose(const float* T, const double* prior, double* out) {
-  float m[3][3];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) m[r][c] = T[c * 4 + r];
   float q[4];
-  float t = (m[0][0] + m[1][1]) + m[2][2];
-  if (t > 0.f) {
-    t = (float)std::sqrt((double)(t + 1.f));
-    q[3] = 0.5f * t;
-    t = 0.5f / t;
-    q[0] = (m[2][1] - m[1][2]) * t;
-    q[1] = (m[0][2] - m[2][0]) * t;
-    q[2] = (m[1][0] - m[0][1]) * t;
-  } else {
-    int i = 0;
-    if (m[1][1] > m[0][0]) i = 1;
-    if (m[2][2] > m[i][i]) i = 2;
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    t = (float)std::sqrt((double)(((m[i][i] - m[j][j]) - m[k][k]) + 1.f));
-    q[i] = 0.5f * t;
-    t = 0.5f / t;
-    q[3] = (m[k][j] - m[j][k]) * t;
-    q[j] = (m[j][i] + m[i][j]) * t;
-    q[k] = (m[k][i] + m[i][k]) * t;
-  }
+  quat_from_rotation(T, q);  // (Quaternionf of the float rotation block)
   const double qd[4] = {q[0], q[1], q[2], q[3]};
   double R[9];
   rotation_from_quat(qd, R);
@@ -3526,6 +3548,45 @@ int pipeline_core(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_risk
 }  // namespace
 
 extern "C" {
+
+// The sweep accumulator's two host-side rules (include/aicp_hip.h), beside the quaternion
+// restatements they share with the risk gate's poses.
+void aicp_hip_accum_pose_matrix(const double pose[16], float out_T[16]) {
+  float P[16], q[4], R[9];
+  for (int k = 0; k < 16; ++k) P[k] = (float)pose[k];  // rotation().cast<float>(), translation().cast<float>()
+  quat_from_rotation(P, q);
+  rotation_from_quat(q, R);
+  for (int k = 0; k < 16; ++k) out_T[k] = (k == 15) ? 1.f : 0.f;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) out_T[c * 4 + r] = R[3 * r + c];
+    out_T[12 + r] = P[12 + r];
+  }
+}
+
+int aicp_hip_motion_gate(const double prev_pose[16], const double pose[16], double min_dist, double min_angle_rad) {
+  // prev^-1 * pose with the Isometry inverse (R^T, -R^T t): rel.R = R^T Rc, rel.t = R^T tc + (-R^T t)
+  double rel[16], nt[3];
+  for (int k = 0; k < 16; ++k) rel[k] = (k == 15) ? 1.0 : 0.0;
+  for (int r = 0; r < 3; ++r)
+    nt[r] = -((pose_at(prev_pose, 0, r) * prev_pose[12] + pose_at(prev_pose, 1, r) * prev_pose[13]) +
+              pose_at(prev_pose, 2, r) * prev_pose[14]);
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c)
+      rel[c * 4 + r] = (pose_at(prev_pose, 0, r) * pose_at(pose, 0, c) + pose_at(prev_pose, 1, r) * pose_at(pose, 1, c)) +
+                       pose_at(prev_pose, 2, r) * pose_at(pose, 2, c);
+    rel[12 + r] = ((pose_at(prev_pose, 0, r) * pose[12] + pose_at(prev_pose, 1, r) * pose[13]) +
+                   pose_at(prev_pose, 2, r) * pose[14]) +
+                  nt[r];
+  }
+  const double dist = std::sqrt((rel[12] * rel[12] + rel[13] * rel[13]) + rel[14] * rel[14]);
+  double q[4], rpy[3];
+  quat_from_rotation(rel, q);
+  euler_from_quat(q, &rpy[0], &rpy[1], &rpy[2]);
+  return (dist > min_dist || std::fabs(rpy[0]) > min_angle_rad || std::fabs(rpy[1]) > min_angle_rad ||
+          std::fabs(rpy[2]) > min_angle_rad)
+             ? 1
+             : 0;
+}
 
 int aicp_hip_svm_predict(aicp_hip_ctx* ctx, const aicp_hip_svm* model, const float* samples, size_t n, float* raw,
                          double* risk) {

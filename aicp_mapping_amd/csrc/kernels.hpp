@@ -118,6 +118,25 @@ bool launch_knn_generic(hipStream_t s, uint32_t nq, const float4* q, const uint4
                         uint32_t* ctr);
 void launch_transform(hipStream_t s, int n, const float* T, const float4* in, float4* out);
 // kernels_crop.hip: order-preserving oriented box crop (getPointsInOrientedBox).
+struct CropBoxArgs {
+  float inv[9];  // row-major local-frame rotation (identity when CropBox would skip it)
+  float t[3];    // translation subtracted first
+  float mn, mx;
+};
+#ifdef __HIPCC__
+// the keep test of every crop kernel and of the sweep accumulator (kernels_accum.hip)
+__device__ __forceinline__ bool crop_keep(const CropBoxArgs& a, float4 p) {
+  if (!isfinite(p.x) || !isfinite(p.y) || !isfinite(p.z)) return false;
+  const float x = __fsub_rn(p.x, a.t[0]), y = __fsub_rn(p.y, a.t[1]), z = __fsub_rn(p.z, a.t[2]);
+  float l[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    l[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(a.inv[3 * r], x), __fmul_rn(a.inv[3 * r + 1], y)),
+                               __fmul_rn(a.inv[3 * r + 2], z)),
+                     0.f);
+  return !(l[0] < a.mn || l[1] < a.mn || l[2] < a.mn || l[0] > a.mx || l[1] > a.mx || l[2] > a.mx);
+}
+#endif
 size_t crop_tiles(size_t n);
 void launch_crop_box(hipStream_t s, int n, const float inv[9], const float t[3], float mn, float mx,
                      const float4* pts, uint32_t* tile_cnt, uint32_t* tile_off, uint32_t* total,
@@ -135,6 +154,18 @@ void launch_crop_count_multi(hipStream_t s, int n, int n_crops, const void* args
 void launch_crop_scatter_multi(hipStream_t s, int n, int n_crops, const void* args, const float4* pts,
                                const uint32_t* tile_off, const uint32_t* base_of, float4* out);
 void launch_solve6(hipStream_t s, const double* A, const double* b, double* x, int32_t* path);
+
+// ---- sweep accumulator (kernels_accum.hip): VelodyneAccumulatorROS::processLidar ---------------
+struct AccumSweep {
+  CropBoxArgs box;  // identity frame, crop_min / crop_max (velodyne_accumulator.cpp:59-60)
+  float T[16];      // the sweep's pose as transformPointCloud takes it (aicp_hip_accum_pose_matrix)
+};
+// Sweep j of a reading, two launches: the rows that pass the box (n rows of `stride` bytes on the
+// device, 12 or 16, xyz first) are moved by T and appended in input order as float4(x, y, z, 1) at
+// out + tails[j]; tails[j + 1] = tails[j] + kept. tile_cnt: crop_tiles(n) words; no write at or past
+// out + cap. n = 0 still writes tails[j + 1].
+void launch_accum_sweep(hipStream_t s, int n, const void* rows, size_t stride, const AccumSweep& a, uint32_t* tile_cnt,
+                        uint32_t* tails, int j, float4* out, uint32_t cap);
 
 // ---- kd-tree construction (kernels_tree.hip) ---------------------------------------------
 struct TreeWork {

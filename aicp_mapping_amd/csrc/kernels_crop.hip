@@ -19,23 +19,7 @@ namespace {
 constexpr int kCropThreads = 256;
 constexpr int kCropTile = 1024;  // 4 rounds of 256
 
-struct CropBoxArgs {
-  float inv[9];  // row-major local-frame rotation (identity when CropBox would skip it)
-  float t[3];    // translation subtracted first
-  float mn, mx;
-};
-
-__device__ __forceinline__ bool crop_keep(const CropBoxArgs& a, float4 p) {
-  if (!isfinite(p.x) || !isfinite(p.y) || !isfinite(p.z)) return false;
-  const float x = __fsub_rn(p.x, a.t[0]), y = __fsub_rn(p.y, a.t[1]), z = __fsub_rn(p.z, a.t[2]);
-  float l[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-    l[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(a.inv[3 * r], x), __fmul_rn(a.inv[3 * r + 1], y)),
-                               __fmul_rn(a.inv[3 * r + 2], z)),
-                     0.f);
-  return !(l[0] < a.mn || l[1] < a.mn || l[2] < a.mn || l[0] > a.mx || l[1] > a.mx || l[2] > a.mx);
-}
+// (CropBoxArgs and crop_keep: kernels.hpp, shared with the sweep accumulator)
 
 __global__ __launch_bounds__(kCropThreads) void k_crop_count(int n, CropBoxArgs a, const float4* __restrict__ pts,
                                                              uint32_t* __restrict__ tile_cnt) {

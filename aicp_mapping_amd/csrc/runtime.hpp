@@ -292,6 +292,11 @@ int map_crop_pairs(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float m
 int stream_prefilter_raw(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf, const aicp_cloud& c, const float* d_initT,
                          double* d_origin, float4* dst, uint32_t* kept);
 int stream_prefilter_check(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf);  // pf_check
+// aicp_hip_prefilter on n device-resident points (float4, w = 1; left unchanged), moved first by T
+// (nullable, host, column-major) as aicp_hip_transform moves them; kept points packed xyz to out
+// (capacity cap points). For the sweep accumulator (accum.cpp).
+int prefilter_resident(aicp_hip_ctx* ctx, const aicp_prefilter_params* prm, const float4* dpts, size_t n,
+                       const float* T, float* out, size_t cap, size_t* out_n);
 
 }  // namespace rt
 }  // namespace aicp

@@ -535,6 +535,65 @@ int aicp_hip_map_merge(aicp_hip_ctx* ctx, aicp_hip_map* map, const float* pts, s
 /* map = regionGrowingUniformPlaneSegmentationFilter(map) (aicp_hip_prefilter on device data) */
 int aicp_hip_map_prefilter(aicp_hip_ctx* ctx, aicp_hip_map* map, const aicp_prefilter_params* prm);
 
+/* ---- sweep accumulator: a raw reading assembled in HBM ----------------------------------------
+ * VelodyneAccumulatorROS::processLidar (aicp_ros/src/velodyne_accumulator.cpp:31-73) per sweep:
+ *   getPointsInOrientedBox(sweep, crop_min, crop_max, Identity): non-finite points dropped, the
+ *     cube inclusive;
+ *   pcl::transformPointCloud(sweep, pose.translation().cast<float>(),
+ *                            Quaternionf(pose.rotation().cast<float>())): x' = r00 x + r01 y +
+ *     r02 z + t0 in float, in that order, no FMA (aicp_hip_transform's expression) with the
+ *     matrix of aicp_hip_accum_pose_matrix;
+ *   accumulated_point_cloud_ += sweep, and after batch_size sweeps the accumulator is finished.
+ * A sweep is uploaded when it is pushed and cropped, moved and appended on the device; the raw
+ * reading never exists on the host. The counts live on the device: push does not synchronise the
+ * host with the device, state / download / prefilter do. One accumulator is driven from one thread
+ * at a time, on its context's stream. */
+typedef struct aicp_hip_accum aicp_hip_accum;
+typedef struct {
+  int32_t batch_size;       /* 80 (aicp_ros_node.cpp:40); aicp.launch uses 7 */
+  float crop_min, crop_max; /* -30, 30 (velodyne_accumulator.cpp:60) */
+} aicp_accum_params;
+void aicp_hip_default_accum_params(aicp_accum_params* p);
+/* capacity_points: the most input points (kept or not) one reading's sweeps may add up to */
+int aicp_hip_accum_create(aicp_hip_ctx* ctx, const aicp_accum_params* prm, size_t capacity_points,
+                          aicp_hip_accum** out);
+void aicp_hip_accum_free(aicp_hip_ctx* ctx, aicp_hip_accum* acc);
+/* One sweep: n rows of `stride` bytes (>= 12, a multiple of 4), xyz first; pose: Isometry3d
+ * (inertial <- sensor), column-major double[16]. The rows are copied into a pinned slot of the
+ * accumulator before the call returns (rows of 12 or 16 bytes as they are, wider rows packed), the
+ * upload and the two kernels are enqueued on the context's stream, and nothing is waited for but a
+ * slot's own earlier upload. The host keeps only the sum of every n since the last clear: a push
+ * that takes it past capacity_points is AICP_ERR_INVALID and changes nothing. A finished
+ * accumulator ignores the push (AICP_OK), as processLidar does; n = 0 counts as a sweep. */
+int aicp_hip_accum_push(aicp_hip_ctx* ctx, aicp_hip_accum* acc, const float* pts, size_t n, size_t stride,
+                        const double pose[16]);
+/* waits for the stream. counter: sweeps taken, finished: counter == batch_size, n_points: the
+ * accumulated cloud's size, kept_per_sweep (nullable, batch_size words): each sweep's kept points
+ * (0 from `counter` on). Every output is nullable. */
+int aicp_hip_accum_state(aicp_hip_ctx* ctx, aicp_hip_accum* acc, int32_t* counter, int32_t* finished,
+                         size_t* n_points, uint32_t* kept_per_sweep);
+/* clearCloud(): nothing is waited for */
+int aicp_hip_accum_clear(aicp_hip_ctx* ctx, aicp_hip_accum* acc);
+/* getCloud(): packed xyz (capacity cap points); waits for the stream */
+int aicp_hip_accum_download(aicp_hip_ctx* ctx, aicp_hip_accum* acc, float* out, size_t cap, size_t* out_n);
+/* regionGrowingUniformPlaneSegmentationFilter of the accumulated cloud where it lies
+ * (aicp_hip_prefilter on device data; the accumulator is left as it is). T (nullable, column-major
+ * float[16]): the cloud is first moved by it as aicp_hip_transform moves it (setAndFilterReading's
+ * debug branch, app.cpp:87-99). out: the kept points, packed xyz, capacity cap points
+ * (AICP_ERR_INVALID if they do not fit). aicp_hip_last_prefilter_stats describes the call. */
+int aicp_hip_accum_prefilter(aicp_hip_ctx* ctx, aicp_hip_accum* acc, const aicp_prefilter_params* prm,
+                             const float T[16], float* out, size_t cap, size_t* out_n);
+/* Host only, no device needed. The sweep's float transform (velodyne_accumulator.cpp:62-63):
+ * R = Quaternionf(pose.rotation().cast<float>()).toRotationMatrix() (Eigen 3.3: rotation() is the
+ * linear part as it stands; Eigen's trace / largest-diagonal branches in float, no normalisation),
+ * t = pose.translation().cast<float>(); out_T = [R | t], column-major. */
+void aicp_hip_accum_pose_matrix(const double pose[16], float out_T[16]);
+/* AppROS::velodyneCallBack's test that the robot moved since the last reading (app_ros.cpp:203-213):
+ * with rel = prev_pose^-1 * pose (the Isometry inverse: R^T, -R^T t), 1 if |rel.translation| >
+ * min_dist (1.0) or any of |roll|, |pitch|, |yaw| of quat_to_euler(Quaterniond(rel.rotation)) >
+ * min_angle_rad (10 degrees), else 0. */
+int aicp_hip_motion_gate(const double prev_pose[16], const double pose[16], double min_dist, double min_angle_rad);
+
 /* App's localization stream on the map (localize_against_prior_map: aicp_localization_only.launch,
  * processCloud app.cpp:282-414 with the aligned-cloud graph empty at the start, so the "first
  * cloud" branch app.cpp:286-289 is skipped). State: the map, n_clouds = 0
