@@ -52,7 +52,7 @@ EXPORTS = [
     "aicp_hip_map_align_batch", "aicp_hip_map_capacity", "aicp_hip_default_built_map_params",
     "aicp_hip_built_map_window", "aicp_hip_built_map_sequence_run", "aicp_hip_last_built_map_timing",
     "aicp_hip_map_sequence_run_raw", "aicp_hip_built_map_sequence_run_raw", "aicp_hip_test_ingest",
-    "aicp_hip_test_tree",
+    "aicp_hip_test_tree", "aicp_hip_test_nn",
     "aicp_hip_svm_load", "aicp_hip_svm_free", "aicp_hip_svm_info", "aicp_hip_svm_predict", "aicp_hip_pipeline",
     "aicp_hip_sequence_run_risk",
     "aicp_hip_default_accum_params", "aicp_hip_accum_create", "aicp_hip_accum_free", "aicp_hip_accum_push",
@@ -78,6 +78,7 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_map_sequence_run_raw", "aicp_hip_built_map_sequence_run_raw",
            "aicp_hip_test_ingest",  # raw readings in the two map streams
            "aicp_hip_test_tree",  # the kd-tree build, node for node
+           "aicp_hip_test_nn",  # the NN search, query by query
            "aicp_hip_svm_load", "aicp_hip_svm_free", "aicp_hip_svm_info", "aicp_hip_svm_predict",
            "aicp_hip_pipeline", "aicp_hip_sequence_run_risk",  # the classifier and the risk gate
            "aicp_hip_default_accum_params", "aicp_hip_accum_create", "aicp_hip_accum_free", "aicp_hip_accum_push",
@@ -581,6 +582,10 @@ def _load():
     if hasattr(L, "aicp_hip_test_tree"):
         u32p = C.POINTER(C.c_uint32)
         L.aicp_hip_test_tree.argtypes = [vp, sz, u32p, fp, C.c_int32, C.c_int32, u32p, u32p, ip, fp, u32p, fp, u32p]
+    if hasattr(L, "aicp_hip_test_nn"):
+        u32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        L.aicp_hip_test_nn.argtypes = [vp, sz, u32p, fp, C.c_int32, sz, u32p, u32p, fp, sz, fp, u8p, C.c_float,
+                                       C.c_float, ip, fp, u32p, ip, ip, up]
     if hasattr(L, "aicp_hip_svm_load"):
         dp, clp, pfp = C.POINTER(C.c_double), C.POINTER(Cloud), C.POINTER(PrefilterParams)
         rpp, prp = C.POINTER(RiskParams), C.POINTER(PipelineRecord)
@@ -1298,6 +1303,47 @@ class Context:
                 parent=rec[:, 2].copy().view(np.int32), depth=rec[:, 3].astype(np.int32)))
             off += n
         return out
+
+    def test_nn(self, refs, bucket, pair_ref, reads, T, active=None, eps=0.0, max_dist=float("inf")):
+        """aicp_hip_test_nn: the production NN launch, once per step. refs: a list of (n, 3) float32
+        reference clouds (built as one batch, no centring); pair_ref: the reference of each pair;
+        reads: one (m, 3) float32 array of readings per pair; T: (n_steps, n_pairs, 16) column-major
+        float32; active: (n_steps, n_pairs) flags or None. Returns dict(match, d2, touched: (n_steps,
+        total) arrays, match a bucket position within the pair's reference; ids: per reference the
+        input id of every bucket position; engine: 0 treelets, 1 node records; dirty; read_off: each
+        pair's first column)."""
+        refs = [np.ascontiguousarray(c, np.float32).reshape(-1, 3) for c in refs]
+        reads = [np.ascontiguousarray(r, np.float32).reshape(-1, 3) for r in reads]
+        counts = np.array([c.shape[0] for c in refs], np.uint32)
+        n_read = np.array([r.shape[0] for r in reads], np.uint32)
+        pair_ref = np.ascontiguousarray(pair_ref, np.uint32).ravel()
+        R, P = counts.size, n_read.size
+        total_ref, total = int(counts.sum(dtype=np.uint64)), int(n_read.sum(dtype=np.uint64))
+        T = np.ascontiguousarray(T, np.float32)
+        S = T.shape[0] if T.ndim == 3 else 0
+        if pair_ref.size != P or T.shape != (S, P, 16):
+            raise ValueError("one reference and one array of readings per pair; T (n_steps, n_pairs, 16)")
+        act = None
+        if active is not None:
+            act = np.ascontiguousarray(active, np.uint8)
+            if act.shape != (S, P):
+                raise ValueError("active (n_steps, n_pairs)")
+        rp = np.ascontiguousarray(np.concatenate(refs, axis=0)) if R else np.zeros((0, 3), np.float32)
+        rd = np.ascontiguousarray(np.concatenate(reads, axis=0)) if P else np.zeros((0, 3), np.float32)
+        match, d2 = np.zeros((S, total), np.int32), np.zeros((S, total), np.float32)
+        touched, ids = np.zeros((S, total), np.uint32), np.zeros(total_ref, np.int32)
+        engine, dirty = C.c_int32(-1), C.c_uint64()
+        ip, u32p, u8p = C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        rc = lib.aicp_hip_test_nn(
+            self.h, R, counts.ctypes.data_as(u32p), _fptr(rp), int(bucket), P, pair_ref.ctypes.data_as(u32p),
+            n_read.ctypes.data_as(u32p), _fptr(rd), S, _fptr(T), act.ctypes.data_as(u8p) if act is not None else None,
+            float(eps), float(max_dist), match.ctypes.data_as(ip), _fptr(d2), touched.ctypes.data_as(u32p),
+            ids.ctypes.data_as(ip), C.byref(engine), C.byref(dirty))
+        self.check(rc)
+        ro = np.concatenate([[0], np.cumsum(counts.astype(np.int64))])
+        return dict(match=match, d2=d2, touched=touched, ids=[ids[ro[r]:ro[r + 1]] for r in range(R)],
+                    engine=engine.value, dirty=int(dirty.value),
+                    read_off=np.concatenate([[0], np.cumsum(n_read.astype(np.int64))]))
 
     def crop_box(self, pts, mn, mx, origin):
         """getPointsInOrientedBox (filteringUtils.cpp:619-637) on device: returns (kept xyz in

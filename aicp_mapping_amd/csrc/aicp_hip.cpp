@@ -841,22 +841,8 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
     dRdesc = ctx->rdesc.as<PairDesc>();
     dRstate = ctx->rstate.as<PairState>();
     std::memcpy(ctx->pin_rdesc.p, B->rdesc.data(), R * sizeof(PairDesc));
-    // matcher treelet records allotted per reference (kernels_tree.hip: at most 1 + 4 per inner
-    // node at even depth); leaf slots hold a 4-bit count, so larger buckets use Trav<1>
-    ctx->tl_total = 0;
-    if (cfg->bucket_size <= 15) {
-      for (size_t r = 0; r < R; ++r) {
-        PairDesc& rd = ctx->pin_rdesc.as<PairDesc>()[r];
-        rd.tl_off = (uint32_t)ctx->tl_total;
-        rd.tl_cap = (uint32_t)(4 * (uint64_t)rd.n_ref + 4);
-        ctx->tl_total += rd.tl_cap;
-      }
-      if (ctx->tl_total >= (1ull << 28)) ctx->tl_total = 0;  // 32-bit byte offsets do not fit: Trav<1>
-      // the NN kernel's LDS frames keep a node id (< 16 * (n_ref + 1)) in 26 bits
-      for (size_t r = 0; r < R; ++r)
-        if (ctx->pin_rdesc.as<PairDesc>()[r].n_ref > 4000000u) ctx->tl_total = 0;
-      if (ctx->opt.nn_engine == 1) ctx->tl_total = 0;
-    }
+    // matcher treelet records allotted per reference, or none: Trav<1> on the node records
+    ctx->tl_total = plan_treelets(ctx->pin_rdesc.as<PairDesc>(), R, cfg->bucket_size, ctx->opt.nn_engine);
     HIPC(hipStreamWaitEvent(s2, ctx->ev[14], 0));  // the reference points (not the readings) are on the device
     HIPC(hipEventRecord(ctx->ev[8], s2));
     uint64_t n_ref_max = 0;
@@ -2064,6 +2050,175 @@ int aicp_hip_test_tree(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* counts,
   HIPC(hipMemcpy(out_bpts, ctx->bpts.p, (size_t)total * 16, hipMemcpyDeviceToHost));
   HIPC(hipMemcpy(out_ctl, T.tw.ctl, sizeof(TreeCtl), hipMemcpyDeviceToHost));
   return rc;
+}
+
+// The production NN launch (launch_active_list, then launch_icp_nn with the grid and engine
+// run_batch gives it) on given references, readings and per-step transforms. The trees are the
+// matcher's batched build as aicp_hip_test_tree runs it (no centring), the treelets matcher_trees'
+// and the engine plan_treelets' choice. The three result arrays live in buffers of this call, 64
+// guard words on both sides, refilled with sentinels before every step. Every argument is
+// checked before the device is touched. Non-finite query coordinates are out of scope (libnabo
+// gives no order for them).
+int aicp_hip_test_nn(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* ref_counts, const float* ref_pts,
+                     int32_t bucket, size_t n_pairs, const uint32_t* pair_ref, const uint32_t* n_read,
+                     const float* read_c, size_t n_steps, const float* T, const uint8_t* active, float epsilon,
+                     float max_dist, int32_t* out_match, float* out_d2, uint32_t* out_touched, int32_t* out_ids,
+                     int32_t* out_engine, uint64_t* out_dirty) {
+  if (!ctx || !ref_counts || !ref_pts || !pair_ref || !n_read || !read_c || !T || !out_match || !out_d2 ||
+      !out_touched || !out_ids || !out_engine || !out_dirty)
+    return AICP_ERR_INVALID;
+  if (n_refs == 0 || n_refs > (size_t)kMaxPairs || n_pairs == 0 || n_pairs > (size_t)kMaxPairs || n_steps == 0 ||
+      bucket < 1 || bucket > 4096)
+    return AICP_ERR_INVALID;
+  if (!(epsilon >= 0.f) || !(max_dist >= 0.f)) return AICP_ERR_INVALID;  // (negative or NaN)
+  const size_t R = n_refs, P = n_pairs;
+  uint64_t total_ref = 0, n_max = 0, total = 0;
+  for (size_t r = 0; r < R; ++r) {
+    if (ref_counts[r] == 0) return AICP_ERR_INVALID;
+    total_ref += ref_counts[r];
+    n_max = std::max<uint64_t>(n_max, ref_counts[r]);
+  }
+  for (size_t p = 0; p < P; ++p) {
+    if (n_read[p] == 0 || pair_ref[p] >= R) return AICP_ERR_INVALID;
+    total += n_read[p];
+  }
+  if (total_ref >= (1ull << 28) || total >= (1ull << 28) || total * n_steps >= (1ull << 32)) return AICP_ERR_INVALID;
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  ctx->refc.invalidate();  // (ctx->bpts / nodes / tl are rewritten)
+  std::vector<PairDesc> rdesc(R, PairDesc{}), desc(P, PairDesc{});
+  uint32_t off = 0;
+  for (size_t r = 0; r < R; ++r) {
+    rdesc[r].ref_off = off;
+    rdesc[r].n_ref = ref_counts[r];
+    rdesc[r].ratio = 0.5f;
+    rdesc[r].ref_id = (int32_t)r;
+    ident4(rdesc[r].Tin);
+    ident4(rdesc[r].Tmean);
+    off += ref_counts[r];
+  }
+  ctx->tl_total = plan_treelets(rdesc.data(), R, bucket, ctx->opt.nn_engine);
+  off = 0;
+  for (size_t p = 0; p < P; ++p) {
+    PairDesc& d = desc[p];
+    d.ref_off = rdesc[pair_ref[p]].ref_off;
+    d.n_ref = rdesc[pair_ref[p]].n_ref;
+    d.read_off = off;
+    d.n_read = n_read[p];
+    d.ratio = 1.f;
+    d.ref_id = (int32_t)pair_ref[p];
+    ident4(d.Tin);
+    off += n_read[p];
+  }
+  constexpr size_t kGuard = 64;
+  const size_t words = (size_t)total + 2 * kGuard;
+  struct Local {  // freed on every return
+    DevBuf read_c, match, d2, touch;
+    ~Local() {
+      release(read_c);
+      release(match);
+      release(d2);
+      release(touch);
+    }
+  } loc;
+  HIPC(ensure(loc.read_c, total * 16));
+  HIPC(ensure(loc.match, words * 4));
+  HIPC(ensure(loc.d2, words * 4));
+  HIPC(ensure(loc.touch, words * 4));
+  HIPC(ensure(ctx->ref1, total_ref * 16));
+  HIPC(ensure(ctx->rdesc, R * sizeof(PairDesc)));
+  HIPC(ensure(ctx->desc, P * sizeof(PairDesc)));
+  HIPC(ensure(ctx->state, P * sizeof(PairState)));
+  HIPC(ensure(ctx->active, active_list_bytes(total, P)));
+  HIPC(ensure(ctx->ctrs, kCtrWords * 4));
+  {
+    std::vector<float> pk(4 * (size_t)std::max(total_ref, total));
+    pack_xyz4(ref_pts, total_ref, 12, pk.data());
+    HIPC(hipMemcpy(ctx->ref1.p, pk.data(), total_ref * 16, hipMemcpyHostToDevice));
+    pack_xyz4(read_c, total, 12, pk.data());
+    HIPC(hipMemcpy(loc.read_c.p, pk.data(), total * 16, hipMemcpyHostToDevice));
+  }
+  PairDesc* dRdesc = ctx->rdesc.as<PairDesc>();
+  PairDesc* dDesc = ctx->desc.as<PairDesc>();
+  PairState* dState = ctx->state.as<PairState>();
+  HIPC(hipMemcpy(dRdesc, rdesc.data(), R * sizeof(PairDesc), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(dDesc, desc.data(), P * sizeof(PairDesc), hipMemcpyHostToDevice));
+  // the trees (aicp_hip_test_tree's build), then the treelets (matcher_trees')
+  TreeBufs& Tb = ctx->tb[1];
+  int rc = device_trees_begin(Tb, ctx->err, s, R, total_ref, dRdesc, ctx->ref1.as<float4>(), 0, bucket, ctx->bpts,
+                              ctx->nodes);
+  if (rc) return rc;
+  rc = device_trees_end(Tb, ctx->err, s, R, total_ref, dRdesc, bucket, ctx->bpts, ctx->nodes,
+                        plan_levels(n_max, Tb, ctx->opt.tree_plan));
+  if (rc) return rc;
+  if (ctx->tl_total) {
+    const uint32_t cap = (uint32_t)(2 * total_ref + 2);  // node records allotted
+    HIPC(ensure(ctx->tl, ctx->tl_total * 16));
+    HIPC(ensure(ctx->ptl, ctx->tl_total * 8));
+    HIPC(ensure(ctx->tl_rank, ((size_t)cap + 1) * 4));
+    HIPC(launch_treelets(s, (int)R, cap, dRdesc, ctx->nodes.as<uint4>(), bucket, ctx->tl_rank.as<uint32_t>(),
+                         ctx->tl.as<uint4>(), ctx->ptl.as<uint2>(), Tb.tw));
+    HIPC(hipMemcpyAsync(Tb.pin_ctl.p, Tb.tw.ctl, sizeof(TreeCtl), hipMemcpyDeviceToHost, s));
+  }
+  launch_pairs_from_refs(s, (int)P, dDesc, dRdesc);
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(s));
+  // a tree deeper than the device stacks, or treelets beyond their allotment: no search is run
+  rc = device_trees_check(Tb, ctx->err);
+  if (rc) return rc;
+  if (ctx->tl_total && (Tb.pin_ctl.as<TreeCtl>()->error & 4))
+    FAIL(AICP_ERR_HIP, "matcher treelets exceed their allotment");
+  *out_engine = ctx->tl_total ? 0 : 1;
+  {
+    std::vector<float> b4(4 * (size_t)total_ref);
+    HIPC(hipMemcpy(b4.data(), ctx->bpts.p, total_ref * 16, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < total_ref; ++i) std::memcpy(out_ids + i, &b4[4 * i + 3], 4);
+  }
+  HIPC(hipMemsetAsync(ctx->ctrs.p, 0, kCtrWords * 4, s));
+  HIPC(hipMemsetAsync(dState, 0, P * sizeof(PairState), s));
+  launch_init_state(s, (int)P, dDesc, dState);
+  std::vector<PairState> hs(P);
+  HIPC(hipMemcpyAsync(hs.data(), dState, P * sizeof(PairState), hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  aicp_icp_config tc{};
+  tc.nn_epsilon = epsilon;
+  tc.nn_max_dist = max_dist;
+  const IcpParams prm = icp_params(&tc);
+  ActiveList* al = ctx->active.as<ActiveList>();
+  const uint4* tl = ctx->tl_total ? ctx->tl.as<uint4>() : nullptr;
+  const uint2* ptl = ctx->tl_total ? ctx->ptl.as<uint2>() : nullptr;
+  constexpr uint32_t kSentinel = AICP_TEST_NN_SENTINEL, kTouchSentinel = AICP_TEST_NN_TOUCH_SENTINEL;
+  std::vector<uint32_t> back(3 * words);
+  uint64_t dirty = 0;
+  for (size_t k = 0; k < n_steps; ++k) {
+    for (size_t p = 0; p < P; ++p) {
+      std::memcpy(hs[p].T, T + 16 * (k * P + p), 64);
+      hs[p].active = !active || active[k * P + p] ? 1 : 0;
+    }
+    HIPC(hipMemcpyAsync(dState, hs.data(), P * sizeof(PairState), hipMemcpyHostToDevice, s));
+    HIPC(hipMemsetD32Async((hipDeviceptr_t)loc.match.p, (int)kSentinel, words, s));
+    HIPC(hipMemsetD32Async((hipDeviceptr_t)loc.d2.p, (int)kSentinel, words, s));
+    HIPC(hipMemsetD32Async((hipDeviceptr_t)loc.touch.p, (int)kTouchSentinel, words, s));
+    launch_active_list(s, (int)P, dDesc, dState, al, ctx->ctrs.as<uint32_t>());
+    launch_icp_nn(s, (int)total, dDesc, dState, al, loc.read_c.as<float4>(), ctx->nodes.as<uint4>(), tl, nullptr,
+                  ctx->bpts.as<float4>(), ptl, loc.match.as<int32_t>() + kGuard, loc.d2.as<float>() + kGuard,
+                  loc.touch.as<uint32_t>() + kGuard, ctx->ctrs.as<uint32_t>(), prm);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(back.data(), loc.match.p, words * 4, hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(back.data() + words, loc.d2.p, words * 4, hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(back.data() + 2 * words, loc.touch.p, words * 4, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    for (size_t a = 0; a < 3; ++a) {
+      const uint32_t* w = back.data() + a * words;
+      const uint32_t want = a == 2 ? kTouchSentinel : kSentinel;
+      for (size_t g = 0; g < kGuard; ++g) dirty += (w[g] != want) + (w[kGuard + total + g] != want);
+    }
+    std::memcpy(out_match + k * total, back.data() + kGuard, total * 4);
+    std::memcpy(out_d2 + k * total, back.data() + words + kGuard, total * 4);
+    std::memcpy(out_touched + k * total, back.data() + 2 * words + kGuard, total * 4);
+  }
+  *out_dirty = dirty;
+  return AICP_OK;
 }
 
 void aicp_hip_default_prefilter(aicp_prefilter_params* p) {

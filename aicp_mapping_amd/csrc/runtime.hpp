@@ -206,6 +206,24 @@ int device_trees_check(TreeBufs& T, std::string& err);
 // force: aicp_hip_options::tree_plan
 int plan_levels(uint64_t n_max, const TreeBufs& T, int force, bool lean = false);
 int check_cfg(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, int flags);
+// The matcher's NN engine for R references: their treelet records allotted (rd[r].tl_off / tl_cap;
+// kernels_tree.hip: at most 1 + 4 per inner node at even depth), returned as the batch's total, or
+// 0 where treelets do not fit and the NN kernel runs on the node records (Trav<1>): leaf slots hold
+// a 4-bit count (bucket <= 15), 32-bit byte offsets hold fewer than 2^28 records, the NN kernel's
+// LDS frames keep a node id (< 16 * (n_ref + 1)) in 26 bits (n_ref <= 4 M), and
+// aicp_hip_options::nn_engine = 1 asks for the node records.
+inline uint64_t plan_treelets(PairDesc* rd, size_t R, int bucket, int nn_engine) {
+  if (bucket > 15) return 0;
+  uint64_t total = 0;
+  bool fits = nn_engine != 1;
+  for (size_t r = 0; r < R; ++r) {
+    rd[r].tl_off = (uint32_t)total;
+    rd[r].tl_cap = (uint32_t)(4 * (uint64_t)rd[r].n_ref + 4);
+    total += rd[r].tl_cap;
+    if (rd[r].n_ref > 4000000u) fits = false;
+  }
+  return fits && total < (1ull << 28) ? total : 0;
+}
 // what the ICP kernels take of a chain (prof_slot 0: the NN launches' callers number it)
 inline IcpParams icp_params(const aicp_icp_config* cfg) {
   IcpParams ip{};

@@ -400,7 +400,9 @@ static int win_upload(C* ctx, SeqState* S, const aicp_icp_config* cfg, const aic
   for (size_t i = 0; i < np; ++i) nread += rd[w.p0 + i].n;
   // slot buffers (sizes grow to the largest window seen)
   const size_t tl_cap = 4 * (size_t)n_ref + 4;
-  const bool use_tl = cfg->bucket_size <= 15 && n_ref <= 4000000u && tl_cap < (1ull << 28) && S->opt.nn_engine != 1;
+  PairDesc one{};
+  one.n_ref = n_ref;
+  const bool use_tl = plan_treelets(&one, 1, cfg->bucket_size, S->opt.nn_engine) != 0;  // (its allotment: tl_cap)
   constexpr uint32_t kRedBlk = kReduceBlock;
   if (sl.used) {
     // the slot's previous window (w - K) must be done before its buffers are rewritten, and so

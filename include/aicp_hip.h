@@ -1007,6 +1007,41 @@ int aicp_hip_test_tree(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* counts,
                        int32_t* out_depth, float* out_mean /* 3 * n_refs */,
                        uint32_t* out_nodes /* 4 * (2 * total + 2) */, float* out_bpts /* 4 * total */,
                        uint32_t* out_ctl /* AICP_TEST_TREE_CTL_WORDS */);
+/* Test surface: the ICP loop's NN search, k_icp_nn as the loop launches it, query by query. The
+ * n_refs reference clouds (ref_pts, 3 floats per point, ref_counts[r] points each, one after
+ * another) are used as given, with no centring: their trees are built as one batch, as
+ * aicp_hip_test_tree builds them, with leaf size `bucket`, then the matcher's treelets where the
+ * batch's rule selects them: bucket <= 15, fewer than 2^28 treelet records, no reference above
+ * 4 M points, nn_engine 0. Pair p searches reference pair_ref[p] (pairs may share one) for its
+ * n_read[p] readings (read_c, 3 floats each, the pairs one after another). Step k writes
+ * T[16 (k n_pairs + p) ..] (column-major) into pair p's state as T_iter and active[k n_pairs + p]
+ * as its active flag (active null: every pair, every step), then runs the active list and the NN
+ * launch with the production grid, epsilon and max_dist as a chain's KDTreeMatcher gives them.
+ * A query is ((T0 x + T1 y) + T2 z) + T3 per row in float. Non-finite query coordinates are out of
+ * scope: libnabo defines no result for them.
+ * Per step and reading, at k * total + the pair's prefix offset, total = sum(n_read): out_match
+ * (the bucket position of the match within the pair's reference, -1: none within max_dist),
+ * out_d2 (+inf then), out_touched (inner nodes << 16 | bucket points, each saturated at 65535).
+ * Before every step the three device arrays are filled with AICP_TEST_NN_SENTINEL (match, d2: a
+ * NaN and a position no search gives) and AICP_TEST_NN_TOUCH_SENTINEL (no inner node but more
+ * points than a bucket holds), 64 guard words on both sides included: a reading of an inactive
+ * pair keeps its sentinels, and out_dirty counts the guard words that changed (0 expected).
+ * out_ids: the input id (within its cloud) of every bucket position, reference r's at its prefix
+ * offset. out_engine: 0 treelets (Trav2C), 1 node records (Trav<1>).
+ * A tree deeper than 47 levels returns AICP_ERR_UNSUPPORTED before any search runs. Invalidates
+ * the context's reference cache.
+ * AICP_ERR_INVALID, before any device work: a null pointer (active may be null), no reference, pair
+ * or step or more than 4096 references or pairs, a count of 0, a pair_ref >= n_refs, bucket outside
+ * [1, 4096], sum(ref_counts) or total >= 2^28, a negative or NaN epsilon or max_dist,
+ * n_steps * total >= 2^32. */
+#define AICP_TEST_NN_SENTINEL 0x7FF8DEADu
+#define AICP_TEST_NN_TOUCH_SENTINEL 0x0000DEADu
+int aicp_hip_test_nn(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* ref_counts, const float* ref_pts,
+                     int32_t bucket, size_t n_pairs, const uint32_t* pair_ref, const uint32_t* n_read,
+                     const float* read_c, size_t n_steps, const float* T /* 16 * n_steps * n_pairs */,
+                     const uint8_t* active /* n_steps * n_pairs, nullable */, float epsilon, float max_dist,
+                     int32_t* out_match, float* out_d2, uint32_t* out_touched /* each n_steps * total */,
+                     int32_t* out_ids /* sum(ref_counts) */, int32_t* out_engine, uint64_t* out_dirty);
 /* Test surface: the raw streams' ingest alone. rows: n rows of `stride` bytes (>= 12, a multiple of
  * 4), xyz first, uploaded as the raw streams upload them (at most 16 bytes: verbatim; wider: packed
  * on the host), then k_stream_ingest: out4[4 i ..] = (x, y, z, 1), moved by T (nullable, column-major

@@ -265,6 +265,65 @@ struct Searcher {
   }
 };
 
+// Searcher::recurse with per-query counters (ao_tree_nn1): the same statements in the same order.
+// depth: the depth of node n; nest: far descents entered and not yet left.
+struct CountedSearcher : Searcher {
+  int32_t nest = 0, maxNest = 0, maxFarDepth = -1;
+  float maxBound = 0;
+
+  bool far(float rd, int depth) {
+    if (rd > maxBound) maxBound = rd;
+    if (!(rd <= maxRadius2 && rd * maxError2 < heap->head())) return false;
+    if (++nest > maxNest) maxNest = nest;
+    if (depth > maxFarDepth) maxFarDepth = depth;
+    return true;
+  }
+  void recurseCounted(unsigned n, float rd, int depth) {
+    const Node& node = t->nodes[n];
+    const uint32_t cd = getDim(node.dimChildBucketSize);
+    if (cd == kDim) {
+      const BucketEntry* bucket = &t->buckets[node.bucketIndex];
+      const uint32_t bucketSize = getChildBucketSize(node.dimChildBucketSize);
+      for (uint32_t i = 0; i < bucketSize; ++i) {
+        float dist = 0;
+        for (unsigned d = 0; d < kDim; ++d) {
+          const float diff = q[d] - bucket->pt[d];
+          dist += diff * diff;
+        }
+        if (dist <= maxRadius2 && dist < heap->head() &&
+            (allowSelf || dist > std::numeric_limits<float>::epsilon()))
+          heap->replaceHead(bucket->index, dist);
+        ++bucket;
+      }
+      touchedPts += bucketSize;
+      return;
+    }
+    touchedNodes++;
+    const unsigned rightChild = getChildBucketSize(node.dimChildBucketSize);
+    const float old_off = off[cd];
+    const float new_off = q[cd] - node.cutVal;
+    if (new_off > 0) {
+      recurseCounted(rightChild, rd, depth + 1);
+      rd += -old_off * old_off + new_off * new_off;
+      if (far(rd, depth)) {
+        off[cd] = new_off;
+        recurseCounted(n + 1, rd, depth + 1);
+        off[cd] = old_off;
+        --nest;
+      }
+    } else {
+      recurseCounted(n + 1, rd, depth + 1);
+      rd += -old_off * old_off + new_off * new_off;
+      if (far(rd, depth)) {
+        off[cd] = new_off;
+        recurseCounted(rightChild, rd, depth + 1);
+        off[cd] = old_off;
+        --nest;
+      }
+    }
+  }
+};
+
 int tree_build_impl(const float* pts, int64_t n, int64_t stride, int bucket, ao_tree* t) {
   t->bucketSize = (uint32_t)bucket;
   t->cloud.resize(3 * (size_t)n);
@@ -951,6 +1010,35 @@ int ao_tree_knn(const ao_tree* t, const float* q, int64_t nq, int64_t qstride, i
   if (!t || k < 1) return 2;
   tree_knn_impl(t, q, nq, qstride, k, epsilon, allow_self != 0, max_radius, ids, d2,
                 touched_points, touched_nodes);
+  return 0;
+}
+
+int ao_tree_nn1(const ao_tree* t, const float* q, int64_t nq, int64_t qstride, float epsilon,
+                float max_radius, int32_t* ids, float* d2, uint32_t* touched_points,
+                uint32_t* touched_nodes, int32_t* nest, int32_t* far_depth, float* max_bound) {
+  if (!t || !q || nq < 0 || qstride < 3 || !ids || !d2 || !touched_points || !touched_nodes || !nest ||
+      !far_depth || !max_bound)
+    return 2;
+  Heap heap(1);
+  for (int64_t i = 0; i < nq; ++i) {
+    CountedSearcher s;
+    s.t = t;
+    s.heap = &heap;
+    s.maxError2 = (1 + epsilon) * (1 + epsilon);
+    s.maxRadius2 = max_radius * max_radius;
+    s.allowSelf = true;
+    s.q = q + i * qstride;
+    s.off[0] = s.off[1] = s.off[2] = 0;
+    heap.reset();
+    s.recurseCounted(0, 0, 0);
+    ids[i] = heap.val[0] == kInf ? -1 : heap.idx[0];
+    d2[i] = heap.val[0];
+    touched_points[i] = (uint32_t)s.touchedPts;
+    touched_nodes[i] = (uint32_t)s.touchedNodes;
+    nest[i] = s.maxNest;
+    far_depth[i] = s.maxFarDepth;
+    max_bound[i] = s.maxBound;
+  }
   return 0;
 }
 

@@ -74,6 +74,14 @@ int ao_tree_knn(const ao_tree* t, const float* q, int64_t nq, int64_t qstride_fl
                 float epsilon, int allow_self, float max_radius, int32_t* ids, float* d2,
                 uint64_t* touched_points, uint64_t* touched_nodes);
 
+/* The matcher's 1-NN (allowSelf) query by query: libnabo's recurse with counters only. Per query:
+ * id (-1: none within max_radius), d2 (+inf then), touched bucket points and inner nodes, the
+ * deepest nesting of far descents, the greatest depth of a node whose far child was entered
+ * (-1: none), and the largest far bound computed (0: none). */
+int ao_tree_nn1(const ao_tree* t, const float* q, int64_t nq, int64_t qstride_floats, float epsilon,
+                float max_radius, int32_t* ids, float* d2, uint32_t* touched_points,
+                uint32_t* touched_nodes, int32_t* nest, int32_t* far_depth, float* max_bound);
+
 /* The two-pass partition of buildNodes, sequential form and the prefix-count form used by a
  * parallel build; both return the permutation of values (for cross-checking). */
 int ao_partition_sequential(float* v, int32_t* idx, int32_t count, float cut, int32_t* br1,

@@ -110,6 +110,8 @@ def lib():
         L.ao_tree_export.argtypes = [vp, ip, fp, ip, ip, ip]
         L.ao_tree_knn.argtypes = [vp, fp, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_int,
                                   C.c_float, ip, fp, up, up]
+        u32 = C.POINTER(C.c_uint32)
+        L.ao_tree_nn1.argtypes = [vp, fp, C.c_int64, C.c_int64, C.c_float, C.c_float, ip, fp, u32, u32, ip, ip, fp]
         L.ao_partition_sequential.argtypes = [fp, ip, C.c_int32, C.c_float, ip, ip]
         L.ao_partition_parallel.argtypes = [fp, ip, C.c_int32, C.c_float, ip, ip]
         L.ao_surface_normals.argtypes = [fp, C.c_int64, C.c_int64, C.c_int, fp, fp, ip]
@@ -182,6 +184,21 @@ class Tree:
         lib().ao_tree_knn(self.h, _f(q), nq, q.shape[1], k, eps, int(allow_self), max_radius,
                           ids.ctypes.data_as(C.POINTER(C.c_int32)), _f(d2), C.byref(tp), C.byref(tn))
         return ids, d2, tp.value, tn.value
+
+    def nn1(self, q, eps=0.0, max_radius=float("inf")):
+        """The matcher's 1-NN query by query (ao_tree_nn1): dict(id, d2, points, nodes, nest,
+        far_depth, max_bound), one entry per query each."""
+        q = _pts(q)
+        nq = q.shape[0]
+        o = dict(id=np.zeros(nq, np.int32), d2=np.zeros(nq, np.float32), points=np.zeros(nq, np.uint32),
+                 nodes=np.zeros(nq, np.uint32), nest=np.zeros(nq, np.int32), far_depth=np.zeros(nq, np.int32),
+                 max_bound=np.zeros(nq, np.float32))
+        ip, up = C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
+        rc = lib().ao_tree_nn1(self.h, _f(q), nq, q.shape[1], eps, max_radius, o["id"].ctypes.data_as(ip), _f(o["d2"]),
+                               o["points"].ctypes.data_as(up), o["nodes"].ctypes.data_as(up),
+                               o["nest"].ctypes.data_as(ip), o["far_depth"].ctypes.data_as(ip), _f(o["max_bound"]))
+        assert rc == 0
+        return o
 
 
 def partition(v, cut, parallel=False):
