@@ -58,6 +58,9 @@ EXPORTS = [
     "aicp_hip_default_accum_params", "aicp_hip_accum_create", "aicp_hip_accum_free", "aicp_hip_accum_push",
     "aicp_hip_accum_state", "aicp_hip_accum_clear", "aicp_hip_accum_download", "aicp_hip_accum_prefilter",
     "aicp_hip_accum_pose_matrix", "aicp_hip_motion_gate",
+    "aicp_hip_session_create", "aicp_hip_session_free", "aicp_hip_session_start", "aicp_hip_session_start_accum",
+    "aicp_hip_session_process", "aicp_hip_session_process_accum", "aicp_hip_session_state",
+    "aicp_hip_session_reference", "aicp_hip_session_last_timing",
 ]
 
 
@@ -83,7 +86,10 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_pipeline", "aicp_hip_sequence_run_risk",  # the classifier and the risk gate
            "aicp_hip_default_accum_params", "aicp_hip_accum_create", "aicp_hip_accum_free", "aicp_hip_accum_push",
            "aicp_hip_accum_state", "aicp_hip_accum_clear", "aicp_hip_accum_download", "aicp_hip_accum_prefilter",
-           "aicp_hip_accum_pose_matrix", "aicp_hip_motion_gate"}  # the sweep accumulator
+           "aicp_hip_accum_pose_matrix", "aicp_hip_motion_gate",  # the sweep accumulator
+           "aicp_hip_session_create", "aicp_hip_session_free", "aicp_hip_session_start",
+           "aicp_hip_session_start_accum", "aicp_hip_session_process", "aicp_hip_session_process_accum",
+           "aicp_hip_session_state", "aicp_hip_session_reference", "aicp_hip_session_last_timing"}  # the live session
 
 
 class IcpConfig(C.Structure):
@@ -612,6 +618,20 @@ def _load():
         L.aicp_hip_accum_pose_matrix.argtypes = [dp, fp]
         L.aicp_hip_accum_pose_matrix.restype = None
         L.aicp_hip_motion_gate.argtypes = [dp, dp, C.c_double, C.c_double]
+    if hasattr(L, "aicp_hip_session_create"):
+        u32p, dp, clp = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(Cloud)
+        srp = C.POINTER(SequenceResult)
+        L.aicp_hip_session_create.argtypes = [vp, cfgp, C.POINTER(SequenceParams), C.POINTER(PrefilterParams),
+                                              C.POINTER(vp)]
+        L.aicp_hip_session_free.argtypes = [vp, vp]
+        L.aicp_hip_session_free.restype = None
+        L.aicp_hip_session_start.argtypes = [vp, vp, clp]
+        L.aicp_hip_session_start_accum.argtypes = [vp, vp, vp, dp]
+        L.aicp_hip_session_process.argtypes = [vp, vp, clp, fp, srp, u32p]
+        L.aicp_hip_session_process_accum.argtypes = [vp, vp, vp, dp, fp, srp, u32p]
+        L.aicp_hip_session_state.argtypes = [vp, vp, up, ip, szp, fp, ip]
+        L.aicp_hip_session_reference.argtypes = [vp, vp, fp, sz, szp, dp]
+        L.aicp_hip_session_last_timing.argtypes = [vp, dp, dp]
     return L
 
 

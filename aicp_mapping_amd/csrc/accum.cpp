@@ -73,6 +73,19 @@ int sync_tails(aicp_hip_ctx* ctx, aicp_hip_accum* a, const uint32_t** t) {
 
 }  // namespace
 
+namespace aicp {
+namespace rt {
+int accum_resident(aicp_hip_ctx* ctx, aicp_hip_accum* acc, const float4** pts, size_t* n) {
+  const uint32_t* t = nullptr;
+  const int rc = sync_tails(ctx, acc, &t);
+  if (rc) return rc;
+  *pts = acc->pts.as<float4>();
+  *n = t[acc->counter];
+  return AICP_OK;
+}
+}  // namespace rt
+}  // namespace aicp
+
 extern "C" {
 
 void aicp_hip_default_accum_params(aicp_accum_params* p) {

@@ -1363,10 +1363,11 @@ bool refcache_begin(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_pa
     }
     for (int k = 0; k < 3; ++k) one_origin &= q.ref_origin[k] == p.ref_origin[k];
   }
-  const bool same = (c.trees || c.ovl) && c.ptr == p.ref && c.n == p.n_ref && c.stride == p.ref_stride &&
+  const bool same = (c.trees || c.ovl) && c.owner == 0 && c.ptr == p.ref && c.n == p.n_ref && c.stride == p.ref_stride &&
                     c.pts.size() == 3 * (size_t)p.n_ref && same_points(ctx_pool(ctx), p.ref, p.n_ref, p.ref_stride, c.pts.data());
   if (!same) {  // a new reference (or the cached one changed in place): rebuilt and kept by this call
     c.invalidate();
+    c.owner = 0;
     c.ptr = p.ref;
     c.n = p.n_ref;
     c.stride = p.ref_stride;
@@ -2702,22 +2703,60 @@ static int ingest_upload(aicp_hip_ctx* ctx, const float* pts, size_t n, size_t s
 
 int stream_prefilter_check(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf) { return pf_check(ctx, pf); }
 
+// refcache_begin for a reference that lives on the device (runtime.hpp): nothing is copied or
+// compared, the cached reference is the caller's when it carries the caller's `owner`
+void refcache_begin_resident(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, uint64_t owner, uint64_t n_ref,
+                             const double origin[3], double res, int flags) {
+  RefCache& c = ctx->refc;
+  c.use = c.hit_trees = c.hit_ovl = false;
+  if (!ctx->opt.reference_cache) {
+    c.invalidate();
+    return;
+  }
+  const bool same = (c.trees || c.ovl) && c.owner == owner && c.n == n_ref;
+  if (!same) {
+    c.invalidate();
+    c.owner = owner;
+    c.ptr = nullptr;
+    c.n = n_ref;
+    c.stride = 0;
+    c.pts.clear();
+  }
+  c.use = true;
+  if (same) {
+    c.hit_trees = (flags & AICP_RUN_ICP) && c.trees && c.bucket == cfg->bucket_size && c.knn == cfg->knn_normals;
+    c.hit_ovl = (flags & AICP_RUN_OVERLAP) && c.ovl && c.res == res && c.origin[0] == origin[0] &&
+                c.origin[1] == origin[1] && c.origin[2] == origin[2];
+  }
+}
+
 // setAndFilterReading (app.cpp:77-100) for one raw reading of a map stream, all on the device
 int stream_prefilter_raw(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf, const aicp_cloud& c, const float* d_initT,
                          double* d_origin, float4* dst, uint32_t* kept) {
+  return stream_ingest_rows(ctx, pf, c.pts, c.n, c.stride, nullptr, d_initT, d_origin, dst, kept);
+}
+
+int stream_ingest_rows(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf, const float* hpts, size_t n, size_t stride,
+                       const float4* dpts, const float* d_initT, double* d_origin, float4* dst, uint32_t* kept) {
   *kept = 0;
   hipStream_t s = ctx->stream;
-  PfLayout Lo;
-  int rc = pf_layout(ctx, c.n, &Lo);
+  PfLayout Lo{};
+  int rc = pf ? pf_layout(ctx, n, &Lo) : AICP_OK;
   if (rc) return rc;
-  const void* drows = nullptr;
-  size_t dstride = 0;
-  rc = ingest_upload(ctx, c.pts, c.n, c.stride, 0, &drows, &dstride);
-  if (rc) return rc;
-  launch_stream_ingest(s, (int)c.n, drows, dstride, d_initT, d_origin, Lo.pts4);
+  const void* drows = dpts;
+  size_t dstride = 16;
+  if (!dpts) {
+    rc = ingest_upload(ctx, hpts, n, stride, 0, &drows, &dstride);
+    if (rc) return rc;
+  }
+  launch_stream_ingest(s, (int)n, drows, dstride, d_initT, d_origin, pf ? Lo.pts4 : dst);
   HIPC(hipGetLastError());
+  if (!pf) {
+    *kept = (uint32_t)n;
+    return AICP_OK;
+  }
   PfRun o;
-  rc = pf_core(ctx, pf, c.n, Lo, &o);  // (returns with the stream idle)
+  rc = pf_core(ctx, pf, n, Lo, &o);  // (returns with the stream idle)
   if (rc) return rc;
   if (!o.V || !o.n_out) return AICP_OK;
   HIPC(hipMemcpyAsync(dst, o.out4, (size_t)o.n_out * 16, hipMemcpyDeviceToDevice, s));

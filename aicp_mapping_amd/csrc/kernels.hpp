@@ -363,6 +363,20 @@ void launch_stream_ingest(hipStream_t s, int n, const void* rows, size_t stride,
 void launch_stream_commit(hipStream_t s, int np, const PairState* st, const float* T, const double* origin,
                           StreamRules r, StreamState* S, StreamRec* rec);
 
+// ---- live App session (kernels_session.hip, session.cpp) --------------------------------------
+struct SessionHeader {  // what describes the session's current reference, beside its points
+  uint32_t count;       // points
+  int32_t id;           // the process call whose reading it is (-1: the first cloud)
+  int32_t pad[2];
+  double origin[3];     // its sensor origin (corrected_origin of that reading)
+  double pad2;
+};
+// Behind launch_stream_commit of one reading (np = 1), no host decision in between: if rec->append,
+// ref[i] = apply4(T, read[i]) for the n points of the reading as registered (k_transform's
+// expression) and hdr = {n, id, rec->corrected_origin}; otherwise nothing is written.
+void launch_session_promote(hipStream_t s, int n, const StreamRec* rec, const float* T, const float4* read, int32_t id,
+                            float4* ref, SessionHeader* hdr);
+
 // ---- pre-filter (kernels_prefilter.hip): regionGrowingUniformPlaneSegmentationFilter -------
 constexpr int kPfMaxNbrs = 16;  // RegionGrowing neighbours per point (edge mask bits)
 struct PfCtl {                  // device control block; lo = 0xFFFFFFFF, everything else 0 at start

@@ -1,0 +1,47 @@
+// kernels_session.hip — the device side of the live App session (session.cpp): what follows one
+// reading's registration without a host decision in between.
+//
+// k_stream_commit (kernels_map_stream.hip) with np = 1 and the built-map rules states
+// app.cpp:366-391, 414 for the frame-to-reference policy too: drop test, count towards
+// reference_update_frequency, corrected origin, initialT_ = correction * initialT_, and `append`
+// when this reading is the next reference. k_session_promote runs right behind it and does what the
+// record says: the reading as it was registered, moved by its correction, becomes the session's
+// reference (app.cpp:375-391: pcl::transformPointCloud in float, apply4's expression, no FMA).
+#include <hip/hip_runtime.h>
+
+#include "aicp_common.hpp"
+#include "icp_math.hpp"
+#include "kernels.hpp"
+
+namespace aicp {
+
+// One thread per point of the reading: one 128-bit load, one 128-bit store. Every thread reads the
+// record's append flag and the correction from device memory (the same addresses for the whole
+// grid: the branch is uniform, the loads are served from the scalar / L2 path). Thread 0 of block 0
+// writes the header. ref never aliases read (the session's spare reference buffer).
+__global__ __launch_bounds__(256) void k_session_promote(int n, const StreamRec* __restrict__ rec,
+                                                         const float* __restrict__ T,
+                                                         const float4* __restrict__ read, int32_t id,
+                                                         float4* __restrict__ ref, SessionHeader* hdr) {
+  if (!rec->append) return;
+  float Tl[16];
+  for (int k = 0; k < 16; ++k) Tl[k] = T[k];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    hdr->count = (uint32_t)n;
+    hdr->id = id;
+    for (int k = 0; k < 3; ++k) hdr->origin[k] = rec->corrected_origin[k];
+  }
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = read[i];
+  float q[3];
+  apply4(Tl, p.x, p.y, p.z, q);
+  ref[i] = make_float4(q[0], q[1], q[2], 1.f);
+}
+
+void launch_session_promote(hipStream_t s, int n, const StreamRec* rec, const float* T, const float4* read, int32_t id,
+                            float4* ref, SessionHeader* hdr) {
+  if (n > 0) k_session_promote<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, rec, T, read, id, ref, hdr);
+}
+
+}  // namespace aicp

@@ -249,6 +249,10 @@ struct RefCache {
   const float* ptr = nullptr;
   uint64_t n = 0, stride = 0;
   std::vector<float> pts;
+  // a reference that lives on the device (session.cpp) has no host array: ptr is null, pts empty,
+  // and its identity is `owner`, a number the session takes from next_owner for every new
+  // reference (0: a caller's host array, the identity above)
+  uint64_t owner = 0, next_owner = 1;
   // ctx->bpts, bnrm, nodes, tl, ptl, rdesc, rstate hold its matcher tree, treelets and normals
   bool trees = false;
   int bucket = 0, knn = 0;
@@ -310,6 +314,19 @@ int map_crop_pairs(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float m
 int stream_prefilter_raw(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf, const aicp_cloud& c, const float* d_initT,
                          double* d_origin, float4* dst, uint32_t* kept);
 int stream_prefilter_check(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf);  // pf_check
+// stream_prefilter_raw for rows that may lie on the device already (session.cpp): dpts non-null: n
+// float4 rows on the device (the sweep accumulator's cloud, left unchanged; hpts / stride not read),
+// else the caller's rows are uploaded. pf null: no pre-filter, the n ingested points go straight to
+// dst and *kept = n (nothing is waited for then).
+int stream_ingest_rows(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf, const float* hpts, size_t n, size_t stride,
+                       const float4* dpts, const float* d_initT, double* d_origin, float4* dst, uint32_t* kept);
+// The reference cache's check for a one-pair call whose reference lives on the device under the
+// identity `owner` (RefCache::owner): sets what the call reuses and records, as refcache_begin does
+// for a host array. The caller clears RefCache::use after its run_batch (and invalidates on an error).
+void refcache_begin_resident(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, uint64_t owner, uint64_t n_ref,
+                             const double origin[3], double res, int flags);
+// the sweep accumulator's cloud where it lies (accum.cpp): waits for the stream, *n points at *pts
+int accum_resident(aicp_hip_ctx* ctx, aicp_hip_accum* acc, const float4** pts, size_t* n);
 // aicp_hip_prefilter on n device-resident points (float4, w = 1; left unchanged), moved first by T
 // (nullable, host, column-major) as aicp_hip_transform moves them; kept points packed xyz to out
 // (capacity cap points). For the sweep accumulator (accum.cpp).

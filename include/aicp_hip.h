@@ -904,6 +904,65 @@ int aicp_hip_sequence_run_risk(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, co
                                const double* poses /* 16*n */, size_t n_readings, float* out_T /* 16*n */,
                                aicp_sequence_result* out /* n */, aicp_pipeline_record* rec /* n */, size_t* n_done);
 
+/* ---- live App session: one reading per call, the reference resident on the device -------------
+ * App::processCloud (app.cpp:282-414) in frame-to-reference mode as the node runs it: a handle keeps
+ * App's state between calls, on the device: the current reference (points, sensor origin, id),
+ * initialT_, the count towards reference_update_frequency, and the last reading as it was
+ * registered. The rules are aicp_hip_sequence_run_raw's:
+ *   robot mode: the reading is pre-filtered as given;
+ *   debug mode (AICP_SEQ_DEBUG): the RAW reading is moved by the device's initialT_
+ *     (pcl::transformPointCloud, float), its origin becomes the translation of initialT_ * prior
+ *     pose, then it is pre-filtered;
+ *   with AICP_RUN_OVERLAP the octree overlap against the reference gives aicp_hip_autotune_ratio,
+ *     otherwise cfg->trimmed_ratio is used;
+ *   a reading with some |t_i| > max_correction_magnitude is dropped and leaves every piece of state
+ *     as it was, initialT_ included;
+ *   the reference_update_frequency-th accepted reading since the last update becomes the reference
+ *     (transformPointCloud by its correction in float, no FMA; origin: corrected_origin; the count
+ *     restarts), and initialT_ = correction * initialT_ after every accepted reading;
+ *   a reading the pre-filter empties has status AICP_ERR_INVALID; it, and any registration error,
+ *     ends the session as it ends App's worker (app.cpp:210): further process calls return
+ *     AICP_ERR_INVALID until aicp_hip_session_start.
+ * pf NULL: the clouds are already App's read_prefiltered (as aicp_hip_sequence_run takes them; debug
+ * mode then moves the filtered cloud, that entry point's documented order). pf non-NULL: the clouds
+ * are RAW and go through setAndFilterReading in App's order.
+ * A point-to-point chain (knn_normals 0) is accepted. A reading crosses the bus at most once (its
+ * raw rows), and not at all when it comes from a sweep accumulator, which is left as it is: the
+ * caller may aicp_hip_accum_clear as soon as the call returns. The reference's trees, treelets,
+ * normals and voxel map stay resident across readings in the context's reference cache; any other
+ * registration on the context in between takes the cache, and the session rebuilds them at its next
+ * reading with the same results. A session is driven from one thread at a time, on its context's
+ * stream; several sessions may share a context. */
+typedef struct aicp_hip_session aicp_hip_session;
+/* prm->flags: AICP_RUN_OVERLAP | AICP_SEQ_DEBUG | AICP_RUN_TIME_NN. cfg, prm and pf are copied. */
+int aicp_hip_session_create(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_sequence_params* prm,
+                            const aicp_prefilter_params* pf /* nullable */, aicp_hip_session** out);
+void aicp_hip_session_free(aicp_hip_ctx* ctx, aicp_hip_session* s);
+/* The first cloud (app.cpp:285-312): pre-filtered as given when pf is set; it becomes reference -1.
+ * Calling start again restarts the session (nothing processed, initialT_ = I, not ended). A first
+ * cloud the pre-filter empties is AICP_ERR_INVALID and leaves the session as it was. */
+int aicp_hip_session_start(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_cloud* first);
+int aicp_hip_session_start_accum(aicp_hip_ctx* ctx, aicp_hip_session* s, aicp_hip_accum* acc, const double origin[3]);
+/* One reading. out_T: its correction (column-major). out->reference: the index of the process call
+ * (counted from 0 since start) whose reading is the reference it was registered against, -1: the
+ * first cloud. kept (nullable): its points after the pre-filter (pf NULL: its points). */
+int aicp_hip_session_process(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_cloud* reading, float out_T[16],
+                             aicp_sequence_result* out, uint32_t* kept);
+int aicp_hip_session_process_accum(aicp_hip_ctx* ctx, aicp_hip_session* s, aicp_hip_accum* acc, const double origin[3],
+                                   float out_T[16], aicp_sequence_result* out, uint32_t* kept);
+/* Every output is nullable. n_processed: process calls since start (dropped and failed readings
+ * count); reference: as aicp_sequence_result.reference for the next reading; initial_T: initialT_,
+ * column-major; ended: 1 after a failed reading. */
+int aicp_hip_session_state(aicp_hip_ctx* ctx, aicp_hip_session* s, uint64_t* n_processed, int32_t* reference,
+                           size_t* reference_points, float initial_T[16], int32_t* ended);
+/* The current reference (App's reference_vis_): packed xyz (capacity cap points, AICP_ERR_INVALID if
+ * it does not fit) and its sensor origin (nullable). */
+int aicp_hip_session_reference(aicp_hip_ctx* ctx, aicp_hip_session* s, float* out, size_t cap, size_t* out_n,
+                               double origin[3]);
+/* The last process call that registered its reading: the whole call on the host, and from the
+ * origin's upload to the promotion on the device (HIP events). Both nullable. */
+int aicp_hip_session_last_timing(const aicp_hip_session* s, double* wall_ms, double* device_ms);
+
 /* ---- kernel-level entry points (parity tests and diagnostics) --------------------------- */
 /* kd-tree over pts (as given, no centring) + k-NN of queries: libnabo
  * KDTreeUnbalancedPtInLeavesImplicitBoundsStackOpt order, ALLOW_SELF_MATCH.
