@@ -61,6 +61,9 @@ EXPORTS = [
     "aicp_hip_session_create", "aicp_hip_session_free", "aicp_hip_session_start", "aicp_hip_session_start_accum",
     "aicp_hip_session_process", "aicp_hip_session_process_accum", "aicp_hip_session_state",
     "aicp_hip_session_reference", "aicp_hip_session_last_timing",
+    "aicp_hip_map_session_create", "aicp_hip_map_session_free", "aicp_hip_map_session_start",
+    "aicp_hip_map_session_process", "aicp_hip_map_session_process_accum", "aicp_hip_map_session_state",
+    "aicp_hip_map_session_last_timing",
 ]
 
 
@@ -89,7 +92,10 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_accum_pose_matrix", "aicp_hip_motion_gate",  # the sweep accumulator
            "aicp_hip_session_create", "aicp_hip_session_free", "aicp_hip_session_start",
            "aicp_hip_session_start_accum", "aicp_hip_session_process", "aicp_hip_session_process_accum",
-           "aicp_hip_session_state", "aicp_hip_session_reference", "aicp_hip_session_last_timing"}  # the live session
+           "aicp_hip_session_state", "aicp_hip_session_reference", "aicp_hip_session_last_timing",  # the live session
+           "aicp_hip_map_session_create", "aicp_hip_map_session_free", "aicp_hip_map_session_start",
+           "aicp_hip_map_session_process", "aicp_hip_map_session_process_accum", "aicp_hip_map_session_state",
+           "aicp_hip_map_session_last_timing"}  # the live map sessions
 
 
 class IcpConfig(C.Structure):
@@ -632,6 +638,17 @@ def _load():
         L.aicp_hip_session_state.argtypes = [vp, vp, up, ip, szp, fp, ip]
         L.aicp_hip_session_reference.argtypes = [vp, vp, fp, sz, szp, dp]
         L.aicp_hip_session_last_timing.argtypes = [vp, dp, dp]
+    if hasattr(L, "aicp_hip_map_session_create"):  # (out: LocalizationResult or BuiltMapResult, one layout)
+        u32p, dp, clp, pfp = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(Cloud), C.POINTER(PrefilterParams)
+        L.aicp_hip_map_session_create.argtypes = [vp, cfgp, C.POINTER(LocalizationParams), C.POINTER(BuiltMapParams),
+                                                  pfp, pfp, C.POINTER(vp)]
+        L.aicp_hip_map_session_free.argtypes = [vp, vp]
+        L.aicp_hip_map_session_free.restype = None
+        L.aicp_hip_map_session_start.argtypes = [vp, vp, vp]
+        L.aicp_hip_map_session_process.argtypes = [vp, vp, clp, fp, fp, vp, u32p]
+        L.aicp_hip_map_session_process_accum.argtypes = [vp, vp, vp, fp, fp, vp, u32p]
+        L.aicp_hip_map_session_state.argtypes = [vp, vp, up, ip, fp, ip]
+        L.aicp_hip_map_session_last_timing.argtypes = [vp, dp, dp]
     return L
 
 

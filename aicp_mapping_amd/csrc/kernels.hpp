@@ -376,6 +376,11 @@ struct SessionHeader {  // what describes the session's current reference, besid
 // expression) and hdr = {n, id, rec->corrected_origin}; otherwise nothing is written.
 void launch_session_promote(hipStream_t s, int n, const StreamRec* rec, const float* T, const float4* read, int32_t id,
                             float4* ref, SessionHeader* hdr);
+// The live map sessions' append (map_stream.cpp), behind launch_stream_commit of one reading in the
+// same way: if rec->append, dst[i] = apply4(T, read[i]) for the n points of the reading as
+// registered; otherwise nothing is written. dst: the map's tail, with room for n points.
+void launch_session_map_append(hipStream_t s, int n, const StreamRec* rec, const float* T, const float4* read,
+                               float4* dst);
 
 // ---- pre-filter (kernels_prefilter.hip): regionGrowingUniformPlaneSegmentationFilter -------
 constexpr int kPfMaxNbrs = 16;  // RegionGrowing neighbours per point (edge mask bits)

@@ -7,6 +7,10 @@
 // when this reading is the next reference. k_session_promote runs right behind it and does what the
 // record says: the reading as it was registered, moved by its correction, becomes the session's
 // reference (app.cpp:375-391: pcl::transformPointCloud in float, apply4's expression, no FMA).
+//
+// k_session_map_append is the same step for the live map sessions (map_stream.cpp): the reading
+// goes behind the caller's map instead (prior map: app.cpp:469-483, built map: app.cpp:383-391,
+// 458-465), where the host has made room before the reading's crop was enqueued.
 #include <hip/hip_runtime.h>
 
 #include "aicp_common.hpp"
@@ -14,6 +18,16 @@
 #include "kernels.hpp"
 
 namespace aicp {
+
+// One point of the reading as it was registered, moved by its correction: one 128-bit load, one
+// 128-bit store (k_transform's expression). The body of both kernels below.
+__device__ __forceinline__ void move_point(const float (&Tl)[16], const float4* __restrict__ read,
+                                           float4* __restrict__ dst, int i) {
+  const float4 p = read[i];
+  float q[3];
+  apply4(Tl, p.x, p.y, p.z, q);
+  dst[i] = make_float4(q[0], q[1], q[2], 1.f);
+}
 
 // One thread per point of the reading: one 128-bit load, one 128-bit store. Every thread reads the
 // record's append flag and the correction from device memory (the same addresses for the whole
@@ -33,15 +47,31 @@ __global__ __launch_bounds__(256) void k_session_promote(int n, const StreamRec*
   }
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float4 p = read[i];
-  float q[3];
-  apply4(Tl, p.x, p.y, p.z, q);
-  ref[i] = make_float4(q[0], q[1], q[2], 1.f);
+  move_point(Tl, read, ref, i);
+}
+
+// k_session_promote's per-point body with the destination the caller gives (the map's tail,
+// map->pts + map->n: room for n points was reserved before the launch) and no header. dst never
+// aliases read (the batch's copy of the reading).
+__global__ __launch_bounds__(256) void k_session_map_append(int n, const StreamRec* __restrict__ rec,
+                                                            const float* __restrict__ T,
+                                                            const float4* __restrict__ read,
+                                                            float4* __restrict__ dst) {
+  if (!rec->append) return;
+  float Tl[16];
+  for (int k = 0; k < 16; ++k) Tl[k] = T[k];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  move_point(Tl, read, dst, i);
 }
 
 void launch_session_promote(hipStream_t s, int n, const StreamRec* rec, const float* T, const float4* read, int32_t id,
                             float4* ref, SessionHeader* hdr) {
   if (n > 0) k_session_promote<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, rec, T, read, id, ref, hdr);
+}
+void launch_session_map_append(hipStream_t s, int n, const StreamRec* rec, const float* T, const float4* read,
+                               float4* dst) {
+  if (n > 0) k_session_map_append<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, rec, T, read, dst);
 }
 
 }  // namespace aicp

@@ -25,6 +25,12 @@
 // window's crop every raw reading is uploaded, unpacked and (debug mode) moved by the device's
 // initialT_ (k_stream_ingest), pre-filtered (stream_prefilter_raw, aicp_hip.cpp), and its kept
 // points wait on the device for the batch; the rest of the window is the same.
+//
+// Live map sessions (aicp_hip_map_session_*): the same window (stream_window) with one reading and
+// a state that persists between calls in the session's own device block. There the append is
+// decided on the device: the host makes room in the map before the crop when the mirrored count
+// says the reading appends if accepted, k_session_map_append runs right behind k_stream_commit and
+// does what the record says, and after the one read-back the host only adds to the map's size.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -130,6 +136,204 @@ int stream_args(aicp_hip_ctx* ctx, const void* cfg, const void* prm, const aicp_
   return AICP_OK;
 }
 
+// Where a window's state, records and prior origins live: the streams' own buffers (MapStreamBufs)
+// or a live session's block. On the device the records lie kRecOff behind the state, as in the mirror.
+struct WinBlock {
+  StreamState* dS;
+  StreamRec* dRec;
+  double* dOrg;
+  char* pin;      // the host's mirror of state and records, read back once per window
+  double* horg;   // pinned staging of the origins
+  DevBuf* stage;  // raw readings: the window's pre-filtered readings, one after another
+};
+
+// A live session's reading (a window of one): where its rows lie, and its append, which the device
+// decides behind the commit (launch_session_map_append) once the host has made room for it
+struct Live {
+  const float4* dpts = nullptr;  // the sweep accumulator's cloud where it lies (null: the caller's rows)
+  size_t dn = 0;
+  hipEvent_t ev_done = nullptr;  // recorded behind the commit and the append
+  bool reserved = false;         // room was made in the map: the append kernel runs
+  bool registered = false;       // the window reached its batch (ev_done is recorded)
+};
+
+// how a window ended its stream, if it did
+struct WinEnd {
+  int status = AICP_OK;
+  bool empty_crop = false, empty_read = false;
+};
+
+// One window: the w readings at `readings` / `poses`, which see the same map. Pre-filter or ingest,
+// crop, staging copy, (debug mode) move, batch, commit, one read-back, the map changes the records
+// ask for. Records and corrections go to out / out_T from index 0; *n_done = base + the records
+// filled so far. *wr: the readings that ran. kept: raw readings, what the pre-filter kept of each.
+// live (nullable): a session's call (w = 1).
+int stream_window(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, aicp_hip_map* map,
+                  const WinBlock& K, const aicp_cloud* readings, const float* poses, size_t w, float* out_T,
+                  aicp_localization_result* out, std::vector<uint32_t>& kept, std::vector<aicp_icp_stats>& stats,
+                  StreamTiming& tm, Live* live, size_t base, size_t* n_done, size_t* wr_out, WinEnd* end) {
+  const bool raw = P.pf_read != nullptr;
+  hipStream_t s = ctx->stream;
+  StreamState* dS = K.dS;
+  const StreamState* hS = reinterpret_cast<const StreamState*>(K.pin);
+  const StreamRec* hrec = reinterpret_cast<const StreamRec*>(K.pin + kRecOff);
+  double* horg = K.horg;
+  int rc = AICP_OK;
+  *wr_out = 0;
+  const size_t map_n = map->n;
+  // built map, debug mode (one reading per window): the overlap's sensor origin of the moved
+  // reading, the translation of initialT_ * prior pose, from the mirror of the device's initialT_
+  // (k_loc_move computes the same for the commit, on the device)
+  double moved[3];
+  const bool use_moved = P.bm && P.debug;
+  if (use_moved) corrected_origin(hS->initT, readings[0].origin, moved);
+  // every reading's crop, straight into the batch's reference array (as the batch call). An
+  // empty crop ends the stream at its reading; the wr readings before it still run
+  size_t wr = 0;
+  const uint32_t* htot = nullptr;
+  // raw streams: setAndFilterReading (app.cpp:77-100) for every reading of the window, before the
+  // crop (the pre-filter and the crop share work space with the batch, not with each other: each
+  // is done before the next starts). The kept points wait in the stage, sized once for the window
+  // (the voxel grid never adds a point). Debug mode (one reading per window): the ingest kernel
+  // moves the raw points and the prior origin by the device's initialT_. A reading the pre-filter
+  // empties ends the window before it, as an empty crop does
+  size_t wp = w;  // readings that reach the crop
+  if (raw) {
+    uint64_t sum = 0;
+    for (size_t i = 0; i < w; ++i) sum += readings[i].n;
+    HIPC(ensure(*K.stage, sum * 16));
+    kept.assign(w, 0u);
+    if (P.debug) {
+      for (int k = 0; k < 3; ++k) horg[k] = readings[0].origin[k];
+      HIPC(hipMemcpyAsync(K.dOrg, horg, 24, hipMemcpyHostToDevice, s));
+    }
+    uint64_t off = 0;
+    for (size_t i = 0; i < w; ++i) {
+      const aicp_cloud& c = readings[i];
+      rc = stream_ingest_rows(ctx, P.pf_read, c.pts, c.n, c.stride, live ? live->dpts : nullptr,
+                              P.debug ? dS->initT : nullptr, P.debug ? K.dOrg : nullptr,
+                              K.stage->as<float4>() + off, &kept[i]);
+      if (rc) return rc;
+      if (!kept[i]) {
+        wp = i;
+        break;
+      }
+      off += kept[i];
+    }
+  }
+  // a session's reading: room in the map now, while nothing that reads the map is in flight (the
+  // pre-filter has returned with the stream idle; growing synchronises and may move the map), if
+  // the mirrored count says this reading appends when it is accepted (k_stream_commit's rule)
+  if (live && wp) {
+    const int32_t c = hS->count;
+    const bool appends = P.bm ? c + 1 == P.rules.freq : (P.rules.merge && c % P.rules.freq == 0);
+    if (appends) {
+      rc = map_reserve(ctx, map, raw ? (size_t)kept[0] : (size_t)readings[0].n);
+      if (rc) return rc;
+      live->reserved = true;
+    }
+  }
+  if (wp) {
+    rc = map_crop_pairs(ctx, map, P.crop_min, P.crop_max, readings, poses, wp, use_moved ? moved : nullptr, &wr,
+                        &htot, raw ? kept.data() : nullptr);
+    if (rc) return rc;
+  }
+  *wr_out = wr;
+  if (wr) {
+    aicp_hip_batch* B = ctx->mapbatch;
+    if (raw) {  // the staged readings into the batch (its sizes are known only after the crop)
+      uint64_t off = 0;
+      for (size_t i = 0; i < wr; ++i) {
+        HIPC(hipMemcpyAsync(B->read_raw.as<float4>() + B->desc[i].read_off, K.stage->as<float4>() + off,
+                            (size_t)kept[i] * 16, hipMemcpyDeviceToDevice, s));
+        off += kept[i];
+      }
+    }
+    if (!(raw && P.debug)) {  // (raw debug mode: up already, and moved by the ingest kernel)
+      for (size_t i = 0; i < wr; ++i)
+        for (int k = 0; k < 3; ++k) horg[3 * i + k] = readings[i].origin[k];
+      HIPC(hipMemcpyAsync(K.dOrg, horg, wr * 24, hipMemcpyHostToDevice, s));
+    }
+    if (P.debug && !raw) {  // (one reading per window) moved by the device's initialT_, its prior pose too
+      launch_loc_move(s, (int)B->desc[0].n_read, dS->initT, K.dOrg, B->read_raw.as<float4>() + B->desc[0].read_off);
+      HIPC(hipGetLastError());
+    }
+    stats.assign(wr, aicp_icp_stats{});
+    for (auto& st : stats) st.status = -1;
+    rc = run_batch(ctx, B, cfg, P.resolution, P.run_flags, out_T, stats.data(), nullptr);
+    if (rc && stats[0].status == -1) return rc;  // the batch did not run to its end (not a reading's status)
+    ++tm.windows;
+    // App's bookkeeping for the window, on the device; one read-back of its state and records
+    launch_stream_commit(s, (int)wr, ctx->state.as<PairState>(), ctx->outT.as<float>(), K.dOrg, P.rules, dS, K.dRec);
+    HIPC(hipGetLastError());
+    if (live) {
+      // the session's append, by the record the commit has just written: no host decision in between
+      if (live->reserved) {
+        const PairDesc& d = B->desc[0];
+        launch_session_map_append(s, (int)d.n_read, K.dRec, ctx->outT.as<float>(),
+                                  B->read_raw.as<float4>() + d.read_off, map->pts.as<float4>() + map->n);
+        HIPC(hipGetLastError());
+      }
+      HIPC(hipEventRecord(live->ev_done, s));
+      live->registered = true;
+    }
+    HIPC(hipMemcpyAsync(K.pin, dS, kRecOff + wr * sizeof(StreamRec), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    // the map changes the records ask for, in order (by the window rule: after the last reading)
+    for (size_t i = 0; i < wr; ++i) {
+      const StreamRec& r = hrec[i];
+      aicp_localization_result& o = out[i];
+      std::memset(&o, 0, sizeof(o));
+      o.status = r.status;
+      o.accepted = r.accepted;
+      o.map_points = map_n;
+      o.crop_points = htot[i];
+      for (int k = 0; k < 3; ++k) o.corrected_origin[k] = r.corrected_origin[k];
+      o.icp = stats[i];
+      *n_done = base + i + 1;
+      if (r.status) {
+        end->status = r.status;
+        break;
+      }
+      if (r.append) {
+        const PairDesc& d = B->desc[i];
+        if (live) {  // (done on the device already)
+          if (!live->reserved) FAIL(AICP_ERR_HIP, "map session: the device's append disagrees with the host's count");
+        } else {
+          rc = map_reserve(ctx, map, d.n_read);
+          if (rc) return rc;
+          launch_transform(s, (int)d.n_read, ctx->outT.as<float>() + 16 * i, B->read_raw.as<float4>() + d.read_off,
+                           map->pts.as<float4>() + map->n);
+          HIPC(hipGetLastError());
+        }
+        map->n += d.n_read;
+        o.merged = 1;
+        ++tm.appends;
+      }
+      if (r.refilter) {
+        rc = aicp_hip_map_prefilter(ctx, map, P.pf);
+        if (rc) return rc;
+        o.refiltered = 1;
+        ++tm.refilters;
+      }
+    }
+  }
+  // the reading with the empty crop, or the one the pre-filter emptied (libpointmatcher throws on
+  // an empty cloud); the lower index ends the stream (wr <= wp: the crop saw the readings before wp)
+  if (!end->status && wr < w) {
+    aicp_localization_result& o = out[wr];
+    std::memset(&o, 0, sizeof(o));
+    o.status = o.icp.status = AICP_ERR_INVALID;
+    o.map_points = map_n;
+    o.icp.overlap_percent = -1.f;
+    ident4(out_T + 16 * wr);
+    *n_done = base + wr + 1;
+    end->status = AICP_ERR_INVALID;
+    (wr < wp ? end->empty_crop : end->empty_read) = true;
+  }
+  return AICP_OK;
+}
+
 int run_stream(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, aicp_hip_map* map,
                const aicp_cloud* readings, const float* poses, size_t n, float* out_T, aicp_localization_result* out,
                uint32_t* out_kept, size_t* n_done) {
@@ -159,7 +363,7 @@ int run_stream(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, a
   StreamState* dS = L->win.as<StreamState>();
   StreamRec* dRec = reinterpret_cast<StreamRec*>(L->win.as<char>() + kRecOff);
   StreamState* hS = reinterpret_cast<StreamState*>(lp);  // the host's mirror, read back with every window's records
-  const StreamRec* hrec = reinterpret_cast<const StreamRec*>(lp + kRecOff);
+  const WinBlock K{dS, dRec, L->origin.as<double>(), lp, reinterpret_cast<double*>(lp + o_org), &L->stage};
   std::memset(hS, 0, sizeof(StreamState));
   ident4(hS->initT);
   HIPC(hipMemcpyAsync(dS, hS, sizeof(StreamState), hipMemcpyHostToDevice, s));
@@ -173,130 +377,14 @@ int run_stream(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, a
     const size_t w = P.bm ? aicp_hip_built_map_window((uint64_t)hS->count, P.bm, n - p)
                           : aicp_hip_localization_window((uint64_t)hS->count, P.loc, n - p);
     if (P.bm && w == 0) FAIL(AICP_ERR_HIP, "built-map stream: the device's count left its range");
-    const size_t map_n = map->n;
-    // built map, debug mode (one reading per window): the overlap's sensor origin of the moved
-    // reading, the translation of initialT_ * prior pose, from the mirror of the device's initialT_
-    // (k_loc_move computes the same for the commit, on the device)
-    double moved[3];
-    const bool use_moved = P.bm && P.debug;
-    if (use_moved) corrected_origin(hS->initT, readings[p].origin, moved);
-    // every reading's crop, straight into the batch's reference array (as the batch call). An
-    // empty crop ends the stream at its reading; the wr readings before it still run
     size_t wr = 0;
-    const uint32_t* htot = nullptr;
-    double* horg = reinterpret_cast<double*>(lp + o_org);
-    // raw streams: setAndFilterReading (app.cpp:77-100) for every reading of the window, before the
-    // crop (the pre-filter and the crop share work space with the batch, not with each other: each
-    // is done before the next starts). The kept points wait in L->stage, sized once for the window
-    // (the voxel grid never adds a point). Debug mode (one reading per window): the ingest kernel
-    // moves the raw points and the prior origin by the device's initialT_. A reading the pre-filter
-    // empties ends the window before it, as an empty crop does
-    size_t wp = w;  // readings that reach the crop
-    if (raw) {
-      uint64_t sum = 0;
-      for (size_t i = 0; i < w; ++i) sum += readings[p + i].n;
-      HIPC(ensure(L->stage, sum * 16));
-      kept.assign(w, 0u);
-      if (P.debug) {
-        for (int k = 0; k < 3; ++k) horg[k] = readings[p].origin[k];
-        HIPC(hipMemcpyAsync(L->origin.p, horg, 24, hipMemcpyHostToDevice, s));
-      }
-      uint64_t off = 0;
-      for (size_t i = 0; i < w; ++i) {
-        rc = stream_prefilter_raw(ctx, P.pf_read, readings[p + i], P.debug ? dS->initT : nullptr,
-                                  P.debug ? L->origin.as<double>() : nullptr, L->stage.as<float4>() + off, &kept[i]);
-        if (rc) return rc;
-        if (!kept[i]) {
-          wp = i;
-          break;
-        }
-        off += kept[i];
-      }
-    }
-    if (wp) {
-      rc = map_crop_pairs(ctx, map, P.crop_min, P.crop_max, readings + p, poses + 16 * p, wp,
-                          use_moved ? moved : nullptr, &wr, &htot, raw ? kept.data() : nullptr);
-      if (rc) return rc;
-    }
-    if (wr) {
-      aicp_hip_batch* B = ctx->mapbatch;
-      if (raw) {  // the staged readings into the batch (its sizes are known only after the crop)
-        uint64_t off = 0;
-        for (size_t i = 0; i < wr; ++i) {
-          HIPC(hipMemcpyAsync(B->read_raw.as<float4>() + B->desc[i].read_off, L->stage.as<float4>() + off,
-                              (size_t)kept[i] * 16, hipMemcpyDeviceToDevice, s));
-          off += kept[i];
-        }
-      }
-      if (!(raw && P.debug)) {  // (raw debug mode: up already, and moved by the ingest kernel)
-        for (size_t i = 0; i < wr; ++i)
-          for (int k = 0; k < 3; ++k) horg[3 * i + k] = readings[p + i].origin[k];
-        HIPC(hipMemcpyAsync(L->origin.p, horg, wr * 24, hipMemcpyHostToDevice, s));
-      }
-      if (P.debug && !raw) {  // (one reading per window) moved by the device's initialT_, its prior pose too
-        launch_loc_move(s, (int)B->desc[0].n_read, dS->initT, L->origin.as<double>(),
-                        B->read_raw.as<float4>() + B->desc[0].read_off);
-        HIPC(hipGetLastError());
-      }
-      stats.assign(wr, aicp_icp_stats{});
-      for (auto& st : stats) st.status = -1;
-      rc = run_batch(ctx, B, cfg, P.resolution, P.run_flags, out_T + 16 * p, stats.data(), nullptr);
-      if (rc && stats[0].status == -1) return rc;  // the batch did not run to its end (not a reading's status)
-      ++tm.windows;
-      // App's bookkeeping for the window, on the device; one read-back of its state and records
-      launch_stream_commit(s, (int)wr, ctx->state.as<PairState>(), ctx->outT.as<float>(), L->origin.as<double>(),
-                           P.rules, dS, dRec);
-      HIPC(hipGetLastError());
-      HIPC(hipMemcpyAsync(lp, L->win.p, kRecOff + wr * sizeof(StreamRec), hipMemcpyDeviceToHost, s));
-      HIPC(hipStreamSynchronize(s));
-      // the map changes the records ask for, in order (by the window rule: after the last reading)
-      for (size_t i = 0; i < wr; ++i) {
-        const StreamRec& r = hrec[i];
-        aicp_localization_result& o = out[p + i];
-        std::memset(&o, 0, sizeof(o));
-        o.status = r.status;
-        o.accepted = r.accepted;
-        o.map_points = map_n;
-        o.crop_points = htot[i];
-        for (int k = 0; k < 3; ++k) o.corrected_origin[k] = r.corrected_origin[k];
-        o.icp = stats[i];
-        *n_done = p + i + 1;
-        if (r.status) {
-          status = r.status;
-          break;
-        }
-        if (r.append) {
-          const PairDesc& d = B->desc[i];
-          rc = map_reserve(ctx, map, d.n_read);
-          if (rc) return rc;
-          launch_transform(s, (int)d.n_read, ctx->outT.as<float>() + 16 * i, B->read_raw.as<float4>() + d.read_off,
-                           map->pts.as<float4>() + map->n);
-          HIPC(hipGetLastError());
-          map->n += d.n_read;
-          o.merged = 1;
-          ++tm.appends;
-        }
-        if (r.refilter) {
-          rc = aicp_hip_map_prefilter(ctx, map, P.pf);
-          if (rc) return rc;
-          o.refiltered = 1;
-          ++tm.refilters;
-        }
-      }
-    }
-    // the reading with the empty crop, or the one the pre-filter emptied (libpointmatcher throws on
-    // an empty cloud); the lower index ends the stream (wr <= wp: the crop saw the readings before wp)
-    if (!status && wr < w) {
-      aicp_localization_result& o = out[p + wr];
-      std::memset(&o, 0, sizeof(o));
-      o.status = o.icp.status = AICP_ERR_INVALID;
-      o.map_points = map_n;
-      o.icp.overlap_percent = -1.f;
-      ident4(out_T + 16 * (p + wr));
-      *n_done = p + wr + 1;
-      status = AICP_ERR_INVALID;
-      (wr < wp ? empty_crop : empty_read) = true;
-    }
+    WinEnd end;
+    rc = stream_window(ctx, P, cfg, map, K, readings + p, poses + 16 * p, w, out_T + 16 * p, out + p, kept, stats, tm,
+                       nullptr, p, n_done, &wr, &end);
+    if (rc) return rc;
+    status = end.status;
+    empty_crop = end.empty_crop;
+    empty_read = end.empty_read;
     if (raw && out_kept)
       for (size_t i = 0; i < w && p + i < *n_done; ++i) out_kept[p + i] = kept[i];
     p += wr;
@@ -313,7 +401,31 @@ int run_stream(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, a
   return status;
 }
 
+// the live map session's small device block and its pinned mirror: StreamState | StreamRec | the
+// reading's prior origin (3 doubles), the streams' window layout with one record
+constexpr size_t kSessOrg = 192, kSessBytes = 256;
+static_assert(kRecOff + sizeof(StreamRec) <= kSessOrg && kSessOrg + 24 <= kSessBytes, "the session block's layout");
+
 }  // namespace
+
+struct aicp_hip_map_session {
+  aicp_icp_config cfg{};
+  aicp_localization_params loc{};
+  aicp_built_map_params bm{};
+  aicp_prefilter_params pf_read{}, pf_map{};
+  Stream P{};  // points into the copies above
+  DevBuf win;  // the block
+  PinBuf pin;  // its mirror
+  DevBuf read;  // raw readings: the last reading as it was registered (the pre-filter's kept points)
+  aicp_hip_map* map = nullptr;  // the caller's
+  uint64_t n_processed = 0;
+  bool started = false, ended = false;
+  uint64_t ended_at = 0;
+  std::vector<uint32_t> kept;
+  std::vector<aicp_icp_stats> stats;
+  hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+  double last_wall_ms = 0, last_device_ms = 0;
+};
 
 extern "C" {
 
@@ -369,6 +481,40 @@ static int raw_args(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf_read) {
   return stream_prefilter_check(ctx, pf_read);
 }
 
+// the two policies as the window code takes them (the parameters stay the caller's)
+static Stream loc_rules(const aicp_localization_params* prm, const aicp_prefilter_params* pf,
+                        const aicp_prefilter_params* pf_read) {
+  Stream P{};
+  P.loc = prm;
+  P.pf = pf;
+  P.pf_read = pf_read;
+  P.rules.freq = prm->reference_update_frequency;
+  P.rules.refilter_every = prm->map_refilter_every;
+  P.rules.merge = (prm->flags & AICP_LOC_MERGE) ? 1 : 0;
+  P.rules.max_corr = prm->max_correction_magnitude;
+  P.crop_min = prm->crop_min;
+  P.crop_max = prm->crop_max;
+  P.debug = prm->flags & AICP_SEQ_DEBUG;
+  P.run_flags = AICP_RUN_ICP | (prm->flags & AICP_RUN_TIME_NN);
+  return P;
+}
+
+static Stream bm_rules(const aicp_built_map_params* prm, const aicp_prefilter_params* pf_read) {
+  Stream P{};
+  P.bm = prm;
+  P.pf_read = pf_read;
+  P.rules.built = 1;
+  P.rules.freq = prm->reference_update_frequency;
+  P.rules.overlap = (prm->flags & AICP_RUN_OVERLAP) ? 1 : 0;
+  P.rules.max_corr = prm->max_correction_magnitude;
+  P.crop_min = prm->crop_min;
+  P.crop_max = prm->crop_max;
+  P.debug = prm->flags & AICP_SEQ_DEBUG;
+  P.run_flags = AICP_RUN_ICP | (prm->flags & (AICP_RUN_OVERLAP | AICP_RUN_TIME_NN));
+  P.resolution = prm->resolution;
+  return P;
+}
+
 // raw: readings as App receives them, pre-filtered by pf_read inside the stream
 static int loc_stream(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* prm,
                       const aicp_prefilter_params* pf, bool raw, const aicp_prefilter_params* pf_read,
@@ -385,19 +531,8 @@ static int loc_stream(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_
   }
   aicp_icp_config c = *cfg;
   c.trimmed_ratio = aicp_hip_autotune_ratio(50.0f);  // octree_overlap_ = 50.0 (app.cpp:123-127)
-  Stream P{};
-  P.loc = prm;
-  P.pf = pf;
-  P.pf_read = raw ? pf_read : nullptr;
-  P.rules.freq = prm->reference_update_frequency;
-  P.rules.refilter_every = prm->map_refilter_every;
-  P.rules.merge = (prm->flags & AICP_LOC_MERGE) ? 1 : 0;
-  P.rules.max_corr = prm->max_correction_magnitude;
-  P.crop_min = prm->crop_min;
-  P.crop_max = prm->crop_max;
-  P.debug = prm->flags & AICP_SEQ_DEBUG;
-  P.run_flags = AICP_RUN_ICP | (prm->flags & AICP_RUN_TIME_NN);
-  return run_stream(ctx, P, &c, map, readings, poses, n, out_T, out, out_kept, n_done);
+  return run_stream(ctx, loc_rules(prm, pf, raw ? pf_read : nullptr), &c, map, readings, poses, n, out_T, out,
+                    out_kept, n_done);
 }
 
 static int bm_stream(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_built_map_params* prm, bool raw,
@@ -408,20 +543,8 @@ static int bm_stream(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_b
   if (!rc && raw) rc = raw_args(ctx, pf_read);
   if (rc) return rc;
   if (!valid_params(prm)) FAIL(AICP_ERR_INVALID, "built-map parameters");
-  Stream P{};
-  P.bm = prm;
-  P.pf_read = raw ? pf_read : nullptr;
-  P.rules.built = 1;
-  P.rules.freq = prm->reference_update_frequency;
-  P.rules.overlap = (prm->flags & AICP_RUN_OVERLAP) ? 1 : 0;
-  P.rules.max_corr = prm->max_correction_magnitude;
-  P.crop_min = prm->crop_min;
-  P.crop_max = prm->crop_max;
-  P.debug = prm->flags & AICP_SEQ_DEBUG;
-  P.run_flags = AICP_RUN_ICP | (prm->flags & (AICP_RUN_OVERLAP | AICP_RUN_TIME_NN));
-  P.resolution = prm->resolution;
-  return run_stream(ctx, P, cfg, map, readings, poses, n, out_T, reinterpret_cast<aicp_localization_result*>(out),
-                    out_kept, n_done);
+  return run_stream(ctx, bm_rules(prm, raw ? pf_read : nullptr), cfg, map, readings, poses, n, out_T,
+                    reinterpret_cast<aicp_localization_result*>(out), out_kept, n_done);
 }
 
 int aicp_hip_map_sequence_run(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* prm,
@@ -463,6 +586,201 @@ int aicp_hip_last_built_map_timing(const aicp_hip_ctx* ctx, aicp_built_map_timin
   if (!ctx || !out) return AICP_ERR_INVALID;
   const StreamTiming t = ctx->ms ? ctx->ms->last[1] : StreamTiming{};
   *out = aicp_built_map_timing{t.windows, t.appends, t.wall_ms, t.device_ms};
+  return AICP_OK;
+}
+
+// ---- the live map sessions: stream_window with w = 1 and a state that persists ----------------
+int aicp_hip_map_session_create(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* loc,
+                                const aicp_built_map_params* bm, const aicp_prefilter_params* pf_read,
+                                const aicp_prefilter_params* pf_map, aicp_hip_map_session** out) {
+  if (!ctx || !out) return AICP_ERR_INVALID;
+  *out = nullptr;
+  if (!cfg) return AICP_ERR_INVALID;
+  if ((loc != nullptr) == (bm != nullptr)) FAIL(AICP_ERR_INVALID, "map session: exactly one of loc / bm");
+  if (bm && pf_map) FAIL(AICP_ERR_INVALID, "map session: the built map is never re-filtered (pf_map)");
+  if (loc && !valid_params(loc)) FAIL(AICP_ERR_INVALID, "localization parameters");
+  if (bm && !valid_params(bm)) FAIL(AICP_ERR_INVALID, "built-map parameters");
+  aicp_hip_map_session* s = new aicp_hip_map_session();
+  s->cfg = *cfg;
+  if (pf_read) s->pf_read = *pf_read;
+  if (loc) {
+    s->loc = *loc;
+    if (pf_map)
+      s->pf_map = *pf_map;
+    else
+      aicp_hip_default_prefilter(&s->pf_map);
+    s->cfg.trimmed_ratio = aicp_hip_autotune_ratio(50.0f);  // octree_overlap_ = 50.0 (app.cpp:123-127)
+    s->P = loc_rules(&s->loc, &s->pf_map, pf_read ? &s->pf_read : nullptr);
+  } else {
+    s->bm = *bm;
+    s->P = bm_rules(&s->bm, pf_read ? &s->pf_read : nullptr);
+  }
+  int rc = check_cfg(ctx, &s->cfg, s->P.run_flags);
+  if (!rc && pf_read) rc = stream_prefilter_check(ctx, pf_read);
+  hipError_t e = hipSuccess;
+  if (!rc) {
+    e = hipSetDevice(ctx->device);
+    if (e == hipSuccess) e = ensure(s->win, kSessBytes);
+    if (e == hipSuccess) e = ensure(s->pin, kSessBytes);
+    if (e == hipSuccess) e = hipEventCreate(&s->ev_begin);
+    if (e == hipSuccess) e = hipEventCreate(&s->ev_end);
+  }
+  if (rc || e != hipSuccess) {
+    const std::string why = ctx->err;
+    aicp_hip_map_session_free(nullptr, s);
+    ctx->err = why;
+    if (rc) return rc;
+    HIPC(e);
+  }
+  *out = s;
+  return AICP_OK;
+}
+
+void aicp_hip_map_session_free(aicp_hip_ctx* ctx, aicp_hip_map_session* s) {
+  if (!s) return;
+  if (ctx) {
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+  }
+  release(s->win);
+  release(s->pin);
+  release(s->read);
+  if (s->ev_begin) (void)hipEventDestroy(s->ev_begin);
+  if (s->ev_end) (void)hipEventDestroy(s->ev_end);
+  delete s;
+}
+
+int aicp_hip_map_session_start(aicp_hip_ctx* ctx, aicp_hip_map_session* s, aicp_hip_map* map) {
+  if (!ctx || !s || !map) return AICP_ERR_INVALID;
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  HIPC(hipStreamSynchronize(st));  // (the mirror is free)
+  // count = 0, initialT_ = I, no record
+  char* h = s->pin.as<char>();
+  std::memset(h, 0, kSessBytes);
+  ident4(reinterpret_cast<StreamState*>(h)->initT);
+  HIPC(hipMemcpyAsync(s->win.p, h, kSessBytes, hipMemcpyHostToDevice, st));
+  HIPC(hipStreamSynchronize(st));
+  s->map = map;
+  s->n_processed = 0;
+  s->started = true;
+  s->ended = false;
+  return AICP_OK;
+}
+
+// the call that ends the session (app.cpp:210: the worker ends), with its status
+static int map_session_end(aicp_hip_ctx* ctx, aicp_hip_map_session* s, int rc) {
+  s->ended = true;
+  s->ended_at = s->n_processed;
+  ++s->n_processed;
+  (void)hipStreamSynchronize(ctx->stream);
+  return rc;
+}
+
+static int map_session_process(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const aicp_cloud* reading,
+                               aicp_hip_accum* acc, const float* pose, float* out_T, void* out, uint32_t* kept_out) {
+  if (!ctx || !s || (!reading && !acc) || !pose || !out_T || !out) return AICP_ERR_INVALID;
+  if (!s->started) FAIL(AICP_ERR_INVALID, "map session: process before start");
+  if (s->ended) FAIL(AICP_ERR_INVALID, "map session ended at reading " + std::to_string(s->ended_at));
+  const Stream& P = s->P;
+  const bool raw = P.pf_read != nullptr;
+  if (acc && !raw) FAIL(AICP_ERR_INVALID, "map session: a reading from the accumulator needs pf_read");
+  if (reading && !valid_cloud(*reading)) FAIL(AICP_ERR_INVALID, "map session: invalid reading");
+  const auto t0 = std::chrono::steady_clock::now();
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  Live live;
+  live.ev_done = s->ev_end;
+  aicp_cloud c{};
+  if (reading) {
+    c = *reading;
+  } else {  // the accumulator's cloud where it lies; its sensor origin is the pose's translation
+    const int rc = accum_resident(ctx, acc, &live.dpts, &live.dn);  // (waits for the pushes)
+    if (rc) return rc;
+    if (live.dn > (size_t)INT32_MAX) FAIL(AICP_ERR_INVALID, "map session: invalid reading");
+    c.pts = reinterpret_cast<const float*>(live.dpts);  // (not read on the host)
+    c.n = live.dn;
+    c.stride = 16;
+    for (int k = 0; k < 3; ++k) c.origin[k] = pose[12 + k];
+  }
+  const std::string id = std::to_string(s->n_processed);
+  aicp_localization_result* o = static_cast<aicp_localization_result*>(out);
+  std::memset(o, 0, sizeof(*o));
+  ident4(out_T);
+  if (kept_out) *kept_out = 0;
+  HIPC(hipStreamSynchronize(st));  // (the mirror is free)
+  char* h = s->pin.as<char>();
+  char* d = s->win.as<char>();
+  const StreamState* hS = reinterpret_cast<const StreamState*>(h);
+  if (P.bm && aicp_hip_built_map_window((uint64_t)hS->count, P.bm, 1) == 0) {
+    (void)map_session_end(ctx, s, AICP_ERR_HIP);
+    FAIL(AICP_ERR_HIP, "map session: the device's count left its range");
+  }
+  const WinBlock K{reinterpret_cast<StreamState*>(d), reinterpret_cast<StreamRec*>(d + kRecOff),
+                   reinterpret_cast<double*>(d + kSessOrg), h, reinterpret_cast<double*>(h + kSessOrg), &s->read};
+  StreamTiming tm;
+  WinEnd end;
+  size_t done = 0, wr = 0;
+  int rc = AICP_OK;
+  if (c.n == 0) {  // (an accumulator with no point) as a reading the pre-filter empties
+    o->status = o->icp.status = end.status = AICP_ERR_INVALID;
+    o->map_points = s->map->n;
+    o->icp.overlap_percent = -1.f;
+    end.empty_read = true;
+  } else {
+    HIPC(hipEventRecord(s->ev_begin, st));
+    s->kept.clear();
+    rc = stream_window(ctx, P, &s->cfg, s->map, K, &c, pose, 1, out_T, o, s->kept, s->stats, tm, &live, 0, &done, &wr,
+                       &end);
+    if (kept_out && (!raw || !s->kept.empty())) *kept_out = raw ? s->kept[0] : (uint32_t)c.n;
+  }
+  if (rc) return map_session_end(ctx, s, rc);  // (a map that cannot grow among them: nothing has changed)
+  if (live.registered) {
+    s->last_device_ms = ev_ms(s->ev_begin, s->ev_end);
+    s->last_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  if (end.status) {
+    const std::string why = ctx->err;
+    (void)map_session_end(ctx, s, end.status);
+    ctx->err = "map session: reading " + id +
+               (end.empty_crop   ? std::string(": empty map crop")
+                : end.empty_read ? std::string(": keeps no point after the pre-filter")
+                                 : ": status " + std::to_string(end.status) + ": " + why);
+    return end.status;
+  }
+  ++s->n_processed;
+  return AICP_OK;
+}
+
+int aicp_hip_map_session_process(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const aicp_cloud* reading,
+                                 const float pose[16], float out_T[16], void* out, uint32_t* kept) {
+  if (!reading) return AICP_ERR_INVALID;
+  return map_session_process(ctx, s, reading, nullptr, pose, out_T, out, kept);
+}
+
+int aicp_hip_map_session_process_accum(aicp_hip_ctx* ctx, aicp_hip_map_session* s, aicp_hip_accum* acc,
+                                       const float pose[16], float out_T[16], void* out, uint32_t* kept) {
+  if (!acc) return AICP_ERR_INVALID;
+  return map_session_process(ctx, s, nullptr, acc, pose, out_T, out, kept);
+}
+
+int aicp_hip_map_session_state(aicp_hip_ctx* ctx, aicp_hip_map_session* s, uint64_t* n_processed, int32_t* count,
+                               float initial_T[16], int32_t* ended) {
+  if (!ctx || !s) return AICP_ERR_INVALID;
+  if (!s->started) FAIL(AICP_ERR_INVALID, "map session: state before start");
+  // (every call ends with the stream idle and the mirror read back: nothing to wait for)
+  const StreamState* hS = s->pin.as<StreamState>();
+  if (n_processed) *n_processed = s->n_processed;
+  if (count) *count = hS->count;
+  if (initial_T) std::memcpy(initial_T, hS->initT, 64);
+  if (ended) *ended = s->ended ? 1 : 0;
+  return AICP_OK;
+}
+
+int aicp_hip_map_session_last_timing(const aicp_hip_map_session* s, double* wall_ms, double* device_ms) {
+  if (!s) return AICP_ERR_INVALID;
+  if (wall_ms) *wall_ms = s->last_wall_ms;
+  if (device_ms) *device_ms = s->last_device_ms;
   return AICP_OK;
 }
 

@@ -1,0 +1,104 @@
+"""Live map sessions: App::processCloud on the prior map or on the built map, one reading per call.
+
+``PriorMap.sequence_run`` / ``BuiltMap.sequence_run`` take a whole recording. A node receives its
+readings one by one: ``MapSession`` (aicp_hip_map_session_*) handles one per call against the
+device-resident map and keeps App's state for the policy, ``initialT_`` and the count, on the
+device between calls. Reading by reading the rules are the streams'; the append to the map is
+decided and done on the device behind the reading's registration.
+
+    session = MapSession(ctx, prior_map, params=L.default_localization_params(), prefilter=True)
+    session.start()
+    for reading, pose in node:                   # or a SweepAccumulator in place of the reading
+        T, result, kept = session.process(reading, pose)
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from .accumulator import SweepAccumulator
+from .built_map import BuiltMap
+
+
+class MapSession:
+    def __init__(self, ctx: "L.Context", map, cfg=None, params=None, prefilter=None, map_prefilter=None):
+        """map: a PriorMap (localize_against_prior_map; params: LocalizationParams) or a BuiltMap
+        (localize_against_built_map, created from App's first cloud; params: BuiltMapParams); the
+        policy follows the map's class and the params' type, which must agree. cfg: IcpConfig
+        (default_config() when None; a point-to-point chain is accepted). prefilter: None when the
+        readings are already pre-filtered, PrefilterParams (or True for the defaults) when they
+        are RAW and go through setAndFilterReading in App's order. map_prefilter: the prior map's
+        re-filter (None: the defaults); not for a BuiltMap."""
+        built = isinstance(map, BuiltMap)
+        if params is None:
+            params = L.default_built_map_params() if built else L.default_localization_params()
+        if isinstance(params, L.BuiltMapParams) != built:
+            raise TypeError("MapSession: a BuiltMap takes BuiltMapParams, a PriorMap LocalizationParams")
+        cfg = cfg or L.default_config()
+        if prefilter is True:
+            prefilter = L.default_prefilter()
+        h = C.c_void_p()
+        ctx.check(L.lib.aicp_hip_map_session_create(
+            ctx.h, C.byref(cfg), None if built else C.byref(params), C.byref(params) if built else None,
+            None if prefilter is None else C.byref(prefilter),
+            None if map_prefilter is None else C.byref(map_prefilter), C.byref(h)))
+        self.ctx = ctx
+        self.map = map
+        self.built = built
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            if getattr(self.ctx, "h", None):
+                L.lib.aicp_hip_map_session_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def start(self) -> None:
+        """count = 0, initialT_ = I, not ended. Calling it again restarts the session on the map
+        as it is now."""
+        self.ctx.check(L.lib.aicp_hip_map_session_start(self.ctx.h, self.h, self.map.h))
+
+    def process(self, reading, pose, raise_on_error=True):
+        """One reading ((N, 3|4|8|12) float32 rows, or a SweepAccumulator, which is left as it is)
+        with its 4x4 row-major prior pose, whose translation is the reading's sensor origin.
+        Returns (T 4x4 row-major correction, result dict as the map's sequence_run gives them with
+        `rc` added, kept points). An empty crop, an emptied reading or a registration error ends
+        the session (AicpError unless raise_on_error is False); start() revives it."""
+        P = np.asarray(pose, np.float64).reshape(4, 4)
+        pz = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(4, 4).T.reshape(16))
+        outT = np.zeros(16, np.float32)
+        res = (L.BuiltMapResult if self.built else L.LocalizationResult)()
+        kept = C.c_uint32(0)
+        if isinstance(reading, SweepAccumulator):
+            rc = L.lib.aicp_hip_map_session_process_accum(self.ctx.h, self.h, reading.h, L._fptr(pz), L._fptr(outT),
+                                                          C.byref(res), C.byref(kept))
+        else:
+            c, keep = L.make_cloud(reading, P[:3, 3])
+            rc = L.lib.aicp_hip_map_session_process(self.ctx.h, self.h, C.byref(c), L._fptr(pz), L._fptr(outT),
+                                                    C.byref(res), C.byref(kept))
+        if raise_on_error and rc != L.AICP_OK:
+            self.ctx.check(rc)
+        d = res.as_dict()
+        d["rc"] = rc
+        return outT.reshape(4, 4).T.copy(), d, int(kept.value)
+
+    def state(self) -> dict:
+        """n_processed (process calls since start), count (prior map: the accepted readings; built
+        map: those since the last reference), initial_T (4x4 row-major), ended."""
+        n, cnt, ended = C.c_uint64(), C.c_int32(), C.c_int32()
+        T = np.zeros(16, np.float32)
+        self.ctx.check(L.lib.aicp_hip_map_session_state(self.ctx.h, self.h, C.byref(n), C.byref(cnt), L._fptr(T),
+                                                        C.byref(ended)))
+        return dict(n_processed=int(n.value), count=int(cnt.value), initial_T=T.reshape(4, 4).T.copy(),
+                    ended=bool(ended.value))
+
+    def last_timing(self) -> dict:
+        """wall_ms / device_ms of the last process call that registered its reading."""
+        w, d = C.c_double(), C.c_double()
+        self.ctx.check(L.lib.aicp_hip_map_session_last_timing(self.h, C.byref(w), C.byref(d)))
+        return dict(wall_ms=w.value, device_ms=d.value)

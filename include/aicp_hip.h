@@ -963,6 +963,65 @@ int aicp_hip_session_reference(aicp_hip_ctx* ctx, aicp_hip_session* s, float* ou
  * origin's upload to the promotion on the device (HIP events). Both nullable. */
 int aicp_hip_session_last_timing(const aicp_hip_session* s, double* wall_ms, double* device_ms);
 
+/* ---- live map sessions: one reading per call on the prior map or on the built map -------------
+ * App::processCloud (app.cpp:282-414) in localize_against_prior_map or localize_against_built_map
+ * mode as the node runs it: a handle keeps App's state for one of the two policies between calls,
+ * on the device: initialT_ and the count (prior map: getNbClouds(); built map: readings accepted
+ * since the last reference), the last reading's record and its prior origin. The map stays the
+ * caller's aicp_hip_map, as in the streams: it must outlive the session, and between two process
+ * calls the caller may use it with the read-only map calls (aicp_hip_map_size, _download, _crop);
+ * its size is final when process returns.
+ * Reading by reading the rules are the streams', with every window one reading long:
+ *   prior map (loc set): rules 1-7 of aicp_hip_map_sequence_run;
+ *   built map (bm set):  rules 1-6 of aicp_hip_built_map_sequence_run;
+ *   pf_read non-NULL: the readings are RAW and go through setAndFilterReading in App's order, as
+ *     the *_run_raw streams treat them (debug mode: the RAW reading is moved by the device's
+ *     initialT_, then pre-filtered);
+ *   pf_read NULL: the readings are already pre-filtered, as the pre-filtered streams take them
+ *     (debug mode then moves the filtered cloud, those entry points' documented order).
+ * A dropped reading changes nothing, initialT_ included. An empty crop, a reading the pre-filter
+ * empties and a non-zero registration status each end the session: the call returns that status,
+ * out is filled as the stream fills the ending reading's record, the map keeps what was committed
+ * before, and further process calls return AICP_ERR_INVALID until aicp_hip_map_session_start. So
+ * does a map that cannot grow for an append: its error is returned before any state changes and the
+ * map is left as it was.
+ * The append (rule: merged / is_reference) is decided and done on the device behind the reading's
+ * registration; the host makes room in the map beforehand, when the count says the reading would
+ * append if accepted, and adds the reading's points to the map's size after the call's one
+ * read-back. A point-to-point chain (knn_normals 0) is accepted. A session is driven from one
+ * thread at a time, on its context's stream; several sessions may share a context, and a session
+ * may alternate with any other call on the context. */
+typedef struct aicp_hip_map_session aicp_hip_map_session;
+/* Exactly one of loc / bm is non-NULL (both or neither: AICP_ERR_INVALID); their checks and flags
+ * are the streams'. pf_read: nullable (above); an unsupported one is refused here. pf_map: the
+ * prior map's re-filter (NULL: the defaults); AICP_ERR_INVALID with bm. Everything is copied. */
+int aicp_hip_map_session_create(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* loc,
+                                const aicp_built_map_params* bm, const aicp_prefilter_params* pf_read,
+                                const aicp_prefilter_params* pf_map, aicp_hip_map_session** out);
+void aicp_hip_map_session_free(aicp_hip_ctx* ctx, aicp_hip_map_session* s);
+/* count = 0, initialT_ = I, not ended, nothing processed, on `map` (built map: the map created from
+ * App's first cloud, as for the stream). Calling start again restarts the session. */
+int aicp_hip_map_session_start(aicp_hip_ctx* ctx, aicp_hip_map_session* s, aicp_hip_map* map);
+/* One reading with its prior pose (16 floats, column-major; reading->origin its sensor origin, as
+ * in the streams). out_T: its correction (column-major). out: aicp_localization_result* (prior map)
+ * or aicp_built_map_result* (built map), one 128-byte layout. kept (nullable): its points after
+ * the pre-filter (pf_read NULL: its points). */
+int aicp_hip_map_session_process(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const aicp_cloud* reading,
+                                 const float pose[16], float out_T[16], void* out, uint32_t* kept);
+/* The reading is the sweep accumulator's cloud where it lies (no bus crossing; the accumulator is
+ * left as it is); its sensor origin is the pose's translation. Needs pf_read (AICP_ERR_INVALID
+ * otherwise). */
+int aicp_hip_map_session_process_accum(aicp_hip_ctx* ctx, aicp_hip_map_session* s, aicp_hip_accum* acc,
+                                       const float pose[16], float out_T[16], void* out, uint32_t* kept);
+/* Every output is nullable. n_processed: process calls since start (dropped and failed readings
+ * count); count: the policy's count (above); initial_T: initialT_, column-major; ended: 1 after a
+ * reading that ended the session. */
+int aicp_hip_map_session_state(aicp_hip_ctx* ctx, aicp_hip_map_session* s, uint64_t* n_processed, int32_t* count,
+                               float initial_T[16], int32_t* ended);
+/* The last process call that registered its reading: the whole call on the host (map changes
+ * included), and from its first enqueue to the append on the device (HIP events). Both nullable. */
+int aicp_hip_map_session_last_timing(const aicp_hip_map_session* s, double* wall_ms, double* device_ms);
+
 /* ---- kernel-level entry points (parity tests and diagnostics) --------------------------- */
 /* kd-tree over pts (as given, no centring) + k-NN of queries: libnabo
  * KDTreeUnbalancedPtInLeavesImplicitBoundsStackOpt order, ALLOW_SELF_MATCH.
