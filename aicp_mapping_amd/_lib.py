@@ -52,7 +52,7 @@ EXPORTS = [
     "aicp_hip_map_align_batch", "aicp_hip_map_capacity", "aicp_hip_default_built_map_params",
     "aicp_hip_built_map_window", "aicp_hip_built_map_sequence_run", "aicp_hip_last_built_map_timing",
     "aicp_hip_map_sequence_run_raw", "aicp_hip_built_map_sequence_run_raw", "aicp_hip_test_ingest",
-    "aicp_hip_test_tree", "aicp_hip_test_nn",
+    "aicp_hip_test_tree", "aicp_hip_test_nn", "aicp_hip_test_normals",
     "aicp_hip_svm_load", "aicp_hip_svm_free", "aicp_hip_svm_info", "aicp_hip_svm_predict", "aicp_hip_pipeline",
     "aicp_hip_sequence_run_risk",
     "aicp_hip_default_accum_params", "aicp_hip_accum_create", "aicp_hip_accum_free", "aicp_hip_accum_push",
@@ -85,6 +85,7 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_test_ingest",  # raw readings in the two map streams
            "aicp_hip_test_tree",  # the kd-tree build, node for node
            "aicp_hip_test_nn",  # the NN search, query by query
+           "aicp_hip_test_normals",  # the SurfaceNormal chain, point by point
            "aicp_hip_svm_load", "aicp_hip_svm_free", "aicp_hip_svm_info", "aicp_hip_svm_predict",
            "aicp_hip_pipeline", "aicp_hip_sequence_run_risk",  # the classifier and the risk gate
            "aicp_hip_default_accum_params", "aicp_hip_accum_create", "aicp_hip_accum_free", "aicp_hip_accum_push",
@@ -598,6 +599,9 @@ def _load():
         u32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
         L.aicp_hip_test_nn.argtypes = [vp, sz, u32p, fp, C.c_int32, sz, u32p, u32p, fp, sz, fp, u8p, C.c_float,
                                        C.c_float, ip, fp, u32p, ip, ip, up]
+    if hasattr(L, "aicp_hip_test_normals"):
+        u32p = C.POINTER(C.c_uint32)
+        L.aicp_hip_test_normals.argtypes = [vp, sz, u32p, fp, C.c_int32, C.c_int32, ip, ip, ip, fp, ip, up, fp, ip, ip, up]
     if hasattr(L, "aicp_hip_svm_load"):
         dp, clp, pfp = C.POINTER(C.c_double), C.POINTER(Cloud), C.POINTER(PrefilterParams)
         rpp, prp = C.POINTER(RiskParams), C.POINTER(PipelineRecord)
@@ -1381,6 +1385,35 @@ class Context:
         return dict(match=match, d2=d2, touched=touched, ids=[ids[ro[r]:ro[r + 1]] for r in range(R)],
                     engine=engine.value, dirty=int(dirty.value),
                     read_off=np.concatenate([[0], np.cumsum(n_read.astype(np.int64))]))
+
+    def test_normals(self, refs, knn=20, matcher_bucket=8):
+        """aicp_hip_test_normals: the SurfaceNormal chain of a batch's references. refs: a list of
+        (n, 3) float32 clouds (one batch). Returns dict(ids, ids2: per reference (n, knn) raw bucket
+        positions in k-best order, -1 for none; raw_id, matcher_id: per reference the input id of
+        every raw / matcher bucket position; nrm, bnrm: per reference (n, 4) float32 in raw / matcher
+        bucket order; degenerate: (n_refs,); touched: (bucket points, inner nodes) of the second kNN
+        launch; engine: 1 octet, 2 per lane; dirty)."""
+        refs = [np.ascontiguousarray(c, np.float32).reshape(-1, 3) for c in refs]
+        counts = np.array([c.shape[0] for c in refs], np.uint32)
+        R, total = counts.size, int(counts.sum(dtype=np.uint64))
+        rp = np.ascontiguousarray(np.concatenate(refs, axis=0)) if R else np.zeros((0, 3), np.float32)
+        k = max(int(knn), 0)
+        ids, ids2 = np.zeros((total, k), np.int32), np.zeros((total, k), np.int32)
+        raw_id, matcher_id = np.zeros(total, np.int32), np.zeros(total, np.int32)
+        nrm, bnrm = np.zeros((total, 4), np.float32), np.zeros((total, 4), np.float32)
+        deg, touched = np.zeros(R, np.int32), np.zeros(2, np.uint64)
+        engine, dirty = C.c_int32(-1), C.c_uint64()
+        ip, u32p, up = C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+        rc = lib.aicp_hip_test_normals(
+            self.h, R, counts.ctypes.data_as(u32p), _fptr(rp), int(knn), int(matcher_bucket), ids.ctypes.data_as(ip),
+            ids2.ctypes.data_as(ip), raw_id.ctypes.data_as(ip), _fptr(nrm), deg.ctypes.data_as(ip),
+            touched.ctypes.data_as(up), _fptr(bnrm), matcher_id.ctypes.data_as(ip), C.byref(engine), C.byref(dirty))
+        self.check(rc)
+        ro = np.concatenate([[0], np.cumsum(counts.astype(np.int64))])
+        cut = lambda a: [a[ro[r]:ro[r + 1]] for r in range(R)]
+        return dict(ids=cut(ids), ids2=cut(ids2), raw_id=cut(raw_id), matcher_id=cut(matcher_id), nrm=cut(nrm),
+                    bnrm=cut(bnrm), degenerate=deg, touched=(int(touched[0]), int(touched[1])), engine=engine.value,
+                    dirty=int(dirty.value))
 
     def crop_box(self, pts, mn, mx, origin):
         """getPointsInOrientedBox (filteringUtils.cpp:619-637) on device: returns (kept xyz in

@@ -2222,6 +2222,157 @@ int aicp_hip_test_nn(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* ref_count
   return AICP_OK;
 }
 
+// The SurfaceNormal chain of run_batch's references on given clouds: the raw trees on tb[0] with
+// the lean plan, launch_init_state, launch_normals with the normals' counters, a second
+// launch_knn_ids with the touched counters, the centred matcher trees on tb[1] and
+// launch_normals_to_matcher, all on one stream (run_batch launches launch_init_state ahead of the
+// raw trees; it reads the descriptors alone, so its place before the normals is all that counts).
+// The id buffers and the two normal arrays are this
+// call's, 64 guard words on both sides, sentinel-filled before the launches. Every argument is
+// checked before the device is touched, each tree before anything searches it.
+int aicp_hip_test_normals(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* counts, const float* pts, int32_t knn,
+                          int32_t matcher_bucket, int32_t* out_ids, int32_t* out_ids2, int32_t* out_raw_id,
+                          float* out_nrm, int32_t* out_degenerate, uint64_t* out_touched, float* out_bnrm,
+                          int32_t* out_matcher_id, int32_t* out_engine, uint64_t* out_dirty) {
+  if (!ctx || !counts || !pts || !out_ids || !out_ids2 || !out_raw_id || !out_nrm || !out_degenerate ||
+      !out_touched || !out_bnrm || !out_matcher_id || !out_engine || !out_dirty)
+    return AICP_ERR_INVALID;
+  if (n_refs == 0 || n_refs > (size_t)kMaxPairs || matcher_bucket < 1 || matcher_bucket > 4096)
+    return AICP_ERR_INVALID;
+  const size_t R = n_refs;
+  uint64_t total = 0, n_max = 0;
+  for (size_t r = 0; r < R; ++r) {
+    if (counts[r] == 0) return AICP_ERR_INVALID;
+    total += counts[r];
+    n_max = std::max<uint64_t>(n_max, counts[r]);
+  }
+  if (total >= (1ull << 28)) return AICP_ERR_INVALID;
+  if (knn != 10 && knn != 20 && knn != 30) FAIL(AICP_ERR_UNSUPPORTED, "knn must be 10, 20 or 30");
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  ctx->refc.invalidate();  // (ctx->rdesc / rstate / bpts / nodes are rewritten)
+  std::vector<PairDesc> rdesc(R, PairDesc{});
+  uint32_t off = 0;
+  for (size_t r = 0; r < R; ++r) {
+    rdesc[r].ref_off = off;
+    rdesc[r].n_ref = counts[r];
+    rdesc[r].ratio = 0.5f;
+    rdesc[r].ref_id = (int32_t)r;
+    ident4(rdesc[r].Tin);
+    off += counts[r];
+  }
+  constexpr size_t kGuard = 64;
+  const size_t id_words = (size_t)total * (size_t)knn + 2 * kGuard, nrm_words = (size_t)total * 4 + 2 * kGuard;
+  struct Local {  // freed on every return
+    DevBuf ids, ids2, nrm, bnrm, touched;
+    ~Local() {
+      release(ids);
+      release(ids2);
+      release(nrm);
+      release(bnrm);
+      release(touched);
+    }
+  } loc;
+  HIPC(ensure(loc.ids, id_words * 4));
+  HIPC(ensure(loc.ids2, id_words * 4));
+  HIPC(ensure(loc.nrm, nrm_words * 4));
+  HIPC(ensure(loc.bnrm, nrm_words * 4));
+  HIPC(ensure(loc.touched, 16));
+  HIPC(ensure(ctx->ref1, total * 16));
+  HIPC(ensure(ctx->rdesc, R * sizeof(PairDesc)));
+  HIPC(ensure(ctx->rdesc_raw, R * sizeof(PairDesc)));
+  HIPC(ensure(ctx->rstate, R * sizeof(PairState)));
+  HIPC(ensure(ctx->inv, total * 4));
+  HIPC(ensure(ctx->ctrs, kCtrWords * 4));
+  {
+    std::vector<float> pk(4 * (size_t)total);
+    pack_xyz4(pts, total, 12, pk.data());
+    HIPC(hipMemcpy(ctx->ref1.p, pk.data(), total * 16, hipMemcpyHostToDevice));
+  }
+  PairDesc* dRaw = ctx->rdesc_raw.as<PairDesc>();
+  PairDesc* dRdesc = ctx->rdesc.as<PairDesc>();
+  PairState* dRstate = ctx->rstate.as<PairState>();
+  HIPC(hipMemcpy(dRaw, rdesc.data(), R * sizeof(PairDesc), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(dRdesc, rdesc.data(), R * sizeof(PairDesc), hipMemcpyHostToDevice));
+  constexpr uint32_t kSentinel = AICP_TEST_NN_SENTINEL;
+  HIPC(hipMemsetD32Async((hipDeviceptr_t)loc.ids.p, (int)kSentinel, id_words, s));
+  HIPC(hipMemsetD32Async((hipDeviceptr_t)loc.ids2.p, (int)kSentinel, id_words, s));
+  HIPC(hipMemsetD32Async((hipDeviceptr_t)loc.nrm.p, (int)kSentinel, nrm_words, s));
+  HIPC(hipMemsetD32Async((hipDeviceptr_t)loc.bnrm.p, (int)kSentinel, nrm_words, s));
+  HIPC(hipMemsetAsync(loc.touched.p, 0, 16, s));
+  HIPC(hipMemsetAsync(ctx->ctrs.p, 0, kCtrWords * 4, s));
+  HIPC(hipMemsetAsync(dRstate, 0, R * sizeof(PairState), s));
+  // 1. the raw-coordinate trees (run_batch's build of them)
+  int rc = device_trees_begin(ctx->tb[0], ctx->err, s, R, total, dRaw, ctx->ref1.as<float4>(), 0, kNormalsBucket,
+                              ctx->bpts_raw, ctx->nodes_raw);
+  if (rc) return rc;
+  rc = device_trees_end(ctx->tb[0], ctx->err, s, R, total, dRaw, kNormalsBucket, ctx->bpts_raw, ctx->nodes_raw,
+                        plan_levels(n_max, ctx->tb[0], ctx->opt.tree_plan, true), nullptr, true);
+  if (rc) return rc;
+  HIPC(hipStreamSynchronize(s));
+  rc = device_trees_check(ctx->tb[0], ctx->err);  // (a tree deeper than the device stacks: no search is run)
+  if (rc) return rc;
+  // 2. - 4. the state, the normals, the kNN again with its counters
+  int32_t* ids = loc.ids.as<int32_t>() + kGuard;
+  int32_t* ids2 = loc.ids2.as<int32_t>() + kGuard;
+  float4* nrm = reinterpret_cast<float4*>(loc.nrm.as<float>() + kGuard);
+  float4* bnrm = reinterpret_cast<float4*>(loc.bnrm.as<float>() + kGuard);
+  uint32_t* nCtr = ctx->ctrs.as<uint32_t>() + kKnnCtrOff;
+  const int engine = ctx->opt.normals_knn_engine;
+  int engine_used = 0;
+  launch_init_state(s, (int)R, dRaw, dRstate);
+  if (!launch_normals(s, (int)R, (uint32_t)total, dRaw, dRstate, ctx->nodes_raw.as<uint4>(), nullptr,
+                      ctx->bpts_raw.as<float4>(), nrm, knn, ids, nCtr, engine))
+    FAIL(AICP_ERR_UNSUPPORTED, "normals knn");
+  if (!launch_knn_ids(s, (int)R, (uint32_t)total, dRaw, ctx->nodes_raw.as<uint4>(), ctx->bpts_raw.as<float4>(), knn,
+                      ids2, nCtr, loc.touched.as<unsigned long long>(), engine, &engine_used))
+    FAIL(AICP_ERR_UNSUPPORTED, "normals knn");
+  *out_engine = engine_used;  // (the kernel that launch launched)
+  HIPC(hipGetLastError());
+  // 5. the matcher trees (matcher_trees' build: centred)
+  rc = device_trees_begin(ctx->tb[1], ctx->err, s, R, total, dRdesc, ctx->ref1.as<float4>(), 1, matcher_bucket,
+                          ctx->bpts, ctx->nodes);
+  if (rc) return rc;
+  rc = device_trees_end(ctx->tb[1], ctx->err, s, R, total, dRdesc, matcher_bucket, ctx->bpts, ctx->nodes,
+                        plan_levels(n_max, ctx->tb[1], ctx->opt.tree_plan));
+  if (rc) return rc;
+  HIPC(hipStreamSynchronize(s));
+  rc = device_trees_check(ctx->tb[1], ctx->err);
+  if (rc) return rc;
+  // 6. the normals in the matcher trees' order
+  launch_normals_to_matcher(s, (int)R, (uint32_t)total, dRdesc, ctx->bpts.as<float4>(), ctx->bpts_raw.as<float4>(),
+                            nrm, ctx->inv.as<uint32_t>(), bnrm);
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(s));
+  uint64_t dirty = 0;
+  {
+    std::vector<uint32_t> back(std::max(id_words, nrm_words));
+    auto fetch = [&](const DevBuf& b, size_t words, void* out) -> hipError_t {
+      const hipError_t e = hipMemcpy(back.data(), b.p, words * 4, hipMemcpyDeviceToHost);
+      if (e != hipSuccess) return e;
+      for (size_t g = 0; g < kGuard; ++g)
+        dirty += (back[g] != kSentinel) + (back[words - kGuard + g] != kSentinel);
+      std::memcpy(out, back.data() + kGuard, (words - 2 * kGuard) * 4);
+      return hipSuccess;
+    };
+    HIPC(fetch(loc.ids, id_words, out_ids));
+    HIPC(fetch(loc.ids2, id_words, out_ids2));
+    HIPC(fetch(loc.nrm, nrm_words, out_nrm));
+    HIPC(fetch(loc.bnrm, nrm_words, out_bnrm));
+    for (int which = 0; which < 2; ++which) {
+      HIPC(hipMemcpy(back.data(), which ? ctx->bpts.p : ctx->bpts_raw.p, (size_t)total * 16, hipMemcpyDeviceToHost));
+      int32_t* out = which ? out_matcher_id : out_raw_id;
+      for (size_t i = 0; i < total; ++i) out[i] = (int32_t)back[4 * i + 3];
+    }
+  }
+  std::vector<PairState> hs(R);
+  HIPC(hipMemcpy(hs.data(), dRstate, R * sizeof(PairState), hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < R; ++r) out_degenerate[r] = hs[r].degenerate;
+  HIPC(hipMemcpy(out_touched, loc.touched.p, 16, hipMemcpyDeviceToHost));
+  *out_dirty = dirty;
+  return AICP_OK;
+}
+
 void aicp_hip_default_prefilter(aicp_prefilter_params* p) {
   if (!p) return;
   *p = aicp_prefilter_params{};

@@ -33,10 +33,11 @@ bool launch_normals(hipStream_t s, int n_pairs, uint32_t total_ref, const PairDe
                     int32_t* ids, uint32_t* ctr, int engine);
 // the kNN of every reference point in its own tree (bucket order in and out: ids are bucket
 // positions of the pair's tree, -1 past the cloud size); eps 0, self included. touched
-// (nullable, zeroed): += touched points, inner nodes
+// (nullable, zeroed): += touched points, inner nodes. engine_used (nullable, tests): the engine
+// whose kernel was launched: 1 one query per octet of lanes (k_knn_oct), 2 one per lane (k_knn_ids)
 bool launch_knn_ids(hipStream_t s, int n_pairs, uint32_t total_ref, const PairDesc* pd, const uint4* nodes,
                     const float4* bpts, int knn, int32_t* ids, uint32_t* ctr, unsigned long long* touched,
-                    int engine);
+                    int engine, int* engine_used = nullptr);
 // host_n (nullable): device pointer of mapped host memory that receives the active count;
 // done_sig (nullable, signal memory): once no pair is active, the final corrections go to outT
 // and *ticket is stored to done_sig (the sequence's next reference waits on it)

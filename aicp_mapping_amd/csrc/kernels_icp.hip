@@ -2753,9 +2753,10 @@ static bool knn_oct_enabled(uint32_t n_queries, int engine) {
 
 bool launch_knn_ids(hipStream_t s, int n_pairs, uint32_t total_ref, const PairDesc* pd, const uint4* nodes,
                     const float4* bpts, int knn, int32_t* ids, uint32_t* ctr, unsigned long long* touched,
-                    int engine) {
+                    int engine, int* engine_used) {
   if (!total_ref) return true;
   if (knn_oct_enabled(total_ref, engine)) {
+    if (engine_used) *engine_used = 1;
     const unsigned go = (unsigned)(((uint64_t)total_ref * 8 + 255) / 256);
     switch (knn) {
       case 10: k_knn_oct<10, 8><<<go, 256, 0, s>>>(n_pairs, total_ref, pd, nodes, bpts, ids, touched); break;
@@ -2768,6 +2769,7 @@ bool launch_knn_ids(hipStream_t s, int n_pairs, uint32_t total_ref, const PairDe
   // the persistent engine's work counters, zeroed here: the octet engine needs none, and a
   // caller's memset ahead of it put a ~5 us fill kernel on the C2 reference chain for nothing
   if (hipMemsetAsync(ctr, 0, kPersistCtrWords * 4, s) != hipSuccess) return false;
+  if (engine_used) *engine_used = 2;
   const int g = persistent_grid((int)total_ref);
   switch (knn) {
     case 10: k_knn_ids<10><<<g, 256, 0, s>>>(n_pairs, total_ref, pd, nodes, nullptr, bpts, ids, ctr, touched); break;

@@ -1160,6 +1160,37 @@ int aicp_hip_test_nn(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* ref_count
                      const uint8_t* active /* n_steps * n_pairs, nullable */, float epsilon, float max_dist,
                      int32_t* out_match, float* out_d2, uint32_t* out_touched /* each n_steps * total */,
                      int32_t* out_ids /* sum(ref_counts) */, int32_t* out_engine, uint64_t* out_dirty);
+/* Test surface: the SurfaceNormal chain of a batch's references, launch by launch, and everything
+ * it writes. The n_refs clouds (pts, 3 floats per point, counts[r] points each, one after another;
+ * total = sum(counts)) go through what a registration batch runs for its references:
+ *  1. the raw-coordinate trees as one batch (no centring, leaf size 8), as aicp_hip_test_tree
+ *     builds a batch with the plan the registration gives the raw tree;
+ *  2. the per-reference state (launch_init_state);
+ *  3. launch_normals: the self-kNN of every point (`knn` neighbours, eps 0, self included) on the
+ *     engine the context's normals_knn_engine option selects, then k_normals_from_ids;
+ *  4. launch_knn_ids once more, into a second id buffer, with the touched counters;
+ *  5. the matcher trees (centred, leaf size matcher_bucket);
+ *  6. launch_normals_to_matcher: the normals into the matcher trees' bucket order.
+ * The two id buffers, the raw normals and the matcher normals live in buffers of this call and are
+ * filled with AICP_TEST_NN_SENTINEL before the launches, 64 guard words on both sides included;
+ * out_dirty counts the guard words that changed (0 expected).
+ * out_ids, out_ids2: knn entries per raw bucket position (reference r's at its prefix offset), in
+ * k-best order, each a raw bucket position within the reference, -1 past the cloud's size.
+ * out_raw_id, out_matcher_id: the input id (within its cloud) of every raw / matcher bucket
+ * position. out_nrm, out_bnrm: 4 floats per raw / matcher bucket position (x, y, z, 0).
+ * out_degenerate: per reference, the points whose covariance had rank <= 1 (normal e_y).
+ * out_touched: the second kNN launch's bucket points and inner nodes. out_engine: 1 one query per
+ * octet of lanes (k_knn_oct), 2 one per lane (k_knn_ids): the kernel step 4 launched.
+ * AICP_ERR_INVALID, before any device work: a null pointer, no cloud or more than 4096, a count of
+ * 0, total >= 2^28, matcher_bucket outside [1, 4096]. AICP_ERR_UNSUPPORTED: knn outside
+ * {10, 20, 30} (before any device work), a tree deeper than 47 levels (before any search).
+ * Invalidates the context's reference cache. */
+int aicp_hip_test_normals(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* counts, const float* pts, int32_t knn,
+                          int32_t matcher_bucket, int32_t* out_ids, int32_t* out_ids2 /* each knn * total */,
+                          int32_t* out_raw_id /* total */, float* out_nrm /* 4 * total */,
+                          int32_t* out_degenerate /* n_refs */, uint64_t* out_touched /* 2 */,
+                          float* out_bnrm /* 4 * total */, int32_t* out_matcher_id /* total */, int32_t* out_engine,
+                          uint64_t* out_dirty);
 /* Test surface: the raw streams' ingest alone. rows: n rows of `stride` bytes (>= 12, a multiple of
  * 4), xyz first, uploaded as the raw streams upload them (at most 16 bytes: verbatim; wider: packed
  * on the host), then k_stream_ingest: out4[4 i ..] = (x, y, z, 1), moved by T (nullable, column-major
