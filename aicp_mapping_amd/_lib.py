@@ -61,6 +61,8 @@ EXPORTS = [
     "aicp_hip_session_create", "aicp_hip_session_free", "aicp_hip_session_start", "aicp_hip_session_start_accum",
     "aicp_hip_session_process", "aicp_hip_session_process_accum", "aicp_hip_session_state",
     "aicp_hip_session_reference", "aicp_hip_session_last_timing",
+    "aicp_hip_session_create_risk", "aicp_hip_session_start_pose", "aicp_hip_session_start_accum_pose",
+    "aicp_hip_session_process_risk", "aicp_hip_session_process_accum_risk", "aicp_hip_session_reference_pose",
     "aicp_hip_map_session_create", "aicp_hip_map_session_free", "aicp_hip_map_session_start",
     "aicp_hip_map_session_process", "aicp_hip_map_session_process_accum", "aicp_hip_map_session_state",
     "aicp_hip_map_session_last_timing",
@@ -96,7 +98,10 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_session_state", "aicp_hip_session_reference", "aicp_hip_session_last_timing",  # the live session
            "aicp_hip_map_session_create", "aicp_hip_map_session_free", "aicp_hip_map_session_start",
            "aicp_hip_map_session_process", "aicp_hip_map_session_process_accum", "aicp_hip_map_session_state",
-           "aicp_hip_map_session_last_timing"}  # the live map sessions
+           "aicp_hip_map_session_last_timing",  # the live map sessions
+           "aicp_hip_session_create_risk", "aicp_hip_session_start_pose", "aicp_hip_session_start_accum_pose",
+           "aicp_hip_session_process_risk", "aicp_hip_session_process_accum_risk",
+           "aicp_hip_session_reference_pose"}  # the live session with the risk gate
 
 
 class IcpConfig(C.Structure):
@@ -642,6 +647,16 @@ def _load():
         L.aicp_hip_session_state.argtypes = [vp, vp, up, ip, szp, fp, ip]
         L.aicp_hip_session_reference.argtypes = [vp, vp, fp, sz, szp, dp]
         L.aicp_hip_session_last_timing.argtypes = [vp, dp, dp]
+    if hasattr(L, "aicp_hip_session_create_risk"):
+        u32p, dp, clp = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(Cloud)
+        srp, prp = C.POINTER(SequenceResult), C.POINTER(PipelineRecord)
+        L.aicp_hip_session_create_risk.argtypes = [vp, cfgp, C.POINTER(SequenceParams), C.POINTER(PrefilterParams),
+                                                   C.POINTER(RiskParams), vp, C.c_double, C.POINTER(vp)]
+        L.aicp_hip_session_start_pose.argtypes = [vp, vp, clp, dp]
+        L.aicp_hip_session_start_accum_pose.argtypes = [vp, vp, vp, dp]
+        L.aicp_hip_session_process_risk.argtypes = [vp, vp, clp, dp, fp, srp, prp, u32p]
+        L.aicp_hip_session_process_accum_risk.argtypes = [vp, vp, vp, dp, fp, srp, prp, u32p]
+        L.aicp_hip_session_reference_pose.argtypes = [vp, vp, dp]
     if hasattr(L, "aicp_hip_map_session_create"):  # (out: LocalizationResult or BuiltMapResult, one layout)
         u32p, dp, clp, pfp = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(Cloud), C.POINTER(PrefilterParams)
         L.aicp_hip_map_session_create.argtypes = [vp, cfgp, C.POINTER(LocalizationParams), C.POINTER(BuiltMapParams),

@@ -3487,11 +3487,20 @@ int aicp_hip_cluster_match(aicp_hip_ctx* ctx, const float* sampled_a, const int3
 
 // d_align (nullable, device): receives the alignability from the device's own result, enqueued on
 // ctx->stream (the pipeline's classifier reads it there)
+// dev_a, dev_b (both or neither): the clouds lie on the device already (float4, stride 16; the live
+// session's reference and reading) and the FOV filters read them where they lie: nothing is packed,
+// uploaded or copied, and of cloud_a / cloud_b only n is read.
 static int alignment_features(aicp_hip_ctx* ctx, const aicp_risk_params* prm, const aicp_cloud* cloud_a,
                               const aicp_cloud* cloud_b, const double pose_a[16], const double pose_b[16],
                               aicp_risk_result* out, float* planes_a, size_t* n_planes_a, float* planes_b,
-                              size_t* n_planes_b, size_t planes_cap, float* d_align) {
-  if (!ctx || !prm || !pose_a || !pose_b || !out || !valid_cloud(cloud_a) || !valid_cloud(cloud_b))
+                              size_t* n_planes_b, size_t planes_cap, float* d_align, const float4* dev_a = nullptr,
+                              const float4* dev_b = nullptr) {
+  if (!ctx || !prm || !pose_a || !pose_b || !out || !cloud_a || !cloud_b || (dev_a == nullptr) != (dev_b == nullptr))
+    return AICP_ERR_INVALID;
+  const bool resident = dev_a != nullptr;
+  if (resident ? (cloud_a->n < 1 || cloud_a->n > (uint64_t)INT32_MAX || cloud_b->n < 1 ||
+                  cloud_b->n > (uint64_t)INT32_MAX)
+               : (!valid_cloud(cloud_a) || !valid_cloud(cloud_b)))
     return AICP_ERR_INVALID;
   int rc = pf_check(ctx, &prm->prefilter);
   if (rc) return rc;
@@ -3509,31 +3518,32 @@ static int alignment_features(aicp_hip_ctx* ctx, const aicp_risk_params* prm, co
   const aicp_cloud* cl[2] = {cloud_a, cloud_b};
   const double* own[2] = {pose_a, pose_b};
   const double* other[2] = {pose_b, pose_a};
-  // per cloud: in[n] | accepted[n] | s8[n] (32 B) | labels[n] | cluster records
-  float4* din[2];
+  // per cloud: in[n] (host input only) | accepted[n] | s8[n] (32 B) | labels[n] | cluster records
+  const float4* dev[2] = {dev_a, dev_b};
+  const float4* din[2];
   float4* dacc[2];
   size_t off_s8[2], off_lab[2], off_cl[2];
   size_t tiles_max = 0;
   for (int x = 0; x < 2; ++x) {
-    const size_t n = cl[x]->n;
-    off_s8[x] = 2 * n * 16;
+    const size_t n = cl[x]->n, off_acc = resident ? 0 : n * 16;
+    off_s8[x] = off_acc + n * 16;
     off_lab[x] = off_s8[x] + n * 32;
     off_cl[x] = (off_lab[x] + n * 4 + 255) & ~size_t(255);
     HIPC(ensure(ctx->risk[x], off_cl[x] + (size_t)kRiskMaxClusters * sizeof(RiskCluster)));
-    din[x] = ctx->risk[x].as<float4>();
-    dacc[x] = din[x] + n;
+    din[x] = resident ? dev[x] : ctx->risk[x].as<float4>();
+    dacc[x] = reinterpret_cast<float4*>(ctx->risk[x].as<char>() + off_acc);
     tiles_max = std::max(tiles_max, fov_tiles(n));
   }
   const size_t tile_b = (2 * tiles_max * 4 + 255) & ~size_t(255);
   HIPC(ensure(ctx->risk[2], 256 + 2 * tile_b));
   HIPC(ensure(ctx->pin_risk, kRiskPinBytes));
-  HIPC(ensure(ctx->pin_io, (cl[0]->n + cl[1]->n) * 16 + 64));
-  {
+  if (!resident) {
+    HIPC(ensure(ctx->pin_io, (cl[0]->n + cl[1]->n) * 16 + 64));
     float* h = ctx->pin_io.as<float>();
     pack_xyz4(cl[0]->pts, cl[0]->n, cl[0]->stride, h);
     pack_xyz4(cl[1]->pts, cl[1]->n, cl[1]->stride, h + 4 * cl[0]->n);
-    HIPC(hipMemcpyAsync(din[0], h, cl[0]->n * 16, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(din[1], h + 4 * cl[0]->n, cl[1]->n * 16, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(ctx->risk[0].p, h, cl[0]->n * 16, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(ctx->risk[1].p, h + 4 * cl[0]->n, cl[1]->n * 16, hipMemcpyHostToDevice, s));
   }
   HIPC(hipEventRecord(E[0], s));
   char* W = ctx->risk[2].as<char>();
@@ -3658,13 +3668,6 @@ int aicp_hip_last_risk_stats(const aicp_hip_ctx* ctx, aicp_risk_stats* out) {
 namespace {
 
 constexpr size_t kSvmModelsKept = 8;  // device copies a context keeps (the oldest goes first)
-
-struct GateRec {  // the pipeline's record in device memory: the classifier's sample, then its outputs
-  float overlap, alignability;
-  float raw, ratio;
-  double risk;
-  int32_t gate, pad;
-};
 
 // the model's device copy in this context: uploaded on first use, found by the model's id afterwards
 int svm_device(aicp_hip_ctx* ctx, const aicp_hip_svm* m, const SvmEntry** entries, SvmParams* prm) {
@@ -3891,6 +3894,42 @@ int pipeline_core(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_risk
 }
 
 }  // namespace
+
+// ---- the gate of the live session (session.cpp): pipeline_core's steps 2 and 3 on resident clouds --
+namespace aicp {
+namespace rt {
+
+void pose_moved(const float* T, const double* prior, double* out) { moved_pose(T, prior, out); }
+void pose_fix_pitch_roll(const double* corrected, const double* odom, double* out) {
+  fix_pitch_roll(corrected, odom, out);
+}
+int risk_params_check(aicp_hip_ctx* ctx, const aicp_risk_params* prm) { return pf_check(ctx, &prm->prefilter); }
+
+int gate_resident(aicp_hip_ctx* ctx, const aicp_risk_params* prm, const aicp_hip_svm* model, double threshold,
+                  const float4* d_ref, size_t n_ref, const float4* d_read, size_t n_read, const double* ref_pose,
+                  const double* read_pose, GateRec* d_gate, float* fov_overlap) {
+  hipStream_t s = ctx->stream;
+  const SvmEntry* entries = nullptr;
+  SvmParams sp;
+  int rc = svm_device(ctx, model, &entries, &sp);
+  if (rc) return rc;
+  sp.threshold = threshold;
+  HIPC(hipMemcpyAsync(&d_gate->overlap, &ctx->state.as<PairState>()[0].overlap, 4, hipMemcpyDeviceToDevice, s));
+  aicp_cloud ca{}, cb{};
+  ca.n = n_ref, ca.stride = 16;
+  cb.n = n_read, cb.stride = 16;
+  aicp_risk_result rr{};
+  rc = alignment_features(ctx, prm, &ca, &cb, ref_pose, read_pose, &rr, nullptr, nullptr, nullptr, nullptr, 0,
+                          &d_gate->alignability, d_ref, d_read);
+  if (rc) return rc;
+  *fov_overlap = rr.fov_overlap;
+  launch_svm_predict(s, 1, sp, entries, &d_gate->overlap, &d_gate->raw, &d_gate->risk, &d_gate->gate, &d_gate->ratio);
+  HIPC(hipGetLastError());
+  return AICP_OK;
+}
+
+}  // namespace rt
+}  // namespace aicp
 
 extern "C" {
 

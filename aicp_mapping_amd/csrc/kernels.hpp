@@ -382,6 +382,23 @@ void launch_session_promote(hipStream_t s, int n, const StreamRec* rec, const fl
 // registered; otherwise nothing is written. dst: the map's tail, with room for n points.
 void launch_session_map_append(hipStream_t s, int n, const StreamRec* rec, const float* T, const float4* read,
                                float4* dst);
+// The risk gate's record in device memory (failure_prediction_mode): the classifier's sample, then
+// what k_svm_predict writes for it
+struct GateRec {
+  float overlap, alignability;
+  float raw, ratio;
+  double risk;
+  int32_t gate, pad;
+};
+// The gated branch of processCloud (app.cpp:401-411) in the live session, right behind
+// launch_svm_predict with no host decision in between. gate->gate == 0: rec->append = 0, nothing
+// else. Otherwise the reading as it was filtered is the next reference, unmoved: ref[i] = read[i]
+// for its n points (the bytes, not apply4 by the identity), rec = {status 0, accepted 1, append 1,
+// corrected_origin = origin (the reading's prior origin, moved in debug mode)}, T = identity,
+// S->count = 0 (S->initT stays), hdr = {n, id, origin}.
+void launch_session_gate_promote(hipStream_t s, int n, const GateRec* gate, const double* origin, const float4* read,
+                                 int32_t id, float4* ref, float* T, StreamState* S, StreamRec* rec,
+                                 SessionHeader* hdr);
 
 // ---- pre-filter (kernels_prefilter.hip): regionGrowingUniformPlaneSegmentationFilter -------
 constexpr int kPfMaxNbrs = 16;  // RegionGrowing neighbours per point (edge mask bits)

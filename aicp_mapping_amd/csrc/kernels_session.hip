@@ -8,6 +8,10 @@
 // record says: the reading as it was registered, moved by its correction, becomes the session's
 // reference (app.cpp:375-391: pcl::transformPointCloud in float, apply4's expression, no FMA).
 //
+// k_session_gate_promote is the gated branch of failure_prediction_mode (app.cpp:401-411) for a risk
+// session, right behind k_svm_predict: the reading becomes the reference unmoved, by the gate the
+// classifier left in device memory.
+//
 // k_session_map_append is the same step for the live map sessions (map_stream.cpp): the reading
 // goes behind the caller's map instead (prior map: app.cpp:469-483, built map: app.cpp:383-391,
 // 458-465), where the host has made room before the reading's crop was enqueued.
@@ -65,9 +69,52 @@ __global__ __launch_bounds__(256) void k_session_map_append(int n, const StreamR
   move_point(Tl, read, dst, i);
 }
 
+// The gated branch (app.cpp:401-411: the unmoved reading joins the graph with its prior pose and is
+// the reference at once, the count restarts, initialT_ stays) behind k_svm_predict. Every thread
+// reads the gate from device memory (one address for the whole grid: the branch is uniform).
+// Gated: one thread per point of the reading copies it with one 128-bit load and one 128-bit store
+// (the bytes: apply4 by the identity would turn -0.0f into +0.0f, the host stream's swap does not),
+// thread 0 of block 0 writes the record, the identity correction, the count and the header. Not
+// gated: thread 0 of block 0 clears rec->append, nothing else is written. ref never aliases read.
+__global__ __launch_bounds__(256) void k_session_gate_promote(int n, const GateRec* __restrict__ gate,
+                                                              const double* __restrict__ origin,
+                                                              const float4* __restrict__ read, int32_t id,
+                                                              float4* __restrict__ ref, float* __restrict__ T,
+                                                              StreamState* S, StreamRec* rec, SessionHeader* hdr) {
+  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+  if (!gate->gate) {
+    if (first) rec->append = 0;
+    return;
+  }
+  if (first) {
+    rec->status = 0;
+    rec->accepted = 1;
+    rec->append = 1;
+    rec->refilter = 0;
+    hdr->count = (uint32_t)n;
+    hdr->id = id;
+    for (int k = 0; k < 3; ++k) {
+      const double o = origin[k];
+      rec->corrected_origin[k] = o;
+      hdr->origin[k] = o;
+    }
+    for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.f : 0.f;
+    S->count = 0;
+  }
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  ref[i] = read[i];
+}
+
 void launch_session_promote(hipStream_t s, int n, const StreamRec* rec, const float* T, const float4* read, int32_t id,
                             float4* ref, SessionHeader* hdr) {
   if (n > 0) k_session_promote<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, rec, T, read, id, ref, hdr);
+}
+void launch_session_gate_promote(hipStream_t s, int n, const GateRec* gate, const double* origin, const float4* read,
+                                 int32_t id, float4* ref, float* T, StreamState* S, StreamRec* rec,
+                                 SessionHeader* hdr) {
+  if (n > 0)
+    k_session_gate_promote<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, gate, origin, read, id, ref, T, S, rec, hdr);
 }
 void launch_session_map_append(hipStream_t s, int n, const StreamRec* rec, const float* T, const float4* read,
                                float4* dst) {

@@ -325,6 +325,18 @@ int stream_ingest_rows(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf, const
 // for a host array. The caller clears RefCache::use after its run_batch (and invalidates on an error).
 void refcache_begin_resident(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, uint64_t owner, uint64_t n_ref,
                              const double origin[3], double res, int flags);
+// The risk gate of the live session (session.cpp) on clouds that lie on the device (float4, stride
+// 16), behind an overlap-only run_batch of the same pair on ctx->stream: the batch's overlap into
+// d_gate->overlap, the alignment features from d_ref / d_read where they lie (alignability into
+// d_gate->alignability, device to device), then k_svm_predict into d_gate's raw, risk, gate and
+// ratio. Nothing of d_gate is read back here. The poses: column-major double[16].
+int gate_resident(aicp_hip_ctx* ctx, const aicp_risk_params* prm, const aicp_hip_svm* model, double threshold,
+                  const float4* d_ref, size_t n_ref, const float4* d_read, size_t n_read, const double* ref_pose,
+                  const double* read_pose, GateRec* d_gate, float* fov_overlap);
+int risk_params_check(aicp_hip_ctx* ctx, const aicp_risk_params* prm);  // its pre-filter's pf_check
+// the gate's pose rules (aicp_hip.cpp: fromMatrix4fToIsometry3d(T) * prior, removePitchRollCorrection)
+void pose_moved(const float* T, const double* prior, double* out);
+void pose_fix_pitch_roll(const double* corrected, const double* odom, double* out);
 // the sweep accumulator's cloud where it lies (accum.cpp): waits for the stream, *n points at *pts
 int accum_resident(aicp_hip_ctx* ctx, aicp_hip_accum* acc, const float4** pts, size_t* n);
 // aicp_hip_prefilter on n device-resident points (float4, w = 1; left unchanged), moved first by T

@@ -11,6 +11,15 @@
 // k_session_promote: the reading moved by its correction into the spare reference buffer when the
 // commit's record says so -> [host] one read-back of state, record and header.
 //
+// A risk session (aicp_hip_session_create_risk: failure_prediction_mode, runAicpPipeline
+// app.cpp:236-245 and the gated branch app.cpp:401-411) splits the batch in two and puts the gate
+// between: overlap-only batch -> alignment features with the FOV filters reading the reference and
+// the reading where they lie -> k_svm_predict -> k_session_gate_promote (gated: the unmoved reading
+// copied into the spare reference buffer, record, identity correction, count and header written on
+// the device) -> [host] one read-back of state, record, header and the gate's record. A gated
+// reading ends there; otherwise the ICP-only batch at the device's ratio, k_stream_commit and
+// k_session_promote follow as above. The reference's pose stays on the host in double.
+//
 // The reference lives in one of two buffers; a promotion writes the other one and the host flips
 // them when the record reports it, so a reading that is dropped or fails leaves the reference as it
 // was and a larger reference never needs a copy. Its identity in the reference cache is a number
@@ -33,10 +42,12 @@ using namespace aicp::rt;
 
 namespace {
 // the session's small device block and its pinned mirror
-constexpr size_t kOffState = 0, kOffRec = 128, kOffHdr = 192, kOffOrigin = 256, kWinBytes = 320;
-constexpr size_t kReadBack = kOffOrigin;  // state + record + header
+constexpr size_t kOffState = 0, kOffRec = 128, kOffHdr = 192, kOffOrigin = 256, kOffGate = 320, kWinBytes = 384;
+constexpr size_t kReadBack = kOffOrigin;                       // state + record + header
+constexpr size_t kReadBackGate = kOffGate + sizeof(GateRec);   // and, behind the origin, the gate's record
 static_assert(sizeof(StreamState) <= kOffRec && kOffRec + sizeof(StreamRec) <= kOffHdr &&
-                  kOffHdr + sizeof(SessionHeader) <= kOffOrigin && kOffRec % alignof(StreamRec) == 0,
+                  kOffHdr + sizeof(SessionHeader) <= kOffOrigin && kOffRec % alignof(StreamRec) == 0 &&
+                  kOffOrigin + 24 <= kOffGate && kReadBackGate <= kWinBytes && kOffGate % alignof(GateRec) == 0,
               "win's layout");
 constexpr int kFlags = AICP_RUN_OVERLAP | AICP_SEQ_DEBUG | AICP_RUN_TIME_NN;
 }  // namespace
@@ -47,7 +58,7 @@ struct aicp_hip_session {
   aicp_prefilter_params pf{};
   bool has_pf = false;
   StreamRules rules{};
-  DevBuf win;     // StreamState | StreamRec | SessionHeader | the reading's prior origin (3 doubles)
+  DevBuf win;     // StreamState | StreamRec | SessionHeader | the reading's prior origin (3 doubles) | GateRec
   PinBuf pin;     // its mirror
   DevBuf ref[2];  // the reference (float4, w = 1) and the buffer the next promotion writes
   int cur = 0;
@@ -61,6 +72,13 @@ struct aicp_hip_session {
   uint64_t ended_at = 0;
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   double last_wall_ms = 0, last_device_ms = 0;
+  // failure_prediction_mode (aicp_hip_session_create_risk): the features' parameters, the caller's
+  // model, the gate's threshold, and the reference's pose (host, double, column-major)
+  bool risk = false;
+  aicp_risk_params rprm{};
+  const aicp_hip_svm* model = nullptr;
+  double threshold = 0;
+  double ref_pose[16] = {};
 };
 
 namespace {
@@ -99,7 +117,9 @@ int end_session(aicp_hip_ctx* ctx, aicp_hip_session* s, int rc) {
   return rc;
 }
 
-int start_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r) {
+// first_pose: a risk session's (nullable otherwise): the reference's pose through updateCloud
+// (app.cpp:293-299), set once nothing can fail any more
+int start_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, const double* first_pose) {
   if (r.n == 0) FAIL(AICP_ERR_INVALID, "session: the first cloud is empty");
   HIPC(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -133,8 +153,43 @@ int start_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r) {
   for (int k = 0; k < 3; ++k) hh->origin[k] = r.origin[k];
   HIPC(hipMemcpyAsync(s->win.p, h, kWinBytes, hipMemcpyHostToDevice, st));
   HIPC(hipStreamSynchronize(st));
+  if (first_pose) pose_fix_pitch_roll(first_pose, first_pose, s->ref_pose);
   return AICP_OK;
 }
+
+// The one-pair batch of the session's reference and reading (kept points), both copied into the
+// batch device to device; the reference's voxel map and trees go through the reference cache under
+// the session's owner number. stats->status stays as the caller set it when the batch did not run
+// to its end; otherwise the return value is the reading's status.
+int pair_batch(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, const double* read_origin,
+               const aicp_icp_config* cfg, double res, int flags, float* out_T, aicp_icp_stats* stats) {
+  hipStream_t st = ctx->stream;
+  aicp_pair p{};
+  p.ref = p.read = s->read.as<float>();  // (not read: references on the device, readings skipped)
+  p.n_ref = s->ref_n;
+  p.n_read = kept;
+  p.ref_stride = p.read_stride = 16;
+  for (int k = 0; k < 3; ++k) {
+    p.ref_origin[k] = s->ref_origin[k];
+    p.read_origin[k] = read_origin[k];
+  }
+  if (!ctx->oneshot) ctx->oneshot = new aicp_hip_batch();
+  aicp_hip_batch* B = ctx->oneshot;
+  int rc = upload_pairs(ctx, &p, 1, B, true, false, true, true);
+  if (rc) return rc;
+  HIPC(hipMemcpyAsync(B->ref_raw.as<float4>() + B->rdesc[0].ref_off, s->ref[s->cur].p, s->ref_n * 16,
+                      hipMemcpyDeviceToDevice, st));
+  HIPC(hipMemcpyAsync(B->read_raw.as<float4>() + B->desc[0].read_off, s->read.p, (size_t)kept * 16,
+                      hipMemcpyDeviceToDevice, st));
+  refcache_begin_resident(ctx, cfg, s->gen, s->ref_n, s->ref_origin, res, flags);
+  rc = run_batch(ctx, B, cfg, res, flags, out_T, stats, nullptr);
+  ctx->refc.use = false;
+  if (rc) ctx->refc.invalidate();  // (an error may leave the reference side half written)
+  return rc;
+}
+
+int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, int32_t id, int rc,
+                   std::chrono::steady_clock::time_point t0, aicp_sequence_result* out, bool* promoted);
 
 int process_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, float* out_T, aicp_sequence_result* out,
                  uint32_t* kept_out) {
@@ -160,8 +215,6 @@ int process_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, float* o
   char* h = s->pin.as<char>();
   char* d = s->win.as<char>();
   StreamState* dS = reinterpret_cast<StreamState*>(d + kOffState);
-  StreamRec* dRec = reinterpret_cast<StreamRec*>(d + kOffRec);
-  SessionHeader* dHdr = reinterpret_cast<SessionHeader*>(d + kOffHdr);
   double* dOrg = reinterpret_cast<double*>(d + kOffOrigin);
   // the overlap's sensor origin of the moved reading, from the mirror of the device's initialT_
   // (k_stream_ingest computes the same for the commit, on the device)
@@ -178,38 +231,33 @@ int process_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, float* o
   if (kept_out) *kept_out = kept;
   if (!kept) return empty_reading();
   // the one-pair batch: both clouds are on the device already
-  aicp_pair p{};
-  p.ref = p.read = s->read.as<float>();  // (not read: references on the device, readings skipped)
-  p.n_ref = s->ref_n;
-  p.n_read = kept;
-  p.ref_stride = p.read_stride = 16;
-  for (int k = 0; k < 3; ++k) {
-    p.ref_origin[k] = s->ref_origin[k];
-    p.read_origin[k] = o[k];
-  }
   const int flags = AICP_RUN_ICP | (s->prm.flags & (AICP_RUN_OVERLAP | AICP_RUN_TIME_NN));
   const double res = doOvl ? s->prm.resolution : 0.0;
-  if (!ctx->oneshot) ctx->oneshot = new aicp_hip_batch();
-  aicp_hip_batch* B = ctx->oneshot;
-  rc = upload_pairs(ctx, &p, 1, B, true, false, true, true);
-  if (rc) return end_session(ctx, s, rc);
-  HIPC(hipMemcpyAsync(B->ref_raw.as<float4>() + B->rdesc[0].ref_off, s->ref[s->cur].p, s->ref_n * 16,
-                      hipMemcpyDeviceToDevice, st));
-  HIPC(hipMemcpyAsync(B->read_raw.as<float4>() + B->desc[0].read_off, s->read.p, (size_t)kept * 16,
-                      hipMemcpyDeviceToDevice, st));
-  refcache_begin_resident(ctx, &s->cfg, s->gen, s->ref_n, s->ref_origin, res, flags);
   aicp_icp_stats stats{};
   stats.status = -1;
-  rc = run_batch(ctx, B, &s->cfg, res, flags, out_T, &stats, nullptr);
-  ctx->refc.use = false;
-  if (rc) ctx->refc.invalidate();  // (an error may leave the reference side half written)
+  rc = pair_batch(ctx, s, kept, o, &s->cfg, res, flags, out_T, &stats);
   if (rc && stats.status == -1) {  // the batch did not run to its end (not the reading's status)
     out->status = out->icp.status = rc;
     return end_session(ctx, s, rc);
   }
   out->icp = stats;
   out->status = out->icp.status = rc;
-  // App's bookkeeping and the promotion, on the device; one read-back
+  return commit_reading(ctx, s, kept, id, rc, t0, out, nullptr);
+}
+
+// Behind the batch that registered the reading (rc: its status, out->icp filled): App's bookkeeping
+// and the promotion, on the device; one read-back. *promoted (nullable): the reading is the new
+// reference (the buffers are flipped, a new owner number is taken).
+int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, int32_t id, int rc,
+                   std::chrono::steady_clock::time_point t0, aicp_sequence_result* out, bool* promoted) {
+  hipStream_t st = ctx->stream;
+  char* h = s->pin.as<char>();
+  char* d = s->win.as<char>();
+  StreamState* dS = reinterpret_cast<StreamState*>(d + kOffState);
+  StreamRec* dRec = reinterpret_cast<StreamRec*>(d + kOffRec);
+  SessionHeader* dHdr = reinterpret_cast<SessionHeader*>(d + kOffHdr);
+  double* dOrg = reinterpret_cast<double*>(d + kOffOrigin);
+  if (promoted) *promoted = false;
   DevBuf& spare = s->ref[1 - s->cur];
   HIPC(ensure(spare, (size_t)kept * 16));
   launch_stream_commit(st, 1, ctx->state.as<PairState>(), ctx->outT.as<float>(), dOrg, s->rules, dS, dRec);
@@ -246,13 +294,150 @@ int process_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, float* o
     s->ref_id = id;
     for (int k = 0; k < 3; ++k) s->ref_origin[k] = hdr.origin[k];
     s->gen = ctx->refc.next_owner++;  // (the cached trees and voxel map are the old reference's: stale)
+    if (promoted) *promoted = true;
   }
   ++s->n_processed;
   return AICP_OK;
 }
 
-int process_args(aicp_hip_ctx* ctx, aicp_hip_session* s, const float* out_T, const aicp_sequence_result* out) {
+// One reading of a risk session: the loop body of aicp_hip_sequence_run_risk (runAicpPipeline with
+// failure_prediction_mode, app.cpp:236-245, and both branches of processCloud's `if`, app.cpp:362-411)
+// on the session's resident buffers. odom: the reading's prior pose (its translation is r.origin).
+int process_rows_risk(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, const double* odom, float* out_T,
+                      aicp_sequence_result* out, aicp_pipeline_record* prec, uint32_t* kept_out) {
+  const auto t0 = std::chrono::steady_clock::now();
+  hipStream_t st = ctx->stream;
+  const bool debug = s->prm.flags & AICP_SEQ_DEBUG;
+  const int32_t id = (int32_t)s->n_processed;
+  *out = aicp_sequence_result{};
+  out->reference = s->ref_id;
+  ident4(out_T);
+  *prec = aicp_pipeline_record{};
+  if (kept_out) *kept_out = 0;
+  auto failed = [&](int rc, const std::string& why) {  // the worker ends here (app.cpp:210)
+    out->status = out->icp.status = rc;
+    (void)end_session(ctx, s, rc);
+    ctx->err = "session: reading " + std::to_string(id) + why;
+    return rc;
+  };
+  if (r.n == 0) return failed(AICP_ERR_INVALID, " keeps no point after the pre-filter");
+  HIPC(hipSetDevice(ctx->device));
+  HIPC(hipStreamSynchronize(st));  // (the mirror is free)
+  char* h = s->pin.as<char>();
+  char* d = s->win.as<char>();
+  StreamState* dS = reinterpret_cast<StreamState*>(d + kOffState);
+  StreamRec* dRec = reinterpret_cast<StreamRec*>(d + kOffRec);
+  SessionHeader* dHdr = reinterpret_cast<SessionHeader*>(d + kOffHdr);
+  double* dOrg = reinterpret_cast<double*>(d + kOffOrigin);
+  GateRec* dGate = reinterpret_cast<GateRec*>(d + kOffGate);
+  // setAndFilterReading (app.cpp:77-100): debug mode moves the raw reading by initialT_ and its prior
+  // pose becomes initialT_ * prior pose, here from the mirror of the device's initialT_
+  // (k_stream_ingest moves the origin the same way for the records, on the device)
+  double prior[16];
+  if (debug)
+    pose_moved(host_state(s)->initT, odom, prior);
+  else
+    std::memcpy(prior, odom, sizeof(prior));
+  std::memcpy(h + kOffOrigin, r.origin, 24);
+  HIPC(hipEventRecord(s->ev_begin, st));
+  HIPC(hipMemcpyAsync(dOrg, h + kOffOrigin, 24, hipMemcpyHostToDevice, st));
+  HIPC(ensure(s->read, r.n * 16));
+  uint32_t kept = 0;
+  int rc = stream_ingest_rows(ctx, s->has_pf ? &s->pf : nullptr, r.hpts, r.n, r.stride, r.dpts,
+                              debug ? dS->initT : nullptr, debug ? dOrg : nullptr, s->read.as<float4>(), &kept);
+  if (rc) return end_session(ctx, s, rc);
+  if (kept_out) *kept_out = kept;
+  if (!kept) return failed(AICP_ERR_INVALID, " keeps no point after the pre-filter");
+  prec->n_read = kept;
+  out->icp.overlap_percent = -1.f;
+  // 1. computeOverlap: an overlap-only batch, the poses' translations are the sensor origins (app.cpp:229)
+  aicp_icp_stats ost{};
+  ost.status = -1;
+  rc = pair_batch(ctx, s, kept, prior + 12, &s->cfg, s->prm.resolution, AICP_RUN_OVERLAP, nullptr, &ost);
+  if (rc) return failed(rc, ": overlap: status " + std::to_string(rc) + ": " + ctx->err);
+  // 2. and 3. the features from both clouds where they lie, the classifier, the gate and the ratio;
+  // 4. the gated branch, taken on the device; one read-back
+  float fov = 0.f;
+  rc = gate_resident(ctx, &s->rprm, s->model, s->threshold, s->ref[s->cur].as<float4>(), s->ref_n,
+                     s->read.as<float4>(), kept, s->ref_pose, prior, dGate, &fov);
+  if (rc) return failed(rc, ": risk gate: status " + std::to_string(rc) + ": " + ctx->err);
+  DevBuf& spare = s->ref[1 - s->cur];
+  HIPC(ensure(spare, (size_t)kept * 16));
+  launch_session_gate_promote(st, (int)kept, dGate, dOrg, s->read.as<float4>(), id, spare.as<float4>(),
+                              ctx->outT.as<float>(), dS, dRec, dHdr);
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(s->ev_end, st));
+  HIPC(hipMemcpyAsync(h, d, kReadBackGate, hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  const GateRec g = *reinterpret_cast<const GateRec*>(h + kOffGate);
+  prec->fov_overlap = fov;
+  prec->octree_overlap = g.overlap;
+  prec->alignability = g.alignability;
+  prec->raw = g.raw;
+  prec->risk = g.risk;
+  prec->trimmed_ratio = g.ratio;
+  prec->registered = g.gate ? 0 : 1;
+  aicp_icp_stats ist{};
+  if (g.gate) {
+    // app.cpp:401-411: the unmoved reading joined the graph with its prior pose and is the reference
+    // at once; the count restarted; the correction stays the identity
+    const StreamRec& rec = *reinterpret_cast<const StreamRec*>(h + kOffRec);
+    const SessionHeader& hdr = *reinterpret_cast<const SessionHeader*>(h + kOffHdr);
+    s->last_device_ms = ev_ms(s->ev_begin, s->ev_end);
+    s->last_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rec.status != 0 || !rec.accepted || !rec.append || hdr.count != kept || hdr.id != id) {
+      (void)end_session(ctx, s, AICP_ERR_HIP);
+      FAIL(AICP_ERR_HIP, "session: the gated reference's record and header");
+    }
+    ist.overlap_percent = g.overlap;
+    ist.trimmed_ratio = g.ratio;
+    for (int k = 0; k < 3; ++k) ist.overlap_keys[k] = ost.overlap_keys[k];
+    out->icp = ist;
+    out->accepted = out->is_reference = 1;
+    for (int k = 0; k < 3; ++k) out->corrected_origin[k] = rec.corrected_origin[k];
+    s->cur = 1 - s->cur;
+    s->ref_n = kept;
+    s->ref_id = id;
+    pose_fix_pitch_roll(prior, odom, s->ref_pose);
+    for (int k = 0; k < 3; ++k) s->ref_origin[k] = s->ref_pose[12 + k];
+    s->gen = ctx->refc.next_owner++;  // (the cached voxel map is the old reference's: stale)
+    ++s->n_processed;
+    return AICP_OK;
+  }
+  // 5. computeRegistration at the device's ratio (app.cpp:243-245): an ICP-only batch, then the
+  // plain session's commit and promotion
+  aicp_icp_config c2 = s->cfg;
+  c2.trimmed_ratio = g.ratio;
+  ist.status = -1;
+  rc = pair_batch(ctx, s, kept, prior + 12, &c2, 0.0, AICP_RUN_ICP | (s->prm.flags & AICP_RUN_TIME_NN), out_T, &ist);
+  if (rc && ist.status == -1) return failed(rc, ": status " + std::to_string(rc) + ": " + ctx->err);
+  ist.overlap_percent = g.overlap;
+  for (int k = 0; k < 3; ++k) ist.overlap_keys[k] = ost.overlap_keys[k];
+  out->icp = ist;
+  out->status = out->icp.status = rc;
+  bool promoted = false;
+  rc = commit_reading(ctx, s, kept, id, rc, t0, out, &promoted);
+  if (rc) return rc;
+  if (promoted) {  // App's corrected pose, in double on the host (aligned_cloud.cpp:31-74)
+    double corrected[16];
+    pose_moved(out_T, prior, corrected);
+    pose_fix_pitch_roll(corrected, odom, s->ref_pose);
+    for (int k = 0; k < 3; ++k) s->ref_origin[k] = s->ref_pose[12 + k];
+  }
+  return AICP_OK;
+}
+
+// risk: the call is a risk session's (_pose / _risk); a handle of the other kind refuses it
+int kind_check(aicp_hip_ctx* ctx, const aicp_hip_session* s, bool risk) {
+  if (s->risk == risk) return AICP_OK;
+  FAIL(AICP_ERR_INVALID, risk ? "session: not made by aicp_hip_session_create_risk"
+                              : "session: a risk session takes the _pose and _risk calls");
+}
+
+int process_args(aicp_hip_ctx* ctx, aicp_hip_session* s, const float* out_T, const aicp_sequence_result* out,
+                 bool risk) {
   if (!ctx || !s || !out_T || !out) return AICP_ERR_INVALID;
+  if (kind_check(ctx, s, risk)) return AICP_ERR_INVALID;
   if (!s->started) FAIL(AICP_ERR_INVALID, "session: process before start");
   if (s->ended) FAIL(AICP_ERR_INVALID, "session ended at reading " + std::to_string(s->ended_at));
   return AICP_OK;
@@ -298,6 +483,29 @@ int aicp_hip_session_create(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const
   return AICP_OK;
 }
 
+int aicp_hip_session_create_risk(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_sequence_params* prm,
+                                 const aicp_prefilter_params* pf, const aicp_risk_params* risk_prm,
+                                 const aicp_hip_svm* model, double threshold, aicp_hip_session** out) {
+  if (!ctx || !out) return AICP_ERR_INVALID;
+  *out = nullptr;
+  if (!cfg || !prm || !risk_prm || !model) return AICP_ERR_INVALID;
+  if (!(threshold == threshold)) FAIL(AICP_ERR_INVALID, "session: threshold");
+  int rc = risk_params_check(ctx, risk_prm);
+  if (rc) return rc;
+  aicp_sequence_params p = *prm;
+  p.flags |= AICP_RUN_OVERLAP;  // (the overlap always runs: the classifier needs it)
+  aicp_hip_session* s = nullptr;
+  rc = aicp_hip_session_create(ctx, cfg, &p, pf, &s);
+  if (rc) return rc;
+  s->risk = true;
+  s->rprm = *risk_prm;
+  s->model = model;
+  s->threshold = threshold;
+  s->rules.overlap = 0;  // (the overlap is a batch of its own, its status checked before the gate)
+  *out = s;
+  return AICP_OK;
+}
+
 void aicp_hip_session_free(aicp_hip_ctx* ctx, aicp_hip_session* s) {
   if (!s) return;
   if (ctx) {
@@ -316,22 +524,44 @@ void aicp_hip_session_free(aicp_hip_ctx* ctx, aicp_hip_session* s) {
 
 int aicp_hip_session_start(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_cloud* first) {
   if (!ctx || !s || !first) return AICP_ERR_INVALID;
+  if (kind_check(ctx, s, false)) return AICP_ERR_INVALID;
   Rows r;
   const int rc = rows_of(ctx, first, nullptr, nullptr, &r);
-  return rc ? rc : start_rows(ctx, s, r);
+  return rc ? rc : start_rows(ctx, s, r, nullptr);
 }
 
 int aicp_hip_session_start_accum(aicp_hip_ctx* ctx, aicp_hip_session* s, aicp_hip_accum* acc, const double origin[3]) {
   if (!ctx || !s || !acc || !origin) return AICP_ERR_INVALID;
+  if (kind_check(ctx, s, false)) return AICP_ERR_INVALID;
   Rows r;
   const int rc = rows_of(ctx, nullptr, acc, origin, &r);
-  return rc ? rc : start_rows(ctx, s, r);
+  return rc ? rc : start_rows(ctx, s, r, nullptr);
+}
+
+int aicp_hip_session_start_pose(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_cloud* first,
+                                const double first_pose[16]) {
+  if (!ctx || !s || !first || !first_pose) return AICP_ERR_INVALID;
+  if (kind_check(ctx, s, true)) return AICP_ERR_INVALID;
+  Rows r;
+  const int rc = rows_of(ctx, first, nullptr, nullptr, &r);
+  if (rc) return rc;
+  for (int k = 0; k < 3; ++k) r.origin[k] = first_pose[12 + k];  // (the sensor origin is the translation)
+  return start_rows(ctx, s, r, first_pose);
+}
+
+int aicp_hip_session_start_accum_pose(aicp_hip_ctx* ctx, aicp_hip_session* s, aicp_hip_accum* acc,
+                                      const double first_pose[16]) {
+  if (!ctx || !s || !acc || !first_pose) return AICP_ERR_INVALID;
+  if (kind_check(ctx, s, true)) return AICP_ERR_INVALID;
+  Rows r;
+  const int rc = rows_of(ctx, nullptr, acc, first_pose + 12, &r);
+  return rc ? rc : start_rows(ctx, s, r, first_pose);
 }
 
 int aicp_hip_session_process(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_cloud* reading, float out_T[16],
                              aicp_sequence_result* out, uint32_t* kept) {
   if (!reading) return AICP_ERR_INVALID;
-  int rc = process_args(ctx, s, out_T, out);
+  int rc = process_args(ctx, s, out_T, out, false);
   if (rc) return rc;
   Rows r;
   rc = rows_of(ctx, reading, nullptr, nullptr, &r);
@@ -341,11 +571,43 @@ int aicp_hip_session_process(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_
 int aicp_hip_session_process_accum(aicp_hip_ctx* ctx, aicp_hip_session* s, aicp_hip_accum* acc, const double origin[3],
                                    float out_T[16], aicp_sequence_result* out, uint32_t* kept) {
   if (!acc || !origin) return AICP_ERR_INVALID;
-  int rc = process_args(ctx, s, out_T, out);
+  int rc = process_args(ctx, s, out_T, out, false);
   if (rc) return rc;
   Rows r;
   rc = rows_of(ctx, nullptr, acc, origin, &r);
   return rc ? rc : process_rows(ctx, s, r, out_T, out, kept);
+}
+
+int aicp_hip_session_process_risk(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_cloud* reading,
+                                  const double pose[16], float out_T[16], aicp_sequence_result* out,
+                                  aicp_pipeline_record* rec, uint32_t* kept) {
+  if (!reading || !pose || !rec) return AICP_ERR_INVALID;
+  int rc = process_args(ctx, s, out_T, out, true);
+  if (rc) return rc;
+  Rows r;
+  rc = rows_of(ctx, reading, nullptr, nullptr, &r);
+  if (rc) return rc;
+  for (int k = 0; k < 3; ++k) r.origin[k] = pose[12 + k];
+  return process_rows_risk(ctx, s, r, pose, out_T, out, rec, kept);
+}
+
+int aicp_hip_session_process_accum_risk(aicp_hip_ctx* ctx, aicp_hip_session* s, aicp_hip_accum* acc,
+                                        const double pose[16], float out_T[16], aicp_sequence_result* out,
+                                        aicp_pipeline_record* rec, uint32_t* kept) {
+  if (!acc || !pose || !rec) return AICP_ERR_INVALID;
+  int rc = process_args(ctx, s, out_T, out, true);
+  if (rc) return rc;
+  Rows r;
+  rc = rows_of(ctx, nullptr, acc, pose + 12, &r);
+  return rc ? rc : process_rows_risk(ctx, s, r, pose, out_T, out, rec, kept);
+}
+
+int aicp_hip_session_reference_pose(aicp_hip_ctx* ctx, aicp_hip_session* s, double pose[16]) {
+  if (!ctx || !s || !pose) return AICP_ERR_INVALID;
+  if (kind_check(ctx, s, true)) return AICP_ERR_INVALID;
+  if (!s->started) FAIL(AICP_ERR_INVALID, "session: reference pose before start");
+  std::memcpy(pose, s->ref_pose, sizeof(s->ref_pose));
+  return AICP_OK;
 }
 
 int aicp_hip_session_state(aicp_hip_ctx* ctx, aicp_hip_session* s, uint64_t* n_processed, int32_t* reference,

@@ -11,6 +11,15 @@ from a ``SweepAccumulator`` does not cross it at all.
     if motion_gate(prev_pose, pose):             # velodyneCallBack's test
         T, result, kept = session.process(acc, pose[:3, 3])
     acc.clear()
+
+With ``risk=dict(model=SvmModel, threshold=..., params=RiskParams)`` the session serves
+``failure_prediction_mode`` (aicp_hip_session_create_risk): every reading goes through the overlap,
+the alignment features and the classifier on the resident buffers, and a reading whose risk is above
+the threshold becomes the reference unmoved, on the device, instead of being registered. Such a
+session takes 4x4 prior poses in place of origins:
+
+    session.start(first, pose=first_pose)
+    T, result, kept, record = session.process(reading, pose=prior_pose)
 """
 from __future__ import annotations
 
@@ -23,18 +32,30 @@ from .accumulator import SweepAccumulator
 
 
 class AppSession:
-    def __init__(self, ctx: "L.Context", cfg=None, params=None, prefilter=None):
+    def __init__(self, ctx: "L.Context", cfg=None, params=None, prefilter=None, risk=None):
         """cfg: IcpConfig (default_config() when None; a point-to-point chain is accepted); params:
         SequenceParams (flags: AICP_RUN_OVERLAP | AICP_SEQ_DEBUG | AICP_RUN_TIME_NN); prefilter:
         None when the clouds are already pre-filtered, PrefilterParams (or True for the defaults)
-        when they are RAW and go through setAndFilterReading in App's order."""
+        when they are RAW and go through setAndFilterReading in App's order; risk: None, or
+        dict(model=SvmModel (kept alive by the session), threshold=float (default 0.5),
+        params=RiskParams (default_risk_params() when left out)) for failure_prediction_mode."""
         cfg = cfg or L.default_config()
         prm = params or L.default_sequence_params()
         if prefilter is True:
             prefilter = L.default_prefilter()
         h = C.c_void_p()
-        ctx.check(L.lib.aicp_hip_session_create(ctx.h, C.byref(cfg), C.byref(prm),
-                                                None if prefilter is None else C.byref(prefilter), C.byref(h)))
+        pf = None if prefilter is None else C.byref(prefilter)
+        self.risk = None
+        if risk is not None:
+            unknown = set(risk) - {"model", "threshold", "params"}
+            if unknown or "model" not in risk:
+                raise ValueError(f"risk: dict(model=, threshold=, params=), got {sorted(risk)}")
+            rp = risk.get("params") or L.default_risk_params()
+            self.risk = dict(model=risk["model"], threshold=float(risk.get("threshold", 0.5)), params=rp)
+            ctx.check(L.lib.aicp_hip_session_create_risk(ctx.h, C.byref(cfg), C.byref(prm), pf, C.byref(rp),
+                                                         risk["model"].h, self.risk["threshold"], C.byref(h)))
+        else:
+            ctx.check(L.lib.aicp_hip_session_create(ctx.h, C.byref(cfg), C.byref(prm), pf, C.byref(h)))
         self.ctx = ctx
         self.h = h
 
@@ -52,10 +73,29 @@ class AppSession:
         o = np.ascontiguousarray(np.asarray(origin, np.float64).reshape(3))
         return o, L._dptr(o)
 
-    def start(self, first, origin=(0, 0, 0)) -> None:
+    def _pose(self, pose):
+        """A risk session's pose argument (4x4 row-major) as column-major double[16]."""
+        if self.risk is None:
+            if pose is not None:
+                raise TypeError("pose= is a risk session's argument (AppSession(..., risk=...))")
+            return None
+        if pose is None:
+            raise TypeError("a risk session takes pose= (4x4 prior pose), not an origin")
+        p = L._pose16(pose)
+        return p, L._dptr(p)
+
+    def start(self, first, origin=(0, 0, 0), pose=None) -> None:
         """The first cloud ((N, 3|4|8|12) float32 rows, or a SweepAccumulator) with its sensor
-        origin: pre-filtered as given when the session has a pre-filter; it becomes reference -1.
-        Calling it again restarts the session."""
+        origin (a risk session: pose=, its 4x4 pose): pre-filtered as given when the session has a
+        pre-filter; it becomes reference -1. Calling it again restarts the session."""
+        pp = self._pose(pose)
+        if pp is not None:
+            if isinstance(first, SweepAccumulator):
+                self.ctx.check(L.lib.aicp_hip_session_start_accum_pose(self.ctx.h, self.h, first.h, pp[1]))
+            else:
+                c, keep = L.make_cloud(first, pp[0][12:15])
+                self.ctx.check(L.lib.aicp_hip_session_start_pose(self.ctx.h, self.h, C.byref(c), pp[1]))
+            return
         if isinstance(first, SweepAccumulator):
             o, op = self._origin(origin)
             self.ctx.check(L.lib.aicp_hip_session_start_accum(self.ctx.h, self.h, first.h, op))
@@ -63,14 +103,30 @@ class AppSession:
         c, keep = L.make_cloud(first, origin)
         self.ctx.check(L.lib.aicp_hip_session_start(self.ctx.h, self.h, C.byref(c)))
 
-    def process(self, reading, origin=(0, 0, 0), raise_on_error=True):
+    def process(self, reading, origin=(0, 0, 0), raise_on_error=True, pose=None):
         """One reading (rows, or a SweepAccumulator, which is left as it is) with its prior-pose
         origin. Returns (T 4x4 row-major correction, result dict as Context.sequence_run's with `rc`
         added, kept points). A failed reading ends the session (AicpError unless raise_on_error is
-        False); start() revives it."""
+        False); start() revives it. A risk session takes pose= (the 4x4 prior pose) and returns the
+        pipeline's record dict (Context.pipeline's) as a fourth value."""
         outT = np.zeros(16, np.float32)
         res = L.SequenceResult()
         kept = C.c_uint32(0)
+        pp = self._pose(pose)
+        if pp is not None:
+            rec = L.PipelineRecord()
+            if isinstance(reading, SweepAccumulator):
+                rc = L.lib.aicp_hip_session_process_accum_risk(self.ctx.h, self.h, reading.h, pp[1], L._fptr(outT),
+                                                               C.byref(res), C.byref(rec), C.byref(kept))
+            else:
+                c, keep = L.make_cloud(reading, pp[0][12:15])
+                rc = L.lib.aicp_hip_session_process_risk(self.ctx.h, self.h, C.byref(c), pp[1], L._fptr(outT),
+                                                         C.byref(res), C.byref(rec), C.byref(kept))
+            if raise_on_error and rc != L.AICP_OK:
+                self.ctx.check(rc)
+            d = res.as_dict()
+            d["rc"] = rc
+            return outT.reshape(4, 4).T.copy(), d, int(kept.value), rec.as_dict()
         if isinstance(reading, SweepAccumulator):
             o, op = self._origin(origin)
             rc = L.lib.aicp_hip_session_process_accum(self.ctx.h, self.h, reading.h, op, L._fptr(outT), C.byref(res),
@@ -104,6 +160,13 @@ class AppSession:
         o = np.zeros(3, np.float64)
         self.ctx.check(L.lib.aicp_hip_session_reference(self.ctx.h, self.h, L._fptr(out), n, C.byref(m), L._dptr(o)))
         return out[:m.value].copy(), o
+
+    def reference_pose(self):
+        """A risk session's current reference pose (4x4 row-major float64): App's corrected pose of
+        the reading that became the reference, through removePitchRollCorrection."""
+        p = np.zeros(16, np.float64)
+        self.ctx.check(L.lib.aicp_hip_session_reference_pose(self.ctx.h, self.h, L._dptr(p)))
+        return p.reshape(4, 4).T.copy()
 
     def last_timing(self) -> dict:
         """wall_ms / device_ms of the last process call that registered its reading."""

@@ -18,7 +18,8 @@
  *   SVM::test (failure_prediction_mode)    aicp_core/src/classification/svm.cpp:48-110
  *                                            -> aicp_hip_svm_load, aicp_hip_svm_predict
  *   App::runAicpPipeline with the risk gate  aicp_core/src/registration/app.cpp:218-247, 362-411
- *                                            -> aicp_hip_pipeline, aicp_hip_sequence_run_risk
+ *                                            -> aicp_hip_pipeline, aicp_hip_sequence_run_risk,
+ *                                               aicp_hip_session_create_risk (live, one reading per call)
  *
  * Conventions
  *   - Plain C, no exceptions cross this boundary; every entry point returns an AICP_* code.
@@ -962,6 +963,51 @@ int aicp_hip_session_reference(aicp_hip_ctx* ctx, aicp_hip_session* s, float* ou
 /* The last process call that registered its reading: the whole call on the host, and from the
  * origin's upload to the promotion on the device (HIP events). Both nullable. */
 int aicp_hip_session_last_timing(const aicp_hip_session* s, double* wall_ms, double* device_ms);
+
+/* The live session with failure_prediction_mode (runAicpPipeline, app.cpp:236-245, and the gated
+ * branch of processCloud, app.cpp:401-411): aicp_hip_sequence_run_risk's rules, one reading per call,
+ * on the session's resident buffers. Per reading: the raw rows up (not at all from a sweep
+ * accumulator), ingest and pre-filter into the session's reading buffer; an overlap-only batch of the
+ * resident reference and reading (device to device; the reference's voxel map from the reference
+ * cache); the alignment features with the two FOV filters reading both clouds where they lie; the
+ * classifier; then k_session_gate_promote, which takes the gated branch on the device: the unmoved
+ * reading is copied into the spare reference buffer, the record says accepted / is_reference with the
+ * reading's prior origin as corrected_origin, the correction is the identity, the count restarts and
+ * initialT_ stays. One read-back (gate record, state, record, header) ends a gated reading, which
+ * builds no tree; otherwise an ICP-only batch at the device's ratio follows (device to device, the
+ * reference's trees from the reference cache), then the plain session's commit and promotion. After
+ * its raw rows no point of a reading or a reference crosses the bus in either direction.
+ * Poses are 16 doubles, column-major (Eigen::Isometry3d::data()); the sensor origin is the
+ * translation. The overlap always runs (prm->resolution > 0; AICP_RUN_OVERLAP may be left out).
+ * The reading's pose in debug mode is fromMatrix4fToIsometry3d(initialT_) * pose. The reference's
+ * pose stays on the host in double: removePitchRollCorrection(first_pose, first_pose) after start,
+ * removePitchRollCorrection(reading's pose, pose) after a gated reading,
+ * removePitchRollCorrection(fromMatrix4fToIsometry3d(T) * reading's pose, pose) after a frequency
+ * promotion. A gated reading: AICP_OK, accepted 1, is_reference 1, corrected_origin = its pose's
+ * translation, out_T the identity, rec->registered 0, icp.iterations 0.
+ * model stays the caller's and must outlive the session; risk_prm is copied. A point-to-point chain
+ * is accepted. Any non-zero status (overlap, features, classifier, registration) and an emptied
+ * reading end the session until the next start. A session made here takes the _pose / _risk calls
+ * below and refuses aicp_hip_session_start / _start_accum / _process / _process_accum with
+ * AICP_ERR_INVALID; a session of aicp_hip_session_create refuses the calls below the same way;
+ * neither refusal changes any state. state, reference, last_timing and free serve both. */
+int aicp_hip_session_create_risk(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_sequence_params* prm,
+                                 const aicp_prefilter_params* pf /* nullable */, const aicp_risk_params* risk_prm,
+                                 const aicp_hip_svm* model, double threshold, aicp_hip_session** out);
+int aicp_hip_session_start_pose(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_cloud* first,
+                                const double first_pose[16]);
+int aicp_hip_session_start_accum_pose(aicp_hip_ctx* ctx, aicp_hip_session* s, aicp_hip_accum* acc,
+                                      const double first_pose[16]);
+/* One reading with its prior pose (reading->origin is not read). rec: the pipeline's record (n_read:
+ * the kept points). out, kept: as aicp_hip_session_process. */
+int aicp_hip_session_process_risk(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_cloud* reading,
+                                  const double pose[16], float out_T[16], aicp_sequence_result* out,
+                                  aicp_pipeline_record* rec, uint32_t* kept);
+int aicp_hip_session_process_accum_risk(aicp_hip_ctx* ctx, aicp_hip_session* s, aicp_hip_accum* acc,
+                                        const double pose[16], float out_T[16], aicp_sequence_result* out,
+                                        aicp_pipeline_record* rec, uint32_t* kept);
+/* The current reference's pose (column-major). */
+int aicp_hip_session_reference_pose(aicp_hip_ctx* ctx, aicp_hip_session* s, double pose[16]);
 
 /* ---- live map sessions: one reading per call on the prior map or on the built map -------------
  * App::processCloud (app.cpp:282-414) in localize_against_prior_map or localize_against_built_map
