@@ -53,6 +53,7 @@ EXPORTS = [
     "aicp_hip_built_map_window", "aicp_hip_built_map_sequence_run", "aicp_hip_last_built_map_timing",
     "aicp_hip_map_sequence_run_raw", "aicp_hip_built_map_sequence_run_raw", "aicp_hip_test_ingest",
     "aicp_hip_test_tree", "aicp_hip_test_nn", "aicp_hip_test_normals",
+    "aicp_hip_test_overlap", "aicp_hip_test_key_bound",
     "aicp_hip_svm_load", "aicp_hip_svm_free", "aicp_hip_svm_info", "aicp_hip_svm_predict", "aicp_hip_pipeline",
     "aicp_hip_sequence_run_risk",
     "aicp_hip_default_accum_params", "aicp_hip_accum_create", "aicp_hip_accum_free", "aicp_hip_accum_push",
@@ -88,6 +89,7 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_test_tree",  # the kd-tree build, node for node
            "aicp_hip_test_nn",  # the NN search, query by query
            "aicp_hip_test_normals",  # the SurfaceNormal chain, point by point
+           "aicp_hip_test_overlap", "aicp_hip_test_key_bound",  # the overlap, set by set
            "aicp_hip_svm_load", "aicp_hip_svm_free", "aicp_hip_svm_info", "aicp_hip_svm_predict",
            "aicp_hip_pipeline", "aicp_hip_sequence_run_risk",  # the classifier and the risk gate
            "aicp_hip_default_accum_params", "aicp_hip_accum_create", "aicp_hip_accum_free", "aicp_hip_accum_push",
@@ -251,6 +253,21 @@ class MonitorResult(C.Structure):
 
 class MonitorStats(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("trees_ms", "nn_ms", "reduce_ms", "device_ms", "wall_ms")]
+
+
+class TestOverlapOut(C.Structure):
+    """aicp_test_overlap_out: what ran, and the caller's arrays the entry fills."""
+    _ip, _up = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+    _fields_ = [
+        ("path", C.c_int32), ("filter", C.c_int32), ("wide", C.c_int32), ("n_groups", C.c_int32),
+        ("pair_group", _ip), ("cloud_keys", _up), ("cloud_err", _ip), ("cloud_bbox", _ip),
+        ("pair_counts", _up), ("pair_percent", C.POINTER(C.c_float)), ("pair_ratio", C.POINTER(C.c_float)),
+        ("pair_err", _ip), ("desc_min", _ip), ("desc_dim", _ip), ("desc_off", _up), ("desc_bytes", _up),
+        ("arena", C.POINTER(C.c_uint8)), ("arena_cap", C.c_uint64), ("arena_bytes", C.c_uint64),
+        ("key_counts", C.POINTER(C.c_uint32)), ("key_offsets", _up), ("points_cap", C.c_uint64),
+        ("n_points", C.c_uint64), ("words", _up), ("words_cap", C.c_uint64), ("n_words", C.c_uint64),
+        ("cloud_bound", _up), ("list_off", _up), ("list_cap", _up), ("dirty", C.c_uint64),
+    ]
 
 
 class Cloud(C.Structure):
@@ -607,6 +624,11 @@ def _load():
     if hasattr(L, "aicp_hip_test_normals"):
         u32p = C.POINTER(C.c_uint32)
         L.aicp_hip_test_normals.argtypes = [vp, sz, u32p, fp, C.c_int32, C.c_int32, ip, ip, ip, fp, ip, up, fp, ip, ip, up]
+    if hasattr(L, "aicp_hip_test_overlap"):
+        u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+        L.aicp_hip_test_overlap.argtypes = [vp, sz, u32p, fp, sz, u32p, u32p, fp, dp, dp, C.c_double, C.c_int32,
+                                            C.c_int32, C.c_int32, C.c_int32, up, C.c_int32, C.POINTER(TestOverlapOut)]
+        L.aicp_hip_test_key_bound.argtypes = [fp, sz, dp, C.c_double, C.c_int32, up, up]
     if hasattr(L, "aicp_hip_svm_load"):
         dp, clp, pfp = C.POINTER(C.c_double), C.POINTER(Cloud), C.POINTER(PrefilterParams)
         rpp, prp = C.POINTER(RiskParams), C.POINTER(PipelineRecord)
@@ -781,6 +803,19 @@ def as_points(p) -> np.ndarray:
     if a.ndim != 2 or a.shape[1] not in (3, 4, 8, 12):
         raise ValueError("points must be (N, 3|4|8|12) float32 rows (PointXYZ / XYZRGB / XYZRGBNormal)")
     return a
+
+
+def key_bound(points, origin, resolution, rigid=0):
+    """aicp_hip_test_key_bound (host only): the stream's bound of a cloud's key-list words, and the
+    cap of one point's share. Returns (bound, point_cap)."""
+    a = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    o = np.ascontiguousarray(origin, np.float64).reshape(3)
+    bound, cap = C.c_uint64(), C.c_uint64()
+    rc = lib.aicp_hip_test_key_bound(_fptr(a), a.shape[0], o.ctypes.data_as(C.POINTER(C.c_double)),
+                                     float(resolution), int(rigid), C.byref(bound), C.byref(cap))
+    if rc:
+        raise ValueError(f"aicp_hip_test_key_bound: {rc}")
+    return int(bound.value), int(cap.value)
 
 
 def make_pair(ref, read, ref_origin=(0, 0, 0), read_origin=(0, 0, 0), init_T=None):
@@ -1400,6 +1435,74 @@ class Context:
         return dict(match=match, d2=d2, touched=touched, ids=[ids[ro[r]:ro[r + 1]] for r in range(R)],
                     engine=engine.value, dirty=int(dirty.value),
                     read_off=np.concatenate([[0], np.cumsum(n_read.astype(np.int64))]))
+
+    def test_overlap(self, refs, pair_ref, reads, ref_origins, read_origins, resolution, path=0, filter=-1,
+                     wide=-1, caps=None, rigid=0, arena_cap=64 << 20, words_cap=4 << 20, check=True):
+        """aicp_hip_test_overlap: the batch's overlap on given clouds, and what it wrote. refs, reads:
+        lists of (n, 3) float32 clouds; pair_ref: each pair's reference; ref_origins, read_origins:
+        (n_pairs, 3). Clouds are numbered groups first, then readings. Returns dict(path, filter, wide
+        (what ran), n_groups, pair_group, cloud_keys, cloud_err, cloud_bbox (n_clouds, 6), pair_counts
+        (n_pairs, 3), pair_percent, pair_ratio, pair_err; dense maps: desc_min, desc_dim (n_clouds, 3),
+        desc_off, desc_bytes, arena (uint8, the whole arena), arena_bytes; sorted keys: key_counts,
+        key_offsets (per point: the groups' references, then the readings), words (sorted), n_words;
+        the stream paths 3 and 4: cloud_bound, list_off, list_cap (two lists per group), dirty).
+        caps: explicit capacities per cloud (groups, then readings) for paths 3 and 4. check=False
+        returns the return code instead of raising."""
+        refs = [np.ascontiguousarray(c, np.float32).reshape(-1, 3) for c in refs]
+        reads = [np.ascontiguousarray(r, np.float32).reshape(-1, 3) for r in reads]
+        counts = np.array([c.shape[0] for c in refs], np.uint32)
+        n_read = np.array([r.shape[0] for r in reads], np.uint32)
+        pair_ref = np.ascontiguousarray(pair_ref, np.uint32).ravel()
+        R, P = counts.size, n_read.size
+        ro = np.ascontiguousarray(ref_origins, np.float64).reshape(-1, 3)
+        do = np.ascontiguousarray(read_origins, np.float64).reshape(-1, 3)
+        if pair_ref.size != P or ro.shape[0] != P or do.shape[0] != P:
+            raise ValueError("one reference, one reading and two origins per pair")
+        rp = np.ascontiguousarray(np.concatenate(refs, axis=0)) if R else np.zeros((0, 3), np.float32)
+        rd = np.ascontiguousarray(np.concatenate(reads, axis=0)) if P else np.zeros((0, 3), np.float32)
+        points_cap = int(n_read.sum(dtype=np.uint64)) + sum(int(counts[r]) for r in pair_ref if r < R)
+        nc = 2 * max(P, 1)
+        a = dict(pair_group=np.zeros(P, np.int32), cloud_keys=np.zeros(nc, np.uint64), cloud_err=np.zeros(nc, np.int32),
+                 cloud_bbox=np.zeros((nc, 6), np.int32), pair_counts=np.zeros((P, 3), np.uint64),
+                 pair_percent=np.zeros(P, np.float32), pair_ratio=np.zeros(P, np.float32),
+                 pair_err=np.zeros(P, np.int32), desc_min=np.zeros((nc, 3), np.int32),
+                 desc_dim=np.zeros((nc, 3), np.int32), desc_off=np.zeros(nc, np.uint64),
+                 desc_bytes=np.zeros(nc, np.uint64), arena=np.zeros(max(int(arena_cap), 1), np.uint8),
+                 key_counts=np.zeros(max(points_cap, 1), np.uint32), key_offsets=np.zeros(max(points_cap, 1), np.uint64),
+                 words=np.zeros(max(int(words_cap), 1), np.uint64), cloud_bound=np.zeros(nc, np.uint64),
+                 list_off=np.zeros(nc, np.uint64), list_cap=np.zeros(nc, np.uint64))
+        cp = None if caps is None else np.ascontiguousarray(caps, np.uint64).ravel()
+        if cp is not None and cp.size > nc:
+            raise ValueError("one capacity per cloud")
+        o = TestOverlapOut()
+        for name, ctype in TestOverlapOut._fields_:
+            if name in a:
+                setattr(o, name, a[name].ctypes.data_as(ctype))
+        o.arena_cap, o.points_cap, o.words_cap = int(arena_cap), points_cap, int(words_cap)
+        u32p, dp = C.POINTER(C.c_uint32), C.POINTER(C.c_double)
+        rc = lib.aicp_hip_test_overlap(
+            self.h, R, counts.ctypes.data_as(u32p), _fptr(rp), P, pair_ref.ctypes.data_as(u32p),
+            n_read.ctypes.data_as(u32p), _fptr(rd), ro.ctypes.data_as(dp), do.ctypes.data_as(dp), float(resolution),
+            int(path), int(filter), int(wide), 0 if cp is None else 1,
+            None if cp is None else cp.ctypes.data_as(C.POINTER(C.c_uint64)), int(rigid), C.byref(o))
+        if not check and rc:
+            return rc
+        self.check(rc)
+        if o.arena_bytes > o.arena_cap or o.n_words > o.words_cap:
+            raise ValueError(f"arena {o.arena_bytes} B / {o.n_words} words exceed the given capacities")
+        n = o.n_groups + P
+        out = dict(path=o.path, filter=o.filter, wide=o.wide, n_groups=o.n_groups, arena_bytes=int(o.arena_bytes),
+                   n_words=int(o.n_words), n_points=int(o.n_points), dirty=int(o.dirty))
+        for k in ("pair_group", "pair_counts", "pair_percent", "pair_ratio", "pair_err"):
+            out[k] = a[k]
+        for k in ("cloud_keys", "cloud_err", "cloud_bbox", "desc_min", "desc_dim", "desc_off", "desc_bytes",
+                  "cloud_bound"):
+            out[k] = a[k][:n]
+        out["list_off"], out["list_cap"] = a["list_off"][:2 * o.n_groups], a["list_cap"][:2 * o.n_groups]
+        out["arena"] = a["arena"][:int(o.arena_bytes)]
+        out["key_counts"], out["key_offsets"] = a["key_counts"][:int(o.n_points)], a["key_offsets"][:int(o.n_points)]
+        out["words"] = a["words"][:int(o.n_words)]
+        return out
 
     def test_normals(self, refs, knn=20, matcher_bucket=8):
         """aicp_hip_test_normals: the SurfaceNormal chain of a batch's references. refs: a list of

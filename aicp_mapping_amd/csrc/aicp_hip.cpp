@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <deque>
 #include <chrono>
@@ -519,8 +520,18 @@ int overlap_sparse(aicp_hip_ctx* ctx, aicp_hip_batch* B, size_t P, size_t G, Pai
   TCHK(launch_ovl_sparse_sets(s, (uint32_t)nb, dbc, dbs, dcl, B->ref_raw.as<float4>(), readS, res, off, n_keys, k0, k1,
                               tmp, sort_b, (int)G, (int)P, dDesc, (unsigned long long*)(d + o_pc),
                               (unsigned long long*)(d + o_pp), dGst, dState));
-  launch_ovl_finish(s, (int)P, dDesc, dState, dGst, set_ratio ? 1 : 0);
+  launch_ovl_finish(s, (int)P, dDesc, dState, dGst, set_ratio || ctx->ovl_probe.on ? 1 : 0);
   TCHK(hipGetLastError());
+  if (ctx->ovl_probe.on) {
+    OvlProbe& probe = ctx->ovl_probe;
+    probe.ran_path = 2;
+    probe.ran_filter = probe.ran_wide = 0;
+    probe.n_points = slots;
+    probe.n_keys = n_keys;
+    probe.cnt = cnt;
+    probe.off = off;
+    probe.keys1 = k1;
+  }
   return AICP_OK;
 }
 
@@ -537,7 +548,9 @@ int overlap_maps(aicp_hip_ctx* ctx, aicp_hip_batch* B, size_t P, size_t G, PairD
   TCHK(hipEventSynchronize(ctx->ev[1]));
   RefCache& rc = ctx->refc;
   const bool hit = rc.hit_ovl;  // the one group's map is the cached reference's (ctx->bitmap[0, rc.od.bytes))
-  if (ctx->opt.overlap_path == 1) {  // the sorted-key path for every batch (tests)
+  OvlProbe& probe = ctx->ovl_probe;
+  set_ratio = set_ratio || probe.on;
+  if (ctx->opt.overlap_path == 1 || (probe.on && probe.keys)) {  // the sorted-key path for every batch (tests)
     rc.ovl = false;
     return overlap_sparse(ctx, B, P, G, dDesc, dState, dGst, readS, res, set_ratio, err);
   }
@@ -593,7 +606,15 @@ int overlap_maps(aicp_hip_ctx* ctx, aicp_hip_batch* B, size_t P, size_t G, PairD
   // the marks' LDS cache of stored voxels pays off where many rays share the maps (C5: 66 against
   // 111 GB written per dispatch); a few clouds mark faster with plain stores (the
   // stream's measurement)
-  const bool filter = P + G > 8;
+  const bool filter = probe.on && probe.filter >= 0 ? probe.filter != 0 : P + G > 8;
+  // the counts' wide grids for the one-shot call of one pair alone (count_bpm, kernels_overlap.hip)
+  const bool wide = probe.on && probe.wide >= 0 ? probe.wide != 0 : P + G <= 2;
+  if (probe.on) {
+    probe.ran_path = 1;
+    probe.ran_filter = filter;
+    probe.ran_wide = wide;
+    probe.arena_bytes = bm_bytes;
+  }
   if (hit) {  // the readings' maps only: the reference's map and |A| are the cached ones
     TCHK(hipMemsetAsync(bm + ref_bytes, 0, bm_bytes - ref_bytes, s));
     launch_ovl_mark(s, B->m_read, dDesc, dOvl, dState, readS, 1, res, bm, filter);
@@ -604,7 +625,7 @@ int overlap_maps(aicp_hip_ctx* ctx, aicp_hip_batch* B, size_t P, size_t G, PairD
     TCHK(hipMemsetAsync(bm, 0, bm_bytes, s));
     launch_ovl_mark(s, B->m_gref, dG, dOvl + P, dGst, B->ref_raw.as<float4>(), 0, res, bm, filter);
     launch_ovl_mark(s, B->m_read, dDesc, dOvl, dState, readS, 1, res, bm, filter);
-    launch_ovl_count(s, (int)P, (int)G, dDesc, dOvl, dOvl + P, dState, dGst, bm);
+    launch_ovl_count(s, (int)P, (int)G, dDesc, dOvl, dOvl + P, dState, dGst, bm, wide);
     rc.ovl = false;
     if (rc.use && G == 1) {  // keep the reference's map (offset 0) and its group state for the next call
       TCHK(ensure(rc.gst, sizeof(PairState)));
@@ -2370,6 +2391,163 @@ int aicp_hip_test_normals(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* coun
   for (size_t r = 0; r < R; ++r) out_degenerate[r] = hs[r].degenerate;
   HIPC(hipMemcpy(out_touched, loc.touched.p, 16, hipMemcpyDeviceToHost));
   *out_dirty = dirty;
+  return AICP_OK;
+}
+
+// The batch's overlap (upload_pairs, run_batch with AICP_RUN_OVERLAP: grouping, key boxes,
+// overlap_maps or overlap_sparse) on given clouds and origins, and everything it wrote: the
+// states, the map descriptors and arena, or the key path's counts, offsets and sorted words.
+// ctx->ovl_probe carries the overrides of the two launch rules in and what ran out. Every
+// argument is checked before the device is touched.
+int aicp_hip_test_overlap(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* ref_counts, const float* ref_pts,
+                          size_t n_pairs, const uint32_t* pair_ref, const uint32_t* n_read, const float* read_pts,
+                          const double* ref_origins, const double* read_origins, double resolution, int32_t path,
+                          int32_t filter, int32_t wide, int32_t cap_mode, const uint64_t* caps, int32_t rigid,
+                          aicp_test_overlap_out* out) {
+  if (!ctx || !ref_counts || !ref_pts || !pair_ref || !n_read || !read_pts || !ref_origins || !read_origins || !out)
+    return AICP_ERR_INVALID;
+  if (!out->pair_group || !out->cloud_keys || !out->cloud_err || !out->cloud_bbox || !out->pair_counts ||
+      !out->pair_percent || !out->pair_ratio || !out->pair_err || !out->desc_min || !out->desc_dim || !out->desc_off ||
+      !out->desc_bytes || !out->arena || !out->key_counts || !out->key_offsets || !out->words || !out->cloud_bound ||
+      !out->list_off || !out->list_cap)
+    return AICP_ERR_INVALID;
+  if (n_refs == 0 || n_refs > (size_t)kMaxPairs || n_pairs == 0 || n_pairs > (size_t)kMaxPairs) return AICP_ERR_INVALID;
+  if (!(resolution > 0) || path < 0 || path > 4 || filter < -1 || filter > 1 || wide < -1 || wide > 1 || cap_mode < 0 ||
+      cap_mode > 1 || rigid < 0 || rigid > 1 || (cap_mode == 1 && (!caps || path < 3)))
+    return AICP_ERR_INVALID;
+  const size_t R = n_refs, P = n_pairs;
+  std::vector<uint64_t> roff(R + 1, 0);
+  for (size_t r = 0; r < R; ++r) {
+    if (ref_counts[r] == 0) return AICP_ERR_INVALID;
+    roff[r + 1] = roff[r] + ref_counts[r];
+  }
+  std::vector<aicp_pair> pairs(P, aicp_pair{});
+  uint64_t wo = 0;
+  for (size_t p = 0; p < P; ++p) {
+    if (n_read[p] == 0 || pair_ref[p] >= R) return AICP_ERR_INVALID;
+    aicp_pair& q = pairs[p];
+    q.ref = ref_pts + 3 * roff[pair_ref[p]];
+    q.n_ref = ref_counts[pair_ref[p]];
+    q.ref_stride = 12;
+    q.read = read_pts + 3 * wo;
+    q.n_read = n_read[p];
+    q.read_stride = 12;
+    for (int k = 0; k < 3; ++k) {
+      q.ref_origin[k] = ref_origins[3 * p + k];
+      q.read_origin[k] = read_origins[3 * p + k];
+    }
+    wo += n_read[p];
+  }
+  {  // the per-point slots of the key path: one per point of every group's reference and reading
+    std::vector<std::pair<uint32_t, std::array<double, 3>>> groups;
+    uint64_t slots = wo;
+    for (size_t p = 0; p < P; ++p) {
+      const std::pair<uint32_t, std::array<double, 3>> g{
+          pair_ref[p], {ref_origins[3 * p], ref_origins[3 * p + 1], ref_origins[3 * p + 2]}};
+      if (std::find(groups.begin(), groups.end(), g) == groups.end()) {
+        groups.push_back(g);
+        slots += ref_counts[pair_ref[p]];
+      }
+    }
+    if (slots > out->points_cap) return AICP_ERR_INVALID;
+  }
+  HIPC(hipSetDevice(ctx->device));
+  ctx->refc.invalidate();  // (ctx->bitmap and the group states are rewritten)
+  ctx->rdc.valid = ctx->rdc.hit = false;
+  struct Local {  // freed, and the probe switched off, on every return
+    aicp_hip_ctx* ctx;
+    aicp_hip_batch* B = new aicp_hip_batch();
+    ~Local() {
+      ctx->ovl_probe = OvlProbe{};
+      (void)hipStreamSynchronize(ctx->stream);
+      free_batch(B);
+    }
+  } loc{ctx};
+  OvlProbe& probe = ctx->ovl_probe;
+  probe = OvlProbe{};
+  probe.on = true;
+  probe.filter = filter;
+  probe.wide = wide;
+  probe.keys = path == 2;
+  aicp_icp_config cfg;
+  aicp_hip_default_config(&cfg);
+  const int saved_path = ctx->opt.overlap_path;
+  if (path == 1) ctx->opt.overlap_path = 0;  // (dense wherever the maps fit)
+  int rc = upload_pairs(ctx, pairs.data(), P, loc.B, false);
+  out->dirty = 0;
+  if (!rc && path >= 3) {  // the stream's windows (sequence.cpp), one per overlap group
+    ctx->opt.overlap_path = saved_path;
+    return ovl_window_test(ctx, loc.B, pairs.data(), resolution, path, filter, wide, cap_mode ? caps : nullptr, rigid,
+                           out);
+  }
+  if (!rc) rc = run_batch(ctx, loc.B, &cfg, resolution, AICP_RUN_OVERLAP, nullptr, nullptr, nullptr);
+  ctx->opt.overlap_path = saved_path;
+  // a cloud's ovl_err comes back as the batch's "pair status": reported in the outputs instead
+  if (rc && !(rc == AICP_ERR_HIP && ctx->err.rfind("pair status", 0) == 0)) return rc;
+  const size_t G = loc.B->gdesc.size();
+  out->path = probe.ran_path;
+  out->filter = probe.ran_filter;
+  out->wide = probe.ran_wide;
+  out->n_groups = (int32_t)G;
+  std::vector<PairState> hs(P), hg(G);
+  HIPC(hipMemcpy(hs.data(), ctx->state.p, P * sizeof(PairState), hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(hg.data(), ctx->gstate.p, G * sizeof(PairState), hipMemcpyDeviceToHost));
+  for (size_t c = 0; c < G + P; ++c) {
+    const PairState& st = c < G ? hg[c] : hs[c - G];
+    out->cloud_keys[c] = st.ovl_counts[c < G ? 0 : 1];
+    out->cloud_err[c] = st.ovl_err;
+    for (int k = 0; k < 6; ++k) out->cloud_bbox[6 * c + k] = st.ovl_bbox[k];
+  }
+  for (size_t p = 0; p < P; ++p) {
+    out->pair_group[p] = loc.B->desc[p].ogroup;
+    for (int k = 0; k < 3; ++k) out->pair_counts[3 * p + k] = hs[p].ovl_counts[k];
+    out->pair_percent[p] = hs[p].overlap;
+    out->pair_ratio[p] = hs[p].ratio;
+    out->pair_err[p] = hs[p].ovl_err;
+  }
+  out->arena_bytes = out->n_points = out->n_words = 0;
+  if (probe.ran_path == 1) {  // the descriptors lie readings first; the outputs groups first
+    std::vector<OvlDesc> od(P + G);
+    HIPC(hipMemcpy(od.data(), ctx->ovl.p, (P + G) * sizeof(OvlDesc), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < G + P; ++c) {
+      const OvlDesc& o = od[c < G ? P + c : c - G];
+      for (int k = 0; k < 3; ++k) {
+        out->desc_min[3 * c + k] = o.min[k];
+        out->desc_dim[3 * c + k] = o.dim[k];
+      }
+      out->desc_off[c] = o.off;
+      out->desc_bytes[c] = o.bytes;
+    }
+    out->arena_bytes = probe.arena_bytes;
+    const uint64_t nb = std::min(out->arena_cap, out->arena_bytes);
+    if (nb) HIPC(hipMemcpy(out->arena, ctx->bitmap.p, nb, hipMemcpyDeviceToHost));
+  } else if (probe.ran_path == 2) {
+    out->n_points = probe.n_points;
+    out->n_words = probe.n_keys;
+    if (probe.n_points > out->points_cap) FAIL(AICP_ERR_INVALID, "points_cap");
+    if (probe.n_points) {
+      HIPC(hipMemcpy(out->key_counts, probe.cnt, probe.n_points * 4, hipMemcpyDeviceToHost));
+      HIPC(hipMemcpy(out->key_offsets, probe.off, probe.n_points * 8, hipMemcpyDeviceToHost));
+    }
+    const uint64_t nw = std::min(out->words_cap, out->n_words);
+    if (nw) HIPC(hipMemcpy(out->words, probe.keys1, nw * 8, hipMemcpyDeviceToHost));
+  } else {
+    FAIL(AICP_ERR_HIP, "the batch ran no overlap");
+  }
+  return AICP_OK;
+}
+
+int aicp_hip_test_key_bound(const float* pts, size_t n, const double origin[3], double resolution, int32_t rigid,
+                            uint64_t* out_bound, uint64_t* out_point_cap) {
+  if (!pts || !origin || !out_bound || !out_point_cap || n == 0 || !(resolution > 0) || rigid < 0 || rigid > 1)
+    return AICP_ERR_INVALID;
+  WorkerPool pool{0};
+  aicp_cloud c{};
+  c.pts = pts;
+  c.n = n;
+  c.stride = 12;
+  *out_bound = key_bound(pool, c, origin, resolution, rigid != 0);
+  *out_point_cap = kMaxRayKeys;
   return AICP_OK;
 }
 

@@ -247,7 +247,7 @@ void launch_ovl_mark(hipStream_t s, BlockMap m, const PairDesc* pd, const OvlDes
                      const float4* pts, int side, double res, uint8_t* maps, bool filter);
 // |A| per group (gst.ovl_counts[0]), |B| and |A∩B| per pair (st.ovl_counts[1], [2])
 void launch_ovl_count(hipStream_t s, int n_pairs, int n_groups, const PairDesc* pd, const OvlDesc* od_read,
-                      const OvlDesc* od_ref, PairState* st, PairState* gst, const uint8_t* maps);
+                      const OvlDesc* od_ref, PairState* st, PairState* gst, const uint8_t* maps, bool wide);
 // the parts of launch_ovl_count: |S| of n maps into st[i].ovl_counts[slot]; |A∩B| per pair
 // wide: many workgroups per map (the one-shot call of a single pair)
 void launch_ovl_popcount(hipStream_t s, int n, const OvlDesc* od, PairState* st, int slot, const uint8_t* maps,

@@ -340,8 +340,7 @@ void launch_ovl_mark(hipStream_t s, BlockMap m, const PairDesc* pd, const OvlDes
     k_ovl_mark<false><<<m.n_blocks, 256, 0, s>>>(m, pd, od, st, pts, side, res, maps);
 }
 void launch_ovl_count(hipStream_t s, int n_pairs, int n_groups, const PairDesc* pd, const OvlDesc* od_read,
-                      const OvlDesc* od_ref, PairState* st, PairState* gst, const uint8_t* maps) {
-  const bool wide = n_pairs + n_groups <= 2;  // (the one-shot call of one pair)
+                      const OvlDesc* od_ref, PairState* st, PairState* gst, const uint8_t* maps, bool wide) {
   const int bg = count_bpm(n_groups, wide), bp = count_bpm(n_pairs, wide);
   k_ovl_popcount<<<n_groups * bg, 256, 0, s>>>(od_ref, gst, 0, maps, bg);
   k_ovl_popcount<<<n_pairs * bp, 256, 0, s>>>(od_read, st, 1, maps, bp);

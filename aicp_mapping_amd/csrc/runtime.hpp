@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -287,6 +288,22 @@ struct ReadCache {
   uint64_t hits = 0;
 };
 
+// aicp_hip_test_overlap's view into the batch's overlap (overlap_maps / overlap_sparse). `on`
+// holds for that call alone: the two launch rules and the path take the given values (-1: the
+// rule), the ratio is set as a registration sets it, and what ran is recorded with where the key
+// path's arrays lie (ctx->ovl_sp / ovl_keys, valid until the next overlap).
+struct OvlProbe {
+  bool on = false;
+  int filter = -1, wide = -1;
+  bool keys = false;  // the sorted-key path whatever the maps' size
+  int ran_path = 0, ran_filter = 0, ran_wide = 0;  // 1 dense maps, 2 sorted keys
+  uint64_t arena_bytes = 0;                        // dense: the map arena as sized
+  uint64_t n_points = 0, n_keys = 0;               // keys: per-point slots, words
+  const uint32_t* cnt = nullptr;
+  const uint64_t* off = nullptr;
+  const uint64_t* keys1 = nullptr;
+};
+
 struct SeqState;  // sequence.cpp
 void seq_state_free(SeqState* s);
 struct MapStreamBufs;  // map_stream.cpp
@@ -302,6 +319,90 @@ int upload_pairs(aicp_hip_ctx* ctx, const aicp_pair* pairs, size_t n, aicp_hip_b
                  bool skip_refs = false, bool skip_reads = false, bool nosync = false);
 int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, double res, int flags, float* outT,
               aicp_icp_stats* stats, float* out_overlap);
+void free_batch(aicp_hip_batch* B);
+// the stream's bound of a cloud's ray keys (sequence.cpp), per-point cap included
+extern const uint64_t kMaxRayKeys;
+uint64_t key_bound(WorkerPool& pool, const aicp_cloud& c, const double* org, double res, bool rigid);
+
+// float AABB of a cloud's points and its sensor origin (the extent bounds its voxel maps)
+struct Box {
+  float lo[3], hi[3];
+  void reset() {
+    for (int k = 0; k < 3; ++k) {
+      lo[k] = INFINITY;
+      hi[k] = -INFINITY;
+    }
+  }
+  void add(float x, float y, float z) {
+    const float v[3] = {x, y, z};
+    for (int k = 0; k < 3; ++k) {
+      lo[k] = std::min(lo[k], v[k]);
+      hi[k] = std::max(hi[k], v[k]);
+    }
+  }
+  void merge(const Box& b) {
+    for (int k = 0; k < 3; ++k) {
+      lo[k] = std::min(lo[k], b.lo[k]);
+      hi[k] = std::max(hi[k], b.hi[k]);
+    }
+  }
+};
+
+// The overlap of one stream window (sequence.cpp): one reference, np readings. The host's part is
+// a plan made from the clouds alone; the device's part runs in three steps that the stream puts
+// on different streams and aicp_hip_test_overlap one after the other.
+struct OvlWinPlan {
+  // voxel maps: slot [0] the reference's, [1 + i] reading i's; off preset, the rest sized on the device
+  std::vector<OvlDesc> od;
+  std::vector<uint64_t> cap;  // the slots' bytes
+  uint64_t bm = 0, cap_max = 0;  // all slots together, and the largest
+  // key lists (ovl_window_keys): clouds readings 0..np-1 then the reference, their blocks of 256
+  // points (cloud, first point; the readings' blocks first), the two lists' capacities
+  std::vector<OvlCloud> scl;
+  std::vector<uint32_t> sbc, sbs;
+  uint64_t cap_r = 0, cap_g = 0;
+  std::vector<uint64_t> kb_read;  // each reading's key bound
+};
+// src_rigid / read_rigid: sized for any rigid motion of that cloud (a corrected reference; debug mode)
+void ovl_window_slots(OvlWinPlan& W, const Box& src_box, const double* src_origin, bool src_rigid, const Box* boxes,
+                      const aicp_cloud* reads, size_t np, double res, bool read_rigid);
+// ref_origin: the origin the reference's rays start from when the host knows it (else 3 zeros, device-written)
+void ovl_window_keys(OvlWinPlan& W, WorkerPool& pool, const aicp_cloud& src, const double* ref_origin, bool ref_rigid,
+                     const aicp_cloud* reads, const uint32_t* loff, size_t np, double res, bool read_rigid);
+// the two key sides on device arrays: dcl / dbc the plan's clouds and block words (sbc then sbs) as
+// uploaded, cnt / off one slot per point (readings, then the reference), keys_r / keys_g 2 cap words each
+void ovl_window_sides(const OvlWinPlan& W, size_t np, uint64_t nread, uint32_t n_ref, OvlCloud* dcl,
+                      const uint32_t* dbc, uint32_t* cnt, uint64_t* off, uint64_t* keys_r, uint64_t* keys_g,
+                      void* tmp_r, size_t tmp_rb, void* tmp_g, size_t tmp_gb, unsigned long long* pc, OvlKeySide& kr,
+                      OvlKeySide& kg);
+struct OvlWinDev {  // where a window's overlap lies on the device
+  bool sparse = false;
+  size_t np = 0;
+  double res = 0;
+  const PairDesc* dDesc = nullptr;  // np readings
+  PairState* dState = nullptr;
+  const PairDesc* dG = nullptr;     // the reference's group
+  PairState* dGst = nullptr;
+  OvlDesc* dOvl = nullptr;          // np + 1 slots
+  const uint64_t* dCap = nullptr;
+  uint8_t* bmp = nullptr;
+  uint64_t cap_max = 0, cap0 = 0;   // the largest reading slot bound given to the clear; the reference's
+  BlockMap m_read{}, m_gref{};
+  const OvlKeySide* kr = nullptr;
+  const OvlKeySide* kg = nullptr;
+  unsigned long long* per_pair = nullptr;
+  bool filter = false, wide = false;  // the stream's choice for both: plain stores, narrow counts
+};
+int ovl_window_read_side(std::string& err, hipStream_t s, const OvlWinDev& D, const float4* readS);
+int ovl_window_ref_side(std::string& err, hipStream_t s, const OvlWinDev& D, const double* origin0,
+                        const float4* ref);
+int ovl_window_counts(std::string& err, hipStream_t s, const OvlWinDev& D);
+// aicp_hip_test_overlap's stream paths: every overlap group of the batch B as one window (path 3
+// maps sized on the device, 4 capped key lists); caps (nullable): explicit capacities per cloud,
+// groups then readings (bytes, or key words). Fills out's per-cloud and per-pair fields, the
+// descriptors and arena or the lists; out_dirty: changed guard words of its own buffers.
+int ovl_window_test(aicp_hip_ctx* ctx, const aicp_hip_batch* B, const aicp_pair* pairs, double res, int path,
+                    int filter, int wide, const uint64_t* caps, int rigid, aicp_test_overlap_out* out);
 // the device-resident map (aicp_hip.cpp), for the streams that grow it and crop it into a batch
 int map_reserve(aicp_hip_ctx* ctx, aicp_hip_map* map, size_t add);
 int map_crop_pairs(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float mx, const aicp_cloud* readings,
@@ -397,6 +498,7 @@ struct aicp_hip_ctx {
   aicp::rt::PinBuf pin_crop;
   aicp::rt::PinBuf pin_maps;  // upload_pairs' block maps
   aicp::rt::RefCache refc;  // the drop-in path's resident reference (runtime.hpp)
+  aicp::rt::OvlProbe ovl_probe;  // aicp_hip_test_overlap (off in every other call)
   aicp::rt::ReadCache rdc;  // and its last reading
   aicp::rt::WorkerPool* pool = nullptr;  // host threads of the one-shot calls (packing, the reference compare)
   uint32_t* poll_host = nullptr;  // the batch loop's active counts (hipHostMalloc, mapped), kBatchPolls words

@@ -173,30 +173,6 @@ void seq_state_free(SeqState* S) {
 
 namespace {
 
-// float AABB of a cloud's points and its sensor origin (the extent bounds its voxel maps)
-struct Box {
-  float lo[3], hi[3];
-  void reset() {
-    for (int k = 0; k < 3; ++k) {
-      lo[k] = INFINITY;
-      hi[k] = -INFINITY;
-    }
-  }
-  void add(float x, float y, float z) {
-    const float v[3] = {x, y, z};
-    for (int k = 0; k < 3; ++k) {
-      lo[k] = std::min(lo[k], v[k]);
-      hi[k] = std::max(hi[k], v[k]);
-    }
-  }
-  void merge(const Box& b) {
-    for (int k = 0; k < 3; ++k) {
-      lo[k] = std::min(lo[k], b.lo[k]);
-      hi[k] = std::max(hi[k], b.hi[k]);
-    }
-  }
-};
-
 // xyz at a byte stride -> float4 (w = 1) and the AABB of the finite points, in chunks over the pool
 void pack_clouds(WorkerPool& pool, const std::vector<PackSeg>& segs, std::vector<Box>& boxes) {
   constexpr uint64_t kChunk = 1 << 15;
@@ -244,9 +220,15 @@ uint64_t map_cap(const Box& b0, const double* o, double res, bool rigid) {
     d2 += ext[k] * ext[k];
   }
   uint64_t vox = 1;
+  double voxd = 1;
   for (int k = 0; k < 3; ++k) {
     const double e = rigid ? std::sqrt(d2) : ext[k];
-    vox *= (uint64_t)std::ceil(e / res) + 8 + 2 * (kOvlBrick0 - 1);
+    const double side = std::ceil(e / res) + 8 + 2 * (kOvlBrick0 - 1);
+    voxd *= side;
+    // a finite return far outside the key range (1e30 m) must not wrap the product into a small
+    // capacity: such a window is over every budget and runs on key lists
+    if (!(voxd < 0x1p50)) return uint64_t(1) << 50;  // (4096 such slots still add up within 64 bits)
+    vox *= (uint64_t)side;
   }
   return (vox + kOvlBrickBytes - 1) / kOvlBrickBytes * kOvlBrickBytes;
 }
@@ -255,7 +237,13 @@ uint64_t map_cap(const Box& b0, const double* o, double res, bool rigid) {
 // instead: a far return (a key box of 10^9+ voxels) or a very wide scan. The C2/C3 scenes need
 // ~3 MB per reading map and ~80 MB for a reference (sized for any rotation of its source).
 constexpr uint64_t kSeqMapBudget = uint64_t(1) << 30;
-constexpr uint64_t kMaxRayKeys = 3 * 65536 + 8;  // keys are 16-bit per axis: a ray's walk is bounded
+
+}  // namespace
+
+namespace aicp {
+namespace rt {
+
+const uint64_t kMaxRayKeys = 3 * 65536 + 8;  // keys are 16-bit per axis: a ray's walk is bounded
 
 // Upper bound of the keys computeRayKeys(o, p) + p's own key visit, summed over a cloud: one
 // step per key crossed on an axis, plus the origin, the endpoint and a margin for the walk's
@@ -294,6 +282,115 @@ uint64_t key_bound(WorkerPool& pool, const aicp_cloud& c, const double* org, dou
   for (uint64_t v : part) s += v;
   return s;
 }
+
+// voxel maps: [0] the reference (capacity for any rigid motion of its source), [1 + i] readings
+void ovl_window_slots(OvlWinPlan& W, const Box& src_box, const double* src_origin, bool src_rigid, const Box* boxes,
+                      const aicp_cloud* reads, size_t np, double res, bool read_rigid) {
+  W.od.assign(np + 1, OvlDesc{});
+  W.cap.assign(np + 1, 0);
+  W.bm = W.cap_max = 0;
+  for (size_t i = 0; i <= np; ++i) {
+    W.cap[i] = i == 0 ? map_cap(src_box, src_origin, res, src_rigid)
+                      : map_cap(boxes[i - 1], reads[i - 1].origin, res, read_rigid);  // debug: moved by initialT_
+    W.od[i].off = W.bm;
+    W.bm += W.cap[i];
+    W.cap_max = std::max(W.cap_max, W.cap[i]);
+  }
+}
+
+// key lists sized by host bounds of the rays' keys (readings from their own points; the reference
+// for any rigid motion of its source), so the stream needs no read-back
+void ovl_window_keys(OvlWinPlan& W, WorkerPool& pool, const aicp_cloud& src, const double* ref_origin, bool ref_rigid,
+                     const aicp_cloud* reads, const uint32_t* loff, size_t np, double res, bool read_rigid) {
+  W.scl.clear();
+  W.sbc.clear();
+  W.sbs.clear();
+  W.kb_read.clear();
+  W.cap_r = W.cap_g = 0;
+  uint64_t slot = 0;
+  for (size_t i = 0; i <= np; ++i) {  // readings 0..np-1, then the reference
+    const bool ref = i == np;
+    const aicp_cloud& c = ref ? src : reads[i];
+    OvlCloud o{};
+    o.pts_off = ref ? 0u : loff[i];
+    o.n = (uint32_t)c.n;
+    o.side = ref ? 0u : 1u;
+    for (int k = 0; k < 3; ++k) o.origin[k] = ref ? ref_origin[k] : c.origin[k];
+    o.slot = ref ? 0 : slot;
+    slot += ref ? 0 : c.n;
+    W.scl.push_back(o);
+    const uint32_t ci = ref ? 0u : (uint32_t)i;
+    for (uint32_t j = 0; j < o.n; j += 256) {
+      W.sbc.push_back(ci);
+      W.sbs.push_back(j);
+    }
+    const uint64_t kb = key_bound(pool, c, c.origin, res, ref ? ref_rigid : read_rigid);
+    if (!ref) W.kb_read.push_back(kb);
+    (ref ? W.cap_g : W.cap_r) += kb;
+  }
+}
+
+void ovl_window_sides(const OvlWinPlan& W, size_t np, uint64_t nread, uint32_t n_ref, OvlCloud* dcl,
+                      const uint32_t* dbc, uint32_t* cnt, uint64_t* off, uint64_t* keys_r, uint64_t* keys_g,
+                      void* tmp_r, size_t tmp_rb, void* tmp_g, size_t tmp_gb, unsigned long long* pc, OvlKeySide& kr,
+                      OvlKeySide& kg) {
+  const size_t nb = W.sbc.size();
+  const uint32_t* dbs = dbc + nb;
+  const uint32_t nbr = (uint32_t)(nb - (n_ref + 255) / 256);  // the readings' blocks come first
+  kr = OvlKeySide{dcl, (int)np, dbc, dbs, nbr, (uint32_t)nread, cnt, off, W.cap_r, keys_r, keys_r + W.cap_r,
+                  tmp_r, tmp_rb, pc};
+  kg = OvlKeySide{dcl + np, 1, dbc + nbr, dbs + nbr, (uint32_t)(nb - nbr), n_ref, cnt + nread, off + nread,
+                  W.cap_g, keys_g, keys_g + W.cap_g, tmp_g, tmp_gb, pc + np};
+}
+
+// the readings' voxel maps and |B| (or their key list)
+int ovl_window_read_side(std::string& err, hipStream_t s, const OvlWinDev& D, const float4* readS) {
+  const int np = (int)D.np;
+  if (D.sparse) {
+    launch_ovl_init(s, np, D.dDesc, D.dState, D.res, 2);
+    TCHK(launch_ovl_keys(s, *D.kr, nullptr, readS, D.res, D.dState, 1));
+  } else {
+    launch_ovl_init(s, np, D.dDesc, D.dState, D.res, 2);
+    launch_ovl_bbox(s, D.m_read, D.dDesc, D.dState, readS, 1, D.res);
+    launch_ovl_size(s, np, D.dState, D.dOvl + 1, D.dCap + 1);
+    launch_ovl_clear(s, np, D.dOvl + 1, D.bmp, D.cap_max);
+    launch_ovl_mark(s, D.m_read, D.dDesc, D.dOvl + 1, D.dState, readS, 1, D.res, D.bmp, D.filter);
+    launch_ovl_popcount(s, np, D.dOvl + 1, D.dState, 1, D.bmp, D.wide);
+  }
+  return AICP_OK;
+}
+
+// the reference's voxel map (or key list) and |A|; origin0 (nullable): its origin where the device wrote it
+int ovl_window_ref_side(std::string& err, hipStream_t s, const OvlWinDev& D, const double* origin0,
+                        const float4* ref) {
+  if (D.sparse) {
+    launch_ovl_init(s, 1, D.dG, D.dGst, D.res, 1);
+    TCHK(launch_ovl_keys(s, *D.kg, origin0, ref, D.res, D.dGst, 0));
+  } else {
+    launch_ovl_init(s, 1, D.dG, D.dGst, D.res, 1);
+    launch_ovl_bbox(s, D.m_gref, D.dG, D.dGst, ref, 0, D.res);
+    launch_ovl_size(s, 1, D.dGst, D.dOvl, D.dCap);
+    launch_ovl_clear(s, 1, D.dOvl, D.bmp, D.cap0);
+    launch_ovl_mark(s, D.m_gref, D.dG, D.dOvl, D.dGst, ref, 0, D.res, D.bmp, D.filter);
+    launch_ovl_popcount(s, 1, D.dOvl, D.dGst, 0, D.bmp, D.wide);
+  }
+  return AICP_OK;
+}
+
+// |A ∩ B| of every reading, the percentage and the ratio
+int ovl_window_counts(std::string& err, hipStream_t s, const OvlWinDev& D) {
+  if (D.sparse)
+    TCHK(launch_ovl_keys_intersect(s, *D.kr, *D.kg, D.per_pair, D.dState));
+  else
+    launch_ovl_intersect(s, (int)D.np, D.dDesc, D.dOvl + 1, D.dOvl, D.dState, D.bmp, D.wide);
+  launch_ovl_finish(s, (int)D.np, D.dDesc, D.dState, D.dGst, 1);
+  return AICP_OK;
+}
+
+}  // namespace rt
+}  // namespace aicp
+
+namespace {
 
 // the error message of work run on a host thread of its own (copied into ctx->err after the join,
 // so two threads never write that string at once)
@@ -499,48 +596,26 @@ static int win_upload(C* ctx, SeqState* S, const aicp_icp_config* cfg, const aic
   PairDesc g = r;
   for (int k = 0; k < 3; ++k) g.ref_origin[k] = w.src < 0 ? first->origin[k] : 0.0;
   // voxel maps: [0] the reference (capacity for any rigid motion of its source), [1 + i] readings
-  std::vector<OvlDesc> od(np + 1);
-  std::vector<uint64_t> cap(np + 1);
-  uint64_t bm = 0, cap_max = 0;
-  for (size_t i = 0; i <= np; ++i) {
-    cap[i] = i == 0 ? map_cap(src_box, src.origin, res, w.src >= 0)
-                    : map_cap(boxes[i - 1], rd[w.p0 + i - 1].origin, res, debug);  // debug: moved by initialT_
-    od[i] = OvlDesc{};
-    od[i].off = bm;
-    bm += cap[i];
-    cap_max = std::max(cap_max, cap[i]);
-  }
+  OvlWinPlan W;
+  ovl_window_slots(W, src_box, src.origin, w.src >= 0, boxes.data(), rd + w.p0, np, res, debug);
+  const std::vector<OvlDesc>& od = W.od;
+  const std::vector<uint64_t>& cap = W.cap;
+  const uint64_t bm = W.bm, cap_max = W.cap_max;
   // a window whose maps do not fit the budget runs its overlap on sorted key lists: sized by host
   // bounds of the rays' keys (readings from their own points; the reference for any rigid
   // motion of its source), so the stream needs no read-back
   const bool sparse = doOvl && (S->opt.overlap_path == 1 || bm > kSeqMapBudget);
-  std::vector<OvlCloud> scl;
-  std::vector<uint32_t> sbc, sbs;
+  const std::vector<OvlCloud>& scl = W.scl;
+  const std::vector<uint32_t>&sbc = W.sbc, &sbs = W.sbs;
   uint64_t cap_r = 0, cap_g = 0;
   size_t tmp_r = 0, tmp_g = 0;
-  std::vector<uint64_t> kb_read;  // each reading's key bound
+  const std::vector<uint64_t>& kb_read = W.kb_read;  // each reading's key bound
   if (sparse) {
-    uint64_t slot = 0;
-    for (size_t i = 0; i <= np; ++i) {  // readings 0..np-1, then the reference
-      const bool ref = i == np;
-      const aicp_cloud& c = ref ? src : rd[w.p0 + i];
-      OvlCloud o{};
-      o.pts_off = ref ? 0u : loff[i];
-      o.n = (uint32_t)c.n;
-      o.side = ref ? 0u : 1u;
-      for (int k = 0; k < 3; ++k) o.origin[k] = ref ? (w.src < 0 ? first->origin[k] : 0.0) : c.origin[k];
-      o.slot = ref ? 0 : slot;
-      slot += ref ? 0 : c.n;
-      scl.push_back(o);
-      const uint32_t ci = ref ? 0u : (uint32_t)i;
-      for (uint32_t j = 0; j < o.n; j += 256) {
-        sbc.push_back(ci);
-        sbs.push_back(j);
-      }
-      const uint64_t kb = key_bound(S->pool, c, c.origin, res, (ref && w.src >= 0) || (!ref && debug));
-      if (!ref) kb_read.push_back(kb);
-      (ref ? cap_g : cap_r) += kb;
-    }
+    const double zero3[3] = {0.0, 0.0, 0.0};  // (device-written for corrected references)
+    ovl_window_keys(W, S->pool, src, w.src < 0 ? first->origin : zero3, w.src >= 0, rd + w.p0, loff.data(), np, res,
+                    debug);
+    cap_r = W.cap_r;
+    cap_g = W.cap_g;
     tmp_r = ovl_keys_temp_bytes(nread, cap_r, (int)np);
     if (debug)  // the readings one at a time: each side's own scan / sort
       for (size_t i = 0; i < np; ++i) tmp_r = std::max(tmp_r, ovl_keys_temp_bytes(rd[w.p0 + i].n, kb_read[i], 1));
@@ -615,14 +690,10 @@ static int win_upload(C* ctx, SeqState* S, const aicp_icp_config* cfg, const aic
     OvlCloud* dcl = reinterpret_cast<OvlCloud*>(D);
     const uint32_t* dbc = reinterpret_cast<const uint32_t*>(D + ncl * sizeof(OvlCloud));
     const uint32_t* dbs = dbc + nb;
-    const uint32_t nbr = (uint32_t)(nb - (n_ref + 255) / 256);  // the readings' blocks come first
     unsigned long long* pc = sl.sp_pc.as<unsigned long long>();
-    R.kr = OvlKeySide{dcl, (int)np, dbc, dbs, nbr, (uint32_t)nread, sl.sp_cnt.as<uint32_t>(),
-                      sl.sp_off.as<uint64_t>(), cap_r, sl.sp_keys_r.as<uint64_t>(),
-                      sl.sp_keys_r.as<uint64_t>() + cap_r, sl.sp_tmp_r.p, tmp_r, pc};
-    R.kg = OvlKeySide{dcl + np, 1, dbc + nbr, dbs + nbr, (uint32_t)(nb - nbr), n_ref,
-                      sl.sp_cnt.as<uint32_t>() + nread, sl.sp_off.as<uint64_t>() + nread, cap_g,
-                      sl.sp_keys_g.as<uint64_t>(), sl.sp_keys_g.as<uint64_t>() + cap_g, sl.sp_tmp_g.p, tmp_g, pc + np};
+    ovl_window_sides(W, np, nread, n_ref, dcl, dbc, sl.sp_cnt.as<uint32_t>(), sl.sp_off.as<uint64_t>(),
+                     sl.sp_keys_r.as<uint64_t>(), sl.sp_keys_g.as<uint64_t>(), sl.sp_tmp_r.p, tmp_r, sl.sp_tmp_g.p,
+                     tmp_g, pc, R.kr, R.kg);
     R.per_pair = pc + np + 1;
     if (debug) {  // reading i alone: cloud i (its key words tagged 0), keys at its own offset
       R.kr1.assign(np, OvlKeySide{});
@@ -771,16 +842,20 @@ static int win_read_side(C* ctx, SeqState* S, const aicp_icp_config* cfg, const 
                            sl.ord_v1.as<uint32_t>(), sl.ord_tmp.p, tb, sl.read_s.as<float4>()));
     readS = sl.read_s.as<float4>();
   }
-  if (doOvl && R.sparse) {
-    launch_ovl_init(sr, (int)np, dDesc, dState, res, 2);
-    HIPC(launch_ovl_keys(sr, R.kr, nullptr, readS, res, dState, 1));
-  } else if (doOvl) {
-    launch_ovl_init(sr, (int)np, dDesc, dState, res, 2);
-    launch_ovl_bbox(sr, m_read, dDesc, dState, readS, 1, res);
-    launch_ovl_size(sr, (int)np, dState, dOvl + 1, dCap + 1);
-    launch_ovl_clear(sr, (int)np, dOvl + 1, bmp, cap_max);
-    launch_ovl_mark(sr, m_read, dDesc, dOvl + 1, dState, readS, 1, res, bmp, false);
-    launch_ovl_popcount(sr, (int)np, dOvl + 1, dState, 1, bmp);
+  if (doOvl) {
+    OvlWinDev D;
+    D.sparse = R.sparse;
+    D.np = np;
+    D.res = res;
+    D.dDesc = dDesc;
+    D.dState = dState;
+    D.dOvl = dOvl;
+    D.dCap = dCap;
+    D.bmp = bmp;
+    D.cap_max = cap_max;
+    D.m_read = m_read;
+    D.kr = &R.kr;
+    if (int rc = ovl_window_read_side(ctx->err, sr, D, readS)) return rc;
   }
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(sl.ev_rd, sr));
@@ -939,30 +1014,33 @@ static int win_ref_icp(aicp_hip_ctx* ctx, SeqState* S, const aicp_icp_config* cf
   const float4* readS = R.readS;
   hipStream_t si = S->s_icp;
   // the reference's voxel map (or key list)
-  if (doOvl && R.sparse) {
+  OvlWinDev D;
+  if (doOvl) {
+    D.sparse = R.sparse;
+    D.np = np;
+    D.res = res;
+    D.dDesc = dDesc;
+    D.dState = dState;
+    D.dG = dG;
+    D.dGst = dGst;
+    D.dOvl = dOvl;
+    D.dCap = dCap;
+    D.bmp = bmp;
+    D.cap0 = R.sparse ? 0 : R.cap[0];
+    D.m_gref = R.m_gref;
+    D.kr = &R.kr;
+    D.kg = &R.kg;
+    D.per_pair = R.per_pair;
     HIPC(hipStreamWaitEvent(si, sl.ev_ref, 0));
-    launch_ovl_init(si, 1, dG, dGst, res, 1);
-    HIPC(launch_ovl_keys(si, R.kg, w.src >= 0 ? dG->ref_origin : nullptr, sl.ref_raw.as<float4>(), res, dGst, 0));
-  } else if (doOvl) {
-    HIPC(hipStreamWaitEvent(si, sl.ev_ref, 0));
-    launch_ovl_init(si, 1, dG, dGst, res, 1);
-    launch_ovl_bbox(si, R.m_gref, dG, dGst, sl.ref_raw.as<float4>(), 0, res);
-    launch_ovl_size(si, 1, dGst, dOvl, dCap);
-    launch_ovl_clear(si, 1, dOvl, bmp, R.cap[0]);
-    launch_ovl_mark(si, R.m_gref, dG, dOvl, dGst, sl.ref_raw.as<float4>(), 0, res, bmp, false);
-    launch_ovl_popcount(si, 1, dOvl, dGst, 0, bmp);
+    if (int rc = ovl_window_ref_side(ctx->err, si, D, w.src >= 0 ? dG->ref_origin : nullptr, sl.ref_raw.as<float4>()))
+      return rc;
   }
   HIPC(hipStreamWaitEvent(si, sl.ev_rd, 0));  // (the slot's previous window is done: its upload waited)
   // the loop's selection histogram, counts and hand-off words: before the wait on the trees
   launch_zero_words3(si, sl.sel_hist.as<uint32_t>(), np * kHistBins, sl.sel_cnt.as<uint32_t>(), np,
                      sl.isync.as<uint32_t>(), icp_sync_words(np));
-  if (doOvl && !R.debug) {
-    if (R.sparse)
-      HIPC(launch_ovl_keys_intersect(si, R.kr, R.kg, R.per_pair, dState));
-    else
-      launch_ovl_intersect(si, (int)np, dDesc, dOvl + 1, dOvl, dState, bmp);
-    launch_ovl_finish(si, (int)np, dDesc, dState, dGst, 1);
-  }
+  if (doOvl && !R.debug)
+    if (int rc = ovl_window_counts(ctx->err, si, D)) return rc;
   HIPC(hipStreamWaitEvent(si, sl.ev_s3, 0));
   launch_pairs_from_refs(si, (int)np, dDesc, dRdesc);
   launch_pairs_degenerate_part(si, (int)np, dDesc, dState, dRst, 2);
@@ -1711,3 +1789,281 @@ int aicp_hip_last_sequence_timing(const aicp_hip_ctx* ctx, aicp_sequence_timing*
 }
 
 }  // extern "C"
+
+namespace aicp {
+namespace rt {
+
+// aicp_hip_test_overlap's paths 3 and 4: each overlap group of the batch as one stream window, on
+// buffers of this call, through the plan and the device steps the stream itself calls.
+int ovl_window_test(aicp_hip_ctx* ctx, const aicp_hip_batch* B, const aicp_pair* pairs, double res, int path,
+                    int filter, int wide, const uint64_t* caps, int rigid, aicp_test_overlap_out* out) {
+  const size_t P = B->P, G = B->gdesc.size();
+  hipStream_t s = ctx->stream;
+  WorkerPool pool{0};
+  constexpr size_t kGuard = 64;  // guard words of 8 bytes
+  constexpr uint32_t kFill32 = 0xA5A5A5A5u;
+  constexpr uint64_t kFill64 = 0xA5A5A5A5A5A5A5A5ull;
+  const bool sparse = path == 4;
+  struct Local {  // freed on every return
+    std::vector<DevBuf> bufs;
+    hipStream_t s;
+    DevBuf& get() {
+      bufs.reserve(64);
+      bufs.emplace_back();
+      return bufs.back();
+    }
+    ~Local() {
+      (void)hipStreamSynchronize(s);
+      for (DevBuf& b : bufs) release(b);
+    }
+  };
+  out->path = path;
+  out->filter = sparse ? 0 : (filter > 0);
+  out->wide = sparse ? 0 : (wide > 0);
+  out->n_groups = (int32_t)G;
+  out->arena_bytes = out->n_points = out->n_words = out->dirty = 0;
+  for (size_t p = 0; p < P; ++p) out->pair_group[p] = B->desc[p].ogroup;
+  uint64_t ref_pts_before = 0, total_ref_pts = 0, total_read_pts = 0;
+  for (size_t g = 0; g < G; ++g) total_ref_pts += B->gdesc[g].n_ref;
+  std::vector<uint64_t> read_first(P + 1, 0);
+  for (size_t p = 0; p < P; ++p) read_first[p + 1] = read_first[p] + pairs[p].n_read;
+  total_read_pts = read_first[P];
+  if (sparse && total_ref_pts + total_read_pts > out->points_cap) FAIL(AICP_ERR_INVALID, "points_cap");
+  if (sparse) out->n_points = total_ref_pts + total_read_pts;
+  for (size_t g = 0; g < G; ++g) {
+    Local loc{{}, s};
+    std::vector<size_t> idx;
+    for (size_t p = 0; p < P; ++p)
+      if ((size_t)B->desc[p].ogroup == g) idx.push_back(p);
+    const size_t np = idx.size();
+    const aicp_pair& p0 = pairs[idx[0]];
+    aicp_cloud src{p0.ref, p0.n_ref, p0.ref_stride, {p0.ref_origin[0], p0.ref_origin[1], p0.ref_origin[2]}};
+    const uint32_t n_ref = (uint32_t)src.n;
+    std::vector<aicp_cloud> reads(np);
+    std::vector<uint32_t> loff(np);
+    uint64_t nread = 0;
+    for (size_t i = 0; i < np; ++i) {
+      const aicp_pair& q = pairs[idx[i]];
+      reads[i] = aicp_cloud{q.read, q.n_read, q.read_stride, {q.read_origin[0], q.read_origin[1], q.read_origin[2]}};
+      loff[i] = (uint32_t)nread;
+      nread += q.n_read;
+    }
+    // pack (+ AABBs), descriptors, block maps: as the stream's window upload
+    std::vector<float> h_read(4 * nread), h_ref(4 * (size_t)n_ref);
+    std::vector<PackSeg> segs;
+    for (size_t i = 0; i < np; ++i) segs.push_back(PackSeg{reads[i].pts, reads[i].n, reads[i].stride, h_read.data() + 4 * (size_t)loff[i]});
+    segs.push_back(PackSeg{src.pts, src.n, src.stride, h_ref.data()});
+    std::vector<Box> boxes;
+    pack_clouds(pool, segs, boxes);
+    Maps mr, mg;
+    std::vector<PairDesc> hd(np + 1, PairDesc{});  // the readings, then the group
+    for (size_t i = 0; i < np; ++i) {
+      PairDesc& d = hd[i];
+      d.n_ref = n_ref;
+      d.read_off = loff[i];
+      d.n_read = (uint32_t)reads[i].n;
+      ident4(d.Tin);
+      d.ratio = 0.7f;
+      for (int k = 0; k < 3; ++k) {
+        d.read_origin[k] = reads[i].origin[k];
+        d.ref_origin[k] = src.origin[k];
+      }
+      mr.add((int)i, d.n_read, kNNBlock);
+    }
+    hd[np].n_ref = n_ref;
+    ident4(hd[np].Tin);
+    for (int k = 0; k < 3; ++k) hd[np].ref_origin[k] = src.origin[k];
+    mg.add(0, n_ref, kNNBlock);
+    OvlWinPlan W;
+    uint64_t cap_r = 0, cap_g = 0;
+    size_t tmp_rb = 0, tmp_gb = 0;
+    if (!sparse) {
+      ovl_window_slots(W, boxes[np], src.origin, rigid != 0, boxes.data(), reads.data(), np, res, false);
+      if (caps) {
+        W.bm = W.cap_max = 0;
+        for (size_t i = 0; i <= np; ++i) {
+          W.cap[i] = i == 0 ? caps[g] : caps[G + idx[i - 1]];
+          W.od[i].off = W.bm;
+          W.bm += (W.cap[i] + 127) & ~uint64_t(127);  // (the maps stay 128-byte aligned)
+          W.cap_max = std::max(W.cap_max, W.cap[i]);
+        }
+      }
+      if (W.bm > kSeqMapBudget)
+        FAIL(AICP_ERR_UNSUPPORTED, "the window's voxel maps exceed the stream's budget: it runs on key lists");
+      out->cloud_bound[g] = W.cap[0];
+      for (size_t i = 0; i < np; ++i) out->cloud_bound[G + idx[i]] = W.cap[1 + i];
+    } else {
+      ovl_window_keys(W, pool, src, src.origin, rigid != 0, reads.data(), loff.data(), np, res, false);
+      if (caps) {
+        W.cap_g = caps[g];
+        W.cap_r = 0;
+        for (size_t i = 0; i < np; ++i) W.cap_r += (W.kb_read[i] = caps[G + idx[i]]);
+      }
+      cap_r = W.cap_r;
+      cap_g = W.cap_g;
+      out->cloud_bound[g] = cap_g;
+      for (size_t i = 0; i < np; ++i) out->cloud_bound[G + idx[i]] = W.kb_read[i];
+      tmp_rb = ovl_keys_temp_bytes(nread, cap_r, (int)np);
+      tmp_gb = ovl_keys_temp_bytes(n_ref, cap_g, 1);
+      size_t free_b = 0, total_b = 0;
+      HIPC(hipMemGetInfo(&free_b, &total_b));
+      if (16 * (cap_r + cap_g) + tmp_rb + tmp_gb > free_b / 2)
+        FAIL(AICP_ERR_UNSUPPORTED, "sparse overlap: " + std::to_string(cap_r + cap_g) + " ray keys do not fit");
+    }
+    // device: points, descriptors, states, block maps
+    DevBuf &d_read = loc.get(), &d_ref = loc.get(), &d_desc = loc.get(), &d_state = loc.get(), &d_maps = loc.get();
+    HIPC(ensure(d_read, nread * 16));
+    HIPC(ensure(d_ref, (size_t)n_ref * 16));
+    HIPC(ensure(d_desc, (np + 1) * sizeof(PairDesc)));
+    HIPC(ensure(d_state, (np + 1) * sizeof(PairState)));
+    const size_t nr = mr.pair.size(), nf = mg.pair.size();
+    std::vector<uint32_t> hm(2 * (nr + nf));
+    std::memcpy(hm.data(), mr.pair.data(), nr * 4);
+    std::memcpy(hm.data() + nr, mr.start.data(), nr * 4);
+    std::memcpy(hm.data() + 2 * nr, mg.pair.data(), nf * 4);
+    std::memcpy(hm.data() + 2 * nr + nf, mg.start.data(), nf * 4);
+    HIPC(ensure(d_maps, hm.size() * 4));
+    HIPC(hipMemcpy(d_read.p, h_read.data(), nread * 16, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_ref.p, h_ref.data(), (size_t)n_ref * 16, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_desc.p, hd.data(), (np + 1) * sizeof(PairDesc), hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(d_maps.p, hm.data(), hm.size() * 4, hipMemcpyHostToDevice));
+    HIPC(hipMemsetAsync(d_state.p, 0, (np + 1) * sizeof(PairState), s));
+    PairDesc* dDesc = d_desc.as<PairDesc>();
+    PairState* dState = d_state.as<PairState>();
+    launch_init_state(s, (int)np + 1, dDesc, dState);
+    OvlWinDev D;
+    D.sparse = sparse;
+    D.np = np;
+    D.res = res;
+    D.dDesc = dDesc;
+    D.dState = dState;
+    D.dG = dDesc + np;
+    D.dGst = dState + np;
+    D.m_read = BlockMap{d_maps.as<int32_t>(), d_maps.as<uint32_t>() + nr, (uint32_t)nr};
+    D.m_gref = BlockMap{d_maps.as<int32_t>() + 2 * nr, d_maps.as<uint32_t>() + 2 * nr + nf, (uint32_t)nf};
+    D.filter = filter > 0;
+    D.wide = wide > 0;
+    OvlKeySide kr{}, kg{};
+    DevBuf &d_arena = loc.get(), &d_ovl = loc.get(), &d_cap = loc.get(), &d_par = loc.get(), &d_cnt = loc.get(),
+           &d_off = loc.get(), &d_kr = loc.get(), &d_kg = loc.get(), &d_tr = loc.get(), &d_tg = loc.get(),
+           &d_pc = loc.get();
+    const size_t kr_words = 2 * cap_r + 3 * kGuard, kg_words = 2 * cap_g + 3 * kGuard;
+    if (!sparse) {
+      HIPC(ensure(d_arena, W.bm + 2 * kGuard * 8));
+      HIPC(ensure(d_ovl, (np + 1) * sizeof(OvlDesc)));
+      HIPC(ensure(d_cap, (np + 1) * 8));
+      HIPC(hipMemsetD32Async((hipDeviceptr_t)d_arena.p, (int)kFill32, (W.bm + 2 * kGuard * 8) / 4, s));
+      HIPC(hipMemcpy(d_ovl.p, W.od.data(), (np + 1) * sizeof(OvlDesc), hipMemcpyHostToDevice));
+      HIPC(hipMemcpy(d_cap.p, W.cap.data(), (np + 1) * 8, hipMemcpyHostToDevice));
+      D.dOvl = d_ovl.as<OvlDesc>();
+      D.dCap = d_cap.as<uint64_t>();
+      D.bmp = d_arena.as<uint8_t>() + kGuard * 8;
+      D.cap_max = W.cap_max;
+      D.cap0 = W.cap[0];
+    } else {
+      const size_t ncl = W.scl.size(), nb = W.sbc.size();
+      std::vector<char> par(ncl * sizeof(OvlCloud) + 8 * nb);
+      std::memcpy(par.data(), W.scl.data(), ncl * sizeof(OvlCloud));
+      std::memcpy(par.data() + ncl * sizeof(OvlCloud), W.sbc.data(), nb * 4);
+      std::memcpy(par.data() + ncl * sizeof(OvlCloud) + nb * 4, W.sbs.data(), nb * 4);
+      HIPC(ensure(d_par, par.size()));
+      HIPC(hipMemcpy(d_par.p, par.data(), par.size(), hipMemcpyHostToDevice));
+      HIPC(ensure(d_cnt, (nread + n_ref) * 4));
+      HIPC(ensure(d_off, (nread + n_ref) * 8));
+      HIPC(ensure(d_kr, kr_words * 8));
+      HIPC(ensure(d_kg, kg_words * 8));
+      HIPC(ensure(d_tr, tmp_rb));
+      HIPC(ensure(d_tg, tmp_gb));
+      HIPC(ensure(d_pc, (2 * np + 1) * 8));
+      HIPC(hipMemsetD32Async((hipDeviceptr_t)d_kr.p, (int)kFill32, kr_words * 2, s));
+      HIPC(hipMemsetD32Async((hipDeviceptr_t)d_kg.p, (int)kFill32, kg_words * 2, s));
+      HIPC(hipMemsetAsync(d_cnt.p, 0, (nread + n_ref) * 4, s));
+      HIPC(hipMemsetAsync(d_off.p, 0, (nread + n_ref) * 8, s));
+      char* Dp = d_par.as<char>();
+      ovl_window_sides(W, np, nread, n_ref, reinterpret_cast<OvlCloud*>(Dp),
+                       reinterpret_cast<const uint32_t*>(Dp + ncl * sizeof(OvlCloud)), d_cnt.as<uint32_t>(),
+                       d_off.as<uint64_t>(), d_kr.as<uint64_t>() + kGuard, d_kg.as<uint64_t>() + kGuard, d_tr.p, tmp_rb,
+                       d_tg.p, tmp_gb, d_pc.as<unsigned long long>(), kr, kg);
+      kr.keys1 = kr.keys0 + cap_r + kGuard;  // (guard words between the emitted and the sorted array too)
+      kg.keys1 = kg.keys0 + cap_g + kGuard;
+      D.kr = &kr;
+      D.kg = &kg;
+      D.per_pair = d_pc.as<unsigned long long>() + np + 1;
+    }
+    int rc = ovl_window_read_side(ctx->err, s, D, d_read.as<float4>());
+    if (!rc) rc = ovl_window_ref_side(ctx->err, s, D, nullptr, d_ref.as<float4>());
+    if (!rc) rc = ovl_window_counts(ctx->err, s, D);
+    if (rc) return rc;
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(s));
+    // results
+    std::vector<PairState> hs(np + 1);
+    HIPC(hipMemcpy(hs.data(), dState, (np + 1) * sizeof(PairState), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i <= np; ++i) {
+      const size_t c = i == np ? g : G + idx[i];
+      out->cloud_keys[c] = hs[i].ovl_counts[i == np ? 0 : 1];
+      out->cloud_err[c] = hs[i].ovl_err;
+      for (int k = 0; k < 6; ++k) out->cloud_bbox[6 * c + k] = hs[i].ovl_bbox[k];
+      if (i == np) continue;
+      const size_t p = idx[i];
+      for (int k = 0; k < 3; ++k) out->pair_counts[3 * p + k] = hs[i].ovl_counts[k];
+      out->pair_percent[p] = hs[i].overlap;
+      out->pair_ratio[p] = hs[i].ratio;
+      out->pair_err[p] = hs[i].ovl_err;
+    }
+    if (!sparse) {
+      std::vector<OvlDesc> od(np + 1);
+      HIPC(hipMemcpy(od.data(), d_ovl.p, (np + 1) * sizeof(OvlDesc), hipMemcpyDeviceToHost));
+      for (size_t i = 0; i <= np; ++i) {
+        const size_t c = i == 0 ? g : G + idx[i - 1];
+        for (int k = 0; k < 3; ++k) {
+          out->desc_min[3 * c + k] = od[i].min[k];
+          out->desc_dim[3 * c + k] = od[i].dim[k];
+        }
+        out->desc_off[c] = out->arena_bytes + od[i].off;
+        out->desc_bytes[c] = od[i].bytes;
+      }
+      std::vector<uint8_t> back(W.bm + 2 * kGuard * 8);
+      HIPC(hipMemcpy(back.data(), d_arena.p, back.size(), hipMemcpyDeviceToHost));
+      const uint64_t* gw = reinterpret_cast<const uint64_t*>(back.data());
+      for (size_t k = 0; k < kGuard; ++k)
+        out->dirty += (gw[k] != kFill64) + (gw[(kGuard * 8 + W.bm) / 8 + k] != kFill64);
+      if (out->arena_bytes < out->arena_cap)
+        std::memcpy(out->arena + out->arena_bytes, back.data() + kGuard * 8,
+                    std::min<uint64_t>(W.bm, out->arena_cap - out->arena_bytes));
+      out->arena_bytes += W.bm;
+    } else {
+      std::vector<uint32_t> cnt(nread + n_ref);
+      std::vector<uint64_t> off(nread + n_ref);
+      HIPC(hipMemcpy(cnt.data(), d_cnt.p, cnt.size() * 4, hipMemcpyDeviceToHost));
+      HIPC(hipMemcpy(off.data(), d_off.p, off.size() * 8, hipMemcpyDeviceToHost));
+      std::memcpy(out->key_counts + ref_pts_before, cnt.data() + nread, (size_t)n_ref * 4);
+      std::memcpy(out->key_offsets + ref_pts_before, off.data() + nread, (size_t)n_ref * 8);
+      for (size_t i = 0; i < np; ++i) {
+        const uint64_t dst = total_ref_pts + read_first[idx[i]];
+        std::memcpy(out->key_counts + dst, cnt.data() + loff[i], (size_t)reads[i].n * 4);
+        std::memcpy(out->key_offsets + dst, off.data() + loff[i], (size_t)reads[i].n * 8);
+      }
+      for (int side = 0; side < 2; ++side) {
+        const uint64_t cap = side ? cap_g : cap_r;
+        const size_t words = side ? kg_words : kr_words;
+        std::vector<uint64_t> back(words);
+        HIPC(hipMemcpy(back.data(), side ? d_kg.p : d_kr.p, words * 8, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < kGuard; ++k)
+          out->dirty += (back[k] != kFill64) + (back[kGuard + cap + k] != kFill64) +
+                        (back[2 * kGuard + 2 * cap + k] != kFill64);
+        out->list_off[2 * g + side] = out->n_words;
+        out->list_cap[2 * g + side] = cap;
+        if (out->n_words < out->words_cap)
+          std::memcpy(out->words + out->n_words, back.data() + 2 * kGuard + cap,
+                      8 * std::min<uint64_t>(cap, out->words_cap - out->n_words));
+        out->n_words += cap;
+      }
+    }
+    ref_pts_before += n_ref;
+  }
+  return AICP_OK;
+}
+
+}  // namespace rt
+}  // namespace aicp

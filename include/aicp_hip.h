@@ -1237,6 +1237,96 @@ int aicp_hip_test_normals(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* coun
                           int32_t* out_degenerate /* n_refs */, uint64_t* out_touched /* 2 */,
                           float* out_bnrm /* 4 * total */, int32_t* out_matcher_id /* total */, int32_t* out_engine,
                           uint64_t* out_dirty);
+/* Test surface: the octree overlap of a batch, set by set. The n_refs reference clouds (ref_pts, 3
+ * floats per point, ref_counts[r] points each, one after another) and the n_pairs readings
+ * (read_pts, n_read[p] points each) go through the batch's own overlap, as aicp_hip_align_batch
+ * with AICP_RUN_OVERLAP runs it: pair p reads reference pair_ref[p] from ref_origins[3 p ..] and
+ * its reading from read_origins[3 p ..]; pairs with the same reference and the same reference
+ * origin form one overlap group, in order of first appearance. Clouds are numbered groups first,
+ * then readings (n_groups + n_pairs of them, at most 2 n_pairs).
+ * path: 0 the batch's own rule, 1 the batch's dense voxel maps, 2 the batch's sorted keys, 3 the
+ * stream's voxel maps sized on the device, 4 the stream's capped key lists. A batch whose maps do
+ * not fit (a map above 2^34 voxels, or all of them above the arena's budget) runs on sorted keys
+ * under 0 and 1 as well; out->path says which ran (1 to 4). Under 3 and 4 every overlap group runs
+ * as one window of the frame-to-reference stream (its reference and the readings paired with it),
+ * through the stream's own host plan (ovl_window_slots / _keys / _sides) and device steps
+ * (ovl_window_read_side / _ref_side / _counts), one window after the other on one stream.
+ * filter / wide: -1 the path's rules (batch: the marks' LDS cache from 9 clouds on, the wide count
+ * grids for one pair in one group; stream: neither), 0 or 1 to override them for this call;
+ * out->filter / out->wide say what was launched (0 on keys). The trimmed ratio is set from the
+ * overlap as a registration sets it.
+ * cap_mode 0: the stream's own capacities (map_cap of the clouds' extents; key_bound of their
+ * rays, the reference's in the form `rigid` selects: 0 as given, 1 for any rigid motion). 1: caps[]
+ * gives them per cloud, groups then readings (path 3: bytes of the map slot; path 4: words; the
+ * readings of a window share one list of the sum of their capacities). A window whose map slots
+ * exceed the stream's 1 GiB budget returns AICP_ERR_UNSUPPORTED under 3 (the stream runs it on
+ * key lists).
+ * Outputs (caller's arrays in aicp_test_overlap_out, all required):
+ *  pair_group[p]; per cloud: cloud_keys (|S|), cloud_err (ovl_err), cloud_bbox (6: key box of its
+ *  valid points and origin, min then max; under 4 of the origin alone, the key lists need no box); per pair: pair_counts (3: |A|, |B|, |A ∩ B|),
+ *  pair_percent, pair_ratio, pair_err.
+ *  Dense maps: desc_min, desc_dim (3 per cloud), desc_off, desc_bytes, and the first
+ *  min(arena_cap, arena_bytes) bytes of the map arena in `arena`. Under 3 the windows' arenas
+ *  follow one another (desc_off counts from the first), each filled with bytes of 0xA5 before its
+ *  window runs: what no kernel wrote (a slot's room beyond its map, a refused slot) still holds them.
+ *  Sorted keys: per point (the groups' reference points, then the readings': n_points of them, at
+ *  most points_cap) key_counts and the exclusive key_offsets; the sorted words
+ *  cloud << 48 | k0 << 32 | k1 << 16 | k2 in `words` (the first min(words_cap, n_words)).
+ *  Under 4: per window g two lists, [2 g] its readings' (tagged 0 .. n - 1 in pair order, pad words
+ *  n << 48) and [2 g + 1] its reference's (tag 0, pad 1 << 48): list_off (first word in `words`) and
+ *  list_cap (all cap words are returned, pads included); key_offsets count within a list;
+ *  cloud_bound: the capacity each cloud contributed (the host's bound, or caps[]); under 3 the
+ *  bytes of its map slot.
+ *  dirty: under 3 and 4 the arena and the key lists are buffers of this call with 64 guard words of
+ *  8 bytes on both sides (under 4 around each of the emitted and the sorted array); the guard
+ *  words that changed (0 expected).
+ * An ovl_err of a cloud is reported in the outputs, not as a return code; a reading's state is its
+ * pair's, so its cloud_err also carries its group's error (k_ovl_finish folds it in). Invalidates the context's
+ * reference cache.
+ * AICP_ERR_INVALID, before any device work: a null pointer (out's arrays included), no reference or
+ * pair or more than 4096, a count of 0, a pair_ref >= n_refs, resolution <= 0 or NaN, path outside
+ * [0, 4], filter, wide outside {-1, 0, 1}, cap_mode or rigid outside {0, 1}, cap_mode 1 without
+ * caps or under a batch path, fewer than n_points points_cap. */
+typedef struct {
+  int32_t path, filter, wide; /* what ran */
+  int32_t n_groups;
+  int32_t* pair_group;        /* n_pairs */
+  uint64_t* cloud_keys;       /* 2 n_pairs */
+  int32_t* cloud_err;         /* 2 n_pairs */
+  int32_t* cloud_bbox;        /* 6 * 2 n_pairs */
+  uint64_t* pair_counts;      /* 3 n_pairs */
+  float* pair_percent;        /* n_pairs */
+  float* pair_ratio;          /* n_pairs */
+  int32_t* pair_err;          /* n_pairs */
+  int32_t* desc_min;          /* 3 * 2 n_pairs */
+  int32_t* desc_dim;          /* 3 * 2 n_pairs */
+  uint64_t* desc_off;         /* 2 n_pairs */
+  uint64_t* desc_bytes;       /* 2 n_pairs */
+  uint8_t* arena;
+  uint64_t arena_cap, arena_bytes;
+  uint32_t* key_counts;       /* points_cap */
+  uint64_t* key_offsets;      /* points_cap */
+  uint64_t points_cap, n_points;
+  uint64_t* words;
+  uint64_t words_cap, n_words;
+  uint64_t* cloud_bound;      /* 2 n_pairs */
+  uint64_t* list_off;         /* 2 n_pairs */
+  uint64_t* list_cap;         /* 2 n_pairs */
+  uint64_t dirty;
+} aicp_test_overlap_out;
+int aicp_hip_test_overlap(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* ref_counts, const float* ref_pts,
+                          size_t n_pairs, const uint32_t* pair_ref, const uint32_t* n_read, const float* read_pts,
+                          const double* ref_origins /* 3 n_pairs */, const double* read_origins /* 3 n_pairs */,
+                          double resolution, int32_t path, int32_t filter, int32_t wide, int32_t cap_mode,
+                          const uint64_t* caps /* nullable: n_groups + n_pairs */, int32_t rigid,
+                          aicp_test_overlap_out* out);
+/* Host only, no device call: the stream's upper bound of the words its key lists hold for a cloud
+ * of n points (3 floats each) seen from origin: every key of computeRayKeys(origin, p) and p's own
+ * key, duplicates included, each point's share capped at *out_point_cap (3 * 65536 + 8). rigid 0:
+ * for the cloud as given; 1: for any rigid motion of cloud and origin together. Returns
+ * AICP_ERR_INVALID for a null pointer, n == 0, resolution <= 0 or NaN, rigid outside {0, 1}. */
+int aicp_hip_test_key_bound(const float* pts, size_t n, const double origin[3], double resolution, int32_t rigid,
+                            uint64_t* out_bound, uint64_t* out_point_cap);
 /* Test surface: the raw streams' ingest alone. rows: n rows of `stride` bytes (>= 12, a multiple of
  * 4), xyz first, uploaded as the raw streams upload them (at most 16 bytes: verbatim; wider: packed
  * on the host), then k_stream_ingest: out4[4 i ..] = (x, y, z, 1), moved by T (nullable, column-major

@@ -311,3 +311,62 @@ def test_isometry_from_matrix4f_matches_oracle(oracle, seed):
     o = rng.uniform(-20, 20, 3)
     got = (R.isometry_from_matrix4f(T) @ np.r_[o, 1.0])[:3]
     np.testing.assert_allclose(got, oracle.corrected_origin(T, o), rtol=0, atol=1e-12)
+
+
+def test_overlap_test_entry_refuses_bad_arguments(L):
+    """Each AICP_ERR_INVALID condition of aicp_hip_test_overlap is met before any device work: the
+    context here is a block of zero bytes that no valid call could use, and every bad call comes
+    back without touching it. The good call they are one change away from runs in
+    test_overlap_kernels.py. aicp_hip_test_key_bound (host only) likewise, and its good call."""
+    n = 4
+    ref, rd = np.ones((5, 3), np.float32), np.ones((6, 3), np.float32)
+    arr = dict(pair_group=np.zeros(n, np.int32), cloud_keys=np.zeros(n, np.uint64), cloud_err=np.zeros(n, np.int32),
+               cloud_bbox=np.zeros(6 * n, np.int32), pair_counts=np.zeros(3 * n, np.uint64),
+               pair_percent=np.zeros(n, np.float32), pair_ratio=np.zeros(n, np.float32), pair_err=np.zeros(n, np.int32),
+               desc_min=np.zeros(3 * n, np.int32), desc_dim=np.zeros(3 * n, np.int32), desc_off=np.zeros(n, np.uint64),
+               desc_bytes=np.zeros(n, np.uint64), arena=np.zeros(64, np.uint8), key_counts=np.zeros(32, np.uint32),
+               key_offsets=np.zeros(32, np.uint64), words=np.zeros(64, np.uint64), cloud_bound=np.zeros(n, np.uint64),
+               list_off=np.zeros(n, np.uint64), list_cap=np.zeros(n, np.uint64))
+    fake_ctx = C.create_string_buffer(1 << 16)
+    base = dict(ctx=C.cast(fake_ctx, C.c_void_p), n_refs=1, counts=np.array([5], np.uint32), ref=ref, n_pairs=2,
+                pair_ref=np.array([0, 0], np.uint32), n_read=np.array([4, 2], np.uint32), rd=rd,
+                ro=np.zeros(6), do=np.zeros(6), res=0.2, path=0, filter=-1, wide=-1, cap_mode=0, caps=None, rigid=0,
+                out=True, null_field=None, points_cap=32)
+    u32p, dp, up = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+
+    def call(**over):
+        a = dict(base, **over)
+        o = L.TestOverlapOut()
+        for name, ctype in L.TestOverlapOut._fields_:
+            if name in arr and name != a["null_field"]:
+                setattr(o, name, arr[name].ctypes.data_as(ctype))
+        o.arena_cap, o.points_cap, o.words_cap = 64, a["points_cap"], 64
+        ptr = lambda k, t: None if a[k] is None else a[k].ctypes.data_as(t)
+        return L.lib.aicp_hip_test_overlap(
+            a["ctx"], a["n_refs"], ptr("counts", u32p), None if a["ref"] is None else L._fptr(a["ref"]), a["n_pairs"],
+            ptr("pair_ref", u32p), ptr("n_read", u32p), None if a["rd"] is None else L._fptr(a["rd"]), ptr("ro", dp),
+            ptr("do", dp), a["res"], a["path"], a["filter"], a["wide"], a["cap_mode"], ptr("caps", up), a["rigid"],
+            C.byref(o) if a["out"] else None)
+
+    bad = [dict(ctx=None), dict(out=False)] + [{k: None} for k in ("counts", "ref", "pair_ref", "n_read", "rd", "ro", "do")]
+    bad += [dict(null_field=k) for k in arr]
+    bad += [dict(n_refs=0), dict(n_refs=4097), dict(n_pairs=0), dict(n_pairs=4097),
+            dict(counts=np.array([0], np.uint32)), dict(n_read=np.array([4, 0], np.uint32)),
+            dict(pair_ref=np.array([0, 1], np.uint32)), dict(res=0.0), dict(res=-0.2), dict(res=float("nan")),
+            dict(path=-1), dict(path=5), dict(filter=-2), dict(filter=2), dict(wide=-2), dict(wide=2),
+            dict(cap_mode=2), dict(cap_mode=-1), dict(cap_mode=1, path=4), dict(rigid=2), dict(rigid=-1),
+            dict(cap_mode=1, caps=np.ones(3, np.uint64), path=2), dict(points_cap=10)]  # (5 + 6 points)
+    for b in bad:
+        assert call(**b) == L.AICP_ERR_INVALID, list(b.items())
+    assert not any(fake_ctx.raw)  # nothing was written into the stand-in context
+
+    bound, cap = C.c_uint64(), C.c_uint64()
+    org = np.zeros(3)
+    kb = lambda pts, n, o, res, rigid, b=bound, c=cap: L.lib.aicp_hip_test_key_bound(
+        None if pts is None else L._fptr(pts), n, None if o is None else o.ctypes.data_as(dp), res, rigid,
+        None if b is None else C.byref(b), None if c is None else C.byref(c))
+    assert kb(ref, 5, org, 0.2, 0) == L.AICP_OK and cap.value == 3 * 65536 + 8 and bound.value >= 5
+    for args in ((None, 5, org, 0.2, 0), (ref, 0, org, 0.2, 0), (ref, 5, None, 0.2, 0), (ref, 5, org, 0.0, 0),
+                 (ref, 5, org, float("nan"), 0), (ref, 5, org, 0.2, 2), (ref, 5, org, 0.2, -1)):
+        assert kb(*args) == L.AICP_ERR_INVALID, args
+    assert kb(ref, 5, org, 0.2, 0, b=None) == L.AICP_ERR_INVALID and kb(ref, 5, org, 0.2, 0, c=None) == L.AICP_ERR_INVALID

@@ -13,6 +13,7 @@ import pytest
 from scipy.spatial import cKDTree
 
 from aicp_mapping_amd import synthetic as sy
+from overlap_reference import ray_keys as py_ray_keys
 
 
 def rand_cloud(n, seed, scale=10.0):
@@ -196,51 +197,6 @@ def test_solve6_planar_structure(oracle):
 
 # ---------------------------------------------------------------- octomap ray keys ---------
 KMAX = 32768
-
-
-def py_ray_keys(o, e, res):
-    """Independent pure-Python restatement of computeRayKeys (float point3d, double DDA)."""
-    f32 = np.float32
-    o = [f32(v) for v in o]
-    e = [f32(v) for v in e]
-    rf = 1.0 / res
-
-    def key(c):
-        return int(math.floor(rf * float(c))) + KMAX
-
-    ko = [key(c) for c in o]
-    ke = [key(c) for c in e]
-    if ko == ke:
-        return []
-    out = [tuple(ko)]
-    d = [f32(e[i] - o[i]) for i in range(3)]
-    nsq = f32(f32(f32(d[0] * d[0]) + f32(d[1] * d[1])) + f32(d[2] * d[2]))
-    length = f32(math.sqrt(float(nsq)))
-    d = [f32(v / length) for v in d]
-    step, tmax, tdelta = [0] * 3, [0.0] * 3, [0.0] * 3
-    cur = list(ko)
-    for i in range(3):
-        step[i] = 1 if d[i] > 0 else (-1 if d[i] < 0 else 0)
-        if step[i]:
-            vb = (float(cur[i] - KMAX) + 0.5) * res
-            vb += float(f32(step[i] * res * 0.5))
-            tmax[i] = (vb - float(o[i])) / float(d[i])
-            tdelta[i] = res / float(abs(d[i]))
-        else:
-            tmax[i] = tdelta[i] = 1.7976931348623157e308
-    while True:
-        if tmax[0] < tmax[1]:
-            dim = 0 if tmax[0] < tmax[2] else 2
-        else:
-            dim = 1 if tmax[1] < tmax[2] else 2
-        cur[dim] += step[dim]
-        tmax[dim] += tdelta[dim]
-        if cur == ke:
-            break
-        if min(tmax) > float(length):
-            break
-        out.append(tuple(cur))
-    return out
 
 
 def unpack(k):
