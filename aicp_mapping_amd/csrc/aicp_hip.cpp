@@ -14,7 +14,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <atomic>
 #include <deque>
 #include <chrono>
@@ -642,6 +641,22 @@ int overlap_maps(aicp_hip_ctx* ctx, aicp_hip_batch* B, size_t P, size_t G, PairD
   return AICP_OK;
 }
 
+// Treelet records of the R matcher trees enqueued on s (Trav2C; nothing where the batch has none),
+// then the control block again: the treelet check reports into its error word, checked after the batch
+int matcher_treelets(aicp_hip_ctx* ctx, hipStream_t s, size_t R, uint64_t total_ref, PairDesc* dRdesc, int bucket,
+                     std::string& err) {
+  if (!ctx->tl_total) return AICP_OK;
+  const uint32_t cap = (uint32_t)(2 * total_ref + 2);  // node records allotted
+  TCHK(ensure(ctx->tl, ctx->tl_total * 16));
+  TCHK(ensure(ctx->ptl, ctx->tl_total * 8));  // treelet links {parent, grandparent}
+  TCHK(ensure(ctx->tl_rank, ((size_t)cap + 1) * 4));
+  TreeBufs& T = ctx->tb[1];
+  TCHK(launch_treelets(s, (int)R, cap, dRdesc, ctx->nodes.as<uint4>(), bucket, ctx->tl_rank.as<uint32_t>(),
+                       ctx->tl.as<uint4>(), ctx->ptl.as<uint2>(), T.tw));
+  TCHK(hipMemcpyAsync(T.pin_ctl.p, T.tw.ctl, sizeof(TreeCtl), hipMemcpyDeviceToHost, s));
+  return AICP_OK;
+}
+
 // the centred reference's matcher tree and the pairs' frames, on stream3 (worker thread)
 int matcher_trees(aicp_hip_ctx* ctx, aicp_hip_batch* B, int bucket, PairDesc* dDesc, PairDesc* dRdesc,
                   int plan, std::string& err, hipEvent_t after = nullptr) {
@@ -657,18 +672,8 @@ int matcher_trees(aicp_hip_ctx* ctx, aicp_hip_batch* B, int bucket, PairDesc* dD
   if (rc) return rc;
   rc = device_trees_end(ctx->tb[1], err, s3, R, B->total_ref, dRdesc, bucket, ctx->bpts, ctx->nodes, plan);
   if (rc) return rc;
-  // treelet records of the matcher trees (Trav2C), then the control block again: the treelet check
-  // reports into its error word, checked after the batch
-  if (ctx->tl_total) {
-    const uint32_t cap = (uint32_t)(2 * B->total_ref + 2);  // node records allotted
-    TCHK(ensure(ctx->tl, ctx->tl_total * 16));
-    TCHK(ensure(ctx->ptl, ctx->tl_total * 8));  // treelet links {parent, grandparent}
-    TCHK(ensure(ctx->tl_rank, ((size_t)cap + 1) * 4));
-    TreeBufs& T = ctx->tb[1];
-    TCHK(launch_treelets(s3, (int)R, cap, dRdesc, ctx->nodes.as<uint4>(), bucket, ctx->tl_rank.as<uint32_t>(),
-                         ctx->tl.as<uint4>(), ctx->ptl.as<uint2>(), T.tw));
-    TCHK(hipMemcpyAsync(T.pin_ctl.p, T.tw.ctl, sizeof(TreeCtl), hipMemcpyDeviceToHost, s3));
-  }
+  rc = matcher_treelets(ctx, s3, R, B->total_ref, dRdesc, bucket, err);
+  if (rc) return rc;
   TCHK(hipStreamWaitEvent(s3, ctx->ev[7], 0));  // the pairs' descriptors are on the device
   launch_pairs_from_refs(s3, (int)B->P, dDesc, dRdesc);
   TCHK(hipEventRecord(ctx->ev[3], s3));
@@ -1207,8 +1212,6 @@ int aicp_hip_get_options(const aicp_hip_ctx* ctx, aicp_hip_options* out) {
   return AICP_OK;
 }
 
-int aicp_hip_test_force_scan_stall(int on) { return set_lb_force_stall(on) == hipSuccess ? AICP_OK : AICP_ERR_HIP; }
-
 int aicp_hip_create(int device, aicp_hip_ctx** out) {
   if (!out) return AICP_ERR_INVALID;
   *out = nullptr;
@@ -1720,837 +1723,6 @@ int aicp_hip_solve6(aicp_hip_ctx* ctx, const double* A, const double* b, double*
   return AICP_OK;
 }
 
-// Any select variant on given distances, set up as batch_run sets the ICP loop up (descriptors,
-// states, the 4096-reading block map, zeroed work space, active list, IcpIterSync); between steps
-// the update kernel's part of an iteration: the group's pairs counter zeroed, the active list rebuilt.
-int aicp_hip_test_select(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* counts, const float* ratios,
-                         const uint8_t* active, size_t n_steps, const int32_t* variant, const float* d2,
-                         float* out_limit, int32_t* out_status, int32_t* out_n_finite, uint32_t* out_b1,
-                         uint32_t* out_miss, uint64_t* out_dirty) {
-  if (!ctx || !counts || !ratios || !variant || !d2 || !out_limit || !out_status || !out_n_finite || !out_b1 ||
-      !out_miss || !out_dirty)
-    return AICP_ERR_INVALID;
-  if (n_pairs == 0 || n_pairs > (size_t)kMaxPairs || n_steps == 0) return AICP_ERR_INVALID;
-  const size_t P = n_pairs;
-  uint64_t total = 0;
-  uint32_t max_read = 0;
-  for (size_t p = 0; p < P; ++p) {
-    if (counts[p] == 0 || !(ratios[p] >= 0.f && ratios[p] <= 1.f)) return AICP_ERR_INVALID;
-    total += counts[p];
-    max_read = std::max(max_read, counts[p]);
-  }
-  if (total >= (1ull << 31) || total * n_steps >= (1ull << 32)) return AICP_ERR_INVALID;
-  for (size_t s = 0; s < n_steps; ++s) {
-    if (variant[s] < 0 || variant[s] > 5) return AICP_ERR_INVALID;
-    if (variant[s] == 5 && !sel_pair_fits(P, max_read, 1)) return AICP_ERR_INVALID;
-  }
-  HIPC(hipSetDevice(ctx->device));
-  hipStream_t st_ = ctx->stream;
-  std::vector<PairDesc> desc(P, PairDesc{});
-  Maps ms;
-  uint32_t off = 0;
-  for (size_t p = 0; p < P; ++p) {
-    desc[p].read_off = off;
-    desc[p].n_read = counts[p];
-    desc[p].ratio = ratios[p];
-    ms.add((int)p, counts[p], kNNBlock * kSelPerThread);
-    off += counts[p];
-  }
-  const size_t nb = ms.pair.size();
-  HIPC(ensure(ctx->desc, P * sizeof(PairDesc)));
-  HIPC(ensure(ctx->state, P * sizeof(PairState)));
-  HIPC(ensure(ctx->d2, total * n_steps * 4));
-  HIPC(ensure(ctx->qmap, nb * 8));
-  HIPC(ensure(ctx->sel_hist, P * kHistBins * 4));
-  HIPC(ensure(ctx->sel_cand, total * 4));
-  HIPC(ensure(ctx->sel_cnt, P * 4));
-  HIPC(ensure(ctx->isync, icp_sync_words(P) * 4));
-  HIPC(ensure(ctx->active, active_list_bytes(total, P)));
-  HIPC(ensure(ctx->ctrs, kCtrWords * 4));
-  PairDesc* dDesc = ctx->desc.as<PairDesc>();
-  PairState* dState = ctx->state.as<PairState>();
-  uint32_t* hist = ctx->sel_hist.as<uint32_t>();
-  uint32_t* cand = ctx->sel_cand.as<uint32_t>();
-  uint32_t* cnt = ctx->sel_cnt.as<uint32_t>();
-  uint32_t* sync = ctx->isync.as<uint32_t>();
-  ActiveList* al = ctx->active.as<ActiveList>();
-  HIPC(hipMemcpy(dDesc, desc.data(), P * sizeof(PairDesc), hipMemcpyHostToDevice));
-  HIPC(hipMemcpy(ctx->d2.p, d2, total * n_steps * 4, hipMemcpyHostToDevice));
-  HIPC(hipMemcpy(ctx->qmap.p, ms.pair.data(), nb * 4, hipMemcpyHostToDevice));
-  HIPC(hipMemcpy(ctx->qmap.as<uint32_t>() + nb, ms.start.data(), nb * 4, hipMemcpyHostToDevice));
-  const BlockMap m{ctx->qmap.as<int32_t>(), ctx->qmap.as<uint32_t>() + nb, (uint32_t)nb};
-  HIPC(hipMemsetAsync(hist, 0, P * kHistBins * 4, st_));
-  HIPC(hipMemsetAsync(cnt, 0, P * 4, st_));
-  HIPC(hipMemsetAsync(sync, 0, icp_sync_words(P) * 4, st_));
-  HIPC(hipMemsetAsync(ctx->ctrs.p, 0, kCtrWords * 4, st_));
-  launch_init_state(st_, (int)P, dDesc, dState);
-  for (size_t p = 0; p < P && active; ++p)
-    if (!active[p]) HIPC(hipMemsetAsync(&dState[p].active, 0, sizeof(int32_t), st_));
-  IcpIterSync y = icp_iter_sync(sync, P, (int)P, dDesc, dState, al, ctx->ctrs.as<uint32_t>());
-  std::vector<PairState> hs(P);
-  for (size_t s = 0; s < n_steps; ++s) {
-    HIPC(hipMemsetAsync(y.pairs, 0, 4, st_));  // (stopped pairs arrived there; the update kernel's arrivals complete it)
-    launch_active_list(st_, (int)P, dDesc, dState, al, y.ctr);
-    const float* d = ctx->d2.as<float>() + s * total;
-    switch (variant[s]) {
-      case 0: launch_icp_select(st_, m, (int)P, dDesc, dState, d, hist, cand, cnt); break;
-      case 1: launch_icp_select_f(st_, m, dDesc, dState, d, hist, cand, cnt, y); break;
-      case 2: launch_icp_select_fused(st_, m, dDesc, dState, d, hist, cand, cnt, y); break;
-      case 3: launch_icp_select_fused(st_, m, dDesc, dState, d, hist, cand, cnt, y, (uint32_t)kHistBins); break;
-      case 4: launch_icp_select_fused(st_, m, dDesc, dState, d, hist, cand, cnt, y, kFinalLds); break;
-      default: launch_icp_select_pair(st_, (int)P, dDesc, dState, d, cand, y); break;
-    }
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(hs.data(), dState, P * sizeof(PairState), hipMemcpyDeviceToHost, st_));
-    HIPC(hipStreamSynchronize(st_));
-    for (size_t p = 0; p < P; ++p) {
-      const size_t o = s * P + p;
-      out_limit[o] = hs[p].limit;
-      out_status[o] = hs[p].status;
-      out_n_finite[o] = hs[p].n_finite;
-      out_b1[o] = hs[p].sel_b1;
-      out_miss[o] = hs[p].sel_miss;
-    }
-  }
-  // what the selects leave for the next iteration: the histograms, the candidate counts and the
-  // arrival counters of both select launches, all zero
-  std::vector<uint32_t> w(P * kHistBins + 3 * P);
-  HIPC(hipMemcpy(w.data(), hist, P * kHistBins * 4, hipMemcpyDeviceToHost));
-  HIPC(hipMemcpy(w.data() + P * kHistBins, cnt, P * 4, hipMemcpyDeviceToHost));
-  HIPC(hipMemcpy(w.data() + P * kHistBins + P, sync, 2 * P * 4, hipMemcpyDeviceToHost));  // sel1 | sel2
-  uint64_t dirty = 0;
-  for (uint32_t v : w) dirty += v != 0;
-  *out_dirty = dirty;
-  return AICP_OK;
-}
-
-// The tail of an ICP iteration (launch_active_list, then launch_icp_reduce_f: k_icp_reduce and
-// k_icp_update_f) on given matches, set up as batch_run sets the ICP loop up (descriptors with
-// red_blk_off / n_red_blk, states, the kReduceBlock-reading block map, zeroed work space,
-// IcpIterSync). Every argument is checked before the device is touched. The readings, reference
-// points and normals live in buffers of this call (the context's hold the resident reference).
-// ref_nrm null: the point-to-point kernels (aicp_hip_test_step_p2p), which read no normals.
-static int test_step_run(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read, const uint32_t* n_ref,
-                       const uint32_t* ref_off, size_t total_ref, const float* read_c, const float* ref_pts,
-                       const float* ref_nrm, const float* init_T, const uint8_t* active, int32_t max_iter,
-                       int32_t smooth, float min_rot, float min_trans, size_t n_steps, const float* limit,
-                       const int32_t* match, const float* d2, const uint32_t* touched, double* out_slab,
-                       float* out_T, int32_t* out_state, float* out_inlier, uint64_t* out_touched,
-                       double* out_dqdt, uint64_t* out_dirty) {
-  if (!ctx || !n_read || !n_ref || !ref_off || !read_c || !ref_pts || !limit || !match || !d2 ||
-      !touched || !out_slab || !out_T || !out_state || !out_inlier || !out_touched || !out_dqdt || !out_dirty)
-    return AICP_ERR_INVALID;
-  if (n_pairs == 0 || n_pairs > (size_t)kMaxPairs || n_steps == 0 || total_ref == 0) return AICP_ERR_INVALID;
-  if (smooth < 1 || smooth >= kHistRing) return AICP_ERR_INVALID;
-  if (total_ref >= (1ull << 28)) return AICP_ERR_INVALID;
-  const size_t P = n_pairs;
-  uint64_t total = 0, rows = 0;
-  for (size_t p = 0; p < P; ++p) {
-    if (n_read[p] == 0 || n_ref[p] == 0 || (uint64_t)ref_off[p] + n_ref[p] > total_ref) return AICP_ERR_INVALID;
-    total += n_read[p];
-    rows += (n_read[p] + (uint32_t)kReduceBlock - 1) / (uint32_t)kReduceBlock;
-  }
-  if (total >= (1ull << 31) || total * n_steps >= (1ull << 32)) return AICP_ERR_INVALID;
-  for (size_t s = 0; s < n_steps; ++s) {
-    uint64_t o = s * total;
-    for (size_t p = 0; p < P; ++p) {
-      const float lim = limit[s * P + p];
-      if (!std::isfinite(lim)) return AICP_ERR_INVALID;
-      for (uint32_t j = 0; j < n_read[p]; ++j, ++o)  // what the reduce would gather
-        if (d2[o] <= lim && (match[o] < 0 || (uint32_t)match[o] >= n_ref[p])) return AICP_ERR_INVALID;
-    }
-  }
-  HIPC(hipSetDevice(ctx->device));
-  hipStream_t st_ = ctx->stream;
-  std::vector<PairDesc> desc(P, PairDesc{});
-  Maps md;
-  uint32_t off = 0, red = 0;
-  for (size_t p = 0; p < P; ++p) {
-    PairDesc& d = desc[p];
-    d.ref_off = ref_off[p];
-    d.n_ref = n_ref[p];
-    d.read_off = off;
-    d.n_read = n_read[p];
-    d.red_blk_off = red;
-    d.n_red_blk = (n_read[p] + (uint32_t)kReduceBlock - 1) / (uint32_t)kReduceBlock;
-    d.ratio = 1.f;
-    ident4(d.Tin);
-    ident4(d.Tinit);
-    ident4(d.Tmean);
-    md.add((int)p, n_read[p], kReduceBlock);
-    off += n_read[p];
-    red += d.n_red_blk;
-  }
-  const size_t nb = md.pair.size();  // one block per slab row
-  struct Local {  // freed on every return
-    DevBuf read_c, bpts, bnrm;
-    ~Local() {
-      release(read_c);
-      release(bpts);
-      release(bnrm);
-    }
-  } loc;
-  HIPC(ensure(loc.read_c, total * 16));
-  HIPC(ensure(loc.bpts, total_ref * 16));
-  if (ref_nrm) HIPC(ensure(loc.bnrm, total_ref * 16));
-  HIPC(ensure(ctx->desc, P * sizeof(PairDesc)));
-  HIPC(ensure(ctx->state, P * sizeof(PairState)));
-  HIPC(ensure(ctx->match, total * n_steps * 4));
-  HIPC(ensure(ctx->d2, total * n_steps * 4));
-  HIPC(ensure(ctx->touch, total * n_steps * 4));
-  HIPC(ensure(ctx->slab, rows * kRedCols * 8));
-  HIPC(ensure(ctx->qmap, nb * 8));
-  HIPC(ensure(ctx->isync, icp_sync_words(P) * 4));
-  HIPC(ensure(ctx->active, active_list_bytes(total, P)));
-  HIPC(ensure(ctx->ctrs, kCtrWords * 4));
-  std::vector<float> pk(std::max<uint64_t>(total, total_ref) * 4);
-  auto upload4 = [&](const float* xyz, uint64_t n, void* dst) {  // xyz -> float4 (w = 1)
-    for (uint64_t i = 0; i < n; ++i) {
-      pk[4 * i] = xyz[3 * i];
-      pk[4 * i + 1] = xyz[3 * i + 1];
-      pk[4 * i + 2] = xyz[3 * i + 2];
-      pk[4 * i + 3] = 1.f;
-    }
-    return hipMemcpy(dst, pk.data(), n * 16, hipMemcpyHostToDevice);
-  };
-  HIPC(upload4(read_c, total, loc.read_c.p));
-  HIPC(upload4(ref_pts, total_ref, loc.bpts.p));
-  if (ref_nrm) HIPC(upload4(ref_nrm, total_ref, loc.bnrm.p));
-  PairDesc* dDesc = ctx->desc.as<PairDesc>();
-  PairState* dState = ctx->state.as<PairState>();
-  uint32_t* sync = ctx->isync.as<uint32_t>();
-  ActiveList* al = ctx->active.as<ActiveList>();
-  double* slab = ctx->slab.as<double>();
-  HIPC(hipMemcpy(dDesc, desc.data(), P * sizeof(PairDesc), hipMemcpyHostToDevice));
-  HIPC(hipMemcpy(ctx->match.p, match, total * n_steps * 4, hipMemcpyHostToDevice));
-  HIPC(hipMemcpy(ctx->d2.p, d2, total * n_steps * 4, hipMemcpyHostToDevice));
-  HIPC(hipMemcpy(ctx->touch.p, touched, total * n_steps * 4, hipMemcpyHostToDevice));
-  HIPC(hipMemcpy(ctx->qmap.p, md.pair.data(), nb * 4, hipMemcpyHostToDevice));
-  HIPC(hipMemcpy(ctx->qmap.as<uint32_t>() + nb, md.start.data(), nb * 4, hipMemcpyHostToDevice));
-  const BlockMap m{ctx->qmap.as<int32_t>(), ctx->qmap.as<uint32_t>() + nb, (uint32_t)nb};
-  HIPC(hipMemsetAsync(sync, 0, icp_sync_words(P) * 4, st_));
-  HIPC(hipMemsetAsync(ctx->ctrs.p, 0, kCtrWords * 4, st_));
-  HIPC(hipMemsetAsync(dState, 0, P * sizeof(PairState), st_));
-  launch_init_state(st_, (int)P, dDesc, dState);
-  for (size_t p = 0; p < P; ++p) {
-    if (init_T) HIPC(hipMemcpyAsync(dState[p].T, init_T + 16 * p, 64, hipMemcpyHostToDevice, st_));
-    if (active && !active[p]) HIPC(hipMemsetAsync(&dState[p].active, 0, sizeof(int32_t), st_));
-  }
-  IcpIterSync y = icp_iter_sync(sync, P, (int)P, dDesc, dState, al, ctx->ctrs.as<uint32_t>());
-  aicp_icp_config tc{};  // (nn_epsilon 0: every match is exact)
-  tc.knn_normals = ref_nrm ? 20 : 0;  // (which pair of kernels launch_icp_reduce_f launches)
-  tc.nn_max_dist = INFINITY;
-  tc.max_iter = max_iter;
-  tc.smooth_length = smooth;
-  tc.min_diff_rot = min_rot;
-  tc.min_diff_trans = min_trans;
-  const IcpParams prm = icp_params(&tc);
-  std::vector<PairState> hs(P);
-  constexpr uint32_t kSentinel = 0x7FF8DEADu;  // both halves: a NaN no sum produces
-  for (size_t s = 0; s < n_steps; ++s) {
-    for (size_t p = 0; p < P; ++p)
-      HIPC(hipMemcpyAsync(&dState[p].limit, limit + s * P + p, 4, hipMemcpyHostToDevice, st_));
-    HIPC(hipMemsetD32Async((hipDeviceptr_t)slab, (int)kSentinel, rows * kRedCols * 2, st_));
-    launch_active_list(st_, (int)P, dDesc, dState, al, y.ctr);
-    launch_icp_reduce_f(st_, m, dDesc, dState, loc.read_c.as<float4>(), ctx->match.as<int32_t>() + s * total,
-                        ctx->d2.as<float>() + s * total, ctx->touch.as<uint32_t>() + s * total,
-                        loc.bpts.as<float4>(), loc.bnrm.as<float4>(), slab, prm, y);
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(out_slab + s * rows * kRedCols, slab, rows * kRedCols * 8, hipMemcpyDeviceToHost, st_));
-    HIPC(hipMemcpyAsync(hs.data(), dState, P * sizeof(PairState), hipMemcpyDeviceToHost, st_));
-    HIPC(hipStreamSynchronize(st_));
-    for (size_t p = 0; p < P; ++p) {
-      const size_t o = s * P + p;
-      const PairState& h = hs[p];
-      std::memcpy(out_T + 16 * o, h.T, 64);
-      int32_t* w = out_state + 6 * o;
-      w[0] = h.kept;
-      w[1] = h.iters;
-      w[2] = h.status;
-      w[3] = h.active;
-      w[4] = h.converged;
-      w[5] = h.hist_count;
-      out_inlier[o] = h.inlier_ratio;
-      out_touched[2 * o] = h.touched_pts;
-      out_touched[2 * o + 1] = h.touched_nodes;
-      const int last = (int)((uint32_t)(h.hist_count - 1) % (uint32_t)kHistRing);  // the entry just pushed
-      out_dqdt[2 * o] = h.dq[last];
-      out_dqdt[2 * o + 1] = h.dt[last];
-    }
-  }
-  // the arrival counters the iteration tail leaves for the next one: red | pairs, all zero
-  std::vector<uint32_t> w(P + 2);
-  HIPC(hipMemcpy(w.data(), y.red, (P + 2) * 4, hipMemcpyDeviceToHost));
-  uint64_t dirty = 0;
-  for (uint32_t v : w) dirty += v != 0;
-  *out_dirty = dirty;
-  return AICP_OK;
-}
-
-int aicp_hip_test_step(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read, const uint32_t* n_ref,
-                       const uint32_t* ref_off, size_t total_ref, const float* read_c, const float* ref_pts,
-                       const float* ref_nrm, const float* init_T, const uint8_t* active, int32_t max_iter,
-                       int32_t smooth, float min_rot, float min_trans, size_t n_steps, const float* limit,
-                       const int32_t* match, const float* d2, const uint32_t* touched, double* out_slab,
-                       float* out_T, int32_t* out_state, float* out_inlier, uint64_t* out_touched,
-                       double* out_dqdt, uint64_t* out_dirty) {
-  if (!ref_nrm) return AICP_ERR_INVALID;
-  return test_step_run(ctx, n_pairs, n_read, n_ref, ref_off, total_ref, read_c, ref_pts, ref_nrm, init_T, active,
-                       max_iter, smooth, min_rot, min_trans, n_steps, limit, match, d2, touched, out_slab, out_T,
-                       out_state, out_inlier, out_touched, out_dqdt, out_dirty);
-}
-
-int aicp_hip_test_step_p2p(aicp_hip_ctx* ctx, size_t n_pairs, const uint32_t* n_read, const uint32_t* n_ref,
-                           const uint32_t* ref_off, size_t total_ref, const float* read_c, const float* ref_pts,
-                           const float* init_T, const uint8_t* active, int32_t max_iter, int32_t smooth,
-                           float min_rot, float min_trans, size_t n_steps, const float* limit, const int32_t* match,
-                           const float* d2, const uint32_t* touched, double* out_slab, float* out_T,
-                           int32_t* out_state, float* out_inlier, uint64_t* out_touched, double* out_dqdt,
-                           uint64_t* out_dirty) {
-  return test_step_run(ctx, n_pairs, n_read, n_ref, ref_off, total_ref, read_c, ref_pts, nullptr, init_T, active,
-                       max_iter, smooth, min_rot, min_trans, n_steps, limit, match, d2, touched, out_slab, out_T,
-                       out_state, out_inlier, out_touched, out_dqdt, out_dirty);
-}
-
-// The matcher's batched build (matcher_trees: device_trees_begin / device_trees_end on tb[1] with
-// run_batch's plan, then device_trees_check) on given clouds, and everything it wrote, verbatim.
-// A build that reports through the control block (a depth beyond the device stack, a scan that
-// took its slow path) still ran to its end, so the outputs are downloaded whatever it reports.
-int aicp_hip_test_tree(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* counts, const float* pts, int32_t center,
-                       int32_t bucket, uint32_t* out_node_off, uint32_t* out_n_nodes, int32_t* out_depth,
-                       float* out_mean, uint32_t* out_nodes, float* out_bpts, uint32_t* out_ctl) {
-  static_assert(sizeof(TreeCtl) == 4 * AICP_TEST_TREE_CTL_WORDS, "aicp_hip.h: the control block's words");
-  if (!ctx || !counts || !pts || !out_node_off || !out_n_nodes || !out_depth || !out_mean || !out_nodes ||
-      !out_bpts || !out_ctl)
-    return AICP_ERR_INVALID;
-  if (n_refs == 0 || n_refs > (size_t)kMaxPairs || center < 0 || center > 1 || bucket < 1 || bucket > 4096)
-    return AICP_ERR_INVALID;
-  const size_t P = n_refs;
-  uint64_t total = 0, n_max = 0;
-  for (size_t p = 0; p < P; ++p) {
-    if (counts[p] == 0) return AICP_ERR_INVALID;
-    total += counts[p];
-    n_max = std::max<uint64_t>(n_max, counts[p]);
-  }
-  if (total >= (1ull << 28)) return AICP_ERR_INVALID;
-  HIPC(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  ctx->refc.invalidate();  // (ctx->bpts / nodes are rewritten)
-  std::vector<PairDesc> desc(P, PairDesc{});
-  uint32_t off = 0;
-  for (size_t p = 0; p < P; ++p) {
-    desc[p].ref_off = off;
-    desc[p].n_ref = counts[p];
-    desc[p].ratio = 0.5f;
-    desc[p].ref_id = (int32_t)p;
-    ident4(desc[p].Tin);
-    off += counts[p];
-  }
-  std::vector<float> raw4(4 * (size_t)total);
-  pack_xyz4(pts, total, 12, raw4.data());
-  HIPC(ensure(ctx->ref1, total * 16));
-  HIPC(ensure(ctx->desc, P * sizeof(PairDesc)));
-  PairDesc* dDesc = ctx->desc.as<PairDesc>();
-  HIPC(hipMemcpy(ctx->ref1.p, raw4.data(), total * 16, hipMemcpyHostToDevice));
-  HIPC(hipMemcpy(dDesc, desc.data(), P * sizeof(PairDesc), hipMemcpyHostToDevice));
-  TreeBufs& T = ctx->tb[1];
-  int rc = device_trees_begin(T, ctx->err, s, P, total, dDesc, ctx->ref1.as<float4>(), center, bucket, ctx->bpts,
-                              ctx->nodes);
-  if (rc) return rc;
-  rc = device_trees_end(T, ctx->err, s, P, total, dDesc, bucket, ctx->bpts, ctx->nodes,
-                        plan_levels(n_max, T, ctx->opt.tree_plan));
-  HIPC(hipStreamSynchronize(s));
-  if (!rc) rc = device_trees_check(T, ctx->err);
-  HIPC(hipMemcpy(desc.data(), dDesc, P * sizeof(PairDesc), hipMemcpyDeviceToHost));
-  for (size_t p = 0; p < P; ++p) {
-    out_node_off[p] = desc[p].node_off;
-    out_n_nodes[p] = desc[p].n_nodes;
-    out_depth[p] = desc[p].tree_depth;
-    for (int k = 0; k < 3; ++k) out_mean[3 * p + k] = desc[p].mean[k];
-  }
-  HIPC(hipMemcpy(out_nodes, ctx->nodes.p, (2 * (size_t)total + 2) * 16, hipMemcpyDeviceToHost));
-  HIPC(hipMemcpy(out_bpts, ctx->bpts.p, (size_t)total * 16, hipMemcpyDeviceToHost));
-  HIPC(hipMemcpy(out_ctl, T.tw.ctl, sizeof(TreeCtl), hipMemcpyDeviceToHost));
-  return rc;
-}
-
-// The production NN launch (launch_active_list, then launch_icp_nn with the grid and engine
-// run_batch gives it) on given references, readings and per-step transforms. The trees are the
-// matcher's batched build as aicp_hip_test_tree runs it (no centring), the treelets matcher_trees'
-// and the engine plan_treelets' choice. The three result arrays live in buffers of this call, 64
-// guard words on both sides, refilled with sentinels before every step. Every argument is
-// checked before the device is touched. Non-finite query coordinates are out of scope (libnabo
-// gives no order for them).
-int aicp_hip_test_nn(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* ref_counts, const float* ref_pts,
-                     int32_t bucket, size_t n_pairs, const uint32_t* pair_ref, const uint32_t* n_read,
-                     const float* read_c, size_t n_steps, const float* T, const uint8_t* active, float epsilon,
-                     float max_dist, int32_t* out_match, float* out_d2, uint32_t* out_touched, int32_t* out_ids,
-                     int32_t* out_engine, uint64_t* out_dirty) {
-  if (!ctx || !ref_counts || !ref_pts || !pair_ref || !n_read || !read_c || !T || !out_match || !out_d2 ||
-      !out_touched || !out_ids || !out_engine || !out_dirty)
-    return AICP_ERR_INVALID;
-  if (n_refs == 0 || n_refs > (size_t)kMaxPairs || n_pairs == 0 || n_pairs > (size_t)kMaxPairs || n_steps == 0 ||
-      bucket < 1 || bucket > 4096)
-    return AICP_ERR_INVALID;
-  if (!(epsilon >= 0.f) || !(max_dist >= 0.f)) return AICP_ERR_INVALID;  // (negative or NaN)
-  const size_t R = n_refs, P = n_pairs;
-  uint64_t total_ref = 0, n_max = 0, total = 0;
-  for (size_t r = 0; r < R; ++r) {
-    if (ref_counts[r] == 0) return AICP_ERR_INVALID;
-    total_ref += ref_counts[r];
-    n_max = std::max<uint64_t>(n_max, ref_counts[r]);
-  }
-  for (size_t p = 0; p < P; ++p) {
-    if (n_read[p] == 0 || pair_ref[p] >= R) return AICP_ERR_INVALID;
-    total += n_read[p];
-  }
-  if (total_ref >= (1ull << 28) || total >= (1ull << 28) || total * n_steps >= (1ull << 32)) return AICP_ERR_INVALID;
-  HIPC(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  ctx->refc.invalidate();  // (ctx->bpts / nodes / tl are rewritten)
-  std::vector<PairDesc> rdesc(R, PairDesc{}), desc(P, PairDesc{});
-  uint32_t off = 0;
-  for (size_t r = 0; r < R; ++r) {
-    rdesc[r].ref_off = off;
-    rdesc[r].n_ref = ref_counts[r];
-    rdesc[r].ratio = 0.5f;
-    rdesc[r].ref_id = (int32_t)r;
-    ident4(rdesc[r].Tin);
-    ident4(rdesc[r].Tmean);
-    off += ref_counts[r];
-  }
-  ctx->tl_total = plan_treelets(rdesc.data(), R, bucket, ctx->opt.nn_engine);
-  off = 0;
-  for (size_t p = 0; p < P; ++p) {
-    PairDesc& d = desc[p];
-    d.ref_off = rdesc[pair_ref[p]].ref_off;
-    d.n_ref = rdesc[pair_ref[p]].n_ref;
-    d.read_off = off;
-    d.n_read = n_read[p];
-    d.ratio = 1.f;
-    d.ref_id = (int32_t)pair_ref[p];
-    ident4(d.Tin);
-    off += n_read[p];
-  }
-  constexpr size_t kGuard = 64;
-  const size_t words = (size_t)total + 2 * kGuard;
-  struct Local {  // freed on every return
-    DevBuf read_c, match, d2, touch;
-    ~Local() {
-      release(read_c);
-      release(match);
-      release(d2);
-      release(touch);
-    }
-  } loc;
-  HIPC(ensure(loc.read_c, total * 16));
-  HIPC(ensure(loc.match, words * 4));
-  HIPC(ensure(loc.d2, words * 4));
-  HIPC(ensure(loc.touch, words * 4));
-  HIPC(ensure(ctx->ref1, total_ref * 16));
-  HIPC(ensure(ctx->rdesc, R * sizeof(PairDesc)));
-  HIPC(ensure(ctx->desc, P * sizeof(PairDesc)));
-  HIPC(ensure(ctx->state, P * sizeof(PairState)));
-  HIPC(ensure(ctx->active, active_list_bytes(total, P)));
-  HIPC(ensure(ctx->ctrs, kCtrWords * 4));
-  {
-    std::vector<float> pk(4 * (size_t)std::max(total_ref, total));
-    pack_xyz4(ref_pts, total_ref, 12, pk.data());
-    HIPC(hipMemcpy(ctx->ref1.p, pk.data(), total_ref * 16, hipMemcpyHostToDevice));
-    pack_xyz4(read_c, total, 12, pk.data());
-    HIPC(hipMemcpy(loc.read_c.p, pk.data(), total * 16, hipMemcpyHostToDevice));
-  }
-  PairDesc* dRdesc = ctx->rdesc.as<PairDesc>();
-  PairDesc* dDesc = ctx->desc.as<PairDesc>();
-  PairState* dState = ctx->state.as<PairState>();
-  HIPC(hipMemcpy(dRdesc, rdesc.data(), R * sizeof(PairDesc), hipMemcpyHostToDevice));
-  HIPC(hipMemcpy(dDesc, desc.data(), P * sizeof(PairDesc), hipMemcpyHostToDevice));
-  // the trees (aicp_hip_test_tree's build), then the treelets (matcher_trees')
-  TreeBufs& Tb = ctx->tb[1];
-  int rc = device_trees_begin(Tb, ctx->err, s, R, total_ref, dRdesc, ctx->ref1.as<float4>(), 0, bucket, ctx->bpts,
-                              ctx->nodes);
-  if (rc) return rc;
-  rc = device_trees_end(Tb, ctx->err, s, R, total_ref, dRdesc, bucket, ctx->bpts, ctx->nodes,
-                        plan_levels(n_max, Tb, ctx->opt.tree_plan));
-  if (rc) return rc;
-  if (ctx->tl_total) {
-    const uint32_t cap = (uint32_t)(2 * total_ref + 2);  // node records allotted
-    HIPC(ensure(ctx->tl, ctx->tl_total * 16));
-    HIPC(ensure(ctx->ptl, ctx->tl_total * 8));
-    HIPC(ensure(ctx->tl_rank, ((size_t)cap + 1) * 4));
-    HIPC(launch_treelets(s, (int)R, cap, dRdesc, ctx->nodes.as<uint4>(), bucket, ctx->tl_rank.as<uint32_t>(),
-                         ctx->tl.as<uint4>(), ctx->ptl.as<uint2>(), Tb.tw));
-    HIPC(hipMemcpyAsync(Tb.pin_ctl.p, Tb.tw.ctl, sizeof(TreeCtl), hipMemcpyDeviceToHost, s));
-  }
-  launch_pairs_from_refs(s, (int)P, dDesc, dRdesc);
-  HIPC(hipGetLastError());
-  HIPC(hipStreamSynchronize(s));
-  // a tree deeper than the device stacks, or treelets beyond their allotment: no search is run
-  rc = device_trees_check(Tb, ctx->err);
-  if (rc) return rc;
-  if (ctx->tl_total && (Tb.pin_ctl.as<TreeCtl>()->error & 4))
-    FAIL(AICP_ERR_HIP, "matcher treelets exceed their allotment");
-  *out_engine = ctx->tl_total ? 0 : 1;
-  {
-    std::vector<float> b4(4 * (size_t)total_ref);
-    HIPC(hipMemcpy(b4.data(), ctx->bpts.p, total_ref * 16, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < total_ref; ++i) std::memcpy(out_ids + i, &b4[4 * i + 3], 4);
-  }
-  HIPC(hipMemsetAsync(ctx->ctrs.p, 0, kCtrWords * 4, s));
-  HIPC(hipMemsetAsync(dState, 0, P * sizeof(PairState), s));
-  launch_init_state(s, (int)P, dDesc, dState);
-  std::vector<PairState> hs(P);
-  HIPC(hipMemcpyAsync(hs.data(), dState, P * sizeof(PairState), hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  aicp_icp_config tc{};
-  tc.nn_epsilon = epsilon;
-  tc.nn_max_dist = max_dist;
-  const IcpParams prm = icp_params(&tc);
-  ActiveList* al = ctx->active.as<ActiveList>();
-  const uint4* tl = ctx->tl_total ? ctx->tl.as<uint4>() : nullptr;
-  const uint2* ptl = ctx->tl_total ? ctx->ptl.as<uint2>() : nullptr;
-  constexpr uint32_t kSentinel = AICP_TEST_NN_SENTINEL, kTouchSentinel = AICP_TEST_NN_TOUCH_SENTINEL;
-  std::vector<uint32_t> back(3 * words);
-  uint64_t dirty = 0;
-  for (size_t k = 0; k < n_steps; ++k) {
-    for (size_t p = 0; p < P; ++p) {
-      std::memcpy(hs[p].T, T + 16 * (k * P + p), 64);
-      hs[p].active = !active || active[k * P + p] ? 1 : 0;
-    }
-    HIPC(hipMemcpyAsync(dState, hs.data(), P * sizeof(PairState), hipMemcpyHostToDevice, s));
-    HIPC(hipMemsetD32Async((hipDeviceptr_t)loc.match.p, (int)kSentinel, words, s));
-    HIPC(hipMemsetD32Async((hipDeviceptr_t)loc.d2.p, (int)kSentinel, words, s));
-    HIPC(hipMemsetD32Async((hipDeviceptr_t)loc.touch.p, (int)kTouchSentinel, words, s));
-    launch_active_list(s, (int)P, dDesc, dState, al, ctx->ctrs.as<uint32_t>());
-    launch_icp_nn(s, (int)total, dDesc, dState, al, loc.read_c.as<float4>(), ctx->nodes.as<uint4>(), tl, nullptr,
-                  ctx->bpts.as<float4>(), ptl, loc.match.as<int32_t>() + kGuard, loc.d2.as<float>() + kGuard,
-                  loc.touch.as<uint32_t>() + kGuard, ctx->ctrs.as<uint32_t>(), prm);
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(back.data(), loc.match.p, words * 4, hipMemcpyDeviceToHost, s));
-    HIPC(hipMemcpyAsync(back.data() + words, loc.d2.p, words * 4, hipMemcpyDeviceToHost, s));
-    HIPC(hipMemcpyAsync(back.data() + 2 * words, loc.touch.p, words * 4, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    for (size_t a = 0; a < 3; ++a) {
-      const uint32_t* w = back.data() + a * words;
-      const uint32_t want = a == 2 ? kTouchSentinel : kSentinel;
-      for (size_t g = 0; g < kGuard; ++g) dirty += (w[g] != want) + (w[kGuard + total + g] != want);
-    }
-    std::memcpy(out_match + k * total, back.data() + kGuard, total * 4);
-    std::memcpy(out_d2 + k * total, back.data() + words + kGuard, total * 4);
-    std::memcpy(out_touched + k * total, back.data() + 2 * words + kGuard, total * 4);
-  }
-  *out_dirty = dirty;
-  return AICP_OK;
-}
-
-// The SurfaceNormal chain of run_batch's references on given clouds: the raw trees on tb[0] with
-// the lean plan, launch_init_state, launch_normals with the normals' counters, a second
-// launch_knn_ids with the touched counters, the centred matcher trees on tb[1] and
-// launch_normals_to_matcher, all on one stream (run_batch launches launch_init_state ahead of the
-// raw trees; it reads the descriptors alone, so its place before the normals is all that counts).
-// The id buffers and the two normal arrays are this
-// call's, 64 guard words on both sides, sentinel-filled before the launches. Every argument is
-// checked before the device is touched, each tree before anything searches it.
-int aicp_hip_test_normals(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* counts, const float* pts, int32_t knn,
-                          int32_t matcher_bucket, int32_t* out_ids, int32_t* out_ids2, int32_t* out_raw_id,
-                          float* out_nrm, int32_t* out_degenerate, uint64_t* out_touched, float* out_bnrm,
-                          int32_t* out_matcher_id, int32_t* out_engine, uint64_t* out_dirty) {
-  if (!ctx || !counts || !pts || !out_ids || !out_ids2 || !out_raw_id || !out_nrm || !out_degenerate ||
-      !out_touched || !out_bnrm || !out_matcher_id || !out_engine || !out_dirty)
-    return AICP_ERR_INVALID;
-  if (n_refs == 0 || n_refs > (size_t)kMaxPairs || matcher_bucket < 1 || matcher_bucket > 4096)
-    return AICP_ERR_INVALID;
-  const size_t R = n_refs;
-  uint64_t total = 0, n_max = 0;
-  for (size_t r = 0; r < R; ++r) {
-    if (counts[r] == 0) return AICP_ERR_INVALID;
-    total += counts[r];
-    n_max = std::max<uint64_t>(n_max, counts[r]);
-  }
-  if (total >= (1ull << 28)) return AICP_ERR_INVALID;
-  if (knn != 10 && knn != 20 && knn != 30) FAIL(AICP_ERR_UNSUPPORTED, "knn must be 10, 20 or 30");
-  HIPC(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  ctx->refc.invalidate();  // (ctx->rdesc / rstate / bpts / nodes are rewritten)
-  std::vector<PairDesc> rdesc(R, PairDesc{});
-  uint32_t off = 0;
-  for (size_t r = 0; r < R; ++r) {
-    rdesc[r].ref_off = off;
-    rdesc[r].n_ref = counts[r];
-    rdesc[r].ratio = 0.5f;
-    rdesc[r].ref_id = (int32_t)r;
-    ident4(rdesc[r].Tin);
-    off += counts[r];
-  }
-  constexpr size_t kGuard = 64;
-  const size_t id_words = (size_t)total * (size_t)knn + 2 * kGuard, nrm_words = (size_t)total * 4 + 2 * kGuard;
-  struct Local {  // freed on every return
-    DevBuf ids, ids2, nrm, bnrm, touched;
-    ~Local() {
-      release(ids);
-      release(ids2);
-      release(nrm);
-      release(bnrm);
-      release(touched);
-    }
-  } loc;
-  HIPC(ensure(loc.ids, id_words * 4));
-  HIPC(ensure(loc.ids2, id_words * 4));
-  HIPC(ensure(loc.nrm, nrm_words * 4));
-  HIPC(ensure(loc.bnrm, nrm_words * 4));
-  HIPC(ensure(loc.touched, 16));
-  HIPC(ensure(ctx->ref1, total * 16));
-  HIPC(ensure(ctx->rdesc, R * sizeof(PairDesc)));
-  HIPC(ensure(ctx->rdesc_raw, R * sizeof(PairDesc)));
-  HIPC(ensure(ctx->rstate, R * sizeof(PairState)));
-  HIPC(ensure(ctx->inv, total * 4));
-  HIPC(ensure(ctx->ctrs, kCtrWords * 4));
-  {
-    std::vector<float> pk(4 * (size_t)total);
-    pack_xyz4(pts, total, 12, pk.data());
-    HIPC(hipMemcpy(ctx->ref1.p, pk.data(), total * 16, hipMemcpyHostToDevice));
-  }
-  PairDesc* dRaw = ctx->rdesc_raw.as<PairDesc>();
-  PairDesc* dRdesc = ctx->rdesc.as<PairDesc>();
-  PairState* dRstate = ctx->rstate.as<PairState>();
-  HIPC(hipMemcpy(dRaw, rdesc.data(), R * sizeof(PairDesc), hipMemcpyHostToDevice));
-  HIPC(hipMemcpy(dRdesc, rdesc.data(), R * sizeof(PairDesc), hipMemcpyHostToDevice));
-  constexpr uint32_t kSentinel = AICP_TEST_NN_SENTINEL;
-  HIPC(hipMemsetD32Async((hipDeviceptr_t)loc.ids.p, (int)kSentinel, id_words, s));
-  HIPC(hipMemsetD32Async((hipDeviceptr_t)loc.ids2.p, (int)kSentinel, id_words, s));
-  HIPC(hipMemsetD32Async((hipDeviceptr_t)loc.nrm.p, (int)kSentinel, nrm_words, s));
-  HIPC(hipMemsetD32Async((hipDeviceptr_t)loc.bnrm.p, (int)kSentinel, nrm_words, s));
-  HIPC(hipMemsetAsync(loc.touched.p, 0, 16, s));
-  HIPC(hipMemsetAsync(ctx->ctrs.p, 0, kCtrWords * 4, s));
-  HIPC(hipMemsetAsync(dRstate, 0, R * sizeof(PairState), s));
-  // 1. the raw-coordinate trees (run_batch's build of them)
-  int rc = device_trees_begin(ctx->tb[0], ctx->err, s, R, total, dRaw, ctx->ref1.as<float4>(), 0, kNormalsBucket,
-                              ctx->bpts_raw, ctx->nodes_raw);
-  if (rc) return rc;
-  rc = device_trees_end(ctx->tb[0], ctx->err, s, R, total, dRaw, kNormalsBucket, ctx->bpts_raw, ctx->nodes_raw,
-                        plan_levels(n_max, ctx->tb[0], ctx->opt.tree_plan, true), nullptr, true);
-  if (rc) return rc;
-  HIPC(hipStreamSynchronize(s));
-  rc = device_trees_check(ctx->tb[0], ctx->err);  // (a tree deeper than the device stacks: no search is run)
-  if (rc) return rc;
-  // 2. - 4. the state, the normals, the kNN again with its counters
-  int32_t* ids = loc.ids.as<int32_t>() + kGuard;
-  int32_t* ids2 = loc.ids2.as<int32_t>() + kGuard;
-  float4* nrm = reinterpret_cast<float4*>(loc.nrm.as<float>() + kGuard);
-  float4* bnrm = reinterpret_cast<float4*>(loc.bnrm.as<float>() + kGuard);
-  uint32_t* nCtr = ctx->ctrs.as<uint32_t>() + kKnnCtrOff;
-  const int engine = ctx->opt.normals_knn_engine;
-  int engine_used = 0;
-  launch_init_state(s, (int)R, dRaw, dRstate);
-  if (!launch_normals(s, (int)R, (uint32_t)total, dRaw, dRstate, ctx->nodes_raw.as<uint4>(), nullptr,
-                      ctx->bpts_raw.as<float4>(), nrm, knn, ids, nCtr, engine))
-    FAIL(AICP_ERR_UNSUPPORTED, "normals knn");
-  if (!launch_knn_ids(s, (int)R, (uint32_t)total, dRaw, ctx->nodes_raw.as<uint4>(), ctx->bpts_raw.as<float4>(), knn,
-                      ids2, nCtr, loc.touched.as<unsigned long long>(), engine, &engine_used))
-    FAIL(AICP_ERR_UNSUPPORTED, "normals knn");
-  *out_engine = engine_used;  // (the kernel that launch launched)
-  HIPC(hipGetLastError());
-  // 5. the matcher trees (matcher_trees' build: centred)
-  rc = device_trees_begin(ctx->tb[1], ctx->err, s, R, total, dRdesc, ctx->ref1.as<float4>(), 1, matcher_bucket,
-                          ctx->bpts, ctx->nodes);
-  if (rc) return rc;
-  rc = device_trees_end(ctx->tb[1], ctx->err, s, R, total, dRdesc, matcher_bucket, ctx->bpts, ctx->nodes,
-                        plan_levels(n_max, ctx->tb[1], ctx->opt.tree_plan));
-  if (rc) return rc;
-  HIPC(hipStreamSynchronize(s));
-  rc = device_trees_check(ctx->tb[1], ctx->err);
-  if (rc) return rc;
-  // 6. the normals in the matcher trees' order
-  launch_normals_to_matcher(s, (int)R, (uint32_t)total, dRdesc, ctx->bpts.as<float4>(), ctx->bpts_raw.as<float4>(),
-                            nrm, ctx->inv.as<uint32_t>(), bnrm);
-  HIPC(hipGetLastError());
-  HIPC(hipStreamSynchronize(s));
-  uint64_t dirty = 0;
-  {
-    std::vector<uint32_t> back(std::max(id_words, nrm_words));
-    auto fetch = [&](const DevBuf& b, size_t words, void* out) -> hipError_t {
-      const hipError_t e = hipMemcpy(back.data(), b.p, words * 4, hipMemcpyDeviceToHost);
-      if (e != hipSuccess) return e;
-      for (size_t g = 0; g < kGuard; ++g)
-        dirty += (back[g] != kSentinel) + (back[words - kGuard + g] != kSentinel);
-      std::memcpy(out, back.data() + kGuard, (words - 2 * kGuard) * 4);
-      return hipSuccess;
-    };
-    HIPC(fetch(loc.ids, id_words, out_ids));
-    HIPC(fetch(loc.ids2, id_words, out_ids2));
-    HIPC(fetch(loc.nrm, nrm_words, out_nrm));
-    HIPC(fetch(loc.bnrm, nrm_words, out_bnrm));
-    for (int which = 0; which < 2; ++which) {
-      HIPC(hipMemcpy(back.data(), which ? ctx->bpts.p : ctx->bpts_raw.p, (size_t)total * 16, hipMemcpyDeviceToHost));
-      int32_t* out = which ? out_matcher_id : out_raw_id;
-      for (size_t i = 0; i < total; ++i) out[i] = (int32_t)back[4 * i + 3];
-    }
-  }
-  std::vector<PairState> hs(R);
-  HIPC(hipMemcpy(hs.data(), dRstate, R * sizeof(PairState), hipMemcpyDeviceToHost));
-  for (size_t r = 0; r < R; ++r) out_degenerate[r] = hs[r].degenerate;
-  HIPC(hipMemcpy(out_touched, loc.touched.p, 16, hipMemcpyDeviceToHost));
-  *out_dirty = dirty;
-  return AICP_OK;
-}
-
-// The batch's overlap (upload_pairs, run_batch with AICP_RUN_OVERLAP: grouping, key boxes,
-// overlap_maps or overlap_sparse) on given clouds and origins, and everything it wrote: the
-// states, the map descriptors and arena, or the key path's counts, offsets and sorted words.
-// ctx->ovl_probe carries the overrides of the two launch rules in and what ran out. Every
-// argument is checked before the device is touched.
-int aicp_hip_test_overlap(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* ref_counts, const float* ref_pts,
-                          size_t n_pairs, const uint32_t* pair_ref, const uint32_t* n_read, const float* read_pts,
-                          const double* ref_origins, const double* read_origins, double resolution, int32_t path,
-                          int32_t filter, int32_t wide, int32_t cap_mode, const uint64_t* caps, int32_t rigid,
-                          aicp_test_overlap_out* out) {
-  if (!ctx || !ref_counts || !ref_pts || !pair_ref || !n_read || !read_pts || !ref_origins || !read_origins || !out)
-    return AICP_ERR_INVALID;
-  if (!out->pair_group || !out->cloud_keys || !out->cloud_err || !out->cloud_bbox || !out->pair_counts ||
-      !out->pair_percent || !out->pair_ratio || !out->pair_err || !out->desc_min || !out->desc_dim || !out->desc_off ||
-      !out->desc_bytes || !out->arena || !out->key_counts || !out->key_offsets || !out->words || !out->cloud_bound ||
-      !out->list_off || !out->list_cap)
-    return AICP_ERR_INVALID;
-  if (n_refs == 0 || n_refs > (size_t)kMaxPairs || n_pairs == 0 || n_pairs > (size_t)kMaxPairs) return AICP_ERR_INVALID;
-  if (!(resolution > 0) || path < 0 || path > 4 || filter < -1 || filter > 1 || wide < -1 || wide > 1 || cap_mode < 0 ||
-      cap_mode > 1 || rigid < 0 || rigid > 1 || (cap_mode == 1 && (!caps || path < 3)))
-    return AICP_ERR_INVALID;
-  const size_t R = n_refs, P = n_pairs;
-  std::vector<uint64_t> roff(R + 1, 0);
-  for (size_t r = 0; r < R; ++r) {
-    if (ref_counts[r] == 0) return AICP_ERR_INVALID;
-    roff[r + 1] = roff[r] + ref_counts[r];
-  }
-  std::vector<aicp_pair> pairs(P, aicp_pair{});
-  uint64_t wo = 0;
-  for (size_t p = 0; p < P; ++p) {
-    if (n_read[p] == 0 || pair_ref[p] >= R) return AICP_ERR_INVALID;
-    aicp_pair& q = pairs[p];
-    q.ref = ref_pts + 3 * roff[pair_ref[p]];
-    q.n_ref = ref_counts[pair_ref[p]];
-    q.ref_stride = 12;
-    q.read = read_pts + 3 * wo;
-    q.n_read = n_read[p];
-    q.read_stride = 12;
-    for (int k = 0; k < 3; ++k) {
-      q.ref_origin[k] = ref_origins[3 * p + k];
-      q.read_origin[k] = read_origins[3 * p + k];
-    }
-    wo += n_read[p];
-  }
-  {  // the per-point slots of the key path: one per point of every group's reference and reading
-    std::vector<std::pair<uint32_t, std::array<double, 3>>> groups;
-    uint64_t slots = wo;
-    for (size_t p = 0; p < P; ++p) {
-      const std::pair<uint32_t, std::array<double, 3>> g{
-          pair_ref[p], {ref_origins[3 * p], ref_origins[3 * p + 1], ref_origins[3 * p + 2]}};
-      if (std::find(groups.begin(), groups.end(), g) == groups.end()) {
-        groups.push_back(g);
-        slots += ref_counts[pair_ref[p]];
-      }
-    }
-    if (slots > out->points_cap) return AICP_ERR_INVALID;
-  }
-  HIPC(hipSetDevice(ctx->device));
-  ctx->refc.invalidate();  // (ctx->bitmap and the group states are rewritten)
-  ctx->rdc.valid = ctx->rdc.hit = false;
-  struct Local {  // freed, and the probe switched off, on every return
-    aicp_hip_ctx* ctx;
-    aicp_hip_batch* B = new aicp_hip_batch();
-    ~Local() {
-      ctx->ovl_probe = OvlProbe{};
-      (void)hipStreamSynchronize(ctx->stream);
-      free_batch(B);
-    }
-  } loc{ctx};
-  OvlProbe& probe = ctx->ovl_probe;
-  probe = OvlProbe{};
-  probe.on = true;
-  probe.filter = filter;
-  probe.wide = wide;
-  probe.keys = path == 2;
-  aicp_icp_config cfg;
-  aicp_hip_default_config(&cfg);
-  const int saved_path = ctx->opt.overlap_path;
-  if (path == 1) ctx->opt.overlap_path = 0;  // (dense wherever the maps fit)
-  int rc = upload_pairs(ctx, pairs.data(), P, loc.B, false);
-  out->dirty = 0;
-  if (!rc && path >= 3) {  // the stream's windows (sequence.cpp), one per overlap group
-    ctx->opt.overlap_path = saved_path;
-    return ovl_window_test(ctx, loc.B, pairs.data(), resolution, path, filter, wide, cap_mode ? caps : nullptr, rigid,
-                           out);
-  }
-  if (!rc) rc = run_batch(ctx, loc.B, &cfg, resolution, AICP_RUN_OVERLAP, nullptr, nullptr, nullptr);
-  ctx->opt.overlap_path = saved_path;
-  // a cloud's ovl_err comes back as the batch's "pair status": reported in the outputs instead
-  if (rc && !(rc == AICP_ERR_HIP && ctx->err.rfind("pair status", 0) == 0)) return rc;
-  const size_t G = loc.B->gdesc.size();
-  out->path = probe.ran_path;
-  out->filter = probe.ran_filter;
-  out->wide = probe.ran_wide;
-  out->n_groups = (int32_t)G;
-  std::vector<PairState> hs(P), hg(G);
-  HIPC(hipMemcpy(hs.data(), ctx->state.p, P * sizeof(PairState), hipMemcpyDeviceToHost));
-  HIPC(hipMemcpy(hg.data(), ctx->gstate.p, G * sizeof(PairState), hipMemcpyDeviceToHost));
-  for (size_t c = 0; c < G + P; ++c) {
-    const PairState& st = c < G ? hg[c] : hs[c - G];
-    out->cloud_keys[c] = st.ovl_counts[c < G ? 0 : 1];
-    out->cloud_err[c] = st.ovl_err;
-    for (int k = 0; k < 6; ++k) out->cloud_bbox[6 * c + k] = st.ovl_bbox[k];
-  }
-  for (size_t p = 0; p < P; ++p) {
-    out->pair_group[p] = loc.B->desc[p].ogroup;
-    for (int k = 0; k < 3; ++k) out->pair_counts[3 * p + k] = hs[p].ovl_counts[k];
-    out->pair_percent[p] = hs[p].overlap;
-    out->pair_ratio[p] = hs[p].ratio;
-    out->pair_err[p] = hs[p].ovl_err;
-  }
-  out->arena_bytes = out->n_points = out->n_words = 0;
-  if (probe.ran_path == 1) {  // the descriptors lie readings first; the outputs groups first
-    std::vector<OvlDesc> od(P + G);
-    HIPC(hipMemcpy(od.data(), ctx->ovl.p, (P + G) * sizeof(OvlDesc), hipMemcpyDeviceToHost));
-    for (size_t c = 0; c < G + P; ++c) {
-      const OvlDesc& o = od[c < G ? P + c : c - G];
-      for (int k = 0; k < 3; ++k) {
-        out->desc_min[3 * c + k] = o.min[k];
-        out->desc_dim[3 * c + k] = o.dim[k];
-      }
-      out->desc_off[c] = o.off;
-      out->desc_bytes[c] = o.bytes;
-    }
-    out->arena_bytes = probe.arena_bytes;
-    const uint64_t nb = std::min(out->arena_cap, out->arena_bytes);
-    if (nb) HIPC(hipMemcpy(out->arena, ctx->bitmap.p, nb, hipMemcpyDeviceToHost));
-  } else if (probe.ran_path == 2) {
-    out->n_points = probe.n_points;
-    out->n_words = probe.n_keys;
-    if (probe.n_points > out->points_cap) FAIL(AICP_ERR_INVALID, "points_cap");
-    if (probe.n_points) {
-      HIPC(hipMemcpy(out->key_counts, probe.cnt, probe.n_points * 4, hipMemcpyDeviceToHost));
-      HIPC(hipMemcpy(out->key_offsets, probe.off, probe.n_points * 8, hipMemcpyDeviceToHost));
-    }
-    const uint64_t nw = std::min(out->words_cap, out->n_words);
-    if (nw) HIPC(hipMemcpy(out->words, probe.keys1, nw * 8, hipMemcpyDeviceToHost));
-  } else {
-    FAIL(AICP_ERR_HIP, "the batch ran no overlap");
-  }
-  return AICP_OK;
-}
-
-int aicp_hip_test_key_bound(const float* pts, size_t n, const double origin[3], double resolution, int32_t rigid,
-                            uint64_t* out_bound, uint64_t* out_point_cap) {
-  if (!pts || !origin || !out_bound || !out_point_cap || n == 0 || !(resolution > 0) || rigid < 0 || rigid > 1)
-    return AICP_ERR_INVALID;
-  WorkerPool pool{0};
-  aicp_cloud c{};
-  c.pts = pts;
-  c.n = n;
-  c.stride = 12;
-  *out_bound = key_bound(pool, c, origin, resolution, rigid != 0);
-  *out_point_cap = kMaxRayKeys;
-  return AICP_OK;
-}
-
 void aicp_hip_default_prefilter(aicp_prefilter_params* p) {
   if (!p) return;
   *p = aicp_prefilter_params{};
@@ -3000,8 +2172,8 @@ int map_crop_pairs(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float m
 // 16 bytes travel as they are (no more bytes than the packed form), wider rows are packed to
 // float4 on the host first. The rows land in ctx->scratch at `off` (a multiple of 16); *drows /
 // *dstride: where, and their stride there. The stream is synchronised first (pin_io is free).
-static int ingest_upload(aicp_hip_ctx* ctx, const float* pts, size_t n, size_t stride, size_t off, const void** drows,
-                         size_t* dstride) {
+int ingest_upload(aicp_hip_ctx* ctx, const float* pts, size_t n, size_t stride, size_t off, const void** drows,
+                  size_t* dstride) {
   hipStream_t s = ctx->stream;
   const bool verbatim = stride <= 16;
   const size_t ds = verbatim ? stride : 16;
@@ -3155,28 +2327,6 @@ int aicp_hip_map_align_batch(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, cons
   const int rc = check_cfg(ctx, cfg, run_flags);
   if (rc) return rc;
   return map_batch(ctx, cfg, map, mn, mx, readings, poses, n, resolution, run_flags, out_T, stats);
-}
-
-// Test surface: the raw streams' ingest alone (the upload policy of ingest_upload, k_stream_ingest)
-int aicp_hip_test_ingest(aicp_hip_ctx* ctx, const float* rows, size_t n, size_t stride, const float* T, float* out4) {
-  if (!ctx || (n && !rows) || stride < 12 || (stride % 4) || n > (size_t)INT32_MAX) return AICP_ERR_INVALID;
-  if (n == 0) return AICP_OK;
-  HIPC(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  // scratch: T | the rows (ingest_upload) | the output
-  const size_t o_rows = 256, o_out = (o_rows + n * std::min<size_t>(stride, 16) + 255) & ~size_t(255);
-  HIPC(ensure(ctx->scratch, o_out + n * 16));
-  const void* drows = nullptr;
-  size_t dstride = 0;
-  const int rc = ingest_upload(ctx, rows, n, stride, o_rows, &drows, &dstride);
-  if (rc) return rc;
-  char* d = ctx->scratch.as<char>();
-  if (T) HIPC(hipMemcpyAsync(d, T, 64, hipMemcpyHostToDevice, s));
-  launch_stream_ingest(s, (int)n, drows, dstride, T ? (const float*)d : nullptr, nullptr, (float4*)(d + o_out));
-  HIPC(hipGetLastError());
-  HIPC(hipStreamSynchronize(s));
-  if (out4) HIPC(hipMemcpy(out4, d + o_out, n * 16, hipMemcpyDeviceToHost));
-  return AICP_OK;
 }
 
 int aicp_hip_map_capacity(const aicp_hip_map* map, size_t* n) {

@@ -1,4 +1,5 @@
-// runtime.hpp — host-side runtime shared by the C-ABI translation units (aicp_hip.cpp, sequence.cpp):
+// runtime.hpp — host-side runtime shared by the C-ABI translation units (aicp_hip.cpp, sequence.cpp,
+// map_stream.cpp, session.cpp, accum.cpp, monitor.cpp, test_entries.cpp):
 // device / pinned buffers, kd-tree work space, the context and batch objects, error macros.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -207,6 +208,9 @@ int device_trees_check(TreeBufs& T, std::string& err);
 // force: aicp_hip_options::tree_plan
 int plan_levels(uint64_t n_max, const TreeBufs& T, int force, bool lean = false);
 int check_cfg(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, int flags);
+// matcher_trees' treelet step (aicp_hip.cpp), behind the R matcher trees enqueued on s
+int matcher_treelets(aicp_hip_ctx* ctx, hipStream_t s, size_t R, uint64_t total_ref, PairDesc* dRdesc, int bucket,
+                     std::string& err);
 // The matcher's NN engine for R references: their treelet records allotted (rd[r].tl_off / tl_cap;
 // kernels_tree.hip: at most 1 + 4 per inner node at even depth), returned as the batch's total, or
 // 0 where treelets do not fit and the NN kernel runs on the node records (Trav<1>): leaf slots hold
@@ -322,6 +326,7 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
 void free_batch(aicp_hip_batch* B);
 // the stream's bound of a cloud's ray keys (sequence.cpp), per-point cap included
 extern const uint64_t kMaxRayKeys;
+extern const uint64_t kSeqMapBudget;  // bytes of a window's voxel maps beyond which it runs on key lists
 uint64_t key_bound(WorkerPool& pool, const aicp_cloud& c, const double* org, double res, bool rigid);
 
 // float AABB of a cloud's points and its sensor origin (the extent bounds its voxel maps)
@@ -347,6 +352,9 @@ struct Box {
     }
   }
 };
+
+// xyz at a byte stride -> float4 (w = 1) and the AABB of each cloud's finite points (sequence.cpp)
+void pack_clouds(WorkerPool& pool, const std::vector<PackSeg>& segs, std::vector<Box>& boxes);
 
 // The overlap of one stream window (sequence.cpp): one reference, np readings. The host's part is
 // a plan made from the clouds alone; the device's part runs in three steps that the stream puts
@@ -397,12 +405,6 @@ int ovl_window_read_side(std::string& err, hipStream_t s, const OvlWinDev& D, co
 int ovl_window_ref_side(std::string& err, hipStream_t s, const OvlWinDev& D, const double* origin0,
                         const float4* ref);
 int ovl_window_counts(std::string& err, hipStream_t s, const OvlWinDev& D);
-// aicp_hip_test_overlap's stream paths: every overlap group of the batch B as one window (path 3
-// maps sized on the device, 4 capped key lists); caps (nullable): explicit capacities per cloud,
-// groups then readings (bytes, or key words). Fills out's per-cloud and per-pair fields, the
-// descriptors and arena or the lists; out_dirty: changed guard words of its own buffers.
-int ovl_window_test(aicp_hip_ctx* ctx, const aicp_hip_batch* B, const aicp_pair* pairs, double res, int path,
-                    int filter, int wide, const uint64_t* caps, int rigid, aicp_test_overlap_out* out);
 // the device-resident map (aicp_hip.cpp), for the streams that grow it and crop it into a batch
 int map_reserve(aicp_hip_ctx* ctx, aicp_hip_map* map, size_t add);
 int map_crop_pairs(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float mx, const aicp_cloud* readings,
@@ -415,6 +417,9 @@ int map_crop_pairs(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float m
 int stream_prefilter_raw(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf, const aicp_cloud& c, const float* d_initT,
                          double* d_origin, float4* dst, uint32_t* kept);
 int stream_prefilter_check(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf);  // pf_check
+// a caller's raw rows into ctx->scratch at byte `off`: *drows / *dstride where, and their stride there
+int ingest_upload(aicp_hip_ctx* ctx, const float* pts, size_t n, size_t stride, size_t off, const void** drows,
+                  size_t* dstride);
 // stream_prefilter_raw for rows that may lie on the device already (session.cpp): dpts non-null: n
 // float4 rows on the device (the sweep accumulator's cloud, left unchanged; hpts / stride not read),
 // else the caller's rows are uploaded. pf null: no pre-filter, the n ingested points go straight to

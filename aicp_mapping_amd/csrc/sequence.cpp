@@ -168,11 +168,6 @@ void seq_state_free(SeqState* S) {
   delete S;
 }
 
-}  // namespace rt
-}  // namespace aicp
-
-namespace {
-
 // xyz at a byte stride -> float4 (w = 1) and the AABB of the finite points, in chunks over the pool
 void pack_clouds(WorkerPool& pool, const std::vector<PackSeg>& segs, std::vector<Box>& boxes) {
   constexpr uint64_t kChunk = 1 << 15;
@@ -206,6 +201,11 @@ void pack_clouds(WorkerPool& pool, const std::vector<PackSeg>& segs, std::vector
   for (size_t t = 0; t < tasks.size(); ++t) boxes[tasks[t].seg].merge(part[t]);
 }
 
+}  // namespace rt
+}  // namespace aicp
+
+namespace {
+
 // voxel-map capacity (bytes) of a cloud with AABB b plus origin o at resolution res: `rigid`
 // allows any rotation (a rigid motion keeps the diameter; the device sizes the box after the
 // transform), otherwise the axis extents. Both include the 2 + 2 voxels of padding, one more
@@ -233,15 +233,15 @@ uint64_t map_cap(const Box& b0, const double* o, double res, bool rigid) {
   return (vox + kOvlBrickBytes - 1) / kOvlBrickBytes * kOvlBrickBytes;
 }
 
-// A window's voxel maps beyond this many bytes (all of them together) take the sorted-key path
-// instead: a far return (a key box of 10^9+ voxels) or a very wide scan. The C2/C3 scenes need
-// ~3 MB per reading map and ~80 MB for a reference (sized for any rotation of its source).
-constexpr uint64_t kSeqMapBudget = uint64_t(1) << 30;
-
 }  // namespace
 
 namespace aicp {
 namespace rt {
+
+// A window's voxel maps beyond this many bytes (all of them together) take the sorted-key path
+// instead: a far return (a key box of 10^9+ voxels) or a very wide scan. The C2/C3 scenes need
+// ~3 MB per reading map and ~80 MB for a reference (sized for any rotation of its source).
+const uint64_t kSeqMapBudget = uint64_t(1) << 30;
 
 const uint64_t kMaxRayKeys = 3 * 65536 + 8;  // keys are 16-bit per axis: a ray's walk is bounded
 
@@ -1789,281 +1789,3 @@ int aicp_hip_last_sequence_timing(const aicp_hip_ctx* ctx, aicp_sequence_timing*
 }
 
 }  // extern "C"
-
-namespace aicp {
-namespace rt {
-
-// aicp_hip_test_overlap's paths 3 and 4: each overlap group of the batch as one stream window, on
-// buffers of this call, through the plan and the device steps the stream itself calls.
-int ovl_window_test(aicp_hip_ctx* ctx, const aicp_hip_batch* B, const aicp_pair* pairs, double res, int path,
-                    int filter, int wide, const uint64_t* caps, int rigid, aicp_test_overlap_out* out) {
-  const size_t P = B->P, G = B->gdesc.size();
-  hipStream_t s = ctx->stream;
-  WorkerPool pool{0};
-  constexpr size_t kGuard = 64;  // guard words of 8 bytes
-  constexpr uint32_t kFill32 = 0xA5A5A5A5u;
-  constexpr uint64_t kFill64 = 0xA5A5A5A5A5A5A5A5ull;
-  const bool sparse = path == 4;
-  struct Local {  // freed on every return
-    std::vector<DevBuf> bufs;
-    hipStream_t s;
-    DevBuf& get() {
-      bufs.reserve(64);
-      bufs.emplace_back();
-      return bufs.back();
-    }
-    ~Local() {
-      (void)hipStreamSynchronize(s);
-      for (DevBuf& b : bufs) release(b);
-    }
-  };
-  out->path = path;
-  out->filter = sparse ? 0 : (filter > 0);
-  out->wide = sparse ? 0 : (wide > 0);
-  out->n_groups = (int32_t)G;
-  out->arena_bytes = out->n_points = out->n_words = out->dirty = 0;
-  for (size_t p = 0; p < P; ++p) out->pair_group[p] = B->desc[p].ogroup;
-  uint64_t ref_pts_before = 0, total_ref_pts = 0, total_read_pts = 0;
-  for (size_t g = 0; g < G; ++g) total_ref_pts += B->gdesc[g].n_ref;
-  std::vector<uint64_t> read_first(P + 1, 0);
-  for (size_t p = 0; p < P; ++p) read_first[p + 1] = read_first[p] + pairs[p].n_read;
-  total_read_pts = read_first[P];
-  if (sparse && total_ref_pts + total_read_pts > out->points_cap) FAIL(AICP_ERR_INVALID, "points_cap");
-  if (sparse) out->n_points = total_ref_pts + total_read_pts;
-  for (size_t g = 0; g < G; ++g) {
-    Local loc{{}, s};
-    std::vector<size_t> idx;
-    for (size_t p = 0; p < P; ++p)
-      if ((size_t)B->desc[p].ogroup == g) idx.push_back(p);
-    const size_t np = idx.size();
-    const aicp_pair& p0 = pairs[idx[0]];
-    aicp_cloud src{p0.ref, p0.n_ref, p0.ref_stride, {p0.ref_origin[0], p0.ref_origin[1], p0.ref_origin[2]}};
-    const uint32_t n_ref = (uint32_t)src.n;
-    std::vector<aicp_cloud> reads(np);
-    std::vector<uint32_t> loff(np);
-    uint64_t nread = 0;
-    for (size_t i = 0; i < np; ++i) {
-      const aicp_pair& q = pairs[idx[i]];
-      reads[i] = aicp_cloud{q.read, q.n_read, q.read_stride, {q.read_origin[0], q.read_origin[1], q.read_origin[2]}};
-      loff[i] = (uint32_t)nread;
-      nread += q.n_read;
-    }
-    // pack (+ AABBs), descriptors, block maps: as the stream's window upload
-    std::vector<float> h_read(4 * nread), h_ref(4 * (size_t)n_ref);
-    std::vector<PackSeg> segs;
-    for (size_t i = 0; i < np; ++i) segs.push_back(PackSeg{reads[i].pts, reads[i].n, reads[i].stride, h_read.data() + 4 * (size_t)loff[i]});
-    segs.push_back(PackSeg{src.pts, src.n, src.stride, h_ref.data()});
-    std::vector<Box> boxes;
-    pack_clouds(pool, segs, boxes);
-    Maps mr, mg;
-    std::vector<PairDesc> hd(np + 1, PairDesc{});  // the readings, then the group
-    for (size_t i = 0; i < np; ++i) {
-      PairDesc& d = hd[i];
-      d.n_ref = n_ref;
-      d.read_off = loff[i];
-      d.n_read = (uint32_t)reads[i].n;
-      ident4(d.Tin);
-      d.ratio = 0.7f;
-      for (int k = 0; k < 3; ++k) {
-        d.read_origin[k] = reads[i].origin[k];
-        d.ref_origin[k] = src.origin[k];
-      }
-      mr.add((int)i, d.n_read, kNNBlock);
-    }
-    hd[np].n_ref = n_ref;
-    ident4(hd[np].Tin);
-    for (int k = 0; k < 3; ++k) hd[np].ref_origin[k] = src.origin[k];
-    mg.add(0, n_ref, kNNBlock);
-    OvlWinPlan W;
-    uint64_t cap_r = 0, cap_g = 0;
-    size_t tmp_rb = 0, tmp_gb = 0;
-    if (!sparse) {
-      ovl_window_slots(W, boxes[np], src.origin, rigid != 0, boxes.data(), reads.data(), np, res, false);
-      if (caps) {
-        W.bm = W.cap_max = 0;
-        for (size_t i = 0; i <= np; ++i) {
-          W.cap[i] = i == 0 ? caps[g] : caps[G + idx[i - 1]];
-          W.od[i].off = W.bm;
-          W.bm += (W.cap[i] + 127) & ~uint64_t(127);  // (the maps stay 128-byte aligned)
-          W.cap_max = std::max(W.cap_max, W.cap[i]);
-        }
-      }
-      if (W.bm > kSeqMapBudget)
-        FAIL(AICP_ERR_UNSUPPORTED, "the window's voxel maps exceed the stream's budget: it runs on key lists");
-      out->cloud_bound[g] = W.cap[0];
-      for (size_t i = 0; i < np; ++i) out->cloud_bound[G + idx[i]] = W.cap[1 + i];
-    } else {
-      ovl_window_keys(W, pool, src, src.origin, rigid != 0, reads.data(), loff.data(), np, res, false);
-      if (caps) {
-        W.cap_g = caps[g];
-        W.cap_r = 0;
-        for (size_t i = 0; i < np; ++i) W.cap_r += (W.kb_read[i] = caps[G + idx[i]]);
-      }
-      cap_r = W.cap_r;
-      cap_g = W.cap_g;
-      out->cloud_bound[g] = cap_g;
-      for (size_t i = 0; i < np; ++i) out->cloud_bound[G + idx[i]] = W.kb_read[i];
-      tmp_rb = ovl_keys_temp_bytes(nread, cap_r, (int)np);
-      tmp_gb = ovl_keys_temp_bytes(n_ref, cap_g, 1);
-      size_t free_b = 0, total_b = 0;
-      HIPC(hipMemGetInfo(&free_b, &total_b));
-      if (16 * (cap_r + cap_g) + tmp_rb + tmp_gb > free_b / 2)
-        FAIL(AICP_ERR_UNSUPPORTED, "sparse overlap: " + std::to_string(cap_r + cap_g) + " ray keys do not fit");
-    }
-    // device: points, descriptors, states, block maps
-    DevBuf &d_read = loc.get(), &d_ref = loc.get(), &d_desc = loc.get(), &d_state = loc.get(), &d_maps = loc.get();
-    HIPC(ensure(d_read, nread * 16));
-    HIPC(ensure(d_ref, (size_t)n_ref * 16));
-    HIPC(ensure(d_desc, (np + 1) * sizeof(PairDesc)));
-    HIPC(ensure(d_state, (np + 1) * sizeof(PairState)));
-    const size_t nr = mr.pair.size(), nf = mg.pair.size();
-    std::vector<uint32_t> hm(2 * (nr + nf));
-    std::memcpy(hm.data(), mr.pair.data(), nr * 4);
-    std::memcpy(hm.data() + nr, mr.start.data(), nr * 4);
-    std::memcpy(hm.data() + 2 * nr, mg.pair.data(), nf * 4);
-    std::memcpy(hm.data() + 2 * nr + nf, mg.start.data(), nf * 4);
-    HIPC(ensure(d_maps, hm.size() * 4));
-    HIPC(hipMemcpy(d_read.p, h_read.data(), nread * 16, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(d_ref.p, h_ref.data(), (size_t)n_ref * 16, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(d_desc.p, hd.data(), (np + 1) * sizeof(PairDesc), hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(d_maps.p, hm.data(), hm.size() * 4, hipMemcpyHostToDevice));
-    HIPC(hipMemsetAsync(d_state.p, 0, (np + 1) * sizeof(PairState), s));
-    PairDesc* dDesc = d_desc.as<PairDesc>();
-    PairState* dState = d_state.as<PairState>();
-    launch_init_state(s, (int)np + 1, dDesc, dState);
-    OvlWinDev D;
-    D.sparse = sparse;
-    D.np = np;
-    D.res = res;
-    D.dDesc = dDesc;
-    D.dState = dState;
-    D.dG = dDesc + np;
-    D.dGst = dState + np;
-    D.m_read = BlockMap{d_maps.as<int32_t>(), d_maps.as<uint32_t>() + nr, (uint32_t)nr};
-    D.m_gref = BlockMap{d_maps.as<int32_t>() + 2 * nr, d_maps.as<uint32_t>() + 2 * nr + nf, (uint32_t)nf};
-    D.filter = filter > 0;
-    D.wide = wide > 0;
-    OvlKeySide kr{}, kg{};
-    DevBuf &d_arena = loc.get(), &d_ovl = loc.get(), &d_cap = loc.get(), &d_par = loc.get(), &d_cnt = loc.get(),
-           &d_off = loc.get(), &d_kr = loc.get(), &d_kg = loc.get(), &d_tr = loc.get(), &d_tg = loc.get(),
-           &d_pc = loc.get();
-    const size_t kr_words = 2 * cap_r + 3 * kGuard, kg_words = 2 * cap_g + 3 * kGuard;
-    if (!sparse) {
-      HIPC(ensure(d_arena, W.bm + 2 * kGuard * 8));
-      HIPC(ensure(d_ovl, (np + 1) * sizeof(OvlDesc)));
-      HIPC(ensure(d_cap, (np + 1) * 8));
-      HIPC(hipMemsetD32Async((hipDeviceptr_t)d_arena.p, (int)kFill32, (W.bm + 2 * kGuard * 8) / 4, s));
-      HIPC(hipMemcpy(d_ovl.p, W.od.data(), (np + 1) * sizeof(OvlDesc), hipMemcpyHostToDevice));
-      HIPC(hipMemcpy(d_cap.p, W.cap.data(), (np + 1) * 8, hipMemcpyHostToDevice));
-      D.dOvl = d_ovl.as<OvlDesc>();
-      D.dCap = d_cap.as<uint64_t>();
-      D.bmp = d_arena.as<uint8_t>() + kGuard * 8;
-      D.cap_max = W.cap_max;
-      D.cap0 = W.cap[0];
-    } else {
-      const size_t ncl = W.scl.size(), nb = W.sbc.size();
-      std::vector<char> par(ncl * sizeof(OvlCloud) + 8 * nb);
-      std::memcpy(par.data(), W.scl.data(), ncl * sizeof(OvlCloud));
-      std::memcpy(par.data() + ncl * sizeof(OvlCloud), W.sbc.data(), nb * 4);
-      std::memcpy(par.data() + ncl * sizeof(OvlCloud) + nb * 4, W.sbs.data(), nb * 4);
-      HIPC(ensure(d_par, par.size()));
-      HIPC(hipMemcpy(d_par.p, par.data(), par.size(), hipMemcpyHostToDevice));
-      HIPC(ensure(d_cnt, (nread + n_ref) * 4));
-      HIPC(ensure(d_off, (nread + n_ref) * 8));
-      HIPC(ensure(d_kr, kr_words * 8));
-      HIPC(ensure(d_kg, kg_words * 8));
-      HIPC(ensure(d_tr, tmp_rb));
-      HIPC(ensure(d_tg, tmp_gb));
-      HIPC(ensure(d_pc, (2 * np + 1) * 8));
-      HIPC(hipMemsetD32Async((hipDeviceptr_t)d_kr.p, (int)kFill32, kr_words * 2, s));
-      HIPC(hipMemsetD32Async((hipDeviceptr_t)d_kg.p, (int)kFill32, kg_words * 2, s));
-      HIPC(hipMemsetAsync(d_cnt.p, 0, (nread + n_ref) * 4, s));
-      HIPC(hipMemsetAsync(d_off.p, 0, (nread + n_ref) * 8, s));
-      char* Dp = d_par.as<char>();
-      ovl_window_sides(W, np, nread, n_ref, reinterpret_cast<OvlCloud*>(Dp),
-                       reinterpret_cast<const uint32_t*>(Dp + ncl * sizeof(OvlCloud)), d_cnt.as<uint32_t>(),
-                       d_off.as<uint64_t>(), d_kr.as<uint64_t>() + kGuard, d_kg.as<uint64_t>() + kGuard, d_tr.p, tmp_rb,
-                       d_tg.p, tmp_gb, d_pc.as<unsigned long long>(), kr, kg);
-      kr.keys1 = kr.keys0 + cap_r + kGuard;  // (guard words between the emitted and the sorted array too)
-      kg.keys1 = kg.keys0 + cap_g + kGuard;
-      D.kr = &kr;
-      D.kg = &kg;
-      D.per_pair = d_pc.as<unsigned long long>() + np + 1;
-    }
-    int rc = ovl_window_read_side(ctx->err, s, D, d_read.as<float4>());
-    if (!rc) rc = ovl_window_ref_side(ctx->err, s, D, nullptr, d_ref.as<float4>());
-    if (!rc) rc = ovl_window_counts(ctx->err, s, D);
-    if (rc) return rc;
-    HIPC(hipGetLastError());
-    HIPC(hipStreamSynchronize(s));
-    // results
-    std::vector<PairState> hs(np + 1);
-    HIPC(hipMemcpy(hs.data(), dState, (np + 1) * sizeof(PairState), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i <= np; ++i) {
-      const size_t c = i == np ? g : G + idx[i];
-      out->cloud_keys[c] = hs[i].ovl_counts[i == np ? 0 : 1];
-      out->cloud_err[c] = hs[i].ovl_err;
-      for (int k = 0; k < 6; ++k) out->cloud_bbox[6 * c + k] = hs[i].ovl_bbox[k];
-      if (i == np) continue;
-      const size_t p = idx[i];
-      for (int k = 0; k < 3; ++k) out->pair_counts[3 * p + k] = hs[i].ovl_counts[k];
-      out->pair_percent[p] = hs[i].overlap;
-      out->pair_ratio[p] = hs[i].ratio;
-      out->pair_err[p] = hs[i].ovl_err;
-    }
-    if (!sparse) {
-      std::vector<OvlDesc> od(np + 1);
-      HIPC(hipMemcpy(od.data(), d_ovl.p, (np + 1) * sizeof(OvlDesc), hipMemcpyDeviceToHost));
-      for (size_t i = 0; i <= np; ++i) {
-        const size_t c = i == 0 ? g : G + idx[i - 1];
-        for (int k = 0; k < 3; ++k) {
-          out->desc_min[3 * c + k] = od[i].min[k];
-          out->desc_dim[3 * c + k] = od[i].dim[k];
-        }
-        out->desc_off[c] = out->arena_bytes + od[i].off;
-        out->desc_bytes[c] = od[i].bytes;
-      }
-      std::vector<uint8_t> back(W.bm + 2 * kGuard * 8);
-      HIPC(hipMemcpy(back.data(), d_arena.p, back.size(), hipMemcpyDeviceToHost));
-      const uint64_t* gw = reinterpret_cast<const uint64_t*>(back.data());
-      for (size_t k = 0; k < kGuard; ++k)
-        out->dirty += (gw[k] != kFill64) + (gw[(kGuard * 8 + W.bm) / 8 + k] != kFill64);
-      if (out->arena_bytes < out->arena_cap)
-        std::memcpy(out->arena + out->arena_bytes, back.data() + kGuard * 8,
-                    std::min<uint64_t>(W.bm, out->arena_cap - out->arena_bytes));
-      out->arena_bytes += W.bm;
-    } else {
-      std::vector<uint32_t> cnt(nread + n_ref);
-      std::vector<uint64_t> off(nread + n_ref);
-      HIPC(hipMemcpy(cnt.data(), d_cnt.p, cnt.size() * 4, hipMemcpyDeviceToHost));
-      HIPC(hipMemcpy(off.data(), d_off.p, off.size() * 8, hipMemcpyDeviceToHost));
-      std::memcpy(out->key_counts + ref_pts_before, cnt.data() + nread, (size_t)n_ref * 4);
-      std::memcpy(out->key_offsets + ref_pts_before, off.data() + nread, (size_t)n_ref * 8);
-      for (size_t i = 0; i < np; ++i) {
-        const uint64_t dst = total_ref_pts + read_first[idx[i]];
-        std::memcpy(out->key_counts + dst, cnt.data() + loff[i], (size_t)reads[i].n * 4);
-        std::memcpy(out->key_offsets + dst, off.data() + loff[i], (size_t)reads[i].n * 8);
-      }
-      for (int side = 0; side < 2; ++side) {
-        const uint64_t cap = side ? cap_g : cap_r;
-        const size_t words = side ? kg_words : kr_words;
-        std::vector<uint64_t> back(words);
-        HIPC(hipMemcpy(back.data(), side ? d_kg.p : d_kr.p, words * 8, hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < kGuard; ++k)
-          out->dirty += (back[k] != kFill64) + (back[kGuard + cap + k] != kFill64) +
-                        (back[2 * kGuard + 2 * cap + k] != kFill64);
-        out->list_off[2 * g + side] = out->n_words;
-        out->list_cap[2 * g + side] = cap;
-        if (out->n_words < out->words_cap)
-          std::memcpy(out->words + out->n_words, back.data() + 2 * kGuard + cap,
-                      8 * std::min<uint64_t>(cap, out->words_cap - out->n_words));
-        out->n_words += cap;
-      }
-    }
-    ref_pts_before += n_ref;
-  }
-  return AICP_OK;
-}
-
-}  // namespace rt
-}  // namespace aicp
