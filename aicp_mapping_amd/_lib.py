@@ -67,6 +67,9 @@ EXPORTS = [
     "aicp_hip_map_session_create", "aicp_hip_map_session_free", "aicp_hip_map_session_start",
     "aicp_hip_map_session_process", "aicp_hip_map_session_process_accum", "aicp_hip_map_session_state",
     "aicp_hip_map_session_last_timing",
+    "aicp_hip_session_set_monitor", "aicp_hip_session_last_monitor", "aicp_hip_session_monitor_counters",
+    "aicp_hip_mapsession_set_monitor", "aicp_hip_mapsession_last_monitor",
+    "aicp_hip_mapsession_monitor_counters", "aicp_hip_test_monitor_resident",
 ]
 
 
@@ -103,7 +106,11 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_map_session_last_timing",  # the live map sessions
            "aicp_hip_session_create_risk", "aicp_hip_session_start_pose", "aicp_hip_session_start_accum_pose",
            "aicp_hip_session_process_risk", "aicp_hip_session_process_accum_risk",
-           "aicp_hip_session_reference_pose"}  # the live session with the risk gate
+           "aicp_hip_session_reference_pose",  # the live session with the risk gate
+           "aicp_hip_session_set_monitor", "aicp_hip_session_last_monitor", "aicp_hip_session_monitor_counters",
+           "aicp_hip_mapsession_set_monitor", "aicp_hip_mapsession_last_monitor",
+           "aicp_hip_mapsession_monitor_counters",
+           "aicp_hip_test_monitor_resident"}  # the quality monitor per reading in the live sessions
 
 
 class IcpConfig(C.Structure):
@@ -690,6 +697,13 @@ def _load():
         L.aicp_hip_map_session_process_accum.argtypes = [vp, vp, vp, fp, fp, vp, u32p]
         L.aicp_hip_map_session_state.argtypes = [vp, vp, up, ip, fp, ip]
         L.aicp_hip_map_session_last_timing.argtypes = [vp, dp, dp]
+    if hasattr(L, "aicp_hip_session_set_monitor"):
+        mpp, mrp = C.POINTER(MonitorParams), C.POINTER(MonitorResult)
+        for kind in ("session", "mapsession"):
+            getattr(L, f"aicp_hip_{kind}_set_monitor").argtypes = [vp, vp, mpp]
+            getattr(L, f"aicp_hip_{kind}_last_monitor").argtypes = [vp, mrp, ip]
+            getattr(L, f"aicp_hip_{kind}_monitor_counters").argtypes = [vp, up]
+        L.aicp_hip_test_monitor_resident.argtypes = [vp, mpp, cfgp, fp, sz, fp, sz, fp, C.c_int32, mrp, up, up]
     return L
 
 
@@ -947,6 +961,63 @@ def default_monitor_params(**kw) -> MonitorParams:
             raise AttributeError(f"aicp_monitor_params has no field {k}")
         setattr(p, k, v)
     return p
+
+
+MONITOR_COUNTERS = ("readings", "trees", "reference_reuses", "chain_trees")
+
+
+def monitor_argument(monitor):
+    """The sessions' monitor= argument as aicp_monitor_params, or None for off: None / False (off),
+    True (the defaults), a MonitorParams, or a dict of quantile, max_accepted_dist and paired (bool:
+    AICP_MON_PAIRED, the paired mean distance through the session's chain)."""
+    if monitor is None or monitor is False:
+        return None
+    if monitor is True:
+        return default_monitor_params()
+    if isinstance(monitor, MonitorParams):
+        return MonitorParams.from_buffer_copy(monitor)
+    if not isinstance(monitor, dict):
+        raise TypeError(f"monitor: None, True, MonitorParams or dict, got {type(monitor).__name__}")
+    unknown = set(monitor) - {"quantile", "max_accepted_dist", "paired"}
+    if unknown:
+        raise ValueError(f"monitor: dict(quantile=, max_accepted_dist=, paired=), got {sorted(unknown)}")
+    kw = {k: monitor[k] for k in ("quantile", "max_accepted_dist") if k in monitor}
+    p = default_monitor_params(**kw)
+    if monitor.get("paired"):
+        p.flags |= AICP_MON_PAIRED
+    return p
+
+
+class SessionMonitor:
+    """set_monitor / last_monitor / monitor_counters of a live session (AppSession: kind "session",
+    MapSession: "mapsession"); the class has ctx and h."""
+    _monitor_kind = "session"
+
+    def _mon(self, name):
+        return getattr(lib, f"aicp_hip_{self._monitor_kind}_{name}")
+
+    def set_monitor(self, monitor=True) -> None:
+        """Switch the per-reading quality monitor on (True, a MonitorParams or a dict: see
+        monitor_argument) or off (None / False), any time after the session was made."""
+        p = monitor_argument(monitor)
+        self.ctx.check(self._mon("set_monitor")(self.ctx.h, self.h, None if p is None else C.byref(p)))
+
+    def last_monitor(self) -> dict:
+        """The last process call's result as Context.monitor's dict ("bytes": the 56 bytes) with
+        "valid": True after a call that registered its reading with the monitor on; otherwise False
+        and all zero bytes."""
+        res, valid = MonitorResult(), C.c_int32(0)
+        self.ctx.check(self._mon("last_monitor")(self.h, C.byref(res), C.byref(valid)))
+        d = res.as_dict()
+        d["valid"] = bool(valid.value)
+        return d
+
+    def monitor_counters(self) -> dict:
+        """readings (valid results), trees (bucket-8 trees built), reference_reuses (readings that
+        reused the session's reference tree), chain_trees (trees at the chain matcher's bucket size)."""
+        c = (C.c_uint64 * 4)()
+        self.ctx.check(self._mon("monitor_counters")(self.h, c))
+        return dict(zip(MONITOR_COUNTERS, (int(x) for x in c)))
 
 
 def _pose16(pose):
@@ -1773,6 +1844,20 @@ class Context:
         self.check(lib.aicp_hip_monitor_batch(self.h, C.byref(prm), C.byref(cfg) if cfg is not None else None, arr, n,
                                               _fptr(t) if t is not None else None, res))
         return [res[i].as_dict() for i in range(n)]
+
+    def test_monitor_resident(self, ref, read, T, cfg=None, params=None, runs=1):
+        """aicp_hip_test_monitor_resident: the monitor's resident core on ref / read (N, 3) and T
+        (4x4 row-major) from guarded device buffers, `runs` times on one reference tree. Returns
+        (result dict as monitor()'s, changed guard / input words, counters dict)."""
+        r = np.ascontiguousarray(as_points(ref)[:, :3], np.float32)
+        q = np.ascontiguousarray(as_points(read)[:, :3], np.float32)
+        prm = self._monitor_params(cfg, params)
+        t = self._T16(T, 1)
+        res, dirty, cnt = MonitorResult(), C.c_uint64(0), (C.c_uint64 * 4)()
+        self.check(lib.aicp_hip_test_monitor_resident(self.h, C.byref(prm), C.byref(cfg) if cfg is not None else None,
+                                                      _fptr(r), r.shape[0], _fptr(q), q.shape[0], _fptr(t), runs,
+                                                      C.byref(res), C.byref(dirty), cnt))
+        return res.as_dict(), int(dirty.value), dict(zip(MONITOR_COUNTERS, (int(x) for x in cnt)))
 
     def last_monitor_stats(self):
         st = MonitorStats()

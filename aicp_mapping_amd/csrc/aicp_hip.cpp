@@ -1203,6 +1203,7 @@ int aicp_hip_set_options(aicp_hip_ctx* ctx, const aicp_hip_options* o) {
   ctx->rdc.valid = false;
   ctx->opt = *o;
   for (auto& t : ctx->tb) tree_opts(t, ctx->opt);
+  tree_opts(ctx->tb_mon, ctx->opt);
   return AICP_OK;
 }
 
@@ -1223,6 +1224,7 @@ int aicp_hip_create(int device, aicp_hip_ctx** out) {
   c->device = device;
   aicp_hip_default_options(&c->opt);
   for (auto& t : c->tb) tree_opts(t, c->opt);
+  tree_opts(c->tb_mon, c->opt);
   // the overlap (stream) yields the CUs to the kd-tree streams, whose chains of short
   // level kernels are the critical path before the ICP loop
   int prio_lo = 0, prio_hi = 0;
@@ -1252,6 +1254,8 @@ void aicp_hip_destroy(aicp_hip_ctx* ctx) {
                     &ctx->tl_rank, &ctx->pf_a, &ctx->pf_b, &ctx->pf_bpts, &ctx->pf_nodes})
     release(*b);
   for (auto& t : ctx->tb) t.release_all();
+  ctx->tb_mon.release_all();
+  ctx->mon_scratch.release_all();
   free_batch(ctx->oneshot);
   free_batch(ctx->mapbatch);
   release(ctx->crop_ws);
@@ -1267,6 +1271,7 @@ void aicp_hip_destroy(aicp_hip_ctx* ctx) {
   release(ctx->pin_svm);
   for (DevBuf* b : {&ctx->mon_bpts, &ctx->mon_nodes, &ctx->mon_bpts2, &ctx->mon_nodes2, &ctx->mon_ws}) release(*b);
   release(ctx->pin_mon);
+  release(ctx->pin_mon_ctl);
   for (auto e : ctx->mon_ev)
     if (e) (void)hipEventDestroy(e);
   release(ctx->refc.gst);

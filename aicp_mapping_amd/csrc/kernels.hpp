@@ -561,6 +561,13 @@ struct MonOut {       // aicp_monitor_result's layout (include/aicp_hip.h)
 };
 // out cloud i (xf[i] = first point, count) = T[16 i ..] * itself, in k_transform's arithmetic
 void launch_mon_transform(hipStream_t s, BlockMap m, const uint2* xf, const float* T, float4* pts);
+// pts[0 .. n_ref) = ref, pts[n_ref + j] = T * read[j] (T: 16 floats in device memory, column-major;
+// k_transform's arithmetic, w = 1) for j < n_read; n_ref + n_read < 2^32, pts aliases neither input
+void launch_mon_stage(hipStream_t s, uint32_t n_ref, uint32_t n_read, const float4* ref, const float4* read,
+                      const float* T, float4* pts);
+// behind a planned tree build on s (ctl: its control block on the device): if the build left an
+// error, segments a[0 .. na) and b[0 .. nb) lose their queries and the 1-NN launches search nothing
+void launch_mon_guard(hipStream_t s, const TreeCtl* ctl, MonSeg* a, int na, MonSeg* b, int nb);
 // partial[2 slot], [2 slot + 1]: the chunk's sums of sqrt(d2) over the valid / the kept values;
 // dist (nullable): sqrt(d2) of every value, at d2's index
 void launch_mon_reduce(hipStream_t s, BlockMap m, const MonRed* red, const float* d2, const PairState* lim_st,

@@ -3,6 +3,8 @@
 // 1-NN launches (k_mon_nn, kernels_icp.hip) and the limits of the exact select (k_sel_*).
 //
 //   k_mon_transform   out = T * cloud for every pair of a batch, in k_transform's arithmetic
+//   k_mon_stage       the resident front end: a reference and a reading that lie on the device go
+//                     into the point arena, the reading moved by a correction in device memory
 //   k_mon_reduce      one pass over the squared distances, a flat grid over chunk slots (segments
 //                     differ in size by orders of magnitude): the maximum, distancesKNN's valid
 //                     count and sum and, under the select's limit, the kept count and sum
@@ -40,6 +42,43 @@ __global__ __launch_bounds__(kMonThreads) void k_mon_transform(BlockMap m, const
   float o[3];
   apply4(Tl, p.x, p.y, p.z, o);
   pts[c.x + j] = make_float4(o[0], o[1], o[2], 1.f);
+}
+
+// The resident front end (monitor.cpp: monitor_resident): a reference and a reading that lie on the
+// device already go into the point arena, the reference first, as the uploaded form lays them out.
+// One thread per point, one 128-bit load and one 128-bit store: a reference point is copied as it
+// is, a point of the reading is moved by the correction the registration left in device memory
+// (every thread reads the same 16 floats: the loads are uniform), in k_mon_transform's and
+// k_transform's expression (apply4, no FMA contraction, w = 1). No LDS, no atomics. pts aliases
+// neither input.
+__global__ __launch_bounds__(kMonThreads) void k_mon_stage(uint32_t n_ref, uint32_t n_read,
+                                                           const float4* __restrict__ ref,
+                                                           const float4* __restrict__ read,
+                                                           const float* __restrict__ T, float4* __restrict__ pts) {
+  const uint32_t i = blockIdx.x * kMonThreads + threadIdx.x;
+  if (i < n_ref) {
+    pts[i] = ref[i];
+    return;
+  }
+  const uint32_t j = i - n_ref;
+  if (j >= n_read) return;
+  float Tl[16];
+  for (int k = 0; k < 16; ++k) Tl[k] = T[k];
+  const float4 p = read[j];
+  float o[3];
+  apply4(Tl, p.x, p.y, p.z, o);
+  pts[i] = make_float4(o[0], o[1], o[2], 1.f);
+}
+
+// Behind a tree build whose levels were planned (nothing read back, so the host cannot refuse a
+// broken tree before the searches are enqueued): when the build left an error in its control block
+// (a tree deeper than the search stacks among them), every segment of the 1-NN launches loses its
+// queries, so that k_mon_nn finds only padding slots and no search enters the tree. The host reads
+// the same control block after the call and drops the result.
+__global__ void k_mon_guard(const TreeCtl* __restrict__ ctl, MonSeg* a, int na, MonSeg* b, int nb) {
+  if (!ctl->error) return;
+  for (int i = threadIdx.x; i < na; i += blockDim.x) a[i].nq = 0;
+  for (int i = threadIdx.x; i < nb; i += blockDim.x) b[i].nq = 0;
 }
 
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
@@ -159,6 +198,14 @@ __global__ void k_mon_finish(int n_pairs, const MonPair* __restrict__ mp, const 
 
 void launch_mon_transform(hipStream_t s, BlockMap m, const uint2* xf, const float* T, float4* pts) {
   if (m.n_blocks) k_mon_transform<<<m.n_blocks, kMonThreads, 0, s>>>(m, xf, T, pts);
+}
+void launch_mon_stage(hipStream_t s, uint32_t n_ref, uint32_t n_read, const float4* ref, const float4* read,
+                      const float* T, float4* pts) {
+  const uint64_t n = (uint64_t)n_ref + n_read;
+  if (n) k_mon_stage<<<(unsigned)((n + kMonThreads - 1) / kMonThreads), kMonThreads, 0, s>>>(n_ref, n_read, ref, read, T, pts);
+}
+void launch_mon_guard(hipStream_t s, const TreeCtl* ctl, MonSeg* a, int na, MonSeg* b, int nb) {
+  k_mon_guard<<<1, 64, 0, s>>>(ctl, a, na, b, nb);
 }
 void launch_mon_reduce(hipStream_t s, BlockMap m, const MonRed* red, const float* d2, const PairState* lim_st,
                        double max_accepted, MonAcc* acc, double* partial, float* dist) {

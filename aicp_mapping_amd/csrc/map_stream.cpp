@@ -31,6 +31,9 @@
 // decided on the device: the host makes room in the map before the crop when the mirrored count
 // says the reading appends if accepted, k_session_map_append runs right behind k_stream_commit and
 // does what the record says, and after the one read-back the host only adds to the map's size.
+// With the quality monitor on (aicp_hip_mapsession_set_monitor) a registered reading's metrics
+// against its crop are enqueued behind the batch and ahead of the commit (monitor_resident,
+// monitor.cpp), and their 56 bytes come back in that read-back.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -155,6 +158,13 @@ struct Live {
   hipEvent_t ev_done = nullptr;  // recorded behind the commit and the append
   bool reserved = false;         // room was made in the map: the append kernel runs
   bool registered = false;       // the window reached its batch (ev_done is recorded)
+  // the session's quality monitor (null: off): its counters, where its 56 bytes go in the session's
+  // block (read back with the record), whether it was enqueued, and its own error if it was not
+  const aicp_monitor_params* mon = nullptr;
+  MonCounters* mon_cnt = nullptr;
+  size_t mon_off = 0;
+  bool mon_ran = false;
+  std::string mon_err;
 };
 
 // how a window ended its stream, if it did
@@ -263,6 +273,21 @@ int stream_window(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg
     rc = run_batch(ctx, B, cfg, P.resolution, P.run_flags, out_T, stats.data(), nullptr);
     if (rc && stats[0].status == -1) return rc;  // the batch did not run to its end (not a reading's status)
     ++tm.windows;
+    // a session's monitor of a registered reading, ahead of the commit and the append: the crop and
+    // the reading where the batch holds them (the batch reads both only), the correction where the
+    // batch left it, the chain at the reading's own ratio. An error of its own only costs the result.
+    if (live && live->mon && stats[0].status == AICP_OK) {
+      aicp_icp_config mc = *cfg;
+      mc.trimmed_ratio = stats[0].trimmed_ratio;
+      const std::string why = ctx->err;
+      ctx->mon_scratch.invalidate();  // (the crop changes with every pose)
+      live->mon_ran = monitor_resident(ctx, live->mon, &mc, B->ref_raw.as<float4>() + B->rdesc[0].ref_off, htot[0],
+                                       B->read_raw.as<float4>() + B->desc[0].read_off, B->desc[0].n_read,
+                                       ctx->outT.as<float>(), &ctx->mon_scratch, live->mon_cnt,
+                                       reinterpret_cast<char*>(dS) + live->mon_off) == AICP_OK;
+      if (!live->mon_ran) live->mon_err = ctx->err;
+      ctx->err = why;
+    }
     // App's bookkeeping for the window, on the device; one read-back of its state and records
     launch_stream_commit(s, (int)wr, ctx->state.as<PairState>(), ctx->outT.as<float>(), K.dOrg, P.rules, dS, K.dRec);
     HIPC(hipGetLastError());
@@ -277,7 +302,8 @@ int stream_window(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg
       HIPC(hipEventRecord(live->ev_done, s));
       live->registered = true;
     }
-    HIPC(hipMemcpyAsync(K.pin, dS, kRecOff + wr * sizeof(StreamRec), hipMemcpyDeviceToHost, s));
+    const size_t back = live && live->mon_ran ? live->mon_off + sizeof(aicp_monitor_result) : kRecOff + wr * sizeof(StreamRec);
+    HIPC(hipMemcpyAsync(K.pin, dS, back, hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
     // the map changes the records ask for, in order (by the window rule: after the last reading)
     for (size_t i = 0; i < wr; ++i) {
@@ -402,9 +428,12 @@ int run_stream(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, a
 }
 
 // the live map session's small device block and its pinned mirror: StreamState | StreamRec | the
-// reading's prior origin (3 doubles), the streams' window layout with one record
-constexpr size_t kSessOrg = 192, kSessBytes = 256;
-static_assert(kRecOff + sizeof(StreamRec) <= kSessOrg && kSessOrg + 24 <= kSessBytes, "the session block's layout");
+// quality monitor's result | the reading's prior origin (3 doubles): the streams' window layout with
+// one record, and the result right behind it, so that one read-back brings both
+constexpr size_t kSessMon = 192, kSessOrg = 256, kSessBytes = 320;
+static_assert(kRecOff + sizeof(StreamRec) <= kSessMon && kSessMon + sizeof(aicp_monitor_result) <= kSessOrg &&
+                  kSessOrg + 24 <= kSessBytes,
+              "the session block's layout");
 
 }  // namespace
 
@@ -425,6 +454,12 @@ struct aicp_hip_map_session {
   std::vector<aicp_icp_stats> stats;
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   double last_wall_ms = 0, last_device_ms = 0;
+  // the per-reading quality monitor (aicp_hip_mapsession_set_monitor)
+  bool mon_on = false;
+  aicp_monitor_params mon_prm{};
+  MonCounters mon_cnt;
+  aicp_monitor_result mon_last{};
+  int32_t mon_valid = 0;
 };
 
 extern "C" {
@@ -665,6 +700,37 @@ int aicp_hip_map_session_start(aicp_hip_ctx* ctx, aicp_hip_map_session* s, aicp_
   s->n_processed = 0;
   s->started = true;
   s->ended = false;
+  s->mon_valid = 0;
+  std::memset(&s->mon_last, 0, sizeof(s->mon_last));
+  return AICP_OK;
+}
+
+int aicp_hip_mapsession_set_monitor(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const aicp_monitor_params* prm) {
+  if (!ctx || !s) return AICP_ERR_INVALID;
+  if (!prm) {
+    s->mon_on = false;
+    return AICP_OK;
+  }
+  const int rc = monitor_params_check(ctx, prm);
+  if (rc) return rc;
+  s->mon_prm = *prm;
+  s->mon_on = true;
+  return AICP_OK;
+}
+
+int aicp_hip_mapsession_last_monitor(const aicp_hip_map_session* s, aicp_monitor_result* out, int32_t* valid) {
+  if (!s || !out || !valid) return AICP_ERR_INVALID;
+  *out = s->mon_last;
+  *valid = s->mon_valid;
+  return AICP_OK;
+}
+
+int aicp_hip_mapsession_monitor_counters(const aicp_hip_map_session* s, uint64_t out[4]) {
+  if (!s || !out) return AICP_ERR_INVALID;
+  out[0] = s->mon_cnt.readings;
+  out[1] = s->mon_cnt.trees;
+  out[2] = s->mon_cnt.reuses;
+  out[3] = s->mon_cnt.trees2;
   return AICP_OK;
 }
 
@@ -691,6 +757,13 @@ static int map_session_process(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const
   hipStream_t st = ctx->stream;
   Live live;
   live.ev_done = s->ev_end;
+  if (s->mon_on) {
+    live.mon = &s->mon_prm;
+    live.mon_cnt = &s->mon_cnt;
+    live.mon_off = kSessMon;
+  }
+  s->mon_valid = 0;
+  std::memset(&s->mon_last, 0, sizeof(s->mon_last));
   aicp_cloud c{};
   if (reading) {
     c = *reading;
@@ -747,6 +820,16 @@ static int map_session_process(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const
                 : end.empty_read ? std::string(": keeps no point after the pre-filter")
                                  : ": status " + std::to_string(end.status) + ": " + why);
     return end.status;
+  }
+  // the monitor's result came back with the record; its own errors leave valid = 0 and the call as it is
+  if (live.mon_ran) {
+    if (monitor_resident_check(ctx, &ctx->mon_scratch, h + kSessMon) == AICP_OK) {
+      std::memcpy(&s->mon_last, h + kSessMon, sizeof(s->mon_last));
+      s->mon_valid = 1;
+      ++s->mon_cnt.readings;
+    }
+  } else if (!live.mon_err.empty()) {
+    ctx->err = live.mon_err;
   }
   ++s->n_processed;
   return AICP_OK;

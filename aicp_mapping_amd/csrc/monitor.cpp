@@ -12,8 +12,16 @@
 //      searches (epsilon > 0, a finite maxDist or another bucket size; else direction 0 serves)
 //   5. [device] the exact select: the quantile of both directions, then the trimmed limit
 //   6. [device] k_mon_reduce, k_mon_finish; D2H of the P results (and the per-point distances)
+//
+// The resident form (monitor_resident: the live sessions' monitor per reading) is
+// the same core behind another front end, for one pair whose clouds lie on the device: the tables
+// up, k_mon_stage instead of steps 1 and 2, every tree built alone with planned levels (the
+// reference's in the caller's buffers, reused while they are valid; k_mon_guard behind each build),
+// one 1-NN launch per direction, steps 5 and 6 with the result written where the caller says. It
+// reads nothing back and waits for nothing; monitor_resident_check follows the caller's own wait.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstddef>
@@ -71,9 +79,24 @@ uint32_t mon_slots(std::vector<MonSeg>& segs, std::vector<uint32_t>& chunk_seg) 
   return (uint32_t)slot;
 }
 
+// The resident form's pair (P = 1): both clouds and the correction where they lie on the device,
+// the reference's trees, and where k_mon_finish writes the result (device memory)
+struct MonResident {
+  const float4 *ref, *read;
+  const float* T;
+  MonRefTree* tree;
+  MonCounters* cnt;
+  MonOut* result;
+};
+
+// The front end gets the points into the arena: host packing, upload and k_mon_transform (R null:
+// aicp_hip_monitor, _batch), or k_mon_stage from resident clouds (R: monitor_resident, whose clouds
+// refs[0] / outs[0] only size). The core behind it starts from the arena: trees, k_mon_nn, the
+// selects, k_mon_reduce, k_mon_finish. The resident form reads nothing back and waits for nothing
+// when its tree levels are planned.
 int monitor_core(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_icp_config* cfg, size_t P,
                  const MonCloud* refs, const MonCloud* outs, const float* T, aicp_monitor_result* res, float* dist_out,
-                 float* dist_ref) {
+                 float* dist_ref, const MonResident* R = nullptr) {
   const auto w0 = std::chrono::steady_clock::now();
   if (!(prm->quantile >= 0.f && prm->quantile <= 1.f)) FAIL(AICP_ERR_INVALID, "monitor: quantile outside [0, 1]");
   const bool paired = (prm->flags & AICP_MON_PAIRED) != 0;
@@ -113,7 +136,8 @@ int monitor_core(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_i
   for (size_t t = 0; t < nT; ++t) {
     const size_t i = t % P;
     PairDesc& d = tdesc[t];
-    d.ref_off = t < P ? ref_off[i] : (uint32_t)(total_ref + out_loc[i]);
+    // (resident: every tree is built alone, from a pointer to its cloud's first point)
+    d.ref_off = R ? 0u : t < P ? ref_off[i] : (uint32_t)(total_ref + out_loc[i]);
     d.n_ref = (uint32_t)(t < P ? refs[i].n : outs[i].n);
     d.ratio = 0.5f;
     ident4(d.Tin);
@@ -159,7 +183,20 @@ int monitor_core(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_i
     mr.add((int)r, x.n, kMonChunk);
   }
   std::vector<uint32_t> chunkA, chunkB;
-  const uint32_t slotsA = mon_slots(segA, chunkA), slotsB = mon_slots(segB, chunkB);
+  uint32_t slotsA = 0, slotsA1 = 0;
+  if (R) {
+    // one launch per direction (the two trees lie in different buffers): each segment is its
+    // launch's segment 0 and its tree its array's tree 0; one table of zeros names both
+    std::vector<MonSeg> one(1);
+    std::vector<uint32_t> c0, c1;
+    segA[1].tree = 0;
+    one[0] = segA[0], slotsA = mon_slots(one, c0), segA[0] = one[0];
+    one[0] = segA[1], slotsA1 = mon_slots(one, c1), segA[1] = one[0];
+    chunkA = c0.size() >= c1.size() ? c0 : c1;
+  } else {
+    slotsA = mon_slots(segA, chunkA);
+  }
+  const uint32_t slotsB = mon_slots(segB, chunkB);
 
   // one block of tables, at the same offsets on both sides
   Arena a;
@@ -177,7 +214,7 @@ int monitor_core(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_i
   const size_t n_hist = std::max(selq.size(), selp.size());
   const size_t o_stq = a.take(selq.size() * sizeof(PairState)), o_stp = a.take(selp.size() * sizeof(PairState));
   const size_t o_zero = a.off;
-  const size_t o_ctr = a.take(2 * kPersistCtrWords * 4), o_hist = a.take(n_hist * kHistBins * 4),
+  const size_t o_ctr = a.take((R ? 3 : 2) * kPersistCtrWords * 4), o_hist = a.take(n_hist * kHistBins * 4),
                o_cnt = a.take(n_hist * 4), o_acc = a.take(red.size() * sizeof(MonAcc));
   const size_t zero_bytes = a.off - o_zero;
   const bool want_dist = dist_out || dist_ref;
@@ -189,7 +226,7 @@ int monitor_core(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_i
   HIPC(ensure(ctx->mon_ws, a.off));
   // pinned: the tables, the packed points, then the results (and the distances) coming back
   Arena h;
-  const size_t h_meta = h.take(meta_bytes), h_pts = h.take(total * 16), h_out = h.take(P * sizeof(MonOut)),
+  const size_t h_meta = h.take(meta_bytes), h_pts = h.take(R ? 0 : total * 16), h_out = h.take(P * sizeof(MonOut)),
                h_dist = h.take(want_dist ? total * 4 : 0);
   HIPC(ensure(ctx->pin_mon, h.off));
   for (auto& e : ctx->mon_ev)
@@ -222,52 +259,129 @@ int monitor_core(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_i
   put(o_xf, xf.data(), P * sizeof(uint2));
   put_map(o_mx, mx);
   if (T) put(o_T, T, P * 64);
-  float* hp = reinterpret_cast<float*>(ctx->pin_mon.as<char>() + h_pts);
-  std::vector<PackSeg> packs;
-  for (size_t i = 0; i < P; ++i) packs.push_back(PackSeg{refs[i].p, refs[i].n, refs[i].stride, hp + 4ull * ref_off[i]});
-  for (size_t i = 0; i < P; ++i)
-    packs.push_back(PackSeg{outs[i].p, outs[i].n, outs[i].stride, hp + 4ull * (total_ref + out_loc[i])});
-  pack_many(packs, ctx_pool(ctx));
-
-  HIPC(hipEventRecord(ctx->mon_ev[0], s));
-  HIPC(hipMemcpyAsync(dv, hm, meta_bytes, hipMemcpyHostToDevice, s));
-  HIPC(hipMemcpyAsync(dv + o_raw, hp, total * 16, hipMemcpyHostToDevice, s));
-  HIPC(hipMemsetAsync(dv + o_zero, 0, zero_bytes, s));
   float4* raw = (float4*)(dv + o_raw);
   PairDesc* dTd = (PairDesc*)(dv + o_td);
   PairDesc* dTd2 = (PairDesc*)(dv + o_td2);
-  if (T) launch_mon_transform(s, dev_map(o_mx, mx), (const uint2*)(dv + o_xf), (const float*)(dv + o_T), raw);
-  HIPC(hipGetLastError());
-
-  // ---- trees (host-polled levels, as the kernel-level entry points build theirs) ----------------
-  int rc = device_trees_begin(ctx->tb[0], ctx->err, s, nT, total, dTd, raw, 0, kMonBucket, ctx->mon_bpts, ctx->mon_nodes);
-  if (rc) return rc;
-  rc = device_trees_end(ctx->tb[0], ctx->err, s, nT, total, dTd, kMonBucket, ctx->mon_bpts, ctx->mon_nodes, 0);
-  if (rc) return rc;
-  if (trees2) {
-    rc = device_trees_begin(ctx->tb[0], ctx->err, s, P, total_ref, dTd2, raw, 0, cfg->bucket_size, ctx->mon_bpts2,
-                            ctx->mon_nodes2);
-    if (rc) return rc;
-    rc = device_trees_end(ctx->tb[0], ctx->err, s, P, total_ref, dTd2, cfg->bucket_size, ctx->mon_bpts2, ctx->mon_nodes2, 0);
-    if (rc) return rc;
-  }
-  HIPC(hipEventRecord(ctx->mon_ev[1], s));
-
-  // ---- 1-NN: squared distances only ---------------------------------------------------------------
+  int rc = AICP_OK;
   float* d2 = (float*)(dv + o_d2);
   uint32_t* ctr = (uint32_t*)(dv + o_ctr);
   const float inf = std::numeric_limits<float>::infinity();
-  launch_mon_nn(s, slotsA, (const MonSeg*)(dv + o_sa), (const uint32_t*)(dv + o_ca), dTd, raw, ctx->mon_nodes.as<uint4>(),
-                ctx->mon_bpts.as<float4>(), 1.f, inf, d2, ctr);
-  if (eps_search) {
-    const float maxE2 = (1 + cfg->nn_epsilon) * (1 + cfg->nn_epsilon);
-    const float maxR2 = cfg->nn_max_dist * cfg->nn_max_dist;
-    launch_mon_nn(s, slotsB, (const MonSeg*)(dv + o_sb), (const uint32_t*)(dv + o_cb), trees2 ? dTd2 : dTd, raw,
-                  (trees2 ? ctx->mon_nodes2 : ctx->mon_nodes).as<uint4>(),
-                  (trees2 ? ctx->mon_bpts2 : ctx->mon_bpts).as<float4>(), maxE2, maxR2, d2, ctr + kPersistCtrWords);
+  const float maxE2 = paired ? (1 + cfg->nn_epsilon) * (1 + cfg->nn_epsilon) : 1.f;
+  const float maxR2 = paired ? cfg->nn_max_dist * cfg->nn_max_dist : inf;
+  if (R) {
+    // ---- the resident front end: the tables up, both clouds into the arena on the device -----------
+    HIPC(hipMemcpyAsync(dv, hm, meta_bytes, hipMemcpyHostToDevice, s));
+    HIPC(hipMemsetAsync(dv + o_zero, 0, zero_bytes, s));
+    launch_mon_stage(s, (uint32_t)total_ref, (uint32_t)total_out, R->ref, R->read, R->T, raw);
+    HIPC(hipGetLastError());
+    // ---- trees: each built alone, its levels planned as run_batch plans its own (a plan of 0, which
+    // aicp_hip_options::tree_plan = -1 asks for there too, polls). The reference's lie in the caller's
+    // buffers and are built only when they are not the current reference's; the reading's, over
+    // `out`, is built every time. The planned builds leave their control blocks in pin_mon_ctl for
+    // monitor_resident_check.
+    MonRefTree& rt = *R->tree;
+    TreeBufs& tb = ctx->tb_mon;
+    HIPC(ensure(ctx->pin_mon_ctl, 3 * sizeof(TreeCtl)));
+    TreeCtl* ctl = ctx->pin_mon_ctl.as<TreeCtl>();
+    for (int& p : ctx->mon_planned) p = 0;
+    const uint64_t n_max = std::max(total_ref, total_out);
+    const int plan = plan_levels(n_max, tb, ctx->opt.tree_plan);
+    // (the work space for the larger cloud first: it is not reallocated between the builds)
+    rc = device_trees_begin(tb, ctx->err, s, 1, n_max, dTd + 1, raw, 0, kMonBucket, ctx->mon_bpts, ctx->mon_nodes, false);
+    if (rc) return rc;
+    auto build = [&](uint64_t n, PairDesc* desc, const float4* pts, int bucket, DevBuf& bpts, DevBuf& nodes, int slot) {
+      int r = device_trees_begin(tb, ctx->err, s, 1, n, desc, pts, 0, bucket, bpts, nodes);
+      if (!r) r = device_trees_end(tb, ctx->err, s, 1, n, desc, bucket, bpts, nodes, plan, ctl + slot);
+      ctx->mon_planned[slot] = r ? 0 : tb.planned;
+      // (a planned build's error is known on the device only: k_mon_guard keeps the searches out of
+      // a tree deeper than their stacks; a polled build has returned it above)
+      if (!r && tb.planned)
+        launch_mon_guard(s, tb.tw.ctl, (MonSeg*)(dv + o_sa), (int)segA.size(), (MonSeg*)(dv + o_sb), (int)segB.size());
+      return r;
+    };
+    HIPC(hipMemsetAsync(d2, 0, total_d2 * 4, s));  // (searches the guard switched off leave it defined)
+    if (rt.valid) {
+      ++R->cnt->reuses;
+    } else {
+      HIPC(ensure(rt.desc, sizeof(PairDesc)));
+      HIPC(hipMemcpyAsync(rt.desc.p, hm + o_td, sizeof(PairDesc), hipMemcpyHostToDevice, s));
+      rc = build(total_ref, rt.desc.as<PairDesc>(), raw, kMonBucket, rt.bpts, rt.nodes, 0);
+      if (rc) return rc;
+      rt.valid = true;
+      ++R->cnt->trees;
+    }
+    if (trees2 && !(rt.valid2 && rt.bucket2 == cfg->bucket_size)) {
+      rt.valid2 = false;
+      HIPC(ensure(rt.desc2, sizeof(PairDesc)));
+      HIPC(hipMemcpyAsync(rt.desc2.p, hm + o_td, sizeof(PairDesc), hipMemcpyHostToDevice, s));
+      rc = build(total_ref, rt.desc2.as<PairDesc>(), raw, cfg->bucket_size, rt.bpts2, rt.nodes2, 1);
+      if (rc) {
+        rt.invalidate();
+        return rc;
+      }
+      rt.valid2 = true;
+      rt.bucket2 = cfg->bucket_size;
+      ++R->cnt->trees2;
+    }
+    rc = build(total_out, dTd + 1, raw + total_ref, kMonBucket, ctx->mon_bpts, ctx->mon_nodes, 2);
+    if (rc) {
+      rt.invalidate();
+      return rc;
+    }
+    ++R->cnt->trees;
+    // ---- 1-NN: one launch per direction, the same searches in the same trees as the joined launch ----
+    const MonSeg* sa = (const MonSeg*)(dv + o_sa);
+    const uint32_t* ca = (const uint32_t*)(dv + o_ca);
+    launch_mon_nn(s, slotsA, sa, ca, rt.desc.as<PairDesc>(), raw, rt.nodes.as<uint4>(), rt.bpts.as<float4>(), 1.f, inf, d2,
+                  ctr);
+    launch_mon_nn(s, slotsA1, sa + 1, ca, dTd + 1, raw, ctx->mon_nodes.as<uint4>(), ctx->mon_bpts.as<float4>(), 1.f, inf,
+                  d2, ctr + kPersistCtrWords);
+    if (eps_search)
+      launch_mon_nn(s, slotsB, (const MonSeg*)(dv + o_sb), (const uint32_t*)(dv + o_cb),
+                    (trees2 ? rt.desc2 : rt.desc).as<PairDesc>(), raw, (trees2 ? rt.nodes2 : rt.nodes).as<uint4>(),
+                    (trees2 ? rt.bpts2 : rt.bpts).as<float4>(), maxE2, maxR2, d2, ctr + 2 * kPersistCtrWords);
+    HIPC(hipGetLastError());
+  } else {
+    float* hp = reinterpret_cast<float*>(ctx->pin_mon.as<char>() + h_pts);
+    std::vector<PackSeg> packs;
+    for (size_t i = 0; i < P; ++i)
+      packs.push_back(PackSeg{refs[i].p, refs[i].n, refs[i].stride, hp + 4ull * ref_off[i]});
+    for (size_t i = 0; i < P; ++i)
+      packs.push_back(PackSeg{outs[i].p, outs[i].n, outs[i].stride, hp + 4ull * (total_ref + out_loc[i])});
+    pack_many(packs, ctx_pool(ctx));
+
+    HIPC(hipEventRecord(ctx->mon_ev[0], s));
+    HIPC(hipMemcpyAsync(dv, hm, meta_bytes, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(dv + o_raw, hp, total * 16, hipMemcpyHostToDevice, s));
+    HIPC(hipMemsetAsync(dv + o_zero, 0, zero_bytes, s));
+    if (T) launch_mon_transform(s, dev_map(o_mx, mx), (const uint2*)(dv + o_xf), (const float*)(dv + o_T), raw);
+    HIPC(hipGetLastError());
+
+    // ---- trees (host-polled levels, as the kernel-level entry points build theirs) ----------------
+    rc = device_trees_begin(ctx->tb[0], ctx->err, s, nT, total, dTd, raw, 0, kMonBucket, ctx->mon_bpts, ctx->mon_nodes);
+    if (rc) return rc;
+    rc = device_trees_end(ctx->tb[0], ctx->err, s, nT, total, dTd, kMonBucket, ctx->mon_bpts, ctx->mon_nodes, 0);
+    if (rc) return rc;
+    if (trees2) {
+      rc = device_trees_begin(ctx->tb[0], ctx->err, s, P, total_ref, dTd2, raw, 0, cfg->bucket_size, ctx->mon_bpts2,
+                              ctx->mon_nodes2);
+      if (rc) return rc;
+      rc = device_trees_end(ctx->tb[0], ctx->err, s, P, total_ref, dTd2, cfg->bucket_size, ctx->mon_bpts2,
+                            ctx->mon_nodes2, 0);
+      if (rc) return rc;
+    }
+    HIPC(hipEventRecord(ctx->mon_ev[1], s));
+
+    // ---- 1-NN: squared distances only ---------------------------------------------------------------
+    launch_mon_nn(s, slotsA, (const MonSeg*)(dv + o_sa), (const uint32_t*)(dv + o_ca), dTd, raw,
+                  ctx->mon_nodes.as<uint4>(), ctx->mon_bpts.as<float4>(), 1.f, inf, d2, ctr);
+    if (eps_search)
+      launch_mon_nn(s, slotsB, (const MonSeg*)(dv + o_sb), (const uint32_t*)(dv + o_cb), trees2 ? dTd2 : dTd, raw,
+                    (trees2 ? ctx->mon_nodes2 : ctx->mon_nodes).as<uint4>(),
+                    (trees2 ? ctx->mon_bpts2 : ctx->mon_bpts).as<float4>(), maxE2, maxR2, d2, ctr + kPersistCtrWords);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(ctx->mon_ev[2], s));
   }
-  HIPC(hipGetLastError());
-  HIPC(hipEventRecord(ctx->mon_ev[2], s));
 
   // ---- quantiles (the exact select), reduction, results ---------------------------------------------
   uint32_t* hist = (uint32_t*)(dv + o_hist);
@@ -285,8 +399,9 @@ int monitor_core(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_i
   launch_mon_reduce(s, dev_map(o_mr, mr), (const MonRed*)(dv + o_rd), d2, paired ? stp : nullptr, prm->max_accepted_dist,
                     (MonAcc*)(dv + o_acc), (double*)(dv + o_part), ddist);
   launch_mon_finish(s, (int)P, (const MonPair*)(dv + o_pr), (const MonRed*)(dv + o_rd), (const MonAcc*)(dv + o_acc),
-                    (const double*)(dv + o_part), stq, paired ? stp : nullptr, (MonOut*)(dv + o_out));
+                    (const double*)(dv + o_part), stq, paired ? stp : nullptr, R ? R->result : (MonOut*)(dv + o_out));
   HIPC(hipGetLastError());
+  if (R) return AICP_OK;  // (the result stays on the device: the caller's read-back brings it)
   HIPC(hipEventRecord(ctx->mon_ev[3], s));
   char* ho = ctx->pin_mon.as<char>() + h_out;
   HIPC(hipMemcpyAsync(ho, dv + o_out, P * sizeof(MonOut), hipMemcpyDeviceToHost, s));
@@ -311,6 +426,52 @@ int monitor_core(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_i
 }
 
 }  // namespace
+
+namespace aicp {
+namespace rt {
+
+int monitor_params_check(aicp_hip_ctx* ctx, const aicp_monitor_params* prm) {
+  if (!(prm->quantile >= 0.f && prm->quantile <= 1.f)) FAIL(AICP_ERR_INVALID, "monitor: quantile outside [0, 1]");
+  return AICP_OK;
+}
+
+int monitor_resident(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_icp_config* cfg,
+                     const float4* d_ref, size_t n_ref, const float4* d_read, size_t n_read, const float* d_T,
+                     MonRefTree* tree, MonCounters* cnt, void* d_result) {
+  const MonCloud r{reinterpret_cast<const float*>(d_ref), n_ref, 16}, o{reinterpret_cast<const float*>(d_read), n_read, 16};
+  const MonResident R{d_ref, d_read, d_T, tree, cnt, static_cast<MonOut*>(d_result)};
+  const int rc = monitor_core(ctx, prm, cfg, 1, &r, &o, nullptr, nullptr, nullptr, nullptr, &R);
+  if (rc) tree->invalidate();
+  return rc;
+}
+
+int monitor_resident_check(aicp_hip_ctx* ctx, MonRefTree* tree, const void* h_result) {
+  TreeBufs& tb = ctx->tb_mon;
+  const TreeCtl* ctl = ctx->pin_mon_ctl.as<TreeCtl>();
+  int rc = AICP_OK, needed = 0;
+  for (int k = 0; k < 3; ++k) {
+    if (!ctx->mon_planned[k]) continue;
+    tb.planned = ctx->mon_planned[k];
+    std::string err;
+    const int r = device_trees_check_ctl(tb, ctl + k, err);
+    needed = std::max(needed, tb.needed);  // (the next plan follows the deepest of the builds)
+    if (r && !rc) {
+      rc = r;
+      ctx->err = "monitor: " + err;
+    }
+    ctx->mon_planned[k] = 0;
+  }
+  if (needed) tb.needed = needed;
+  if (!rc && static_cast<const MonOut*>(h_result)->pad) {
+    rc = AICP_ERR_CONVERGENCE;
+    ctx->err = "monitor: a direction without a finite distance";
+  }
+  if (rc) tree->invalidate();
+  return rc;
+}
+
+}  // namespace rt
+}  // namespace aicp
 
 extern "C" {
 

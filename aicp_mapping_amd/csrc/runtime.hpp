@@ -208,6 +208,45 @@ int device_trees_check(TreeBufs& T, std::string& err);
 // force: aicp_hip_options::tree_plan
 int plan_levels(uint64_t n_max, const TreeBufs& T, int force, bool lean = false);
 int check_cfg(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, int flags);
+
+// ---- the resident form of the quality monitor (monitor.cpp) -----------------------------------
+// The monitor's trees over one reference, in buffers of their own: the bucket-8 tree of both exact
+// searches and, when the chain matcher's bucket size differs, the matcher's. A live App session
+// owns one and keeps it for as long as its reference stays (valid / valid2: the trees were built
+// from the current reference); the map sessions' crops change with every pose, so theirs (the
+// context's) is rebuilt per reading.
+struct MonRefTree {
+  DevBuf bpts, nodes, desc;     // bucket 8; desc: the tree's one PairDesc, filled in by the build
+  DevBuf bpts2, nodes2, desc2;  // the chain matcher's bucket size
+  bool valid = false, valid2 = false;
+  int bucket2 = 0;
+  void invalidate() { valid = valid2 = false; }
+  void release_all() {
+    for (DevBuf* b : {&bpts, &nodes, &desc, &bpts2, &nodes2, &desc2}) release(*b);
+    invalidate();
+  }
+};
+// monitored readings, bucket-8 trees built, reference-tree reuses, chain-bucket trees built
+struct MonCounters {
+  uint64_t readings = 0, trees = 0, reuses = 0, trees2 = 0;
+};
+// One resident pair behind everything enqueued on ctx->stream: d_ref (n_ref float4) and d_read
+// (n_read float4) where they lie, d_T the 16 floats of the correction in device memory;
+// k_mon_stage, the trees (tree's when it is valid, else built into it), the searches, the selects,
+// the reduction, and k_mon_finish writes the 56 bytes to d_result (device memory). Nothing is read
+// back and nothing is waited for when the tree levels are planned (plan_levels on ctx->tb_mon, as
+// run_batch plans its own; aicp_hip_options::tree_plan = -1 polls, as there). cfg: with
+// AICP_MON_PAIRED, the chain. A non-zero return: nothing usable was enqueued (tree->valid is
+// cleared). Otherwise, once the stream has been waited for, monitor_resident_check.
+int monitor_resident(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_icp_config* cfg,
+                     const float4* d_ref, size_t n_ref, const float4* d_read, size_t n_read, const float* d_T,
+                     MonRefTree* tree, MonCounters* cnt, void* d_result);
+// After the stream that ran monitor_resident has completed, with the host's copy of its 56 bytes: a
+// planned tree deeper than the device stacks (AICP_ERR_UNSUPPORTED) or a direction without a finite
+// distance (AICP_ERR_CONVERGENCE), the reason in ctx->err; tree->valid is cleared then.
+int monitor_resident_check(aicp_hip_ctx* ctx, MonRefTree* tree, const void* h_result);
+int monitor_params_check(aicp_hip_ctx* ctx, const aicp_monitor_params* prm);
+
 // matcher_trees' treelet step (aicp_hip.cpp), behind the R matcher trees enqueued on s
 int matcher_treelets(aicp_hip_ctx* ctx, hipStream_t s, size_t R, uint64_t total_ref, PairDesc* dRdesc, int bucket,
                      std::string& err);
@@ -531,6 +570,13 @@ struct aicp_hip_ctx {
   aicp::rt::PinBuf pin_mon;
   hipEvent_t mon_ev[5] = {};
   aicp_monitor_stats last_mon{};
+  // its resident form (monitor_resident): the tree builder's work space and plan of its own (tb[0]'s
+  // plan follows run_batch's raw trees), the planned builds' control blocks (reference tree, chain
+  // matcher's tree, the reading's tree) and the map sessions' per-reading reference trees
+  aicp::rt::TreeBufs tb_mon;
+  aicp::rt::PinBuf pin_mon_ctl;
+  int mon_planned[3] = {0, 0, 0};  // the levels planned for each control block's build (0: none, or polled)
+  aicp::rt::MonRefTree mon_scratch;
   aicp_hip_options opt{};  // aicp_hip_set_options (read by the calls; nothing reads the environment)
 };
 constexpr int kBatchPolls = 64;

@@ -20,6 +20,12 @@
 // reading ends there; otherwise the ICP-only batch at the device's ratio, k_stream_commit and
 // k_session_promote follow as above. The reference's pose stays on the host in double.
 //
+// With the quality monitor on (aicp_hip_session_set_monitor), a registered reading's metrics are
+// enqueued behind its batch and ahead of k_stream_commit (monitor_resident, monitor.cpp: the
+// reference where it lies, the reading as registered, the correction in device memory; the
+// monitor's tree over the reference is the session's and is kept while the reference stays), and
+// their 56 bytes come back in the same read-back.
+//
 // The reference lives in one of two buffers; a promotion writes the other one and the host flips
 // them when the record reports it, so a reading that is dropped or fails leaves the reference as it
 // was and a larger reference never needs a copy. Its identity in the reference cache is a number
@@ -42,12 +48,15 @@ using namespace aicp::rt;
 
 namespace {
 // the session's small device block and its pinned mirror
-constexpr size_t kOffState = 0, kOffRec = 128, kOffHdr = 192, kOffOrigin = 256, kOffGate = 320, kWinBytes = 384;
-constexpr size_t kReadBack = kOffOrigin;                       // state + record + header
-constexpr size_t kReadBackGate = kOffGate + sizeof(GateRec);   // and, behind the origin, the gate's record
+constexpr size_t kOffState = 0, kOffRec = 128, kOffHdr = 192, kOffGate = 256, kOffMon = 320, kOffOrigin = 384,
+                 kWinBytes = 448;
+constexpr size_t kReadBack = kOffGate;                            // state + record + header
+constexpr size_t kReadBackGate = kOffGate + sizeof(GateRec);      // and the gate's record
+constexpr size_t kReadBackMon = kOffMon + sizeof(aicp_monitor_result);  // a monitored reading: and its 56 bytes
 static_assert(sizeof(StreamState) <= kOffRec && kOffRec + sizeof(StreamRec) <= kOffHdr &&
-                  kOffHdr + sizeof(SessionHeader) <= kOffOrigin && kOffRec % alignof(StreamRec) == 0 &&
-                  kOffOrigin + 24 <= kOffGate && kReadBackGate <= kWinBytes && kOffGate % alignof(GateRec) == 0,
+                  kOffHdr + sizeof(SessionHeader) <= kOffGate && kOffRec % alignof(StreamRec) == 0 &&
+                  kReadBackGate <= kOffMon && kOffGate % alignof(GateRec) == 0 && kReadBackMon <= kOffOrigin &&
+                  kOffMon % 8 == 0 && kOffOrigin + 24 <= kWinBytes,
               "win's layout");
 constexpr int kFlags = AICP_RUN_OVERLAP | AICP_SEQ_DEBUG | AICP_RUN_TIME_NN;
 }  // namespace
@@ -58,7 +67,7 @@ struct aicp_hip_session {
   aicp_prefilter_params pf{};
   bool has_pf = false;
   StreamRules rules{};
-  DevBuf win;     // StreamState | StreamRec | SessionHeader | the reading's prior origin (3 doubles) | GateRec
+  DevBuf win;     // StreamState | StreamRec | SessionHeader | GateRec | the monitor's result | the prior origin (3 doubles)
   PinBuf pin;     // its mirror
   DevBuf ref[2];  // the reference (float4, w = 1) and the buffer the next promotion writes
   int cur = 0;
@@ -79,11 +88,26 @@ struct aicp_hip_session {
   const aicp_hip_svm* model = nullptr;
   double threshold = 0;
   double ref_pose[16] = {};
+  // the per-reading quality monitor (aicp_hip_session_set_monitor): its parameters, the monitor's
+  // trees over the current reference (built on the first monitored reading against it, kept until
+  // the reference changes), the counters, and the last call's result
+  bool mon_on = false;
+  aicp_monitor_params mon_prm{};
+  MonRefTree mon_tree;
+  MonCounters mon_cnt;
+  aicp_monitor_result mon_last{};
+  int32_t mon_valid = 0;
 };
 
 namespace {
 
 StreamState* host_state(aicp_hip_session* s) { return reinterpret_cast<StreamState*>(s->pin.as<char>() + kOffState); }
+
+// this call leaves no monitor result (valid = 0, all zero bytes)
+void no_monitor(aicp_hip_session* s) {
+  s->mon_valid = 0;
+  std::memset(&s->mon_last, 0, sizeof(s->mon_last));
+}
 
 // rows of a reading: the caller's (c) or the accumulator's cloud where it lies
 struct Rows {
@@ -140,6 +164,8 @@ int start_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, const doub
   s->ref_id = -1;
   for (int k = 0; k < 3; ++k) s->ref_origin[k] = r.origin[k];
   s->gen = ctx->refc.next_owner++;
+  s->mon_tree.invalidate();
+  no_monitor(s);
   s->n_processed = 0;
   s->started = true;
   s->ended = false;
@@ -201,6 +227,7 @@ int process_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, float* o
   out->reference = s->ref_id;
   ident4(out_T);
   if (kept_out) *kept_out = 0;
+  no_monitor(s);
   // a reading with no point, or one the pre-filter empties, fails its registration (libpointmatcher
   // throws on an empty cloud), which ends the worker (app.cpp:210)
   auto empty_reading = [&]() {
@@ -260,12 +287,27 @@ int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, int32_
   if (promoted) *promoted = false;
   DevBuf& spare = s->ref[1 - s->cur];
   HIPC(ensure(spare, (size_t)kept * 16));
+  // The monitor of a registered reading, ahead of the commit and the promotion: it reads the
+  // reference the reading was registered against where it lies (a promotion writes the spare
+  // buffer), the reading as registered and the correction the batch left in device memory, with
+  // the chain at the reading's own tuned ratio. An error of its own only costs the result.
+  bool mon_ran = false;
+  std::string mon_err;
+  if (s->mon_on && rc == AICP_OK) {
+    aicp_icp_config mc = s->cfg;
+    mc.trimmed_ratio = out->icp.trimmed_ratio;
+    const std::string why = ctx->err;
+    mon_ran = monitor_resident(ctx, &s->mon_prm, &mc, s->ref[s->cur].as<float4>(), s->ref_n, s->read.as<float4>(), kept,
+                               ctx->outT.as<float>(), &s->mon_tree, &s->mon_cnt, d + kOffMon) == AICP_OK;
+    if (!mon_ran) mon_err = ctx->err;
+    ctx->err = why;
+  }
   launch_stream_commit(st, 1, ctx->state.as<PairState>(), ctx->outT.as<float>(), dOrg, s->rules, dS, dRec);
   launch_session_promote(st, (int)kept, dRec, ctx->outT.as<float>(), s->read.as<float4>(), id, spare.as<float4>(),
                          dHdr);
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(s->ev_end, st));
-  HIPC(hipMemcpyAsync(h, d, kReadBack, hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(h, d, mon_ran ? kReadBackMon : kReadBack, hipMemcpyDeviceToHost, st));
   HIPC(hipStreamSynchronize(st));
   const StreamRec& rec = *reinterpret_cast<const StreamRec*>(h + kOffRec);
   const SessionHeader& hdr = *reinterpret_cast<const SessionHeader*>(h + kOffHdr);
@@ -296,6 +338,16 @@ int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, int32_
     s->gen = ctx->refc.next_owner++;  // (the cached trees and voxel map are the old reference's: stale)
     if (promoted) *promoted = true;
   }
+  if (mon_ran) {  // (before the reference's trees are dropped: the check clears them on an error anyway)
+    if (monitor_resident_check(ctx, &s->mon_tree, h + kOffMon) == AICP_OK) {
+      std::memcpy(&s->mon_last, h + kOffMon, sizeof(s->mon_last));
+      s->mon_valid = 1;
+      ++s->mon_cnt.readings;
+    }
+  } else if (!mon_err.empty()) {
+    ctx->err = mon_err;
+  }
+  if (rec.append) s->mon_tree.invalidate();  // (the monitor's trees are the old reference's)
   ++s->n_processed;
   return AICP_OK;
 }
@@ -314,6 +366,7 @@ int process_rows_risk(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, con
   ident4(out_T);
   *prec = aicp_pipeline_record{};
   if (kept_out) *kept_out = 0;
+  no_monitor(s);
   auto failed = [&](int rc, const std::string& why) {  // the worker ends here (app.cpp:210)
     out->status = out->icp.status = rc;
     (void)end_session(ctx, s, rc);
@@ -401,6 +454,7 @@ int process_rows_risk(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, con
     pose_fix_pitch_roll(prior, odom, s->ref_pose);
     for (int k = 0; k < 3; ++k) s->ref_origin[k] = s->ref_pose[12 + k];
     s->gen = ctx->refc.next_owner++;  // (the cached voxel map is the old reference's: stale)
+    s->mon_tree.invalidate();
     ++s->n_processed;
     return AICP_OK;
   }
@@ -517,9 +571,40 @@ void aicp_hip_session_free(aicp_hip_ctx* ctx, aicp_hip_session* s) {
   release(s->ref[0]);
   release(s->ref[1]);
   release(s->read);
+  s->mon_tree.release_all();
   if (s->ev_begin) (void)hipEventDestroy(s->ev_begin);
   if (s->ev_end) (void)hipEventDestroy(s->ev_end);
   delete s;
+}
+
+int aicp_hip_session_set_monitor(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_monitor_params* prm) {
+  if (!ctx || !s) return AICP_ERR_INVALID;
+  if (!prm) {
+    s->mon_on = false;
+    return AICP_OK;
+  }
+  const int rc = monitor_params_check(ctx, prm);
+  if (rc) return rc;
+  s->mon_prm = *prm;
+  s->mon_on = true;
+  s->mon_tree.invalidate();  // (built again on the first monitored reading)
+  return AICP_OK;
+}
+
+int aicp_hip_session_last_monitor(const aicp_hip_session* s, aicp_monitor_result* out, int32_t* valid) {
+  if (!s || !out || !valid) return AICP_ERR_INVALID;
+  *out = s->mon_last;
+  *valid = s->mon_valid;
+  return AICP_OK;
+}
+
+int aicp_hip_session_monitor_counters(const aicp_hip_session* s, uint64_t out[4]) {
+  if (!s || !out) return AICP_ERR_INVALID;
+  out[0] = s->mon_cnt.readings;
+  out[1] = s->mon_cnt.trees;
+  out[2] = s->mon_cnt.reuses;
+  out[3] = s->mon_cnt.trees2;
+  return AICP_OK;
 }
 
 int aicp_hip_session_start(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_cloud* first) {

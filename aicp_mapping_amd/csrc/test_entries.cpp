@@ -1115,4 +1115,78 @@ int aicp_hip_test_ingest(aicp_hip_ctx* ctx, const float* rows, size_t n, size_t 
   return AICP_OK;
 }
 
+// The monitor's resident core (monitor_resident: k_mon_stage, the trees, k_mon_nn, the selects,
+// k_mon_reduce, k_mon_finish) as a live session runs it: the reference, the reading, T and the
+// result's 56 bytes in guarded device buffers of their own, a reference tree that `runs` calls in a
+// row share (the first builds it, the others reuse it, as a session's readings against one
+// reference), the wait and monitor_resident_check after each. result: the last run's; *dirty: guard
+// words that changed plus input words that no longer hold what was uploaded; counters:
+// aicp_hip_session_monitor_counters' four.
+int aicp_hip_test_monitor_resident(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_icp_config* cfg,
+                                   const float* ref_xyz, size_t n_ref, const float* read_xyz, size_t n_read,
+                                   const float T[16], int32_t runs, aicp_monitor_result* result, uint64_t* dirty,
+                                   uint64_t counters[4]) {
+  if (!ctx || !prm || !ref_xyz || !read_xyz || !T || !result || !dirty || !counters || n_ref == 0 || n_read == 0 ||
+      n_ref + n_read >= (1ull << 28) || runs < 1 || runs > 8)
+    return AICP_ERR_INVALID;
+  if ((prm->flags & AICP_MON_PAIRED) && !cfg) return AICP_ERR_INVALID;
+  int rc = monitor_params_check(ctx, prm);
+  if (rc) return rc;
+  *dirty = 0;
+  std::memset(result, 0, sizeof(*result));
+  std::memset(counters, 0, 4 * sizeof(uint64_t));
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  HIPC(hipStreamSynchronize(s));
+  CallBufs loc;
+  loc.sync = s;
+  constexpr size_t kResWords = sizeof(aicp_monitor_result) / 4;
+  Guarded gref, gread, gT, gres;
+  HIPC(gref.alloc(loc, 4 * n_ref, 0x7fc0aaaau));
+  HIPC(gread.alloc(loc, 4 * n_read, 0x7fc0bbbbu));
+  HIPC(gT.alloc(loc, 16, 0x7fc0ccccu));
+  HIPC(gres.alloc(loc, kResWords, 0xddddddddu));
+  for (const Guarded* g : {&gref, &gread, &gT, &gres}) HIPC(g->refill(s));
+  HIPC(hipStreamSynchronize(s));
+  std::vector<float> pk, href(4 * n_ref), hread(4 * n_read);
+  HIPC(upload_xyz4(pk, ref_xyz, n_ref, gref.payload()));
+  std::memcpy(href.data(), pk.data(), href.size() * 4);
+  HIPC(upload_xyz4(pk, read_xyz, n_read, gread.payload()));
+  std::memcpy(hread.data(), pk.data(), hread.size() * 4);
+  HIPC(hipMemcpy(gT.payload(), T, 64, hipMemcpyHostToDevice));
+  MonRefTree tree;
+  MonCounters cnt;
+  std::vector<uint32_t> back;
+  aicp_monitor_result last{};
+  for (int r = 0; r < runs && !rc; ++r) {
+    rc = monitor_resident(ctx, prm, cfg, static_cast<const float4*>(gref.payload()), n_ref,
+                          static_cast<const float4*>(gread.payload()), n_read, static_cast<const float*>(gT.payload()),
+                          &tree, &cnt, gres.payload());
+    const hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) {
+      ctx->err = std::string("hipStreamSynchronize: ") + hipGetErrorString(e);
+      rc = AICP_ERR_HIP;
+    }
+    if (!rc && gres.fetch(back, &last, *dirty) != hipSuccess) rc = AICP_ERR_HIP;
+    if (!rc) rc = monitor_resident_check(ctx, &tree, &last);
+    if (!rc) ++cnt.readings;
+  }
+  tree.release_all();  // (the stream is idle: every run was waited for)
+  if (rc) return rc;
+  // the inputs: guards untouched, payloads as uploaded
+  std::vector<float> in(std::max({href.size(), hread.size(), (size_t)16}));
+  if (gref.fetch(back, in.data(), *dirty) != hipSuccess) return AICP_ERR_HIP;
+  *dirty += std::memcmp(in.data(), href.data(), href.size() * 4) != 0;
+  if (gread.fetch(back, in.data(), *dirty) != hipSuccess) return AICP_ERR_HIP;
+  *dirty += std::memcmp(in.data(), hread.data(), hread.size() * 4) != 0;
+  if (gT.fetch(back, in.data(), *dirty) != hipSuccess) return AICP_ERR_HIP;
+  *dirty += std::memcmp(in.data(), T, 64) != 0;
+  *result = last;
+  counters[0] = cnt.readings;
+  counters[1] = cnt.trees;
+  counters[2] = cnt.reuses;
+  counters[3] = cnt.trees2;
+  return AICP_OK;
+}
+
 }  // extern "C"

@@ -22,15 +22,21 @@ from .accumulator import SweepAccumulator
 from .built_map import BuiltMap
 
 
-class MapSession:
-    def __init__(self, ctx: "L.Context", map, cfg=None, params=None, prefilter=None, map_prefilter=None):
+class MapSession(L.SessionMonitor):
+    _monitor_kind = "mapsession"
+
+    def __init__(self, ctx: "L.Context", map, cfg=None, params=None, prefilter=None, map_prefilter=None,
+                 monitor=None):
         """map: a PriorMap (localize_against_prior_map; params: LocalizationParams) or a BuiltMap
         (localize_against_built_map, created from App's first cloud; params: BuiltMapParams); the
         policy follows the map's class and the params' type, which must agree. cfg: IcpConfig
         (default_config() when None; a point-to-point chain is accepted). prefilter: None when the
         readings are already pre-filtered, PrefilterParams (or True for the defaults) when they
         are RAW and go through setAndFilterReading in App's order. map_prefilter: the prior map's
-        re-filter (None: the defaults); not for a BuiltMap."""
+        re-filter (None: the defaults); not for a BuiltMap. monitor: None (off), True or
+        dict(quantile=, max_accepted_dist=, paired=) for the quality monitor per reading, against
+        the reading's map crop (set_monitor, last_monitor, monitor_counters)."""
+        mon = L.monitor_argument(monitor)  # (a bad argument before anything is made)
         built = isinstance(map, BuiltMap)
         if params is None:
             params = L.default_built_map_params() if built else L.default_localization_params()
@@ -48,6 +54,8 @@ class MapSession:
         self.map = map
         self.built = built
         self.h = h
+        if mon is not None:
+            self.set_monitor(mon)
 
     def close(self):
         if getattr(self, "h", None):

@@ -31,14 +31,19 @@ from . import _lib as L
 from .accumulator import SweepAccumulator
 
 
-class AppSession:
-    def __init__(self, ctx: "L.Context", cfg=None, params=None, prefilter=None, risk=None):
+class AppSession(L.SessionMonitor):
+    _monitor_kind = "session"
+
+    def __init__(self, ctx: "L.Context", cfg=None, params=None, prefilter=None, risk=None, monitor=None):
         """cfg: IcpConfig (default_config() when None; a point-to-point chain is accepted); params:
         SequenceParams (flags: AICP_RUN_OVERLAP | AICP_SEQ_DEBUG | AICP_RUN_TIME_NN); prefilter:
         None when the clouds are already pre-filtered, PrefilterParams (or True for the defaults)
         when they are RAW and go through setAndFilterReading in App's order; risk: None, or
         dict(model=SvmModel (kept alive by the session), threshold=float (default 0.5),
-        params=RiskParams (default_risk_params() when left out)) for failure_prediction_mode."""
+        params=RiskParams (default_risk_params() when left out)) for failure_prediction_mode;
+        monitor: None (off), True or dict(quantile=, max_accepted_dist=, paired=) for the quality
+        monitor per reading (set_monitor, last_monitor, monitor_counters)."""
+        mon = L.monitor_argument(monitor)  # (a bad argument before anything is made)
         cfg = cfg or L.default_config()
         prm = params or L.default_sequence_params()
         if prefilter is True:
@@ -58,6 +63,8 @@ class AppSession:
             ctx.check(L.lib.aicp_hip_session_create(ctx.h, C.byref(cfg), C.byref(prm), pf, C.byref(h)))
         self.ctx = ctx
         self.h = h
+        if mon is not None:
+            self.set_monitor(mon)
 
     def close(self):
         if getattr(self, "h", None):

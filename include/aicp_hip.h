@@ -963,6 +963,30 @@ int aicp_hip_session_reference(aicp_hip_ctx* ctx, aicp_hip_session* s, float* ou
 /* The last process call that registered its reading: the whole call on the host, and from the
  * origin's upload to the promotion on the device (HIP events). Both nullable. */
 int aicp_hip_session_last_timing(const aicp_hip_session* s, double* wall_ms, double* device_ms);
+/* The quality monitor per reading (aicp_hip_monitor's metrics, above), on the
+ * clouds where they lie when the registration returns: ref = the reference the reading was
+ * registered against (what aicp_hip_session_reference returned before the call), out = T * the
+ * reading as registered, T the correction the call returns, read from device memory. Allowed any
+ * time after create, plain and risk sessions alike; prm NULL switches it off (the default), and a
+ * process call then enqueues what it enqueues without this entry. AICP_ERR_INVALID: a quantile
+ * outside [0, 1]. With AICP_MON_PAIRED the chain is the session's cfg with trimmed_ratio replaced
+ * by the reading's own tuned ratio (the result's icp.trimmed_ratio).
+ * A process call that registered its reading (accepted, or dropped by max_correction_magnitude)
+ * leaves a result with valid = 1; a gated reading of a risk session, a call that ends the session,
+ * a call with the monitor off and a session before its first process call leave valid = 0 and a
+ * result of all zero bytes. The monitor runs behind the registration and ahead of the commit and
+ * the promotion, and its 56 bytes come back in the call's one read-back. An error of its own (a
+ * direction without a finite distance, a kd-tree deeper than 48 levels) never ends the session and
+ * changes nothing the call returns: valid = 0, the reason in aicp_hip_last_error.
+ * The bucket-8 tree over the reference lives in the session and is built on the first monitored
+ * reading after start, after a promotion or after set_monitor; later readings against that
+ * reference reuse it and build only the tree over out (the chain matcher's tree, when its bucket
+ * size is not 8, is kept the same way). */
+int aicp_hip_session_set_monitor(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_monitor_params* prm /* NULL: off */);
+int aicp_hip_session_last_monitor(const aicp_hip_session* s, aicp_monitor_result* out, int32_t* valid);
+/* out[0] monitored readings (valid results), [1] bucket-8 trees built (over references and over
+ * out), [2] readings that reused the session's reference tree, [3] chain-bucket trees built. */
+int aicp_hip_session_monitor_counters(const aicp_hip_session* s, uint64_t out[4]);
 
 /* The live session with failure_prediction_mode (runAicpPipeline, app.cpp:236-245, and the gated
  * branch of processCloud, app.cpp:401-411): aicp_hip_sequence_run_risk's rules, one reading per call,
@@ -1067,6 +1091,15 @@ int aicp_hip_map_session_state(aicp_hip_ctx* ctx, aicp_hip_map_session* s, uint6
 /* The last process call that registered its reading: the whole call on the host (map changes
  * included), and from its first enqueue to the append on the device (HIP events). Both nullable. */
 int aicp_hip_map_session_last_timing(const aicp_hip_map_session* s, double* wall_ms, double* device_ms);
+/* aicp_hip_session_set_monitor's rules for the map sessions: ref = the reading's map crop (what
+ * aicp_hip_map_crop returns just before the call at the call's pose; debug mode: at the moved
+ * pose), out = T * the reading as registered. The crop changes with every pose, so both trees are
+ * built per reading (out[2] of the counters stays 0). A call that ends the session (an emptied
+ * reading, an empty crop, a failed registration) leaves valid = 0. (The three are spelled
+ * aicp_hip_mapsession_*: the aicp_hip_map_session_* family stays the seven entry points above.) */
+int aicp_hip_mapsession_set_monitor(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const aicp_monitor_params* prm);
+int aicp_hip_mapsession_last_monitor(const aicp_hip_map_session* s, aicp_monitor_result* out, int32_t* valid);
+int aicp_hip_mapsession_monitor_counters(const aicp_hip_map_session* s, uint64_t out[4]);
 
 /* ---- kernel-level entry points (parity tests and diagnostics) --------------------------- */
 /* kd-tree over pts (as given, no centring) + k-NN of queries: libnabo
@@ -1333,6 +1366,18 @@ int aicp_hip_test_key_bound(const float* pts, size_t n, const double origin[3], 
  * float[16]) in aicp_hip_transform's float expression. out4 (nullable: nothing is downloaded). */
 int aicp_hip_test_ingest(aicp_hip_ctx* ctx, const float* rows, size_t n, size_t stride,
                          const float* T /* nullable */, float* out4 /* 4*n, nullable */);
+/* The quality monitor's resident core as the live sessions run it: ref and read
+ * (packed xyz) are placed in guarded device buffers, T (column-major float[16]) in device memory,
+ * and the core runs `runs` (1..8) times in a row on them with one reference tree, built by the
+ * first run and reused by the others (a session's readings against one reference). result: the last
+ * run's 56 bytes, equal to aicp_hip_monitor(ref, read, T)'s. *dirty: guard words that changed
+ * around the four buffers, plus 1 for every input that no longer holds what was uploaded (0 when
+ * all is well). counters: aicp_hip_session_monitor_counters' four. cfg: nullable without
+ * AICP_MON_PAIRED. Errors as aicp_hip_monitor's. */
+int aicp_hip_test_monitor_resident(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_icp_config* cfg,
+                                   const float* ref_xyz, size_t n_ref, const float* read_xyz, size_t n_read,
+                                   const float T[16], int32_t runs, aicp_monitor_result* result, uint64_t* dirty,
+                                   uint64_t counters[4]);
 
 #ifdef __cplusplus
 }
