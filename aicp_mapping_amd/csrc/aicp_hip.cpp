@@ -2392,31 +2392,19 @@ int aicp_hip_map_prefilter(aicp_hip_ctx* ctx, aicp_hip_map* map, const aicp_pref
 }  // extern "C"
 
 namespace {
-// One raw cloud through regionGrowingUniformPlaneSegmentationFilter on the device, moved first
-// by T when T is given (pcl::transformPointCloud in float, launch_transform: setAndFilterReading's
-// debug branch, app.cpp:90-99). The kept points come back packed xyz (clusters concatenated).
-int pf_cloud(aicp_hip_ctx* ctx, const aicp_prefilter_params* prm, const aicp_cloud& c, const float* T,
-             std::vector<float>& out) {
+// One raw cloud through regionGrowingUniformPlaneSegmentationFilter on the device, as given (robot
+// mode, app.cpp:87-88). The kept points come back packed xyz (clusters concatenated).
+int pf_cloud(aicp_hip_ctx* ctx, const aicp_prefilter_params* prm, const aicp_cloud& c, std::vector<float>& out) {
   out.clear();
   hipStream_t s = ctx->stream;
   PfLayout Lo;
   int rc = pf_layout(ctx, c.n, &Lo);
   if (rc) return rc;
   HIPC(hipStreamSynchronize(s));  // (pin_io and scratch are free)
-  HIPC(ensure(ctx->pin_io, c.n * 16 + 64));
+  HIPC(ensure(ctx->pin_io, c.n * 16));
   float* h = ctx->pin_io.as<float>();
-  if (T) {
-    HIPC(ensure(ctx->scratch, 64 + c.n * 16));
-    std::memcpy(h, T, 64);
-    pack_xyz4(c.pts, c.n, c.stride, h + 16);
-    char* d = ctx->scratch.as<char>();
-    HIPC(hipMemcpyAsync(d, h, 64 + c.n * 16, hipMemcpyHostToDevice, s));
-    launch_transform(s, (int)c.n, (const float*)d, (const float4*)(d + 64), Lo.pts4);
-    HIPC(hipGetLastError());
-  } else {
-    pack_xyz4(c.pts, c.n, c.stride, h);
-    HIPC(hipMemcpyAsync(Lo.pts4, h, c.n * 16, hipMemcpyHostToDevice, s));
-  }
+  pack_xyz4(c.pts, c.n, c.stride, h);
+  HIPC(hipMemcpyAsync(Lo.pts4, h, c.n * 16, hipMemcpyHostToDevice, s));
   PfRun o;
   rc = pf_core(ctx, prm, c.n, Lo, &o);  // (returns with the stream idle)
   if (rc) return rc;
@@ -2460,94 +2448,36 @@ int aicp_hip_sequence_run_raw(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, con
   for (size_t i = 0; i < n; ++i)
     if (!valid_cloud(readings[i])) FAIL(AICP_ERR_INVALID, "invalid reading " + std::to_string(i));
   HIPC(hipSetDevice(ctx->device));
-  // the first cloud: pre-filtered as given (processCloud, app.cpp:293-297)
+  if (debug)  // reading after reading on a session's step (initialT_ carries every accepted correction)
+    return session_replay(ctx, cfg, prm, pf, nullptr, first, readings, n, out_T, out, n_done);
+  // robot mode: every cloud pre-filtered as given (processCloud, app.cpp:293-297; app.cpp:87-88), then the stream
   std::vector<float> ref;
-  rc = pf_cloud(ctx, pf, *first, nullptr, ref);
+  rc = pf_cloud(ctx, pf, *first, ref);
   if (rc) return rc;
   if (ref.empty()) FAIL(AICP_ERR_INVALID, "the first cloud keeps no point after the pre-filter");
+  std::vector<std::vector<float>> kept(n);
+  std::vector<aicp_cloud> clouds(n);
+  size_t m = n;
+  for (size_t i = 0; i < n && m == n; ++i) {
+    rc = pf_cloud(ctx, pf, readings[i], kept[i]);
+    if (rc) return rc;
+    if (kept[i].empty()) m = i;
+    clouds[i] = packed_cloud(kept[i], readings[i].origin);
+  }
+  const aicp_cloud c0 = packed_cloud(ref, first->origin);
+  rc = aicp_hip_sequence_run(ctx, cfg, prm, &c0, clouds.data(), m, out_T, out, n_done);
+  if (rc || m == n) return rc;
   // a reading the pre-filter empties fails its registration (libpointmatcher throws on an empty
   // cloud), which ends the stream like any registration error (app.cpp:210)
-  auto empty_reading = [&](size_t i, int reference) {
-    out[i] = aicp_sequence_result{};
-    out[i].status = out[i].icp.status = AICP_ERR_INVALID;
-    out[i].reference = reference;
-    ident4(out_T + 16 * i);
-    *n_done = i + 1;
-    FAIL(AICP_ERR_INVALID, "reading " + std::to_string(i) + " keeps no point after the pre-filter");
-  };
-  if (!debug) {  // robot mode: each reading pre-filtered as given (app.cpp:87-88), then the stream
-    std::vector<std::vector<float>> kept(n);
-    std::vector<aicp_cloud> clouds(n);
-    size_t m = n;
-    for (size_t i = 0; i < n && m == n; ++i) {
-      rc = pf_cloud(ctx, pf, readings[i], nullptr, kept[i]);
-      if (rc) return rc;
-      if (kept[i].empty()) m = i;
-      clouds[i] = packed_cloud(kept[i], readings[i].origin);
-    }
-    const aicp_cloud c0 = packed_cloud(ref, first->origin);
-    rc = aicp_hip_sequence_run(ctx, cfg, prm, &c0, clouds.data(), m, out_T, out, n_done);
-    if (rc || m == n) return rc;
-    int reference = -1;
-    for (size_t i = 0; i < m; ++i)
-      if (out[i].is_reference) reference = (int)i;
-    return empty_reading(m, reference);
-  }
-  // debug mode: reading after reading (initialT_ carries every accepted correction)
-  float initT[16];
-  ident4(initT);
-  double ref_origin[3] = {first->origin[0], first->origin[1], first->origin[2]};
-  int ref_id = -1, acc = 0;
-  const int flags = AICP_RUN_ICP | (doOvl ? AICP_RUN_OVERLAP : 0) | (prm->flags & AICP_RUN_TIME_NN);
-  std::vector<float> rd;
-  for (size_t i = 0; i < n; ++i) {
-    // setAndFilterReading (app.cpp:90-99): the raw reading moved by initialT_, then pre-filtered;
-    // its prior pose becomes initialT_iso * prior pose
-    double o[3];
-    corrected_origin(initT, readings[i].origin, o);
-    rc = pf_cloud(ctx, pf, readings[i], initT, rd);
-    if (rc) return rc;
-    if (rd.empty()) return empty_reading(i, ref_id);
-    aicp_pair p{};
-    p.ref = ref.data();
-    p.n_ref = ref.size() / 3;
-    p.ref_stride = 12;
-    p.read = rd.data();
-    p.n_read = rd.size() / 3;
-    p.read_stride = 12;
-    for (int k = 0; k < 3; ++k) {
-      p.ref_origin[k] = ref_origin[k];
-      p.read_origin[k] = o[k];
-    }
-    aicp_sequence_result& r = out[i];
-    r = aicp_sequence_result{};
-    r.reference = ref_id;
-    float* T = out_T + 16 * i;
-    ident4(T);
-    // computeOverlap -> ratio -> registerClouds against the resident reference (app.cpp:218-247)
-    rc = oneshot(ctx, cfg, &p, 1, doOvl ? prm->resolution : 0.0, flags, T, &r.icp, nullptr);
-    if (!rc) rc = r.icp.status;
-    r.status = r.icp.status = rc;
-    *n_done = i + 1;
-    if (rc) {  // the worker ends here (app.cpp:210)
-      ctx->err = "reading " + std::to_string(i) + ": status " + std::to_string(rc) + ": " + ctx->err;
-      return rc;
-    }
-    if (correction_rejected(T, prm->max_correction_magnitude)) continue;  // app.cpp:366-373
-    r.accepted = 1;
-    corrected_origin(T, o, r.corrected_origin);
-    if (++acc == F) {  // the corrected reading is the next reference (app.cpp:375-391)
-      std::vector<float> next(rd.size());
-      for (size_t j = 0; j < rd.size(); j += 3) apply4(T, rd[j], rd[j + 1], rd[j + 2], &next[j]);
-      ref.swap(next);
-      for (int k = 0; k < 3; ++k) ref_origin[k] = r.corrected_origin[k];
-      ref_id = (int)i;
-      r.is_reference = 1;
-      acc = 0;
-    }
-    mul4(T, initT, initT);  // initialT_ = correction * initialT_ (app.cpp:414)
-  }
-  return AICP_OK;
+  int reference = -1;
+  for (size_t i = 0; i < m; ++i)
+    if (out[i].is_reference) reference = (int)i;
+  out[m] = aicp_sequence_result{};
+  out[m].status = out[m].icp.status = AICP_ERR_INVALID;
+  out[m].reference = reference;
+  ident4(out_T + 16 * m);
+  *n_done = m + 1;
+  FAIL(AICP_ERR_INVALID, "reading " + std::to_string(m) + " keeps no point after the pre-filter");
 }
 
 int aicp_hip_last_prefilter_stats(const aicp_hip_ctx* ctx, aicp_prefilter_stats* out) {
@@ -3154,12 +3084,51 @@ void fix_pitch_roll(const double* corrected, const double* odom, double* out) {
   }
 }
 
-// runAicpPipeline with failure_prediction_mode for one pair (include/aicp_hip.h). icp_flags:
-// AICP_RUN_TIME_NN or 0. *risk_rc: the features' result for the callers that want it (nullable).
+}  // namespace
+
+// ---- the session's view of the gate (runtime.hpp) -------------------------------------------------
+namespace aicp {
+namespace rt {
+
+void pose_moved(const float* T, const double* prior, double* out) { moved_pose(T, prior, out); }
+void pose_fix_pitch_roll(const double* corrected, const double* odom, double* out) {
+  fix_pitch_roll(corrected, odom, out);
+}
+int risk_params_check(aicp_hip_ctx* ctx, const aicp_risk_params* prm) { return pf_check(ctx, &prm->prefilter); }
+
+// runAicpPipeline's middle (app.cpp:153-167, 236-244): computeAlignmentRisk's features on the
+// overlap's clouds and poses, then the classifier, the gate and the ratio from the device's own
+// features
+int gate_resident(aicp_hip_ctx* ctx, const aicp_risk_params* prm, const aicp_hip_svm* model, double threshold,
+                  const aicp_cloud& ref, const aicp_cloud& read, const float4* d_ref, const float4* d_read,
+                  const double* ref_pose, const double* read_pose, GateRec* d_gate, float* fov_overlap) {
+  hipStream_t s = ctx->stream;
+  const SvmEntry* entries = nullptr;
+  SvmParams sp;
+  int rc = svm_device(ctx, model, &entries, &sp);
+  if (rc) return rc;
+  sp.threshold = threshold;
+  HIPC(hipMemcpyAsync(&d_gate->overlap, &ctx->state.as<PairState>()[0].overlap, 4, hipMemcpyDeviceToDevice, s));
+  aicp_risk_result rr{};
+  rc = alignment_features(ctx, prm, &ref, &read, ref_pose, read_pose, &rr, nullptr, nullptr, nullptr, nullptr, 0,
+                          &d_gate->alignability, d_ref, d_read);
+  if (rc) return rc;
+  *fov_overlap = rr.fov_overlap;
+  launch_svm_predict(s, 1, sp, entries, &d_gate->overlap, &d_gate->raw, &d_gate->risk, &d_gate->gate, &d_gate->ratio);
+  HIPC(hipGetLastError());
+  return AICP_OK;
+}
+
+}  // namespace rt
+}  // namespace aicp
+
+namespace {
+
+// runAicpPipeline with failure_prediction_mode for one pair (aicp_hip_pipeline, include/aicp_hip.h)
 int pipeline_core(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_risk_params* risk_prm,
                   const aicp_hip_svm* model, double threshold, const aicp_pair* pair, const double* ref_pose,
-                  const double* read_pose, double resolution, int icp_flags, float* out_T,
-                  aicp_pipeline_record* rec, aicp_icp_stats* stats) {
+                  const double* read_pose, double resolution, float* out_T, aicp_pipeline_record* rec,
+                  aicp_icp_stats* stats) {
   hipStream_t s = ctx->stream;
   ident4(out_T);
   *rec = aicp_pipeline_record{};
@@ -3170,11 +3139,6 @@ int pipeline_core(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_risk
   HIPC(ensure(ctx->svm_io, sizeof(GateRec)));
   HIPC(ensure(ctx->pin_svm, sizeof(GateRec)));
   GateRec* dg = ctx->svm_io.as<GateRec>();
-  const SvmEntry* entries = nullptr;
-  SvmParams sp;
-  int rc = svm_device(ctx, model, &entries, &sp);
-  if (rc) return rc;
-  sp.threshold = threshold;
   // 1. computeOverlap: the poses' translations are the sensor origins (app.cpp:229)
   aicp_pair p = *pair;
   for (int k = 0; k < 3; ++k) {
@@ -3182,25 +3146,20 @@ int pipeline_core(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_risk
     p.read_origin[k] = read_pose[12 + k];
   }
   aicp_icp_stats ost{};
-  rc = oneshot(ctx, cfg, &p, 1, resolution, AICP_RUN_OVERLAP, nullptr, &ost, nullptr);
+  int rc = oneshot(ctx, cfg, &p, 1, resolution, AICP_RUN_OVERLAP, nullptr, &ost, nullptr);
   if (!rc) rc = ost.status;
   if (rc) return rc;
-  HIPC(hipMemcpyAsync(&dg->overlap, &ctx->state.as<PairState>()[0].overlap, 4, hipMemcpyDeviceToDevice, s));
-  // 2. computeAlignmentRisk's features on the same clouds and poses (app.cpp:153-167)
+  // 2. and 3. the features on the same clouds and poses, the classifier, the gate and the ratio
   aicp_cloud ca{}, cb{};
   ca.pts = pair->ref, ca.n = pair->n_ref, ca.stride = pair->ref_stride;
   cb.pts = pair->read, cb.n = pair->n_read, cb.stride = pair->read_stride;
-  aicp_risk_result rr{};
-  rc = alignment_features(ctx, risk_prm, &ca, &cb, ref_pose, read_pose, &rr, nullptr, nullptr, nullptr, nullptr, 0,
-                          &dg->alignability);
+  float fov = 0.f;
+  rc = gate_resident(ctx, risk_prm, model, threshold, ca, cb, nullptr, nullptr, ref_pose, read_pose, dg, &fov);
   if (rc) return rc;
-  // 3. the classifier, the gate and the ratio, from the device's own features
-  launch_svm_predict(s, 1, sp, entries, &dg->overlap, &dg->raw, &dg->risk, &dg->gate, &dg->ratio);
-  HIPC(hipGetLastError());
   GateRec* hg = ctx->pin_svm.as<GateRec>();
   HIPC(hipMemcpyAsync(hg, dg, sizeof(GateRec), hipMemcpyDeviceToHost, s));
   HIPC(hipStreamSynchronize(s));
-  rec->fov_overlap = rr.fov_overlap;
+  rec->fov_overlap = fov;
   rec->octree_overlap = hg->overlap;
   rec->alignability = hg->alignability;
   rec->raw = hg->raw;
@@ -3215,7 +3174,7 @@ int pipeline_core(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_risk
     aicp_icp_config c2 = *cfg;
     c2.trimmed_ratio = hg->ratio;
     aicp_icp_stats ist{};
-    rc = oneshot(ctx, &c2, &p, 1, 0.0, AICP_RUN_ICP | icp_flags, out_T, &ist, nullptr);
+    rc = oneshot(ctx, &c2, &p, 1, 0.0, AICP_RUN_ICP, out_T, &ist, nullptr);
     if (!rc) rc = ist.status;
     ist.overlap_percent = st.overlap_percent;
     for (int k = 0; k < 3; ++k) ist.overlap_keys[k] = st.overlap_keys[k];
@@ -3227,42 +3186,6 @@ int pipeline_core(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_risk
 }
 
 }  // namespace
-
-// ---- the gate of the live session (session.cpp): pipeline_core's steps 2 and 3 on resident clouds --
-namespace aicp {
-namespace rt {
-
-void pose_moved(const float* T, const double* prior, double* out) { moved_pose(T, prior, out); }
-void pose_fix_pitch_roll(const double* corrected, const double* odom, double* out) {
-  fix_pitch_roll(corrected, odom, out);
-}
-int risk_params_check(aicp_hip_ctx* ctx, const aicp_risk_params* prm) { return pf_check(ctx, &prm->prefilter); }
-
-int gate_resident(aicp_hip_ctx* ctx, const aicp_risk_params* prm, const aicp_hip_svm* model, double threshold,
-                  const float4* d_ref, size_t n_ref, const float4* d_read, size_t n_read, const double* ref_pose,
-                  const double* read_pose, GateRec* d_gate, float* fov_overlap) {
-  hipStream_t s = ctx->stream;
-  const SvmEntry* entries = nullptr;
-  SvmParams sp;
-  int rc = svm_device(ctx, model, &entries, &sp);
-  if (rc) return rc;
-  sp.threshold = threshold;
-  HIPC(hipMemcpyAsync(&d_gate->overlap, &ctx->state.as<PairState>()[0].overlap, 4, hipMemcpyDeviceToDevice, s));
-  aicp_cloud ca{}, cb{};
-  ca.n = n_ref, ca.stride = 16;
-  cb.n = n_read, cb.stride = 16;
-  aicp_risk_result rr{};
-  rc = alignment_features(ctx, prm, &ca, &cb, ref_pose, read_pose, &rr, nullptr, nullptr, nullptr, nullptr, 0,
-                          &d_gate->alignability, d_ref, d_read);
-  if (rc) return rc;
-  *fov_overlap = rr.fov_overlap;
-  launch_svm_predict(s, 1, sp, entries, &d_gate->overlap, &d_gate->raw, &d_gate->risk, &d_gate->gate, &d_gate->ratio);
-  HIPC(hipGetLastError());
-  return AICP_OK;
-}
-
-}  // namespace rt
-}  // namespace aicp
 
 extern "C" {
 
@@ -3347,8 +3270,7 @@ int aicp_hip_pipeline(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_
   rc = pf_check(ctx, &risk_prm->prefilter);
   if (rc) return rc;
   HIPC(hipSetDevice(ctx->device));
-  return pipeline_core(ctx, cfg, risk_prm, model, threshold, pair, ref_pose, read_pose, resolution, 0, out_T, rec,
-                       stats);
+  return pipeline_core(ctx, cfg, risk_prm, model, threshold, pair, ref_pose, read_pose, resolution, out_T, rec, stats);
 }
 
 // App's stream from raw clouds with the risk gate (app.cpp:282-414): see include/aicp_hip.h.
@@ -3365,9 +3287,7 @@ int aicp_hip_sequence_run_risk(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, co
   if (rc) return rc;
   rc = pf_check(ctx, &risk_prm->prefilter);
   if (rc) return rc;
-  const int F = prm->reference_update_frequency;
-  if (F < 1) FAIL(AICP_ERR_INVALID, "reference_update_frequency must be >= 1");
-  const bool debug = prm->flags & AICP_SEQ_DEBUG;
+  if (prm->reference_update_frequency < 1) FAIL(AICP_ERR_INVALID, "reference_update_frequency must be >= 1");
   if (!(prm->resolution > 0)) FAIL(AICP_ERR_INVALID, "resolution");
   rc = check_cfg(ctx, cfg, AICP_RUN_ICP | AICP_RUN_OVERLAP);
   if (rc) return rc;
@@ -3376,84 +3296,8 @@ int aicp_hip_sequence_run_risk(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, co
   for (size_t i = 0; i < n; ++i)
     if (!valid_cloud(&readings[i])) FAIL(AICP_ERR_INVALID, "invalid reading " + std::to_string(i));
   HIPC(hipSetDevice(ctx->device));
-  // the first cloud: pre-filtered as given, its pose through updateCloud (app.cpp:293-299)
-  std::vector<float> ref;
-  rc = pf_cloud(ctx, pf, *first, nullptr, ref);
-  if (rc) return rc;
-  if (ref.empty()) FAIL(AICP_ERR_INVALID, "the first cloud keeps no point after the pre-filter");
-  double ref_pose[16];
-  fix_pitch_roll(first_pose, first_pose, ref_pose);
-  float initT[16];
-  ident4(initT);
-  int ref_id = -1, acc = 0;
-  const int icp_flags = prm->flags & AICP_RUN_TIME_NN;
-  std::vector<float> rd;
-  for (size_t i = 0; i < n; ++i) {
-    // setAndFilterReading (app.cpp:77-100): robot mode filters the reading as given; debug mode
-    // moves the raw reading by initialT_ first and its prior pose becomes initialT_iso * prior pose
-    const double* odom = poses + 16 * i;
-    double prior[16];
-    if (debug)
-      moved_pose(initT, odom, prior);
-    else
-      std::memcpy(prior, odom, sizeof(prior));
-    aicp_sequence_result& r = out[i];
-    r = aicp_sequence_result{};
-    r.reference = ref_id;
-    float* T = out_T + 16 * i;
-    ident4(T);
-    rec[i] = aicp_pipeline_record{};
-    rc = pf_cloud(ctx, pf, readings[i], debug ? initT : nullptr, rd);
-    if (rc) return rc;
-    if (rd.empty()) {  // libpointmatcher throws on an empty cloud: the worker ends (app.cpp:210)
-      r.status = r.icp.status = AICP_ERR_INVALID;
-      *n_done = i + 1;
-      FAIL(AICP_ERR_INVALID, "reading " + std::to_string(i) + " keeps no point after the pre-filter");
-    }
-    aicp_pair p{};
-    p.ref = ref.data();
-    p.n_ref = ref.size() / 3;
-    p.ref_stride = 12;
-    p.read = rd.data();
-    p.n_read = rd.size() / 3;
-    p.read_stride = 12;
-    rc = pipeline_core(ctx, cfg, risk_prm, model, threshold, &p, ref_pose, prior, prm->resolution, icp_flags, T,
-                       &rec[i], &r.icp);
-    r.status = r.icp.status = rc;
-    *n_done = i + 1;
-    if (rc) {
-      ctx->err = "reading " + std::to_string(i) + ": status " + std::to_string(rc) + ": " + ctx->err;
-      return rc;
-    }
-    if (!rec[i].registered) {
-      // app.cpp:401-411: the unmoved reading joins the graph with its prior pose and is the
-      // reference at once; the count restarts; the correction stays the identity
-      r.accepted = 1;
-      r.is_reference = 1;
-      for (int k = 0; k < 3; ++k) r.corrected_origin[k] = prior[12 + k];
-      ref.swap(rd);
-      fix_pitch_roll(prior, odom, ref_pose);
-      ref_id = (int)i;
-      acc = 0;
-      continue;
-    }
-    if (correction_rejected(T, prm->max_correction_magnitude)) continue;  // app.cpp:366-373
-    r.accepted = 1;
-    corrected_origin(T, prior + 12, r.corrected_origin);
-    if (++acc == F) {  // the corrected reading is the next reference (app.cpp:375-391)
-      std::vector<float> next(rd.size());
-      for (size_t j = 0; j < rd.size(); j += 3) apply4(T, rd[j], rd[j + 1], rd[j + 2], &next[j]);
-      ref.swap(next);
-      double corrected[16];
-      moved_pose(T, prior, corrected);
-      fix_pitch_roll(corrected, odom, ref_pose);
-      ref_id = (int)i;
-      r.is_reference = 1;
-      acc = 0;
-    }
-    mul4(T, initT, initT);  // initialT_ = correction * initialT_ (app.cpp:414)
-  }
-  return AICP_OK;
+  const ReplayRisk risk{risk_prm, model, threshold, first_pose, poses, rec};
+  return session_replay(ctx, cfg, prm, pf, &risk, first, readings, n, out_T, out, n_done);
 }
 
 }  // extern "C"

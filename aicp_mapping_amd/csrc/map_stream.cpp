@@ -454,12 +454,7 @@ struct aicp_hip_map_session {
   std::vector<aicp_icp_stats> stats;
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   double last_wall_ms = 0, last_device_ms = 0;
-  // the per-reading quality monitor (aicp_hip_mapsession_set_monitor)
-  bool mon_on = false;
-  aicp_monitor_params mon_prm{};
-  MonCounters mon_cnt;
-  aicp_monitor_result mon_last{};
-  int32_t mon_valid = 0;
+  MonState mon;  // the per-reading quality monitor (aicp_hip_mapsession_set_monitor)
 };
 
 extern "C" {
@@ -700,38 +695,21 @@ int aicp_hip_map_session_start(aicp_hip_ctx* ctx, aicp_hip_map_session* s, aicp_
   s->n_processed = 0;
   s->started = true;
   s->ended = false;
-  s->mon_valid = 0;
-  std::memset(&s->mon_last, 0, sizeof(s->mon_last));
+  s->mon.none();
   return AICP_OK;
 }
 
 int aicp_hip_mapsession_set_monitor(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const aicp_monitor_params* prm) {
   if (!ctx || !s) return AICP_ERR_INVALID;
-  if (!prm) {
-    s->mon_on = false;
-    return AICP_OK;
-  }
-  const int rc = monitor_params_check(ctx, prm);
-  if (rc) return rc;
-  s->mon_prm = *prm;
-  s->mon_on = true;
-  return AICP_OK;
+  return s->mon.set(ctx, prm);
 }
 
 int aicp_hip_mapsession_last_monitor(const aicp_hip_map_session* s, aicp_monitor_result* out, int32_t* valid) {
-  if (!s || !out || !valid) return AICP_ERR_INVALID;
-  *out = s->mon_last;
-  *valid = s->mon_valid;
-  return AICP_OK;
+  return s ? s->mon.get_last(out, valid) : AICP_ERR_INVALID;
 }
 
 int aicp_hip_mapsession_monitor_counters(const aicp_hip_map_session* s, uint64_t out[4]) {
-  if (!s || !out) return AICP_ERR_INVALID;
-  out[0] = s->mon_cnt.readings;
-  out[1] = s->mon_cnt.trees;
-  out[2] = s->mon_cnt.reuses;
-  out[3] = s->mon_cnt.trees2;
-  return AICP_OK;
+  return s ? s->mon.counters(out) : AICP_ERR_INVALID;
 }
 
 // the call that ends the session (app.cpp:210: the worker ends), with its status
@@ -757,13 +735,12 @@ static int map_session_process(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const
   hipStream_t st = ctx->stream;
   Live live;
   live.ev_done = s->ev_end;
-  if (s->mon_on) {
-    live.mon = &s->mon_prm;
-    live.mon_cnt = &s->mon_cnt;
+  if (s->mon.on) {
+    live.mon = &s->mon.prm;
+    live.mon_cnt = &s->mon.cnt;
     live.mon_off = kSessMon;
   }
-  s->mon_valid = 0;
-  std::memset(&s->mon_last, 0, sizeof(s->mon_last));
+  s->mon.none();
   aicp_cloud c{};
   if (reading) {
     c = *reading;
@@ -822,15 +799,7 @@ static int map_session_process(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const
     return end.status;
   }
   // the monitor's result came back with the record; its own errors leave valid = 0 and the call as it is
-  if (live.mon_ran) {
-    if (monitor_resident_check(ctx, &ctx->mon_scratch, h + kSessMon) == AICP_OK) {
-      std::memcpy(&s->mon_last, h + kSessMon, sizeof(s->mon_last));
-      s->mon_valid = 1;
-      ++s->mon_cnt.readings;
-    }
-  } else if (!live.mon_err.empty()) {
-    ctx->err = live.mon_err;
-  }
+  s->mon.take(ctx, &ctx->mon_scratch, live.mon_ran, h + kSessMon, live.mon_err);
   ++s->n_processed;
   return AICP_OK;
 }

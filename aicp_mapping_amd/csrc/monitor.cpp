@@ -435,6 +435,30 @@ int monitor_params_check(aicp_hip_ctx* ctx, const aicp_monitor_params* prm) {
   return AICP_OK;
 }
 
+int MonState::set(aicp_hip_ctx* ctx, const aicp_monitor_params* p) {
+  if (!p) {
+    on = false;
+    return AICP_OK;
+  }
+  const int rc = monitor_params_check(ctx, p);
+  if (rc) return rc;
+  prm = *p;
+  on = true;
+  return AICP_OK;
+}
+
+void MonState::take(aicp_hip_ctx* ctx, MonRefTree* tree, bool ran, const void* h_result, const std::string& err) {
+  if (ran) {
+    if (monitor_resident_check(ctx, tree, h_result) == AICP_OK) {
+      std::memcpy(&last, h_result, sizeof(last));
+      valid = 1;
+      ++cnt.readings;
+    }
+  } else if (!err.empty()) {
+    ctx->err = err;
+  }
+}
+
 int monitor_resident(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const aicp_icp_config* cfg,
                      const float4* d_ref, size_t n_ref, const float4* d_read, size_t n_read, const float* d_T,
                      MonRefTree* tree, MonCounters* cnt, void* d_result) {

@@ -8,6 +8,7 @@
 #include <atomic>
 #include <cmath>
 #include <condition_variable>
+#include <cstring>
 #include <functional>
 #include <mutex>
 #include <string>
@@ -246,6 +247,38 @@ int monitor_resident(aicp_hip_ctx* ctx, const aicp_monitor_params* prm, const ai
 // distance (AICP_ERR_CONVERGENCE), the reason in ctx->err; tree->valid is cleared then.
 int monitor_resident_check(aicp_hip_ctx* ctx, MonRefTree* tree, const void* h_result);
 int monitor_params_check(aicp_hip_ctx* ctx, const aicp_monitor_params* prm);
+// The per-reading monitor of a live session (session.cpp's and map_stream.cpp's): its switch and
+// parameters, the counters and the last call's result, with the bodies of the sessions' three
+// monitor entry points (monitor.cpp).
+struct MonState {
+  bool on = false;
+  aicp_monitor_params prm{};
+  MonCounters cnt;
+  aicp_monitor_result last{};
+  int32_t valid = 0;
+  // this call leaves no result (valid = 0, all zero bytes)
+  void none() {
+    valid = 0;
+    std::memset(&last, 0, sizeof(last));
+  }
+  int set(aicp_hip_ctx* ctx, const aicp_monitor_params* p);  // p null: off
+  int get_last(aicp_monitor_result* out, int32_t* out_valid) const {
+    if (!out || !out_valid) return AICP_ERR_INVALID;
+    *out = last;
+    *out_valid = valid;
+    return AICP_OK;
+  }
+  int counters(uint64_t out[4]) const {
+    if (!out) return AICP_ERR_INVALID;
+    out[0] = cnt.readings, out[1] = cnt.trees, out[2] = cnt.reuses, out[3] = cnt.trees2;
+    return AICP_OK;
+  }
+  // After the read-back of a reading that went through: ran: monitor_resident was enqueued for it
+  // and its 56 bytes are at h_result (checked with monitor_resident_check on `tree`); else err, the
+  // reason it was not (empty: the monitor is off), becomes ctx->err. The monitor's own errors leave
+  // valid = 0 and the call as it is.
+  void take(aicp_hip_ctx* ctx, MonRefTree* tree, bool ran, const void* h_result, const std::string& err);
+};
 
 // matcher_trees' treelet step (aicp_hip.cpp), behind the R matcher trees enqueued on s
 int matcher_treelets(aicp_hip_ctx* ctx, hipStream_t s, size_t R, uint64_t total_ref, PairDesc* dRdesc, int bucket,
@@ -470,14 +503,31 @@ int stream_ingest_rows(aicp_hip_ctx* ctx, const aicp_prefilter_params* pf, const
 // for a host array. The caller clears RefCache::use after its run_batch (and invalidates on an error).
 void refcache_begin_resident(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, uint64_t owner, uint64_t n_ref,
                              const double origin[3], double res, int flags);
-// The risk gate of the live session (session.cpp) on clouds that lie on the device (float4, stride
-// 16), behind an overlap-only run_batch of the same pair on ctx->stream: the batch's overlap into
-// d_gate->overlap, the alignment features from d_ref / d_read where they lie (alignability into
-// d_gate->alignability, device to device), then k_svm_predict into d_gate's raw, risk, gate and
-// ratio. Nothing of d_gate is read back here. The poses: column-major double[16].
+// The risk gate of aicp_hip_pipeline and of the live session (session.cpp), behind an overlap-only
+// run_batch of the same pair on ctx->stream: the batch's overlap into d_gate->overlap, the alignment
+// features (alignability into d_gate->alignability, device to device), then k_svm_predict into
+// d_gate's raw, risk, gate and ratio. The clouds: the caller's host arrays (ref / read: pts, n,
+// stride), or, with d_ref / d_read given, where they lie on the device (float4; then only n is
+// read). Nothing of d_gate is read back here. The poses: column-major double[16].
 int gate_resident(aicp_hip_ctx* ctx, const aicp_risk_params* prm, const aicp_hip_svm* model, double threshold,
-                  const float4* d_ref, size_t n_ref, const float4* d_read, size_t n_read, const double* ref_pose,
-                  const double* read_pose, GateRec* d_gate, float* fov_overlap);
+                  const aicp_cloud& ref, const aicp_cloud& read, const float4* d_ref, const float4* d_read,
+                  const double* ref_pose, const double* read_pose, GateRec* d_gate, float* fov_overlap);
+// The loop of the two offline App-order entry points (aicp_hip_sequence_run_raw in debug mode,
+// aicp_hip_sequence_run_risk; session.cpp): a session private to the call, started on `first` and
+// fed the readings one by one into out_T + 16 i, out[i] (and risk->rec[i]); *n_done = i + 1 after
+// every reading that ran; the first non-zero return ends the loop and is the call's, with
+// ctx->err in the entry points' wording. The arguments are the entry points', already checked.
+struct ReplayRisk {  // aicp_hip_sequence_run_risk's part
+  const aicp_risk_params* prm;
+  const aicp_hip_svm* model;
+  double threshold;
+  const double* first_pose;
+  const double* poses;
+  aicp_pipeline_record* rec;
+};
+int session_replay(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_sequence_params* prm,
+                   const aicp_prefilter_params* pf, const ReplayRisk* risk, const aicp_cloud* first,
+                   const aicp_cloud* readings, size_t n, float* out_T, aicp_sequence_result* out, size_t* n_done);
 int risk_params_check(aicp_hip_ctx* ctx, const aicp_risk_params* prm);  // its pre-filter's pf_check
 // the gate's pose rules (aicp_hip.cpp: fromMatrix4fToIsometry3d(T) * prior, removePitchRollCorrection)
 void pose_moved(const float* T, const double* prior, double* out);

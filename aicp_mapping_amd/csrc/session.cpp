@@ -30,6 +30,10 @@
 // them when the record reports it, so a reading that is dropped or fails leaves the reference as it
 // was and a larger reference never needs a copy. Its identity in the reference cache is a number
 // taken from the cache for every new reference (RefCache::owner): no host copy, no compare.
+//
+// The two offline App-order entry points (aicp_hip_sequence_run_raw in debug mode,
+// aicp_hip_sequence_run_risk; aicp_hip.cpp) are session_replay below: the same step, reading after
+// reading, on a session private to the call.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -91,23 +95,13 @@ struct aicp_hip_session {
   // the per-reading quality monitor (aicp_hip_session_set_monitor): its parameters, the monitor's
   // trees over the current reference (built on the first monitored reading against it, kept until
   // the reference changes), the counters, and the last call's result
-  bool mon_on = false;
-  aicp_monitor_params mon_prm{};
+  MonState mon;
   MonRefTree mon_tree;
-  MonCounters mon_cnt;
-  aicp_monitor_result mon_last{};
-  int32_t mon_valid = 0;
 };
 
 namespace {
 
 StreamState* host_state(aicp_hip_session* s) { return reinterpret_cast<StreamState*>(s->pin.as<char>() + kOffState); }
-
-// this call leaves no monitor result (valid = 0, all zero bytes)
-void no_monitor(aicp_hip_session* s) {
-  s->mon_valid = 0;
-  std::memset(&s->mon_last, 0, sizeof(s->mon_last));
-}
 
 // rows of a reading: the caller's (c) or the accumulator's cloud where it lies
 struct Rows {
@@ -165,7 +159,7 @@ int start_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, const doub
   for (int k = 0; k < 3; ++k) s->ref_origin[k] = r.origin[k];
   s->gen = ctx->refc.next_owner++;
   s->mon_tree.invalidate();
-  no_monitor(s);
+  s->mon.none();
   s->n_processed = 0;
   s->started = true;
   s->ended = false;
@@ -214,55 +208,79 @@ int pair_batch(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, const doub
   return rc;
 }
 
-int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, int32_t id, int rc,
-                   std::chrono::steady_clock::time_point t0, aicp_sequence_result* out, bool* promoted);
+// a reading that fails its registration ends the worker (app.cpp:210); why: the text behind "reading <id>"
+int reading_failed(aicp_hip_ctx* ctx, aicp_hip_session* s, aicp_sequence_result* out, int rc, const std::string& why) {
+  out->status = out->icp.status = rc;
+  const std::string id = std::to_string(s->n_processed);
+  (void)end_session(ctx, s, rc);
+  ctx->err = "session: reading " + id + why;
+  return rc;
+}
 
-int process_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, float* out_T, aicp_sequence_result* out,
-                 uint32_t* kept_out) {
-  const auto t0 = std::chrono::steady_clock::now();
+// The head of a reading's call, for both kinds of session: the outputs reset, the prior origin up,
+// the rows ingested (debug mode: moved by the device's initialT_) and pre-filtered into s->read.
+// odom: a risk session's prior pose (its translation is r.origin), null for a plain one. prior: the
+// reading's prior pose as setAndFilterReading leaves it (app.cpp:77-100: debug mode, initialT_ *
+// prior pose, from the mirror of the device's initialT_; k_stream_ingest moves the origin the same
+// way for the records, on the device); a plain session has only its translation, the overlap's
+// sensor origin. A non-zero return is the call's; otherwise *kept > 0 points lie in s->read.
+int ingest_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, const double* odom, float* out_T,
+                   aicp_sequence_result* out, uint32_t* kept_out, uint32_t* kept, double prior[16]) {
   hipStream_t st = ctx->stream;
-  const bool debug = s->prm.flags & AICP_SEQ_DEBUG, doOvl = s->prm.flags & AICP_RUN_OVERLAP;
-  const int32_t id = (int32_t)s->n_processed;
+  const bool debug = s->prm.flags & AICP_SEQ_DEBUG;
   *out = aicp_sequence_result{};
   out->reference = s->ref_id;
   ident4(out_T);
   if (kept_out) *kept_out = 0;
-  no_monitor(s);
+  s->mon.none();
   // a reading with no point, or one the pre-filter empties, fails its registration (libpointmatcher
-  // throws on an empty cloud), which ends the worker (app.cpp:210)
-  auto empty_reading = [&]() {
-    out->status = out->icp.status = AICP_ERR_INVALID;
-    const int rc = end_session(ctx, s, AICP_ERR_INVALID);
-    ctx->err = "session: reading " + std::to_string(id) + " keeps no point after the pre-filter";
-    return rc;
-  };
-  if (r.n == 0) return empty_reading();
+  // throws on an empty cloud)
+  if (r.n == 0) return reading_failed(ctx, s, out, AICP_ERR_INVALID, " keeps no point after the pre-filter");
   HIPC(hipSetDevice(ctx->device));
   HIPC(hipStreamSynchronize(st));  // (the mirror is free)
   char* h = s->pin.as<char>();
   char* d = s->win.as<char>();
   StreamState* dS = reinterpret_cast<StreamState*>(d + kOffState);
   double* dOrg = reinterpret_cast<double*>(d + kOffOrigin);
-  // the overlap's sensor origin of the moved reading, from the mirror of the device's initialT_
-  // (k_stream_ingest computes the same for the commit, on the device)
-  double o[3] = {r.origin[0], r.origin[1], r.origin[2]};
-  if (debug) corrected_origin(host_state(s)->initT, r.origin, o);
+  if (odom) {
+    if (debug)
+      pose_moved(host_state(s)->initT, odom, prior);
+    else
+      std::memcpy(prior, odom, 16 * sizeof(double));
+  } else {
+    std::memcpy(prior + 12, r.origin, 24);
+    if (debug) corrected_origin(host_state(s)->initT, r.origin, prior + 12);
+  }
   std::memcpy(h + kOffOrigin, r.origin, 24);
   HIPC(hipEventRecord(s->ev_begin, st));
   HIPC(hipMemcpyAsync(dOrg, h + kOffOrigin, 24, hipMemcpyHostToDevice, st));
   HIPC(ensure(s->read, r.n * 16));
-  uint32_t kept = 0;
-  int rc = stream_ingest_rows(ctx, s->has_pf ? &s->pf : nullptr, r.hpts, r.n, r.stride, r.dpts,
-                              debug ? dS->initT : nullptr, debug ? dOrg : nullptr, s->read.as<float4>(), &kept);
+  const int rc = stream_ingest_rows(ctx, s->has_pf ? &s->pf : nullptr, r.hpts, r.n, r.stride, r.dpts,
+                                    debug ? dS->initT : nullptr, debug ? dOrg : nullptr, s->read.as<float4>(), kept);
   if (rc) return end_session(ctx, s, rc);
-  if (kept_out) *kept_out = kept;
-  if (!kept) return empty_reading();
+  if (kept_out) *kept_out = *kept;
+  if (!*kept) return reading_failed(ctx, s, out, AICP_ERR_INVALID, " keeps no point after the pre-filter");
+  return AICP_OK;
+}
+
+int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, int32_t id, int rc,
+                   std::chrono::steady_clock::time_point t0, aicp_sequence_result* out, bool* promoted);
+
+int process_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, float* out_T, aicp_sequence_result* out,
+                 uint32_t* kept_out) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const bool doOvl = s->prm.flags & AICP_RUN_OVERLAP;
+  const int32_t id = (int32_t)s->n_processed;
+  uint32_t kept = 0;
+  double prior[16];
+  int rc = ingest_reading(ctx, s, r, nullptr, out_T, out, kept_out, &kept, prior);
+  if (rc) return rc;
   // the one-pair batch: both clouds are on the device already
   const int flags = AICP_RUN_ICP | (s->prm.flags & (AICP_RUN_OVERLAP | AICP_RUN_TIME_NN));
   const double res = doOvl ? s->prm.resolution : 0.0;
   aicp_icp_stats stats{};
   stats.status = -1;
-  rc = pair_batch(ctx, s, kept, o, &s->cfg, res, flags, out_T, &stats);
+  rc = pair_batch(ctx, s, kept, prior + 12, &s->cfg, res, flags, out_T, &stats);
   if (rc && stats.status == -1) {  // the batch did not run to its end (not the reading's status)
     out->status = out->icp.status = rc;
     return end_session(ctx, s, rc);
@@ -293,12 +311,12 @@ int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, int32_
   // the chain at the reading's own tuned ratio. An error of its own only costs the result.
   bool mon_ran = false;
   std::string mon_err;
-  if (s->mon_on && rc == AICP_OK) {
+  if (s->mon.on && rc == AICP_OK) {
     aicp_icp_config mc = s->cfg;
     mc.trimmed_ratio = out->icp.trimmed_ratio;
     const std::string why = ctx->err;
-    mon_ran = monitor_resident(ctx, &s->mon_prm, &mc, s->ref[s->cur].as<float4>(), s->ref_n, s->read.as<float4>(), kept,
-                               ctx->outT.as<float>(), &s->mon_tree, &s->mon_cnt, d + kOffMon) == AICP_OK;
+    mon_ran = monitor_resident(ctx, &s->mon.prm, &mc, s->ref[s->cur].as<float4>(), s->ref_n, s->read.as<float4>(), kept,
+                               ctx->outT.as<float>(), &s->mon_tree, &s->mon.cnt, d + kOffMon) == AICP_OK;
     if (!mon_ran) mon_err = ctx->err;
     ctx->err = why;
   }
@@ -338,44 +356,30 @@ int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, int32_
     s->gen = ctx->refc.next_owner++;  // (the cached trees and voxel map are the old reference's: stale)
     if (promoted) *promoted = true;
   }
-  if (mon_ran) {  // (before the reference's trees are dropped: the check clears them on an error anyway)
-    if (monitor_resident_check(ctx, &s->mon_tree, h + kOffMon) == AICP_OK) {
-      std::memcpy(&s->mon_last, h + kOffMon, sizeof(s->mon_last));
-      s->mon_valid = 1;
-      ++s->mon_cnt.readings;
-    }
-  } else if (!mon_err.empty()) {
-    ctx->err = mon_err;
-  }
+  // (before the reference's trees are dropped: the check clears them on an error anyway)
+  s->mon.take(ctx, &s->mon_tree, mon_ran, h + kOffMon, mon_err);
   if (rec.append) s->mon_tree.invalidate();  // (the monitor's trees are the old reference's)
   ++s->n_processed;
   return AICP_OK;
 }
 
-// One reading of a risk session: the loop body of aicp_hip_sequence_run_risk (runAicpPipeline with
-// failure_prediction_mode, app.cpp:236-245, and both branches of processCloud's `if`, app.cpp:362-411)
-// on the session's resident buffers. odom: the reading's prior pose (its translation is r.origin).
+// One reading of a risk session, and the loop body of aicp_hip_sequence_run_risk: runAicpPipeline
+// with failure_prediction_mode (app.cpp:236-245) and both branches of processCloud's `if`
+// (app.cpp:362-411) on the session's resident buffers. odom: the reading's prior pose (its
+// translation is r.origin).
 int process_rows_risk(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, const double* odom, float* out_T,
                       aicp_sequence_result* out, aicp_pipeline_record* prec, uint32_t* kept_out) {
   const auto t0 = std::chrono::steady_clock::now();
   hipStream_t st = ctx->stream;
-  const bool debug = s->prm.flags & AICP_SEQ_DEBUG;
   const int32_t id = (int32_t)s->n_processed;
-  *out = aicp_sequence_result{};
-  out->reference = s->ref_id;
-  ident4(out_T);
   *prec = aicp_pipeline_record{};
-  if (kept_out) *kept_out = 0;
-  no_monitor(s);
-  auto failed = [&](int rc, const std::string& why) {  // the worker ends here (app.cpp:210)
-    out->status = out->icp.status = rc;
-    (void)end_session(ctx, s, rc);
-    ctx->err = "session: reading " + std::to_string(id) + why;
-    return rc;
+  auto failed = [&](int rc, const std::string& stage) {
+    return reading_failed(ctx, s, out, rc, ": status " + std::to_string(rc) + ": " + stage + ctx->err);
   };
-  if (r.n == 0) return failed(AICP_ERR_INVALID, " keeps no point after the pre-filter");
-  HIPC(hipSetDevice(ctx->device));
-  HIPC(hipStreamSynchronize(st));  // (the mirror is free)
+  uint32_t kept = 0;
+  double prior[16];
+  int rc = ingest_reading(ctx, s, r, odom, out_T, out, kept_out, &kept, prior);
+  if (rc) return rc;
   char* h = s->pin.as<char>();
   char* d = s->win.as<char>();
   StreamState* dS = reinterpret_cast<StreamState*>(d + kOffState);
@@ -383,37 +387,22 @@ int process_rows_risk(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, con
   SessionHeader* dHdr = reinterpret_cast<SessionHeader*>(d + kOffHdr);
   double* dOrg = reinterpret_cast<double*>(d + kOffOrigin);
   GateRec* dGate = reinterpret_cast<GateRec*>(d + kOffGate);
-  // setAndFilterReading (app.cpp:77-100): debug mode moves the raw reading by initialT_ and its prior
-  // pose becomes initialT_ * prior pose, here from the mirror of the device's initialT_
-  // (k_stream_ingest moves the origin the same way for the records, on the device)
-  double prior[16];
-  if (debug)
-    pose_moved(host_state(s)->initT, odom, prior);
-  else
-    std::memcpy(prior, odom, sizeof(prior));
-  std::memcpy(h + kOffOrigin, r.origin, 24);
-  HIPC(hipEventRecord(s->ev_begin, st));
-  HIPC(hipMemcpyAsync(dOrg, h + kOffOrigin, 24, hipMemcpyHostToDevice, st));
-  HIPC(ensure(s->read, r.n * 16));
-  uint32_t kept = 0;
-  int rc = stream_ingest_rows(ctx, s->has_pf ? &s->pf : nullptr, r.hpts, r.n, r.stride, r.dpts,
-                              debug ? dS->initT : nullptr, debug ? dOrg : nullptr, s->read.as<float4>(), &kept);
-  if (rc) return end_session(ctx, s, rc);
-  if (kept_out) *kept_out = kept;
-  if (!kept) return failed(AICP_ERR_INVALID, " keeps no point after the pre-filter");
   prec->n_read = kept;
   out->icp.overlap_percent = -1.f;
   // 1. computeOverlap: an overlap-only batch, the poses' translations are the sensor origins (app.cpp:229)
   aicp_icp_stats ost{};
   ost.status = -1;
   rc = pair_batch(ctx, s, kept, prior + 12, &s->cfg, s->prm.resolution, AICP_RUN_OVERLAP, nullptr, &ost);
-  if (rc) return failed(rc, ": overlap: status " + std::to_string(rc) + ": " + ctx->err);
+  if (rc) return failed(rc, "overlap: ");
   // 2. and 3. the features from both clouds where they lie, the classifier, the gate and the ratio;
   // 4. the gated branch, taken on the device; one read-back
   float fov = 0.f;
-  rc = gate_resident(ctx, &s->rprm, s->model, s->threshold, s->ref[s->cur].as<float4>(), s->ref_n,
-                     s->read.as<float4>(), kept, s->ref_pose, prior, dGate, &fov);
-  if (rc) return failed(rc, ": risk gate: status " + std::to_string(rc) + ": " + ctx->err);
+  aicp_cloud ca{}, cb{};
+  ca.n = s->ref_n, cb.n = kept;
+  ca.stride = cb.stride = 16;
+  rc = gate_resident(ctx, &s->rprm, s->model, s->threshold, ca, cb, s->ref[s->cur].as<float4>(), s->read.as<float4>(),
+                     s->ref_pose, prior, dGate, &fov);
+  if (rc) return failed(rc, "risk gate: ");
   DevBuf& spare = s->ref[1 - s->cur];
   HIPC(ensure(spare, (size_t)kept * 16));
   launch_session_gate_promote(st, (int)kept, dGate, dOrg, s->read.as<float4>(), id, spare.as<float4>(),
@@ -464,7 +453,7 @@ int process_rows_risk(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, con
   c2.trimmed_ratio = g.ratio;
   ist.status = -1;
   rc = pair_batch(ctx, s, kept, prior + 12, &c2, 0.0, AICP_RUN_ICP | (s->prm.flags & AICP_RUN_TIME_NN), out_T, &ist);
-  if (rc && ist.status == -1) return failed(rc, ": status " + std::to_string(rc) + ": " + ctx->err);
+  if (rc && ist.status == -1) return failed(rc, "");
   ist.overlap_percent = g.overlap;
   for (int k = 0; k < 3; ++k) ist.overlap_keys[k] = ost.overlap_keys[k];
   out->icp = ist;
@@ -497,24 +486,23 @@ int process_args(aicp_hip_ctx* ctx, aicp_hip_session* s, const float* out_T, con
   return AICP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int aicp_hip_session_create(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_sequence_params* prm,
-                            const aicp_prefilter_params* pf, aicp_hip_session** out) {
-  if (!ctx || !out) return AICP_ERR_INVALID;
-  *out = nullptr;
-  if (!cfg || !prm) return AICP_ERR_INVALID;
+// aicp_hip_session_create's checks
+int create_check(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_sequence_params* prm,
+                 const aicp_prefilter_params* pf) {
   if (prm->reference_update_frequency < 1) FAIL(AICP_ERR_INVALID, "reference_update_frequency must be >= 1");
   if (prm->flags & ~kFlags) FAIL(AICP_ERR_INVALID, "session: flags");
   if (!(prm->max_correction_magnitude == prm->max_correction_magnitude))
     FAIL(AICP_ERR_INVALID, "session: max_correction_magnitude");
   const bool doOvl = prm->flags & AICP_RUN_OVERLAP;
   if (doOvl && !(prm->resolution > 0)) FAIL(AICP_ERR_INVALID, "resolution");
-  int rc = check_cfg(ctx, cfg, AICP_RUN_ICP | (doOvl ? AICP_RUN_OVERLAP : 0));
-  if (!rc && pf) rc = stream_prefilter_check(ctx, pf);
-  if (rc) return rc;
+  const int rc = check_cfg(ctx, cfg, AICP_RUN_ICP | (doOvl ? AICP_RUN_OVERLAP : 0));
+  return !rc && pf ? stream_prefilter_check(ctx, pf) : rc;
+}
+
+// a session of checked parameters; risk_prm: failure_prediction_mode (null: a plain session)
+int create_session(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_sequence_params* prm,
+                   const aicp_prefilter_params* pf, const aicp_risk_params* risk_prm, const aicp_hip_svm* model,
+                   double threshold, aicp_hip_session** out) {
   HIPC(hipSetDevice(ctx->device));
   aicp_hip_session* s = new aicp_hip_session();
   s->cfg = *cfg;
@@ -523,8 +511,16 @@ int aicp_hip_session_create(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const
   s->has_pf = pf != nullptr;
   s->rules.built = 1;  // the drop test on every reading, the count restarts at a new reference
   s->rules.freq = prm->reference_update_frequency;
-  s->rules.overlap = doOvl ? 1 : 0;
+  s->rules.overlap = prm->flags & AICP_RUN_OVERLAP ? 1 : 0;
   s->rules.max_corr = prm->max_correction_magnitude;
+  if (risk_prm) {
+    s->risk = true;
+    s->rprm = *risk_prm;
+    s->model = model;
+    s->threshold = threshold;
+    s->prm.flags |= AICP_RUN_OVERLAP;  // (the overlap always runs: the classifier needs it)
+    s->rules.overlap = 0;  // (the overlap is a batch of its own, its status checked before the gate)
+  }
   hipError_t e = ensure(s->win, kWinBytes);
   if (e == hipSuccess) e = ensure(s->pin, kWinBytes);
   if (e == hipSuccess) e = hipEventCreate(&s->ev_begin);
@@ -537,6 +533,50 @@ int aicp_hip_session_create(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const
   return AICP_OK;
 }
 
+}  // namespace
+
+// The two offline entry points' loop (aicp_hip.cpp; declared in runtime.hpp).
+int aicp::rt::session_replay(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_sequence_params* prm,
+                             const aicp_prefilter_params* pf, const ReplayRisk* risk, const aicp_cloud* first,
+                             const aicp_cloud* readings, size_t n, float* out_T, aicp_sequence_result* out,
+                             size_t* n_done) {
+  aicp_sequence_params p = *prm;
+  p.flags &= kFlags;  // (the entry points ignore the other bits; a NaN bound rejects nothing)
+  aicp_hip_session* s = nullptr;
+  int rc = create_session(ctx, cfg, &p, pf, risk ? risk->prm : nullptr, risk ? risk->model : nullptr,
+                          risk ? risk->threshold : 0.0, &s);
+  if (rc) return rc;
+  // a risk stream's sensor origins are its poses' translations
+  auto rows = [&](const aicp_cloud& c, const double* pose) {
+    Rows r;
+    r.hpts = c.pts, r.n = c.n, r.stride = c.stride;
+    for (int k = 0; k < 3; ++k) r.origin[k] = pose ? pose[12 + k] : c.origin[k];
+    return r;
+  };
+  rc = start_rows(ctx, s, rows(*first, risk ? risk->first_pose : nullptr), risk ? risk->first_pose : nullptr);
+  for (size_t i = 0; i < n && !rc; ++i) {
+    const double* pose = risk ? risk->poses + 16 * i : nullptr;
+    rc = risk ? process_rows_risk(ctx, s, rows(readings[i], pose), pose, out_T + 16 * i, &out[i], &risk->rec[i], nullptr)
+              : process_rows(ctx, s, rows(readings[i], nullptr), out_T + 16 * i, &out[i], nullptr);
+    // (a reading that failed before it was looked at, its pre-filter for one, is not counted)
+    if (!rc || out[i].status) *n_done = i + 1;
+  }
+  if (rc && ctx->err.rfind("session: ", 0) == 0) ctx->err.erase(0, 9);  // the entry points' wording
+  aicp_hip_session_free(ctx, s);
+  return rc;
+}
+
+extern "C" {
+
+int aicp_hip_session_create(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_sequence_params* prm,
+                            const aicp_prefilter_params* pf, aicp_hip_session** out) {
+  if (!ctx || !out) return AICP_ERR_INVALID;
+  *out = nullptr;
+  if (!cfg || !prm) return AICP_ERR_INVALID;
+  const int rc = create_check(ctx, cfg, prm, pf);
+  return rc ? rc : create_session(ctx, cfg, prm, pf, nullptr, nullptr, 0.0, out);
+}
+
 int aicp_hip_session_create_risk(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_sequence_params* prm,
                                  const aicp_prefilter_params* pf, const aicp_risk_params* risk_prm,
                                  const aicp_hip_svm* model, double threshold, aicp_hip_session** out) {
@@ -547,17 +587,9 @@ int aicp_hip_session_create_risk(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, 
   int rc = risk_params_check(ctx, risk_prm);
   if (rc) return rc;
   aicp_sequence_params p = *prm;
-  p.flags |= AICP_RUN_OVERLAP;  // (the overlap always runs: the classifier needs it)
-  aicp_hip_session* s = nullptr;
-  rc = aicp_hip_session_create(ctx, cfg, &p, pf, &s);
-  if (rc) return rc;
-  s->risk = true;
-  s->rprm = *risk_prm;
-  s->model = model;
-  s->threshold = threshold;
-  s->rules.overlap = 0;  // (the overlap is a batch of its own, its status checked before the gate)
-  *out = s;
-  return AICP_OK;
+  p.flags |= AICP_RUN_OVERLAP;  // (checked as the session runs: with the overlap)
+  rc = create_check(ctx, cfg, &p, pf);
+  return rc ? rc : create_session(ctx, cfg, &p, pf, risk_prm, model, threshold, out);
 }
 
 void aicp_hip_session_free(aicp_hip_ctx* ctx, aicp_hip_session* s) {
@@ -579,32 +611,17 @@ void aicp_hip_session_free(aicp_hip_ctx* ctx, aicp_hip_session* s) {
 
 int aicp_hip_session_set_monitor(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_monitor_params* prm) {
   if (!ctx || !s) return AICP_ERR_INVALID;
-  if (!prm) {
-    s->mon_on = false;
-    return AICP_OK;
-  }
-  const int rc = monitor_params_check(ctx, prm);
-  if (rc) return rc;
-  s->mon_prm = *prm;
-  s->mon_on = true;
-  s->mon_tree.invalidate();  // (built again on the first monitored reading)
-  return AICP_OK;
+  const int rc = s->mon.set(ctx, prm);
+  if (!rc && prm) s->mon_tree.invalidate();  // (built again on the first monitored reading)
+  return rc;
 }
 
 int aicp_hip_session_last_monitor(const aicp_hip_session* s, aicp_monitor_result* out, int32_t* valid) {
-  if (!s || !out || !valid) return AICP_ERR_INVALID;
-  *out = s->mon_last;
-  *valid = s->mon_valid;
-  return AICP_OK;
+  return s ? s->mon.get_last(out, valid) : AICP_ERR_INVALID;
 }
 
 int aicp_hip_session_monitor_counters(const aicp_hip_session* s, uint64_t out[4]) {
-  if (!s || !out) return AICP_ERR_INVALID;
-  out[0] = s->mon_cnt.readings;
-  out[1] = s->mon_cnt.trees;
-  out[2] = s->mon_cnt.reuses;
-  out[3] = s->mon_cnt.trees2;
-  return AICP_OK;
+  return s ? s->mon.counters(out) : AICP_ERR_INVALID;
 }
 
 int aicp_hip_session_start(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_cloud* first) {

@@ -869,8 +869,11 @@ int aicp_hip_last_sequence_timing(const aicp_hip_ctx* ctx, aicp_sequence_timing*
  * (pcl::transformPointCloud, float), the moved cloud is pre-filtered there, its prior pose becomes
  * initialT_ * prior pose, and it is registered against the current reference (overlap ->
  * auto-tuned ratio -> ICP; the reference's trees stay resident across readings); then the drop
- * test, the reference update and initialT_ = correction * initialT_ (app.cpp:362-414). The
- * pre-filter's region growing is host-driven, so debug mode takes host round trips per reading.
+ * test, the reference update and initialT_ = correction * initialT_ (app.cpp:362-414). Debug mode
+ * is a loop over the live session's reading step (aicp_hip_session_process below) on a session
+ * private to the call: the reference, initialT_ and the count stay on the device between readings
+ * and no kept cloud comes back to the host. The pre-filter's region growing is host-driven, so
+ * debug mode takes host round trips per reading.
  * pf: the pre-filter (aicp_hip_default_prefilter). A reading the pre-filter empties ends the
  * stream with AICP_ERR_INVALID as its status (libpointmatcher throws on an empty cloud).
  * Results as aicp_hip_sequence_run (corrected_origin from initialT_ * prior pose in debug mode);
@@ -883,7 +886,9 @@ int aicp_hip_sequence_run_raw(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, con
 /* App's stream from RAW clouds with failure_prediction_mode (processCloud, app.cpp:282-414 with both
  * branches of the `if` at app.cpp:362): aicp_hip_sequence_run_raw's rules, reading by reading in
  * robot and in debug mode (the features take host round trips per pair), with the pair going through
- * aicp_hip_pipeline against the current reference and its pose:
+ * aicp_hip_pipeline's steps against the current reference and its pose. The call is a loop over the
+ * gated session's reading step (aicp_hip_session_process_risk below) on a session private to the
+ * call, so the clouds stay on the device between the steps and between the readings:
  *   risk <= threshold: the drop test, the correction, the frequency update and initialT_ =
  *     correction * initialT_ as in aicp_hip_sequence_run_raw;
  *   otherwise (app.cpp:401-411): the unmoved pre-filtered reading joins the graph with its prior pose

@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Per-reading time of failure_prediction_mode served live (AppSession(..., risk=...), one reading
 per call on the resident buffers) against aicp_hip_sequence_run_risk on the same recording: the raw
-C2 stream, the golden opencv3 model, thresholds 0.5 and 1.0, robot and debug mode. One process, one
+C2 stream, the golden opencv3 model, thresholds 0.5 and 1.0, robot and debug mode. The "baseline",
+aicp_hip_sequence_run_risk, is the same reading step driven from C on a session private to the call,
+so the comparison shows the overhead of calling reading by reading from Python and nothing else
+(profiles/session_risk_timing.json records it when it was a host loop of its own; the `baseline`
+list of copies_of_the_median_reading describes that loop). One process, one
 device; the two variants alternate inside every round; one warm-up round, then medians of the rounds
 with (min, max); wall time around synchronising calls. Results are compared for bit equality before
 anything is timed.

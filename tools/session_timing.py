@@ -4,9 +4,13 @@
              session_robot / session_debug   AppSession.process per reading (wall: the call on the
                                              host; device: HIP events around its device work)
              run_raw_debug                   aicp_hip_sequence_run_raw in debug mode over the whole
-                                             recording, the library's own reading-by-reading path
-                                             (host reference, download and re-upload per reading):
-                                             the per-reading mean. Its code is the parent's.
+                                             recording: the per-reading mean. It is the session's
+                                             reading step driven from C on a session private to the
+                                             call, so against session_debug it shows what calling
+                                             reading by reading from Python costs, nothing else.
+                                             (profiles/session_timing.json records it when it was a
+                                             host loop of its own: host reference, a download and a
+                                             re-upload per reading.)
              run_raw_robot                   the windowed stream, for scale (it batches readings)
            session_debug and run_raw_debug must give the same bits.
   accum    one reading of 80 sweeps of 32 k points from a SweepAccumulator, from the last push to the
