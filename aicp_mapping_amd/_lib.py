@@ -70,6 +70,7 @@ EXPORTS = [
     "aicp_hip_session_set_monitor", "aicp_hip_session_last_monitor", "aicp_hip_session_monitor_counters",
     "aicp_hip_mapsession_set_monitor", "aicp_hip_mapsession_last_monitor",
     "aicp_hip_mapsession_monitor_counters", "aicp_hip_test_monitor_resident",
+    "aicp_hip_mapsession_create_risk", "aicp_hip_mapsession_process_risk", "aicp_hip_mapsession_process_accum_risk",
 ]
 
 
@@ -110,7 +111,9 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_session_set_monitor", "aicp_hip_session_last_monitor", "aicp_hip_session_monitor_counters",
            "aicp_hip_mapsession_set_monitor", "aicp_hip_mapsession_last_monitor",
            "aicp_hip_mapsession_monitor_counters",
-           "aicp_hip_test_monitor_resident"}  # the quality monitor per reading in the live sessions
+           "aicp_hip_test_monitor_resident",  # the quality monitor per reading in the live sessions
+           "aicp_hip_mapsession_create_risk", "aicp_hip_mapsession_process_risk",
+           "aicp_hip_mapsession_process_accum_risk"}  # the live map sessions with the risk gate
 
 
 class IcpConfig(C.Structure):
@@ -697,6 +700,14 @@ def _load():
         L.aicp_hip_map_session_process_accum.argtypes = [vp, vp, vp, fp, fp, vp, u32p]
         L.aicp_hip_map_session_state.argtypes = [vp, vp, up, ip, fp, ip]
         L.aicp_hip_map_session_last_timing.argtypes = [vp, dp, dp]
+    if hasattr(L, "aicp_hip_mapsession_create_risk"):  # (out: as aicp_hip_map_session_process)
+        u32p, dp, clp, pfp = C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(Cloud), C.POINTER(PrefilterParams)
+        prp = C.POINTER(PipelineRecord)
+        L.aicp_hip_mapsession_create_risk.argtypes = [vp, cfgp, C.POINTER(LocalizationParams),
+                                                      C.POINTER(BuiltMapParams), pfp, pfp, C.POINTER(RiskParams), vp,
+                                                      C.c_double, C.POINTER(vp)]
+        L.aicp_hip_mapsession_process_risk.argtypes = [vp, vp, clp, dp, fp, vp, prp, u32p]
+        L.aicp_hip_mapsession_process_accum_risk.argtypes = [vp, vp, vp, dp, fp, vp, prp, u32p]
     if hasattr(L, "aicp_hip_session_set_monitor"):
         mpp, mrp = C.POINTER(MonitorParams), C.POINTER(MonitorResult)
         for kind in ("session", "mapsession"):

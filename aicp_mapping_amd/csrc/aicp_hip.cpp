@@ -3101,14 +3101,16 @@ int risk_params_check(aicp_hip_ctx* ctx, const aicp_risk_params* prm) { return p
 // features
 int gate_resident(aicp_hip_ctx* ctx, const aicp_risk_params* prm, const aicp_hip_svm* model, double threshold,
                   const aicp_cloud& ref, const aicp_cloud& read, const float4* d_ref, const float4* d_read,
-                  const double* ref_pose, const double* read_pose, GateRec* d_gate, float* fov_overlap) {
+                  const double* ref_pose, const double* read_pose, GateRec* d_gate, float* fov_overlap,
+                  const float* d_overlap) {
   hipStream_t s = ctx->stream;
   const SvmEntry* entries = nullptr;
   SvmParams sp;
   int rc = svm_device(ctx, model, &entries, &sp);
   if (rc) return rc;
   sp.threshold = threshold;
-  HIPC(hipMemcpyAsync(&d_gate->overlap, &ctx->state.as<PairState>()[0].overlap, 4, hipMemcpyDeviceToDevice, s));
+  if (!d_overlap) d_overlap = &ctx->state.as<PairState>()[0].overlap;
+  HIPC(hipMemcpyAsync(&d_gate->overlap, d_overlap, 4, hipMemcpyDeviceToDevice, s));
   aicp_risk_result rr{};
   rc = alignment_features(ctx, prm, &ref, &read, ref_pose, read_pose, &rr, nullptr, nullptr, nullptr, nullptr, 0,
                           &d_gate->alignability, d_ref, d_read);

@@ -399,6 +399,16 @@ struct GateRec {
 void launch_session_gate_promote(hipStream_t s, int n, const GateRec* gate, const double* origin, const float4* read,
                                  int32_t id, float4* ref, float* T, StreamState* S, StreamRec* rec,
                                  SessionHeader* hdr);
+// The gated branch in the live map sessions (aicp_hip_mapsession_create_risk), right behind
+// launch_svm_predict in the same way (n > 0: the reading's kept points). gate->gate == 0:
+// rec->append = 0, nothing else. Otherwise T = identity, rec = {status 0, accepted 1,
+// corrected_origin = origin}, S->initT stays, and
+//   r.built: dst[i] = read[i] for the reading's n points (the bytes; dst: the map's tail, with room
+//     for n points), rec->append = 1, rec->refilter = 0, S->count = 0;
+//   prior map (one block, read / dst not used): c = ++S->count, rec->append = 0, rec->refilter =
+//     r.merge && r.refilter_every > 0 && (c - 1) % r.refilter_every == 0.
+void launch_session_map_gate(hipStream_t s, int n, const StreamRules& r, const GateRec* gate, const double* origin,
+                             const float4* read, float4* dst, float* T, StreamState* S, StreamRec* rec);
 
 // ---- pre-filter (kernels_prefilter.hip): regionGrowingUniformPlaneSegmentationFilter -------
 constexpr int kPfMaxNbrs = 16;  // RegionGrowing neighbours per point (edge mask bits)

@@ -15,6 +15,11 @@
 // k_session_map_append is the same step for the live map sessions (map_stream.cpp): the reading
 // goes behind the caller's map instead (prior map: app.cpp:469-483, built map: app.cpp:383-391,
 // 458-465), where the host has made room before the reading's crop was enqueued.
+//
+// k_session_map_gate is the gated branch for the live map sessions made by
+// aicp_hip_mapsession_create_risk, right behind k_svm_predict: on the built map the unmoved reading
+// goes behind the map and the count restarts, on the prior map the cloud joins the graph without a
+// merge and the re-filter rule still applies (app.cpp:401-411, 458-493).
 #include <hip/hip_runtime.h>
 
 #include "aicp_common.hpp"
@@ -31,6 +36,12 @@ __device__ __forceinline__ void move_point(const float (&Tl)[16], const float4* 
   float q[3];
   apply4(Tl, p.x, p.y, p.z, q);
   dst[i] = make_float4(q[0], q[1], q[2], 1.f);
+}
+
+// One point of the reading as it was filtered, unmoved: its bytes, one 128-bit load, one 128-bit
+// store (apply4 by the identity would turn -0.0f into +0.0f). The body of the two gate kernels.
+__device__ __forceinline__ void copy_point(const float4* __restrict__ read, float4* __restrict__ dst, int i) {
+  dst[i] = read[i];
 }
 
 // One thread per point of the reading: one 128-bit load, one 128-bit store. Every thread reads the
@@ -103,7 +114,48 @@ __global__ __launch_bounds__(256) void k_session_gate_promote(int n, const GateR
   }
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  ref[i] = read[i];
+  copy_point(read, ref, i);
+}
+
+// The gated branch for the live map sessions (built: app.cpp:401-411, 458-465; prior map:
+// app.cpp:401-411, 469-493) behind k_svm_predict. Every thread reads the gate from device memory
+// (one address for the whole grid: the branch is uniform). Not gated: thread 0 of block 0 clears
+// rec->append, nothing else is written. Gated, built map (r.built): one thread per point of the
+// reading copies it to the map's tail (dst: room for n points was reserved before the launch; it
+// never aliases read, the batch's copy of the reading), thread 0 of block 0 writes the record
+// (append 1), the identity correction and the count 0. Gated, prior map (one block; n, read and dst
+// are not used): the cloud joins the graph marked a reference, so the merge of app.cpp:469-483 is not
+// reached (append 0) while the re-filter test of app.cpp:487-493 still applies to the new count.
+// S->initT is never written.
+__global__ __launch_bounds__(256) void k_session_map_gate(int n, StreamRules r, const GateRec* __restrict__ gate,
+                                                          const double* __restrict__ origin,
+                                                          const float4* __restrict__ read, float4* __restrict__ dst,
+                                                          float* __restrict__ T, StreamState* S, StreamRec* rec) {
+  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+  if (!gate->gate) {
+    if (first) rec->append = 0;
+    return;
+  }
+  if (first) {
+    int32_t refilter = 0;
+    if (r.built) {
+      S->count = 0;
+    } else {
+      const int32_t c = S->count + 1;  // ++n_clouds
+      refilter = r.merge && r.refilter_every > 0 && (c - 1) % r.refilter_every == 0;
+      S->count = c;
+    }
+    rec->status = 0;
+    rec->accepted = 1;
+    rec->append = r.built ? 1 : 0;
+    rec->refilter = refilter;
+    for (int k = 0; k < 3; ++k) rec->corrected_origin[k] = origin[k];
+    for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.f : 0.f;
+  }
+  if (!r.built) return;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  copy_point(read, dst, i);
 }
 
 void launch_session_promote(hipStream_t s, int n, const StreamRec* rec, const float* T, const float4* read, int32_t id,
@@ -119,6 +171,12 @@ void launch_session_gate_promote(hipStream_t s, int n, const GateRec* gate, cons
 void launch_session_map_append(hipStream_t s, int n, const StreamRec* rec, const float* T, const float4* read,
                                float4* dst) {
   if (n > 0) k_session_map_append<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, rec, T, read, dst);
+}
+void launch_session_map_gate(hipStream_t s, int n, const StreamRules& r, const GateRec* gate, const double* origin,
+                             const float4* read, float4* dst, float* T, StreamState* S, StreamRec* rec) {
+  // built map: sized by the kept count; prior map: one block (no point is copied)
+  const unsigned blocks = r.built ? (unsigned)((n + 255) / 256) : 1u;
+  if (n > 0) k_session_map_gate<<<blocks, 256, 0, s>>>(n, r, gate, origin, read, dst, T, S, rec);
 }
 
 }  // namespace aicp

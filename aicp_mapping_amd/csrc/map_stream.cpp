@@ -34,6 +34,14 @@
 // With the quality monitor on (aicp_hip_mapsession_set_monitor) a registered reading's metrics
 // against its crop are enqueued behind the batch and ahead of the commit (monitor_resident,
 // monitor.cpp), and their 56 bytes come back in that read-back.
+//
+// A risk session (aicp_hip_mapsession_create_risk: failure_prediction_mode, runAicpPipeline
+// app.cpp:236-245 and the gated branch app.cpp:401-411 under the two map policies) splits the
+// reading's batch in two and puts the gate between, on the same crop: (built map) overlap-only batch
+// -> alignment features with the FOV filters reading the crop and the reading where the batch holds
+// them -> k_svm_predict -> k_session_map_gate -> [host] one read-back of state, record and the gate's
+// record. A gated reading ends there; otherwise the ICP-only batch at the device's ratio, then the
+// commit, the append and the read-back as above.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -165,6 +173,18 @@ struct Live {
   size_t mon_off = 0;
   bool mon_ran = false;
   std::string mon_err;
+  // a risk session's gate (null: a plain session): the features' parameters, the caller's model, the
+  // threshold, the reading's prior pose (column-major double), where the gate's record and the prior
+  // map's constant overlap lie in the session's block, and the pipeline's record for the caller
+  struct Risk {
+    const aicp_risk_params* prm;
+    const aicp_hip_svm* model;
+    double threshold;
+    const double* pose;
+    size_t gate_off, fifty_off, back;  // back: the read-back that brings state | record | gate record
+    aicp_pipeline_record* rec;
+  };
+  const Risk* risk = nullptr;
 };
 
 // how a window ended its stream, if it did
@@ -172,6 +192,129 @@ struct WinEnd {
   int status = AICP_OK;
   bool empty_crop = false, empty_read = false;
 };
+
+// A risk session's reading between its crop and its commit: runAicpPipeline's overlap, features,
+// classifier and gate (app.cpp:236-245) on the batch's crop and reading where they lie, the gated
+// branch taken on the device (k_session_map_gate), one read-back. *gated: the reading ended here
+// (out is filled, the map changed as its record says). end->status: the overlap, the features or the
+// classifier failed (out is filled). Otherwise the ICP-only batch at the device's ratio has run
+// (st: its stats with the overlap's put in) and the caller goes on with the commit.
+int gate_reading(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, aicp_hip_map* map, const WinBlock& K,
+                 aicp_hip_batch* B, uint32_t crop_n, size_t map_n, float* out_T, aicp_localization_result* out,
+                 aicp_icp_stats& st, StreamTiming& tm, Live* live, bool* gated, WinEnd* end) {
+  const Live::Risk& R = *live->risk;
+  hipStream_t s = ctx->stream;
+  char* d = reinterpret_cast<char*>(K.dS);
+  GateRec* dGate = reinterpret_cast<GateRec*>(d + R.gate_off);
+  const StreamState* hS = reinterpret_cast<const StreamState*>(K.pin);
+  const PairDesc& pd = B->desc[0];
+  const float4* dref = B->ref_raw.as<float4>() + B->rdesc[0].ref_off;
+  const float4* dread = B->read_raw.as<float4>() + pd.read_off;
+  aicp_pipeline_record* prec = R.rec;
+  prec->n_read = pd.n_read;
+  auto failed = [&](int rc) {  // the reading's status: the session ends at it
+    aicp_localization_result& o = out[0];
+    std::memset(&o, 0, sizeof(o));
+    o.status = o.icp.status = rc;
+    o.map_points = map_n;
+    o.crop_points = crop_n;
+    o.icp.overlap_percent = -1.f;
+    end->status = rc;
+    return AICP_OK;
+  };
+  // the reading's pose as setAndFilterReading leaves it (app.cpp:87-96: debug mode, initialT_ * prior
+  // pose, from the mirror of the device's initialT_); the reference's is the prior pose as given
+  double prior[16];
+  if (P.debug)
+    pose_moved(hS->initT, R.pose, prior);
+  else
+    std::memcpy(prior, R.pose, sizeof(prior));
+  // 1. computeOverlap. Built map: an overlap-only batch on the crop. Prior map: octree_overlap_ = 50.0
+  // (app.cpp:123-127), no octree
+  aicp_icp_stats ost{};
+  int rc;
+  if (P.bm) {
+    ost.status = -1;
+    rc = run_batch(ctx, B, cfg, P.resolution, AICP_RUN_OVERLAP, nullptr, &ost, nullptr);
+    if (rc && ost.status == -1) return rc;  // the batch did not run to its end
+    if (rc) {
+      ctx->err = "overlap: " + ctx->err;
+      return failed(rc);
+    }
+  } else {
+    HIPC(ensure(ctx->outT, 64));  // (the gate kernel's correction slot; no batch has sized it yet)
+  }
+  // 2. and 3. the features on the crop and the reading where the batch holds them (the features'
+  // pre-filters write the context's work space, never the batch's own ref_raw / read_raw; its
+  // descriptors go up again with the next run_batch), the classifier, the gate and the ratio
+  float fov = 0.f;
+  aicp_cloud ca{}, cb{};
+  ca.n = crop_n, cb.n = pd.n_read;
+  ca.stride = cb.stride = 16;
+  rc = gate_resident(ctx, R.prm, R.model, R.threshold, ca, cb, dref, dread, R.pose, prior, dGate, &fov,
+                     P.bm ? nullptr : reinterpret_cast<const float*>(d + R.fifty_off));
+  if (rc) {
+    ctx->err = "risk gate: " + ctx->err;
+    return failed(rc);
+  }
+  // 4. the gated branch, on the device; one read-back
+  if (P.bm && !live->reserved) FAIL(AICP_ERR_HIP, "map session: no room was made for a gated reading");
+  launch_session_map_gate(s, (int)pd.n_read, P.rules, dGate, K.dOrg, dread,
+                          P.bm ? map->pts.as<float4>() + map->n : nullptr, ctx->outT.as<float>(), K.dS, K.dRec);
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(live->ev_done, s));
+  HIPC(hipMemcpyAsync(K.pin, d, R.back, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  const GateRec g = *reinterpret_cast<const GateRec*>(K.pin + R.gate_off);
+  prec->fov_overlap = fov;
+  prec->octree_overlap = g.overlap;
+  prec->alignability = g.alignability;
+  prec->raw = g.raw;
+  prec->risk = g.risk;
+  prec->trimmed_ratio = g.ratio;
+  prec->registered = g.gate ? 0 : 1;
+  if (g.gate) {
+    // app.cpp:401-411: the correction is the identity, initialT_ stays, no drop test
+    const StreamRec& r = *reinterpret_cast<const StreamRec*>(K.pin + kRecOff);
+    if (r.status != 0 || !r.accepted || r.append != (P.bm ? 1 : 0))
+      FAIL(AICP_ERR_HIP, "map session: the gated reading's record");
+    live->registered = true;  // (ev_done is recorded)
+    aicp_localization_result& o = out[0];
+    std::memset(&o, 0, sizeof(o));
+    o.accepted = 1;
+    o.map_points = map_n;
+    o.crop_points = crop_n;
+    for (int k = 0; k < 3; ++k) o.corrected_origin[k] = r.corrected_origin[k];
+    o.icp.overlap_percent = g.overlap;
+    o.icp.trimmed_ratio = g.ratio;
+    for (int k = 0; k < 3; ++k) o.icp.overlap_keys[k] = ost.overlap_keys[k];
+    ident4(out_T);
+    if (r.append) {  // built map: the reading is the reference at once (done on the device already)
+      map->n += pd.n_read;
+      o.merged = 1;
+      ++tm.appends;
+    }
+    if (r.refilter) {  // prior map: app.cpp:487-493 stands outside the merge and still applies
+      rc = aicp_hip_map_prefilter(ctx, map, P.pf);
+      if (rc) return rc;
+      o.refiltered = 1;
+      ++tm.refilters;
+    }
+    *gated = true;
+    return AICP_OK;
+  }
+  // 5. computeRegistration at the device's ratio (app.cpp:243-245): an ICP-only batch on the same crop
+  aicp_icp_config c2 = *cfg;
+  c2.trimmed_ratio = g.ratio;
+  st.status = -1;
+  rc = run_batch(ctx, B, &c2, 0.0, AICP_RUN_ICP | (P.run_flags & AICP_RUN_TIME_NN), out_T, &st, nullptr);
+  if (rc && st.status == -1) return rc;
+  if (P.bm) {
+    st.overlap_percent = g.overlap;
+    for (int k = 0; k < 3; ++k) st.overlap_keys[k] = ost.overlap_keys[k];
+  }
+  return AICP_OK;
+}
 
 // One window: the w readings at `readings` / `poses`, which see the same map. Pre-filter or ingest,
 // crop, staging copy, (debug mode) move, batch, commit, one read-back, the map changes the records
@@ -236,7 +379,9 @@ int stream_window(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg
   // the mirrored count says this reading appends when it is accepted (k_stream_commit's rule)
   if (live && wp) {
     const int32_t c = hS->count;
-    const bool appends = P.bm ? c + 1 == P.rules.freq : (P.rules.merge && c % P.rules.freq == 0);
+    // (a risk session on the built map: every reading, because any reading may be gated)
+    const bool appends =
+        P.bm ? (c + 1 == P.rules.freq || live->risk) : (P.rules.merge && c % P.rules.freq == 0);
     if (appends) {
       rc = map_reserve(ctx, map, raw ? (size_t)kept[0] : (size_t)readings[0].n);
       if (rc) return rc;
@@ -270,8 +415,18 @@ int stream_window(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg
     }
     stats.assign(wr, aicp_icp_stats{});
     for (auto& st : stats) st.status = -1;
-    rc = run_batch(ctx, B, cfg, P.resolution, P.run_flags, out_T, stats.data(), nullptr);
-    if (rc && stats[0].status == -1) return rc;  // the batch did not run to its end (not a reading's status)
+    if (live && live->risk) {
+      bool gated = false;
+      rc = gate_reading(ctx, P, cfg, map, K, B, htot[0], map_n, out_T, out, stats[0], tm, live, &gated, end);
+      if (rc) return rc;
+      if (gated || end->status) {
+        *n_done = base + 1;
+        return AICP_OK;
+      }
+    } else {
+      rc = run_batch(ctx, B, cfg, P.resolution, P.run_flags, out_T, stats.data(), nullptr);
+      if (rc && stats[0].status == -1) return rc;  // the batch did not run to its end (not a reading's status)
+    }
     ++tm.windows;
     // a session's monitor of a registered reading, ahead of the commit and the append: the crop and
     // the reading where the batch holds them (the batch reads both only), the correction where the
@@ -429,10 +584,13 @@ int run_stream(aicp_hip_ctx* ctx, const Stream& P, const aicp_icp_config* cfg, a
 
 // the live map session's small device block and its pinned mirror: StreamState | StreamRec | the
 // quality monitor's result | the reading's prior origin (3 doubles): the streams' window layout with
-// one record, and the result right behind it, so that one read-back brings both
-constexpr size_t kSessMon = 192, kSessOrg = 256, kSessBytes = 320;
+// one record, and the result right behind it, so that one read-back brings both. A risk session's
+// gate record lies behind the origin (its read-back runs to the record's end), and behind that the
+// prior map's constant overlap, 50.0f, written at start
+constexpr size_t kSessMon = 192, kSessOrg = 256, kSessGate = 288, kSessFifty = 320, kSessBytes = 384;
 static_assert(kRecOff + sizeof(StreamRec) <= kSessMon && kSessMon + sizeof(aicp_monitor_result) <= kSessOrg &&
-                  kSessOrg + 24 <= kSessBytes,
+                  kSessOrg + 24 <= kSessGate && kSessGate % alignof(GateRec) == 0 &&
+                  kSessGate + sizeof(GateRec) <= kSessFifty && kSessFifty + 4 <= kSessBytes,
               "the session block's layout");
 
 }  // namespace
@@ -455,6 +613,12 @@ struct aicp_hip_map_session {
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   double last_wall_ms = 0, last_device_ms = 0;
   MonState mon;  // the per-reading quality monitor (aicp_hip_mapsession_set_monitor)
+  // failure_prediction_mode (aicp_hip_mapsession_create_risk): the features' parameters, the caller's
+  // model and the gate's threshold
+  bool risk = false;
+  aicp_risk_params rprm{};
+  const aicp_hip_svm* model = nullptr;
+  double threshold = 0;
 };
 
 extern "C" {
@@ -620,13 +784,18 @@ int aicp_hip_last_built_map_timing(const aicp_hip_ctx* ctx, aicp_built_map_timin
 }
 
 // ---- the live map sessions: stream_window with w = 1 and a state that persists ----------------
-int aicp_hip_map_session_create(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* loc,
-                                const aicp_built_map_params* bm, const aicp_prefilter_params* pf_read,
-                                const aicp_prefilter_params* pf_map, aicp_hip_map_session** out) {
-  if (!ctx || !out) return AICP_ERR_INVALID;
-  *out = nullptr;
-  if (!cfg) return AICP_ERR_INVALID;
+// risk_prm (null: a plain session): failure_prediction_mode, with the caller's model and the threshold
+static int map_session_make(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* loc,
+                            const aicp_built_map_params* bm, const aicp_prefilter_params* pf_read,
+                            const aicp_prefilter_params* pf_map, const aicp_risk_params* risk_prm,
+                            const aicp_hip_svm* model, double threshold, aicp_hip_map_session** out) {
   if ((loc != nullptr) == (bm != nullptr)) FAIL(AICP_ERR_INVALID, "map session: exactly one of loc / bm");
+  aicp_built_map_params bmo;
+  if (bm && risk_prm) {  // (the overlap always runs: the classifier needs it)
+    bmo = *bm;
+    bmo.flags |= AICP_RUN_OVERLAP;
+    bm = &bmo;
+  }
   if (bm && pf_map) FAIL(AICP_ERR_INVALID, "map session: the built map is never re-filtered (pf_map)");
   if (loc && !valid_params(loc)) FAIL(AICP_ERR_INVALID, "localization parameters");
   if (bm && !valid_params(bm)) FAIL(AICP_ERR_INVALID, "built-map parameters");
@@ -644,6 +813,13 @@ int aicp_hip_map_session_create(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, c
   } else {
     s->bm = *bm;
     s->P = bm_rules(&s->bm, pf_read ? &s->pf_read : nullptr);
+  }
+  if (risk_prm) {
+    s->risk = true;
+    s->rprm = *risk_prm;
+    s->model = model;
+    s->threshold = threshold;
+    s->P.rules.overlap = 0;  // (the overlap is a batch of its own, its status checked before the gate)
   }
   int rc = check_cfg(ctx, &s->cfg, s->P.run_flags);
   if (!rc && pf_read) rc = stream_prefilter_check(ctx, pf_read);
@@ -664,6 +840,27 @@ int aicp_hip_map_session_create(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, c
   }
   *out = s;
   return AICP_OK;
+}
+
+int aicp_hip_map_session_create(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* loc,
+                                const aicp_built_map_params* bm, const aicp_prefilter_params* pf_read,
+                                const aicp_prefilter_params* pf_map, aicp_hip_map_session** out) {
+  if (!ctx || !out) return AICP_ERR_INVALID;
+  *out = nullptr;
+  if (!cfg) return AICP_ERR_INVALID;
+  return map_session_make(ctx, cfg, loc, bm, pf_read, pf_map, nullptr, nullptr, 0.0, out);
+}
+
+int aicp_hip_mapsession_create_risk(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* loc,
+                                    const aicp_built_map_params* bm, const aicp_prefilter_params* pf_read,
+                                    const aicp_prefilter_params* pf_map, const aicp_risk_params* risk_prm,
+                                    const aicp_hip_svm* model, double threshold, aicp_hip_map_session** out) {
+  if (!ctx || !out) return AICP_ERR_INVALID;
+  *out = nullptr;
+  if (!cfg || !risk_prm || !model) return AICP_ERR_INVALID;
+  if (!(threshold == threshold)) FAIL(AICP_ERR_INVALID, "map session: threshold");
+  const int rc = risk_params_check(ctx, risk_prm);
+  return rc ? rc : map_session_make(ctx, cfg, loc, bm, pf_read, pf_map, risk_prm, model, threshold, out);
 }
 
 void aicp_hip_map_session_free(aicp_hip_ctx* ctx, aicp_hip_map_session* s) {
@@ -689,6 +886,7 @@ int aicp_hip_map_session_start(aicp_hip_ctx* ctx, aicp_hip_map_session* s, aicp_
   char* h = s->pin.as<char>();
   std::memset(h, 0, kSessBytes);
   ident4(reinterpret_cast<StreamState*>(h)->initT);
+  *reinterpret_cast<float*>(h + kSessFifty) = 50.0f;  // octree_overlap_ on the prior map (app.cpp:123-127)
   HIPC(hipMemcpyAsync(s->win.p, h, kSessBytes, hipMemcpyHostToDevice, st));
   HIPC(hipStreamSynchronize(st));
   s->map = map;
@@ -721,9 +919,17 @@ static int map_session_end(aicp_hip_ctx* ctx, aicp_hip_map_session* s, int rc) {
   return rc;
 }
 
+// pose_d, prec: a risk session's call (the prior pose in double, column-major, and the pipeline's
+// record); both null: a plain session's (pose). A handle of the other kind refuses the call.
 static int map_session_process(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const aicp_cloud* reading,
-                               aicp_hip_accum* acc, const float* pose, float* out_T, void* out, uint32_t* kept_out) {
-  if (!ctx || !s || (!reading && !acc) || !pose || !out_T || !out) return AICP_ERR_INVALID;
+                               aicp_hip_accum* acc, const float* pose, const double* pose_d, float* out_T, void* out,
+                               aicp_pipeline_record* prec, uint32_t* kept_out) {
+  const bool risk = pose_d != nullptr;
+  if (!ctx || !s || (!reading && !acc) || (!pose && !pose_d) || !out_T || !out || (risk && !prec))
+    return AICP_ERR_INVALID;
+  if (s->risk != risk)
+    FAIL(AICP_ERR_INVALID, risk ? "map session: not made by aicp_hip_mapsession_create_risk"
+                                : "map session: a risk session takes the _risk calls");
   if (!s->started) FAIL(AICP_ERR_INVALID, "map session: process before start");
   if (s->ended) FAIL(AICP_ERR_INVALID, "map session ended at reading " + std::to_string(s->ended_at));
   const Stream& P = s->P;
@@ -741,9 +947,22 @@ static int map_session_process(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const
     live.mon_off = kSessMon;
   }
   s->mon.none();
+  // a risk session: the crop is taken at the pose cast to float (app.cpp:47, 63), the sensor origin
+  // is the pose's translation
+  float posef[16];
+  Live::Risk lr{};
+  if (risk) {
+    for (int k = 0; k < 16; ++k) posef[k] = (float)pose_d[k];
+    pose = posef;
+    *prec = aicp_pipeline_record{};
+    lr = Live::Risk{&s->rprm, s->model, s->threshold, pose_d, kSessGate, kSessFifty, kSessGate + sizeof(GateRec), prec};
+    live.risk = &lr;
+  }
   aicp_cloud c{};
   if (reading) {
     c = *reading;
+    if (risk)
+      for (int k = 0; k < 3; ++k) c.origin[k] = pose_d[12 + k];
   } else {  // the accumulator's cloud where it lies; its sensor origin is the pose's translation
     const int rc = accum_resident(ctx, acc, &live.dpts, &live.dn);  // (waits for the pushes)
     if (rc) return rc;
@@ -751,7 +970,7 @@ static int map_session_process(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const
     c.pts = reinterpret_cast<const float*>(live.dpts);  // (not read on the host)
     c.n = live.dn;
     c.stride = 16;
-    for (int k = 0; k < 3; ++k) c.origin[k] = pose[12 + k];
+    for (int k = 0; k < 3; ++k) c.origin[k] = risk ? pose_d[12 + k] : (double)pose[12 + k];
   }
   const std::string id = std::to_string(s->n_processed);
   aicp_localization_result* o = static_cast<aicp_localization_result*>(out);
@@ -806,14 +1025,28 @@ static int map_session_process(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const
 
 int aicp_hip_map_session_process(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const aicp_cloud* reading,
                                  const float pose[16], float out_T[16], void* out, uint32_t* kept) {
-  if (!reading) return AICP_ERR_INVALID;
-  return map_session_process(ctx, s, reading, nullptr, pose, out_T, out, kept);
+  if (!reading || !pose) return AICP_ERR_INVALID;
+  return map_session_process(ctx, s, reading, nullptr, pose, nullptr, out_T, out, nullptr, kept);
 }
 
 int aicp_hip_map_session_process_accum(aicp_hip_ctx* ctx, aicp_hip_map_session* s, aicp_hip_accum* acc,
                                        const float pose[16], float out_T[16], void* out, uint32_t* kept) {
-  if (!acc) return AICP_ERR_INVALID;
-  return map_session_process(ctx, s, nullptr, acc, pose, out_T, out, kept);
+  if (!acc || !pose) return AICP_ERR_INVALID;
+  return map_session_process(ctx, s, nullptr, acc, pose, nullptr, out_T, out, nullptr, kept);
+}
+
+int aicp_hip_mapsession_process_risk(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const aicp_cloud* reading,
+                                     const double pose[16], float out_T[16], void* out, aicp_pipeline_record* rec,
+                                     uint32_t* kept) {
+  if (!reading || !pose || !rec) return AICP_ERR_INVALID;
+  return map_session_process(ctx, s, reading, nullptr, nullptr, pose, out_T, out, rec, kept);
+}
+
+int aicp_hip_mapsession_process_accum_risk(aicp_hip_ctx* ctx, aicp_hip_map_session* s, aicp_hip_accum* acc,
+                                           const double pose[16], float out_T[16], void* out,
+                                           aicp_pipeline_record* rec, uint32_t* kept) {
+  if (!acc || !pose || !rec) return AICP_ERR_INVALID;
+  return map_session_process(ctx, s, nullptr, acc, nullptr, pose, out_T, out, rec, kept);
 }
 
 int aicp_hip_map_session_state(aicp_hip_ctx* ctx, aicp_hip_map_session* s, uint64_t* n_processed, int32_t* count,

@@ -508,10 +508,12 @@ void refcache_begin_resident(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, uint
 // features (alignability into d_gate->alignability, device to device), then k_svm_predict into
 // d_gate's raw, risk, gate and ratio. The clouds: the caller's host arrays (ref / read: pts, n,
 // stride), or, with d_ref / d_read given, where they lie on the device (float4; then only n is
-// read). Nothing of d_gate is read back here. The poses: column-major double[16].
+// read). Nothing of d_gate is read back here. The poses: column-major double[16]. d_overlap (device,
+// nullable): the overlap to classify instead of the batch's (the prior map's constant: no batch ran).
 int gate_resident(aicp_hip_ctx* ctx, const aicp_risk_params* prm, const aicp_hip_svm* model, double threshold,
                   const aicp_cloud& ref, const aicp_cloud& read, const float4* d_ref, const float4* d_read,
-                  const double* ref_pose, const double* read_pose, GateRec* d_gate, float* fov_overlap);
+                  const double* ref_pose, const double* read_pose, GateRec* d_gate, float* fov_overlap,
+                  const float* d_overlap = nullptr);
 // The loop of the two offline App-order entry points (aicp_hip_sequence_run_raw in debug mode,
 // aicp_hip_sequence_run_risk; session.cpp): a session private to the call, started on `first` and
 // fed the readings one by one into out_T + 16 i, out[i] (and risk->rec[i]); *n_done = i + 1 after

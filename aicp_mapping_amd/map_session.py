@@ -10,6 +10,16 @@ decided and done on the device behind the reading's registration.
     session.start()
     for reading, pose in node:                   # or a SweepAccumulator in place of the reading
         T, result, kept = session.process(reading, pose)
+
+With ``risk=dict(model=SvmModel, threshold=..., params=RiskParams)`` the session serves
+``failure_prediction_mode`` under the map's policy (aicp_hip_mapsession_create_risk): every reading
+goes through the overlap (built map; the prior map's is the constant 50), the alignment features and
+the classifier on the crop and the reading where they lie on the device, and a reading whose risk is
+above the threshold is not registered: on the built map it becomes the reference unmoved, on the
+prior map it joins the graph without a merge. ``process`` then takes the 4x4 prior pose in double
+and returns the pipeline's record as a fourth value:
+
+    T, result, kept, record = session.process(reading, pose)
 """
 from __future__ import annotations
 
@@ -26,7 +36,7 @@ class MapSession(L.SessionMonitor):
     _monitor_kind = "mapsession"
 
     def __init__(self, ctx: "L.Context", map, cfg=None, params=None, prefilter=None, map_prefilter=None,
-                 monitor=None):
+                 monitor=None, risk=None):
         """map: a PriorMap (localize_against_prior_map; params: LocalizationParams) or a BuiltMap
         (localize_against_built_map, created from App's first cloud; params: BuiltMapParams); the
         policy follows the map's class and the params' type, which must agree. cfg: IcpConfig
@@ -35,7 +45,10 @@ class MapSession(L.SessionMonitor):
         are RAW and go through setAndFilterReading in App's order. map_prefilter: the prior map's
         re-filter (None: the defaults); not for a BuiltMap. monitor: None (off), True or
         dict(quantile=, max_accepted_dist=, paired=) for the quality monitor per reading, against
-        the reading's map crop (set_monitor, last_monitor, monitor_counters)."""
+        the reading's map crop (set_monitor, last_monitor, monitor_counters). risk: None, or
+        dict(model=SvmModel (kept alive by the session), threshold=float (default 0.5),
+        params=RiskParams (default_risk_params() when left out)) for failure_prediction_mode; on a
+        BuiltMap the overlap then always runs."""
         mon = L.monitor_argument(monitor)  # (a bad argument before anything is made)
         built = isinstance(map, BuiltMap)
         if params is None:
@@ -46,10 +59,20 @@ class MapSession(L.SessionMonitor):
         if prefilter is True:
             prefilter = L.default_prefilter()
         h = C.c_void_p()
-        ctx.check(L.lib.aicp_hip_map_session_create(
-            ctx.h, C.byref(cfg), None if built else C.byref(params), C.byref(params) if built else None,
-            None if prefilter is None else C.byref(prefilter),
-            None if map_prefilter is None else C.byref(map_prefilter), C.byref(h)))
+        args = (ctx.h, C.byref(cfg), None if built else C.byref(params), C.byref(params) if built else None,
+                None if prefilter is None else C.byref(prefilter),
+                None if map_prefilter is None else C.byref(map_prefilter))
+        self.risk = None
+        if risk is not None:
+            unknown = set(risk) - {"model", "threshold", "params"}
+            if unknown or "model" not in risk:
+                raise ValueError(f"risk: dict(model=, threshold=, params=), got {sorted(risk)}")
+            rp = risk.get("params") or L.default_risk_params()
+            self.risk = dict(model=risk["model"], threshold=float(risk.get("threshold", 0.5)), params=rp)
+            ctx.check(L.lib.aicp_hip_mapsession_create_risk(*args, C.byref(rp), risk["model"].h,
+                                                            self.risk["threshold"], C.byref(h)))
+        else:
+            ctx.check(L.lib.aicp_hip_map_session_create(*args, C.byref(h)))
         self.ctx = ctx
         self.map = map
         self.built = built
@@ -76,7 +99,12 @@ class MapSession(L.SessionMonitor):
         with its 4x4 row-major prior pose, whose translation is the reading's sensor origin.
         Returns (T 4x4 row-major correction, result dict as the map's sequence_run gives them with
         `rc` added, kept points). An empty crop, an emptied reading or a registration error ends
-        the session (AicpError unless raise_on_error is False); start() revives it."""
+        the session (AicpError unless raise_on_error is False); start() revives it. A risk session
+        reads the pose in double (the crop is taken at its float cast), ends on a failed overlap,
+        feature or classifier step too, and returns the pipeline's record dict (Context.pipeline's)
+        as a fourth value."""
+        if self.risk is not None:
+            return self._process_risk(reading, pose, raise_on_error)
         P = np.asarray(pose, np.float64).reshape(4, 4)
         pz = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(4, 4).T.reshape(16))
         outT = np.zeros(16, np.float32)
@@ -95,6 +123,25 @@ class MapSession(L.SessionMonitor):
         d["rc"] = rc
         return outT.reshape(4, 4).T.copy(), d, int(kept.value)
 
+    def _process_risk(self, reading, pose, raise_on_error):
+        pd = L._pose16(pose)
+        outT = np.zeros(16, np.float32)
+        res = (L.BuiltMapResult if self.built else L.LocalizationResult)()
+        kept = C.c_uint32(0)
+        rec = L.PipelineRecord()
+        if isinstance(reading, SweepAccumulator):
+            rc = L.lib.aicp_hip_mapsession_process_accum_risk(self.ctx.h, self.h, reading.h, L._dptr(pd), L._fptr(outT),
+                                                              C.byref(res), C.byref(rec), C.byref(kept))
+        else:
+            c, keep = L.make_cloud(reading, pd[12:15])
+            rc = L.lib.aicp_hip_mapsession_process_risk(self.ctx.h, self.h, C.byref(c), L._dptr(pd), L._fptr(outT),
+                                                        C.byref(res), C.byref(rec), C.byref(kept))
+        if raise_on_error and rc != L.AICP_OK:
+            self.ctx.check(rc)
+        d = res.as_dict()
+        d["rc"] = rc
+        return outT.reshape(4, 4).T.copy(), d, int(kept.value), rec.as_dict()
+
     def state(self) -> dict:
         """n_processed (process calls since start), count (prior map: the accepted readings; built
         map: those since the last reference), initial_T (4x4 row-major), ended."""
@@ -106,7 +153,8 @@ class MapSession(L.SessionMonitor):
                     ended=bool(ended.value))
 
     def last_timing(self) -> dict:
-        """wall_ms / device_ms of the last process call that registered its reading."""
+        """wall_ms / device_ms of the last process call that registered its reading (a risk
+        session: or gated it)."""
         w, d = C.c_double(), C.c_double()
         self.ctx.check(L.lib.aicp_hip_map_session_last_timing(self.h, C.byref(w), C.byref(d)))
         return dict(wall_ms=w.value, device_ms=d.value)

@@ -1106,6 +1106,66 @@ int aicp_hip_mapsession_set_monitor(aicp_hip_ctx* ctx, aicp_hip_map_session* s, 
 int aicp_hip_mapsession_last_monitor(const aicp_hip_map_session* s, aicp_monitor_result* out, int32_t* valid);
 int aicp_hip_mapsession_monitor_counters(const aicp_hip_map_session* s, uint64_t out[4]);
 
+/* ---- live map sessions with failure_prediction_mode: the alignment-risk gate per reading ----------
+ * runAicpPipeline's gate (app.cpp:236-245) and both branches of processCloud's `if`
+ * (app.cpp:362-411) under the two map policies, as aicp_hip_session_create_risk serves them for the
+ * frame-to-reference policy. For a reading with prior pose P (16 doubles, column-major;
+ * Eigen::Isometry3d::data()), both policies:
+ *  1. The crop is taken at P cast to float (app.cpp:47, 63). The reference pose for the features is
+ *     P as given: setReference runs before setAndFilterReading (app.cpp:333, 337), so in debug mode
+ *     it is the unmoved P.
+ *  2. The reading is pre-filtered in App's order (pf_read as in aicp_hip_map_session_create). In
+ *     debug mode the raw reading is moved by initialT_ first and the reading's pose is
+ *     fromMatrix4fToIsometry3d(initialT_) * P. The sensor origin is the translation of that pose;
+ *     reading->origin is not read.
+ *  3. The overlap. Prior map: the constant 50.0 (app.cpp:123-127), no octree is built. Built map:
+ *     the octree overlap between the crop and the reading, as the built-map session computes it (the
+ *     crop's origin is the translation of the float pose, the reading's its own, moved in debug
+ *     mode); it always runs (bm->resolution > 0; AICP_RUN_OVERLAP may be left out).
+ *  4. fov_overlap and alignability are overlapFilter's and alignabilityFilter's on (crop, reading as
+ *     registered, reference pose, reading pose). The classifier takes ((float)overlap,
+ *     (float)alignability); the reading is gated when !(risk <= threshold); the ratio is
+ *     aicp_hip_autotune_ratio(overlap).
+ *  5. Not gated: ICP at that ratio on the same crop; then the policy's rules apply unchanged (drop
+ *     test, count, initialT_, append, the prior map's re-filter), as in a plain session.
+ *  6. Gated (app.cpp:401-411, 414, 458-493): the correction is the identity (out_T), initialT_
+ *     stays, no drop test is applied, status 0, accepted 1, corrected_origin is the reading's prior
+ *     origin (moved in debug mode), rec->registered 0, icp.iterations 0 (icp: overlap_percent and
+ *     trimmed_ratio of step 3 and 4, on the built map the overlap's keys; the rest 0). Then
+ *       built map: the reading is the reference at once: map += the reading as filtered, unmoved
+ *         (its bytes: -0.0f survives), count = 0, is_reference = 1;
+ *       prior map: the cloud joins the graph (++count) marked a reference, so the merge of
+ *         app.cpp:469-483 is not reached: the map gets no point and merged = 0. The re-filter test
+ *         of app.cpp:487-493 stands outside that branch and still applies: refiltered = AICP_LOC_MERGE
+ *         && map_refilter_every > 0 && (count - 1) % map_refilter_every == 0 with the new count. A
+ *         gated first reading therefore re-filters the map, and after it the count is 1, so later
+ *         readings can be dropped.
+ * The gated branch is taken on the device (k_session_map_gate, right behind the classifier); on the
+ * built map the host makes room for the kept points before every reading's crop, because any
+ * reading may be gated. A gated reading ends with one read-back and builds no tree. The crop is taken
+ * once per reading, and after its raw rows no point of the reading or the crop crosses the bus.
+ * The endings are the plain session's (all reached before the gate: an empty crop, an emptied
+ * reading; and a non-zero registration status) and a non-zero status of the overlap, the features or
+ * the classifier. The quality monitor: a gated reading leaves valid = 0, a registered reading runs
+ * it as in a plain session. model stays the caller's and must outlive the session; risk_prm is
+ * copied. A point-to-point chain is accepted.
+ * start, state, last_timing (a gated reading: up to its gate), free and the monitor calls serve both
+ * kinds of handle. A handle made here refuses aicp_hip_map_session_process / _process_accum with
+ * AICP_ERR_INVALID and no state change; a handle of aicp_hip_map_session_create refuses the two
+ * calls below the same way. */
+int aicp_hip_mapsession_create_risk(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_localization_params* loc,
+                                    const aicp_built_map_params* bm, const aicp_prefilter_params* pf_read,
+                                    const aicp_prefilter_params* pf_map, const aicp_risk_params* risk_prm,
+                                    const aicp_hip_svm* model, double threshold, aicp_hip_map_session** out);
+/* out, out_T, kept: as aicp_hip_map_session_process. rec: the pipeline's record (n_read: the kept
+ * points). */
+int aicp_hip_mapsession_process_risk(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const aicp_cloud* reading,
+                                     const double pose[16], float out_T[16], void* out, aicp_pipeline_record* rec,
+                                     uint32_t* kept);
+int aicp_hip_mapsession_process_accum_risk(aicp_hip_ctx* ctx, aicp_hip_map_session* s, aicp_hip_accum* acc,
+                                           const double pose[16], float out_T[16], void* out,
+                                           aicp_pipeline_record* rec, uint32_t* kept);
+
 /* ---- kernel-level entry points (parity tests and diagnostics) --------------------------- */
 /* kd-tree over pts (as given, no centring) + k-NN of queries: libnabo
  * KDTreeUnbalancedPtInLeavesImplicitBoundsStackOpt order, ALLOW_SELF_MATCH.
