@@ -258,24 +258,9 @@ void launch_ovl_finish(hipStream_t s, int n_pairs, const PairDesc* pd, PairState
                        int set_ratio);
 
 // ---- sparse overlap (kernels_overlap_sparse.hip): sorted key words instead of voxel maps -------
-size_t ovl_sparse_scan_bytes(size_t n_points);
-size_t ovl_sparse_sort_bytes(size_t n_keys);
-// per point key counts (cnt, n_points slots) and their exclusive prefix (off)
-hipError_t launch_ovl_sparse_count(hipStream_t s, uint32_t n_blocks, const uint32_t* blk_cloud,
-                                   const uint32_t* blk_start, const OvlCloud* clouds, const float4* ref,
-                                   const float4* read, double res, uint32_t n_points, uint32_t* cnt, uint64_t* off,
-                                   void* temp, size_t temp_bytes);
-// keys -> sorted words -> |S| of every cloud (gst[g].ovl_counts[0], st[p].ovl_counts[1]) and
-// |A ∩ B| per pair (st[p].ovl_counts[2]); clouds: n_groups groups then n_pairs readings
-hipError_t launch_ovl_sparse_sets(hipStream_t s, uint32_t n_blocks, const uint32_t* blk_cloud,
-                                  const uint32_t* blk_start, const OvlCloud* clouds, const float4* ref,
-                                  const float4* read, double res, const uint64_t* off, uint64_t n_keys,
-                                  uint64_t* keys0, uint64_t* keys1, void* temp, size_t temp_bytes, int n_groups,
-                                  int n_pairs, const PairDesc* pd, unsigned long long* per_cloud,
-                                  unsigned long long* per_pair, PairState* gst, PairState* st);
-
-// The stream's sorted-key overlap: one side of a window (its readings, or its reference) as a
-// key list of `cap` words, cap = a host bound of the keys (no read-back of the true count).
+// One side of an overlap as a key list of `cap` words: the batch's groups then readings (cap = the
+// exact key total, read back between the two halves below), or a stream window's readings or its
+// reference (cap = a host bound of the keys, no read-back; the tail is padding).
 struct OvlKeySide {
   OvlCloud* clouds;            // n_clouds (device)
   int n_clouds;
@@ -293,14 +278,27 @@ struct OvlKeySide {
   unsigned long long* per_cloud;  // n_clouds
 };
 size_t ovl_keys_temp_bytes(size_t n_points, size_t cap, int n_clouds);
-// keys of the side's clouds (points at pts + clouds[c].pts_off), sorted; |S_c| into
-// st[c].ovl_counts[slot]; origin0 (nullable, 3 device doubles): clouds[0].origin := origin0 first.
-// A cloud whose keys exceed cap reports st[c].ovl_err.
+// first half: per point key counts (cnt) and their exclusive prefix (off); the points of cloud c
+// at (clouds[c].side ? read : ref) + clouds[c].pts_off. origin0 (nullable, 3 device doubles):
+// clouds[0].origin := origin0 first. Uses cnt, off, temp; cap and the key arrays not yet.
+hipError_t launch_ovl_keys_count(hipStream_t s, const OvlKeySide& k, const double* origin0, const float4* ref,
+                                 const float4* read, double res);
+// second half: the words, sorted, and |S_c| in k.per_cloud. With st: the words past the true total
+// are padded, a cloud whose keys exceed cap reports st[c].ovl_err, and |S_c| goes to
+// st[c].ovl_counts[slot] (slot 0 or 1). Without (the batch): cap is the exact total, so there is
+// nothing to pad or report, and launch_ovl_keys_intersect writes the counts.
+hipError_t launch_ovl_keys_sets(hipStream_t s, const OvlKeySide& k, const float4* ref, const float4* read,
+                                double res, PairState* st, int slot);
+// both halves in a row (the stream: every cloud of the side in pts)
 hipError_t launch_ovl_keys(hipStream_t s, const OvlKeySide& k, const double* origin0, const float4* pts,
                            double res, PairState* st, int slot);
-// |A ∩ B| of every reading of rd against the reference side (one cloud) into st[p].ovl_counts[2]
-hipError_t launch_ovl_keys_intersect(hipStream_t s, const OvlKeySide& rd, const OvlKeySide& ref,
-                                     unsigned long long* per_pair, PairState* st);
+// |A ∩ B| of the readings of rd (its clouds from first_read on) against their groups in ref's list
+// into st[p].ovl_counts[2]: group pd[p].ogroup, or cloud 0 without pd. With gst (the batch, rd and
+// ref the same side): also |S| of the groups into gst[g].ovl_counts[0] and of the readings into
+// st[p].ovl_counts[1], in the same launch.
+hipError_t launch_ovl_keys_intersect(hipStream_t s, const OvlKeySide& rd, const OvlKeySide& ref, int first_read,
+                                     const PairDesc* pd, unsigned long long* per_pair, PairState* gst,
+                                     PairState* st);
 
 // ---- frame-to-reference stream (kernels_sequence.hip) ---------------------------------------
 // gd->ref_origin = translation of fromMatrix4fToIsometry3d(T) * prior pose of src (1 thread);

@@ -5,6 +5,9 @@
 // float direction, double tMax) plus every endpoint key; overlap% = min(|A∩B|/|A|,
 // |A∩B|/|B|) * 100. octomap stores S in an octree, prunes and expands it; only the set matters.
 //
+// The key rule and the ray walk are overlap_keys.hpp's (ovl_key, ray_keys), shared with the sorted
+// key lists of kernels_overlap_sparse.hip; the host side is overlap.cpp.
+//
 // Device form: one byte per voxel of a padded key box per cloud, in 8 x 8 x 2 bricks of 128 B
 // (aicp_common.hpp: ovl_index). Every ray key is a plain byte store of 1 -- concurrent writers store the same value, so no atomics and no
 // read-before-write are needed. A reference cloud seen from one origin has one voxel set
@@ -20,20 +23,9 @@
 #include "aicp_common.hpp"
 #include "icp_math.hpp"
 #include "kernels.hpp"
+#include "overlap_keys.hpp"
 
 namespace aicp {
-
-constexpr int kTreeMaxVal = 32768;
-
-// coordToKeyChecked: the key exists iff floor(c / res) is in [-32768, 32768) (x86 converts NaN
-// and out-of-range values to INT_MIN, which octomap's range test rejects; written out here so a
-// NaN coordinate is rejected on the device as well, instead of converting to 0)
-__device__ __forceinline__ bool key_checked(double rf, float c, int& key) {
-  const double f = floor(rf * (double)c);
-  if (!(f >= -(double)kTreeMaxVal && f < (double)kTreeMaxVal)) return false;
-  key = (int)f + kTreeMaxVal;
-  return true;
-}
 
 // sides: 1 = the reference origin, 2 = the reading origin
 __global__ void k_ovl_init(int n_pairs, const PairDesc* __restrict__ pd, PairState* st, double res, int sides) {
@@ -46,7 +38,7 @@ __global__ void k_ovl_init(int n_pairs, const PairDesc* __restrict__ pd, PairSta
     const double* o = side ? pd[p].read_origin : pd[p].ref_origin;
     int k[3];
     bool ok = true;
-    for (int i = 0; i < 3; ++i) ok &= key_checked(rf, (float)o[i], k[i]);
+    for (int i = 0; i < 3; ++i) ok &= ovl_key(rf, (float)o[i], k[i]);
     if (!ok) continue;
     for (int i = 0; i < 3; ++i) {
       lo[i] = min(lo[i], k[i]);
@@ -74,7 +66,7 @@ __global__ __launch_bounds__(256) void k_ovl_bbox(BlockMap m, const PairDesc* __
   if (j < n) {
     const float4 p = pts[off + j];
     int k[3];
-    if (key_checked(rf, p.x, k[0]) && key_checked(rf, p.y, k[1]) && key_checked(rf, p.z, k[2]))
+    if (ovl_key(rf, p.x, k[0]) && ovl_key(rf, p.y, k[1]) && ovl_key(rf, p.z, k[2]))
       for (int i = 0; i < 3; ++i) lo[i] = hi[i] = k[i];
   }
   // block reduction, then at most 6 atomics per block, skipped when they cannot change the box
@@ -104,7 +96,7 @@ __global__ __launch_bounds__(256) void k_ovl_bbox(BlockMap m, const PairDesc* __
   }
 }
 
-// computeRayKeys(origin, end) + endpoint key, marking bits of one bitmap.
+// computeRayKeys(origin, end) + endpoint key, marking bytes of one map.
 // kFilter: a workgroup-local direct-mapped cache in LDS of the voxel indices its lanes have
 // stored skips repeats (maps of < 2^32 voxels). Every store leaves L2 (MI355X_MICROARCH.md: "all
 // bytes leave L2 every pass"), and the ~100 ray steps per point fall on far fewer distinct
@@ -159,38 +151,14 @@ __global__ __launch_bounds__(256) void k_ovl_mark(BlockMap m, const PairDesc* __
     }
     put((int64_t)ovl_index((uint32_t)a, (uint32_t)b, (uint32_t)c, (uint32_t)dm1, (uint32_t)dm2));
   };
-  const double* org = side ? d.read_origin : d.ref_origin;
-  const float o[3] = {(float)org[0], (float)org[1], (float)org[2]};
-  const float4 p4 = pts[off + j];
-  const float e[3] = {p4.x, p4.y, p4.z};
-  const double rf = 1.0 / res;
-  int ko[3], ke[3];
-  const bool okO = key_checked(rf, o[0], ko[0]) && key_checked(rf, o[1], ko[1]) &&
-                   key_checked(rf, o[2], ko[2]);
-  const bool okE = key_checked(rf, e[0], ke[0]) && key_checked(rf, e[1], ke[1]) &&
-                   key_checked(rf, e[2], ke[2]);
-  if (okO && okE && !(ko[0] == ke[0] && ko[1] == ke[1] && ko[2] == ke[2])) {
-    mark(ko[0], ko[1], ko[2]);
-    float dir[3] = {e[0] - o[0], e[1] - o[1], e[2] - o[2]};
-    const float nsq = dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2];
-    const float length = (float)sqrt((double)nsq);
-    for (int i = 0; i < 3; ++i) dir[i] /= length;
-    int step[3];
-    double tMax[3], tDelta[3];
-    int cur[3] = {ko[0], ko[1], ko[2]};
-    for (int i = 0; i < 3; ++i) {
-      step[i] = dir[i] > 0.0f ? 1 : (dir[i] < 0.0f ? -1 : 0);
-      if (step[i] != 0) {
-        double vb = (double(cur[i] - kTreeMaxVal) + 0.5) * res;
-        vb += (float)(step[i] * res * 0.5);
-        tMax[i] = (vb - (double)o[i]) / (double)dir[i];
-        tDelta[i] = res / (double)fabsf(dir[i]);
-      } else {
-        tMax[i] = 1.7976931348623157e308;
-        tDelta[i] = 1.7976931348623157e308;
-      }
-    }
-    const double len = (double)length;
+  RayWalk w;  // the end keys and the set-up are overlap_keys.hpp's, shared with the key lists' ray_keys
+  if (ray_ends(res, side ? d.read_origin : d.ref_origin, pts[off + j], w)) {
+    mark(w.ko[0], w.ko[1], w.ko[2]);
+    ray_setup(res, w);
+    int* cur = w.cur;
+    const int *step = w.step, *ke = w.ke;
+    double *tMax = w.tMax, *tDelta = w.tDelta;
+    const double len = w.len;
     // the box coordinates follow the walk (one bounds test on the axis that moved: the other two
     // are unchanged); the brick index is formed from them per step
     int rel[3] = {cur[0] - mn0, cur[1] - mn1, cur[2] - mn2};
@@ -226,7 +194,7 @@ __global__ __launch_bounds__(256) void k_ovl_mark(BlockMap m, const PairDesc* __
     int64_t g;
     while (walk(g)) put(g);
   }
-  if (okE) mark(ke[0], ke[1], ke[2]);
+  if (w.okE) mark(w.ke[0], w.ke[1], w.ke[2]);
   if (err) atomicOr(&st[pair].ovl_err, 1);
 }
 

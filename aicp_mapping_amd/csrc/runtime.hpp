@@ -1,5 +1,5 @@
 // runtime.hpp — host-side runtime shared by the C-ABI translation units (aicp_hip.cpp, sequence.cpp,
-// map_stream.cpp, session.cpp, accum.cpp, monitor.cpp, test_entries.cpp):
+// overlap.cpp, map_stream.cpp, session.cpp, accum.cpp, monitor.cpp, test_entries.cpp):
 // device / pinned buffers, kd-tree work space, the context and batch objects, error macros.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -396,7 +396,10 @@ int upload_pairs(aicp_hip_ctx* ctx, const aicp_pair* pairs, size_t n, aicp_hip_b
 int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, double res, int flags, float* outT,
               aicp_icp_stats* stats, float* out_overlap);
 void free_batch(aicp_hip_batch* B);
-// the stream's bound of a cloud's ray keys (sequence.cpp), per-point cap included
+// the batch's overlap after its key boxes (overlap.cpp): voxel maps, or sorted key words where they do not fit
+int overlap_maps(aicp_hip_ctx* ctx, aicp_hip_batch* B, size_t P, size_t G, PairDesc* dDesc, PairState* dState,
+                 PairDesc* dG, PairState* dGst, const float4* readS, double res, bool set_ratio, std::string& err);
+// the stream's bound of a cloud's ray keys (overlap.cpp), per-point cap included
 extern const uint64_t kMaxRayKeys;
 extern const uint64_t kSeqMapBudget;  // bytes of a window's voxel maps beyond which it runs on key lists
 uint64_t key_bound(WorkerPool& pool, const aicp_cloud& c, const double* org, double res, bool rigid);
@@ -428,7 +431,7 @@ struct Box {
 // xyz at a byte stride -> float4 (w = 1) and the AABB of each cloud's finite points (sequence.cpp)
 void pack_clouds(WorkerPool& pool, const std::vector<PackSeg>& segs, std::vector<Box>& boxes);
 
-// The overlap of one stream window (sequence.cpp): one reference, np readings. The host's part is
+// The overlap of one stream window (overlap.cpp): one reference, np readings. The host's part is
 // a plan made from the clouds alone; the device's part runs in three steps that the stream puts
 // on different streams and aicp_hip_test_overlap one after the other.
 struct OvlWinPlan {
@@ -473,9 +476,10 @@ struct OvlWinDev {  // where a window's overlap lies on the device
   unsigned long long* per_pair = nullptr;
   bool filter = false, wide = false;  // the stream's choice for both: plain stores, narrow counts
 };
-int ovl_window_read_side(std::string& err, hipStream_t s, const OvlWinDev& D, const float4* readS);
-int ovl_window_ref_side(std::string& err, hipStream_t s, const OvlWinDev& D, const double* origin0,
-                        const float4* ref);
+// side 1: the readings (pts their points), side 0: the reference (origin0, nullable: its origin
+// where the device wrote it)
+int ovl_window_side(std::string& err, hipStream_t s, const OvlWinDev& D, int side, const double* origin0,
+                    const float4* pts);
 int ovl_window_counts(std::string& err, hipStream_t s, const OvlWinDev& D);
 // the device-resident map (aicp_hip.cpp), for the streams that grow it and crop it into a batch
 int map_reserve(aicp_hip_ctx* ctx, aicp_hip_map* map, size_t add);

@@ -206,192 +206,6 @@ void pack_clouds(WorkerPool& pool, const std::vector<PackSeg>& segs, std::vector
 
 namespace {
 
-// voxel-map capacity (bytes) of a cloud with AABB b plus origin o at resolution res: `rigid`
-// allows any rotation (a rigid motion keeps the diameter; the device sizes the box after the
-// transform), otherwise the axis extents. Both include the 2 + 2 voxels of padding, one more
-// for the floor of each end, the rounding of the corrected origin, and the brick alignment of
-// both box ends (ovl_axis: up to 2 x 7 voxels).
-uint64_t map_cap(const Box& b0, const double* o, double res, bool rigid) {
-  Box b = b0;
-  b.add((float)o[0], (float)o[1], (float)o[2]);
-  double ext[3], d2 = 0;
-  for (int k = 0; k < 3; ++k) {
-    ext[k] = std::max(0.0, (double)b.hi[k] - (double)b.lo[k]);
-    d2 += ext[k] * ext[k];
-  }
-  uint64_t vox = 1;
-  double voxd = 1;
-  for (int k = 0; k < 3; ++k) {
-    const double e = rigid ? std::sqrt(d2) : ext[k];
-    const double side = std::ceil(e / res) + 8 + 2 * (kOvlBrick0 - 1);
-    voxd *= side;
-    // a finite return far outside the key range (1e30 m) must not wrap the product into a small
-    // capacity: such a window is over every budget and runs on key lists
-    if (!(voxd < 0x1p50)) return uint64_t(1) << 50;  // (4096 such slots still add up within 64 bits)
-    vox *= (uint64_t)side;
-  }
-  return (vox + kOvlBrickBytes - 1) / kOvlBrickBytes * kOvlBrickBytes;
-}
-
-}  // namespace
-
-namespace aicp {
-namespace rt {
-
-// A window's voxel maps beyond this many bytes (all of them together) take the sorted-key path
-// instead: a far return (a key box of 10^9+ voxels) or a very wide scan. The C2/C3 scenes need
-// ~3 MB per reading map and ~80 MB for a reference (sized for any rotation of its source).
-const uint64_t kSeqMapBudget = uint64_t(1) << 30;
-
-const uint64_t kMaxRayKeys = 3 * 65536 + 8;  // keys are 16-bit per axis: a ray's walk is bounded
-
-// Upper bound of the keys computeRayKeys(o, p) + p's own key visit, summed over a cloud: one
-// step per key crossed on an axis, plus the origin, the endpoint and a margin for the walk's
-// float overshoot. rigid: for any rigid motion of both cloud and origin (the corrected reference
-// of the next window), from the distance: sum_i |dk_i| <= sqrt(3) |p - o| / res + 3.
-// A point without a key (non-finite or beyond the key range) visits nothing.
-uint64_t key_bound(WorkerPool& pool, const aicp_cloud& c, const double* org, double res, bool rigid) {
-  constexpr uint64_t kChunk = 1 << 15;
-  const size_t tasks = (size_t)((c.n + kChunk - 1) / kChunk);
-  std::vector<uint64_t> part(tasks, 0);
-  const double rf = 1.0 / res;
-  const float of[3] = {(float)org[0], (float)org[1], (float)org[2]};
-  double ko[3];
-  for (int k = 0; k < 3; ++k) ko[k] = std::floor(rf * (double)of[k]);
-  pool.run(tasks, [&](size_t t) {
-    const char* src = reinterpret_cast<const char*>(c.pts);
-    uint64_t sum = 0;
-    const uint64_t a = t * kChunk, b = std::min<uint64_t>(c.n, a + kChunk);
-    for (uint64_t i = a; i < b; ++i) {
-      const float* p = reinterpret_cast<const float*>(src + i * c.stride);
-      if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]))) continue;
-      double v;
-      if (rigid) {
-        double d2 = 0;
-        for (int k = 0; k < 3; ++k) d2 += ((double)p[k] - org[k]) * ((double)p[k] - org[k]);
-        v = std::ceil(1.7320508075688772 * (std::sqrt(d2) * (1 + 1e-5) + 1e-3) * rf) + 8;
-      } else {
-        v = 8;
-        for (int k = 0; k < 3; ++k) v += std::fabs(std::floor(rf * (double)p[k]) - ko[k]);
-      }
-      sum += v < (double)kMaxRayKeys ? (uint64_t)v : kMaxRayKeys;
-    }
-    part[t] = sum;
-  });
-  uint64_t s = 0;
-  for (uint64_t v : part) s += v;
-  return s;
-}
-
-// voxel maps: [0] the reference (capacity for any rigid motion of its source), [1 + i] readings
-void ovl_window_slots(OvlWinPlan& W, const Box& src_box, const double* src_origin, bool src_rigid, const Box* boxes,
-                      const aicp_cloud* reads, size_t np, double res, bool read_rigid) {
-  W.od.assign(np + 1, OvlDesc{});
-  W.cap.assign(np + 1, 0);
-  W.bm = W.cap_max = 0;
-  for (size_t i = 0; i <= np; ++i) {
-    W.cap[i] = i == 0 ? map_cap(src_box, src_origin, res, src_rigid)
-                      : map_cap(boxes[i - 1], reads[i - 1].origin, res, read_rigid);  // debug: moved by initialT_
-    W.od[i].off = W.bm;
-    W.bm += W.cap[i];
-    W.cap_max = std::max(W.cap_max, W.cap[i]);
-  }
-}
-
-// key lists sized by host bounds of the rays' keys (readings from their own points; the reference
-// for any rigid motion of its source), so the stream needs no read-back
-void ovl_window_keys(OvlWinPlan& W, WorkerPool& pool, const aicp_cloud& src, const double* ref_origin, bool ref_rigid,
-                     const aicp_cloud* reads, const uint32_t* loff, size_t np, double res, bool read_rigid) {
-  W.scl.clear();
-  W.sbc.clear();
-  W.sbs.clear();
-  W.kb_read.clear();
-  W.cap_r = W.cap_g = 0;
-  uint64_t slot = 0;
-  for (size_t i = 0; i <= np; ++i) {  // readings 0..np-1, then the reference
-    const bool ref = i == np;
-    const aicp_cloud& c = ref ? src : reads[i];
-    OvlCloud o{};
-    o.pts_off = ref ? 0u : loff[i];
-    o.n = (uint32_t)c.n;
-    o.side = ref ? 0u : 1u;
-    for (int k = 0; k < 3; ++k) o.origin[k] = ref ? ref_origin[k] : c.origin[k];
-    o.slot = ref ? 0 : slot;
-    slot += ref ? 0 : c.n;
-    W.scl.push_back(o);
-    const uint32_t ci = ref ? 0u : (uint32_t)i;
-    for (uint32_t j = 0; j < o.n; j += 256) {
-      W.sbc.push_back(ci);
-      W.sbs.push_back(j);
-    }
-    const uint64_t kb = key_bound(pool, c, c.origin, res, ref ? ref_rigid : read_rigid);
-    if (!ref) W.kb_read.push_back(kb);
-    (ref ? W.cap_g : W.cap_r) += kb;
-  }
-}
-
-void ovl_window_sides(const OvlWinPlan& W, size_t np, uint64_t nread, uint32_t n_ref, OvlCloud* dcl,
-                      const uint32_t* dbc, uint32_t* cnt, uint64_t* off, uint64_t* keys_r, uint64_t* keys_g,
-                      void* tmp_r, size_t tmp_rb, void* tmp_g, size_t tmp_gb, unsigned long long* pc, OvlKeySide& kr,
-                      OvlKeySide& kg) {
-  const size_t nb = W.sbc.size();
-  const uint32_t* dbs = dbc + nb;
-  const uint32_t nbr = (uint32_t)(nb - (n_ref + 255) / 256);  // the readings' blocks come first
-  kr = OvlKeySide{dcl, (int)np, dbc, dbs, nbr, (uint32_t)nread, cnt, off, W.cap_r, keys_r, keys_r + W.cap_r,
-                  tmp_r, tmp_rb, pc};
-  kg = OvlKeySide{dcl + np, 1, dbc + nbr, dbs + nbr, (uint32_t)(nb - nbr), n_ref, cnt + nread, off + nread,
-                  W.cap_g, keys_g, keys_g + W.cap_g, tmp_g, tmp_gb, pc + np};
-}
-
-// the readings' voxel maps and |B| (or their key list)
-int ovl_window_read_side(std::string& err, hipStream_t s, const OvlWinDev& D, const float4* readS) {
-  const int np = (int)D.np;
-  if (D.sparse) {
-    launch_ovl_init(s, np, D.dDesc, D.dState, D.res, 2);
-    TCHK(launch_ovl_keys(s, *D.kr, nullptr, readS, D.res, D.dState, 1));
-  } else {
-    launch_ovl_init(s, np, D.dDesc, D.dState, D.res, 2);
-    launch_ovl_bbox(s, D.m_read, D.dDesc, D.dState, readS, 1, D.res);
-    launch_ovl_size(s, np, D.dState, D.dOvl + 1, D.dCap + 1);
-    launch_ovl_clear(s, np, D.dOvl + 1, D.bmp, D.cap_max);
-    launch_ovl_mark(s, D.m_read, D.dDesc, D.dOvl + 1, D.dState, readS, 1, D.res, D.bmp, D.filter);
-    launch_ovl_popcount(s, np, D.dOvl + 1, D.dState, 1, D.bmp, D.wide);
-  }
-  return AICP_OK;
-}
-
-// the reference's voxel map (or key list) and |A|; origin0 (nullable): its origin where the device wrote it
-int ovl_window_ref_side(std::string& err, hipStream_t s, const OvlWinDev& D, const double* origin0,
-                        const float4* ref) {
-  if (D.sparse) {
-    launch_ovl_init(s, 1, D.dG, D.dGst, D.res, 1);
-    TCHK(launch_ovl_keys(s, *D.kg, origin0, ref, D.res, D.dGst, 0));
-  } else {
-    launch_ovl_init(s, 1, D.dG, D.dGst, D.res, 1);
-    launch_ovl_bbox(s, D.m_gref, D.dG, D.dGst, ref, 0, D.res);
-    launch_ovl_size(s, 1, D.dGst, D.dOvl, D.dCap);
-    launch_ovl_clear(s, 1, D.dOvl, D.bmp, D.cap0);
-    launch_ovl_mark(s, D.m_gref, D.dG, D.dOvl, D.dGst, ref, 0, D.res, D.bmp, D.filter);
-    launch_ovl_popcount(s, 1, D.dOvl, D.dGst, 0, D.bmp, D.wide);
-  }
-  return AICP_OK;
-}
-
-// |A ∩ B| of every reading, the percentage and the ratio
-int ovl_window_counts(std::string& err, hipStream_t s, const OvlWinDev& D) {
-  if (D.sparse)
-    TCHK(launch_ovl_keys_intersect(s, *D.kr, *D.kg, D.per_pair, D.dState));
-  else
-    launch_ovl_intersect(s, (int)D.np, D.dDesc, D.dOvl + 1, D.dOvl, D.dState, D.bmp, D.wide);
-  launch_ovl_finish(s, (int)D.np, D.dDesc, D.dState, D.dGst, 1);
-  return AICP_OK;
-}
-
-}  // namespace rt
-}  // namespace aicp
-
-namespace {
-
 // the error message of work run on a host thread of its own (copied into ctx->err after the join,
 // so two threads never write that string at once)
 struct ErrSink {
@@ -855,7 +669,7 @@ static int win_read_side(C* ctx, SeqState* S, const aicp_icp_config* cfg, const 
     D.cap_max = cap_max;
     D.m_read = m_read;
     D.kr = &R.kr;
-    if (int rc = ovl_window_read_side(ctx->err, sr, D, readS)) return rc;
+    if (int rc = ovl_window_side(ctx->err, sr, D, 1, nullptr, readS)) return rc;
   }
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(sl.ev_rd, sr));
@@ -1032,7 +846,7 @@ static int win_ref_icp(aicp_hip_ctx* ctx, SeqState* S, const aicp_icp_config* cf
     D.kg = &R.kg;
     D.per_pair = R.per_pair;
     HIPC(hipStreamWaitEvent(si, sl.ev_ref, 0));
-    if (int rc = ovl_window_ref_side(ctx->err, si, D, w.src >= 0 ? dG->ref_origin : nullptr, sl.ref_raw.as<float4>()))
+    if (int rc = ovl_window_side(ctx->err, si, D, 0, w.src >= 0 ? dG->ref_origin : nullptr, sl.ref_raw.as<float4>()))
       return rc;
   }
   HIPC(hipStreamWaitEvent(si, sl.ev_rd, 0));  // (the slot's previous window is done: its upload waited)
@@ -1264,7 +1078,7 @@ static int sub_prep(aicp_hip_ctx* ctx, SeqState* S, const aicp_sequence_params* 
     launch_ovl_init(si, 1, dDesc + r, dState + r, res, 2);
     if (R.sparse) {
       HIPC(launch_ovl_keys(si, R.kr1[r], dDesc[r].read_origin, sl.read_raw.as<float4>(), res, dState + r, 1));
-      HIPC(launch_ovl_keys_intersect(si, R.kr1[r], R.kg, R.per_pair + r, dState + r));
+      HIPC(launch_ovl_keys_intersect(si, R.kr1[r], R.kg, 0, nullptr, R.per_pair + r, nullptr, dState + r));
     } else {
       launch_ovl_bbox(si, mrd, dDesc, dState, sl.read_raw.as<float4>(), 1, res);
       launch_ovl_size(si, 1, dState + r, dOvl + 1 + r, dCap + 1 + r);

@@ -376,8 +376,8 @@ int ovl_window_test(aicp_hip_ctx* ctx, const aicp_hip_batch* B, const aicp_pair*
       D.kg = &kg;
       D.per_pair = d_pc.as<unsigned long long>() + np + 1;
     }
-    int rc = ovl_window_read_side(ctx->err, s, D, d_read.as<float4>());
-    if (!rc) rc = ovl_window_ref_side(ctx->err, s, D, nullptr, d_ref.as<float4>());
+    int rc = ovl_window_side(ctx->err, s, D, 1, nullptr, d_read.as<float4>());
+    if (!rc) rc = ovl_window_side(ctx->err, s, D, 0, nullptr, d_ref.as<float4>());
     if (!rc) rc = ovl_window_counts(ctx->err, s, D);
     if (rc) return rc;
     HIPC(hipGetLastError());

@@ -1348,7 +1348,8 @@ int aicp_hip_test_normals(aicp_hip_ctx* ctx, size_t n_refs, const uint32_t* coun
  * under 0 and 1 as well; out->path says which ran (1 to 4). Under 3 and 4 every overlap group runs
  * as one window of the frame-to-reference stream (its reference and the readings paired with it),
  * through the stream's own host plan (ovl_window_slots / _keys / _sides) and device steps
- * (ovl_window_read_side / _ref_side / _counts), one window after the other on one stream.
+ * (ovl_window_side for the readings and for the reference, ovl_window_counts), one window after
+ * the other on one stream.
  * filter / wide: -1 the path's rules (batch: the marks' LDS cache from 9 clouds on, the wide count
  * grids for one pair in one group; stream: neither), 0 or 1 to override them for this call;
  * out->filter / out->wide say what was launched (0 on keys). The trimmed ratio is set from the

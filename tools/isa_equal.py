@@ -8,7 +8,8 @@ for equality after removing what differs between two compiles of one source or m
 function of the file is removed: trailing `;` comments, the function ordinal in local labels and the
 __hip_cuid_ symbol. Prints one line per kernel; exits 1 unless every kernel present in both trees is
 the same (kernels whose demangled name contains an --allow NAME may differ; for those that do, both
-sides' resource entries and spill counts are printed). Needs no GPU.
+sides' resource entries and spill counts are printed, and for a kernel only the new tree has, its
+own). Needs no GPU.
 """
 import argparse, collections, concurrent.futures, os, re, shlex, subprocess, sys, tempfile
 
@@ -96,6 +97,8 @@ def main():
             if state.endswith("(allowed)"):
                 for side, k in (("OLD", old[sym]), ("NEW", new[sym])):
                     print(f"    {side} " + "  ".join(k[1] or []))
+            elif state == "only in NEW" and new[sym][1]:  # (a kernel: device functions have no metadata)
+                print("    NEW " + "  ".join(new[sym][1]))
     return 1 if bad else 0
 
 
