@@ -71,6 +71,8 @@ EXPORTS = [
     "aicp_hip_mapsession_set_monitor", "aicp_hip_mapsession_last_monitor",
     "aicp_hip_mapsession_monitor_counters", "aicp_hip_test_monitor_resident",
     "aicp_hip_mapsession_create_risk", "aicp_hip_mapsession_process_risk", "aicp_hip_mapsession_process_accum_risk",
+    "aicp_hip_session_keep_aligned_map", "aicp_hip_session_aligned_map", "aicp_hip_session_take_aligned_map",
+    "aicp_hip_mapsession_start_go_back", "aicp_hip_session_start_on_map", "aicp_hip_test_promote_map",
 ]
 
 
@@ -113,7 +115,10 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_mapsession_monitor_counters",
            "aicp_hip_test_monitor_resident",  # the quality monitor per reading in the live sessions
            "aicp_hip_mapsession_create_risk", "aicp_hip_mapsession_process_risk",
-           "aicp_hip_mapsession_process_accum_risk"}  # the live map sessions with the risk gate
+           "aicp_hip_mapsession_process_accum_risk",  # the live map sessions with the risk gate
+           "aicp_hip_session_keep_aligned_map", "aicp_hip_session_aligned_map", "aicp_hip_session_take_aligned_map",
+           "aicp_hip_mapsession_start_go_back", "aicp_hip_session_start_on_map",
+           "aicp_hip_test_promote_map"}  # the mapping session's built map, the go-back, the start on a map
 
 
 class IcpConfig(C.Structure):
@@ -708,6 +713,13 @@ def _load():
                                                       C.c_double, C.POINTER(vp)]
         L.aicp_hip_mapsession_process_risk.argtypes = [vp, vp, clp, dp, fp, vp, prp, u32p]
         L.aicp_hip_mapsession_process_accum_risk.argtypes = [vp, vp, vp, dp, fp, vp, prp, u32p]
+    if hasattr(L, "aicp_hip_session_keep_aligned_map"):
+        L.aicp_hip_session_keep_aligned_map.argtypes = [vp, vp, C.c_int]
+        L.aicp_hip_session_aligned_map.argtypes = [vp, vp, C.POINTER(vp)]
+        L.aicp_hip_session_take_aligned_map.argtypes = [vp, vp, C.POINTER(vp)]
+        L.aicp_hip_mapsession_start_go_back.argtypes = [vp, vp, vp, vp]
+        L.aicp_hip_session_start_on_map.argtypes = [vp, vp, vp, fp, C.c_float, C.c_float]
+        L.aicp_hip_test_promote_map.argtypes = [vp, C.c_int32, fp, sz, sz, C.c_int32, vp, fp, fp, up]
     if hasattr(L, "aicp_hip_session_set_monitor"):
         mpp, mrp = C.POINTER(MonitorParams), C.POINTER(MonitorResult)
         for kind in ("session", "mapsession"):

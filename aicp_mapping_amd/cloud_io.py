@@ -324,6 +324,98 @@ def save_pcd_xyz(path: str, xyz: np.ndarray, data: str = "binary") -> None:
             raise ValueError(data)
 
 
+_PLY_NP = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2",
+           "ushort": "u2", "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4",
+           "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def load_ply_xyz(path: str) -> np.ndarray:
+    """The map file of load_map_from_file as pcl::io::loadPLYFile<PointXYZ> reads it
+    (app_ros.cpp:301): PLY `ascii` or `binary_little_endian`, an `element vertex` with `float` or
+    `double` x, y and z among any other scalar properties; other elements (faces, ...) are skipped.
+    Returns the (n, 3) float32 points. Anything else (big-endian files, a vertex element without
+    x, y or z or with a list property, a truncated body) is refused with CloudFormatError, a
+    ValueError."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    end = buf.find(b"end_header")
+    nl = buf.find(b"\n", end)
+    if not buf.startswith(b"ply") or end < 0 or nl < 0:
+        raise CloudFormatError("ply: no header")
+    try:
+        lines = [ln.split() for ln in buf[:end].decode("ascii").splitlines()[1:]]
+    except UnicodeDecodeError as e:
+        raise CloudFormatError("ply: header is not ascii") from e
+    fmt = None
+    elements = []  # [name, count, [(property name, dtype, list count dtype or None)]]
+    try:
+        for w in lines:
+            if not w or w[0] in ("comment", "obj_info"):
+                continue
+            if w[0] == "format":
+                fmt = w[1]
+            elif w[0] == "element":
+                elements.append([w[1], int(w[2]), []])
+            elif w[0] == "property" and w[1] == "list":
+                elements[-1][2].append((w[4], _PLY_NP[w[3]], _PLY_NP[w[2]]))
+            elif w[0] == "property":
+                elements[-1][2].append((w[2], _PLY_NP[w[1]], None))
+            else:
+                raise CloudFormatError(f"ply: header line {' '.join(w)!r}")
+    except (IndexError, KeyError, ValueError) as e:
+        raise CloudFormatError(f"ply: malformed header: {e}") from e
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise CloudFormatError(f"ply: format {fmt} is not supported (ascii, binary_little_endian)")
+    if any(c < 0 for _, c, _ in elements):
+        raise CloudFormatError("ply: negative element count")
+    body = buf[nl + 1:]
+    rows = body.decode("ascii", "replace").splitlines() if fmt == "ascii" else None
+    if rows is not None:
+        rows = [r for r in rows if r.strip()]
+    pos = 0  # a row (ascii) or a byte (binary) of the body
+    for name, count, props in elements:
+        if name != "vertex":  # skipped; a list makes its binary records variable in size
+            if fmt == "ascii":
+                pos += count
+            elif all(lt is None for _, _, lt in props):
+                pos += count * sum(np.dtype(t).itemsize for _, t, _ in props)
+            else:
+                for _ in range(count):
+                    for _, t, lt in props:
+                        k = 1
+                        if lt is not None:
+                            if pos + np.dtype(lt).itemsize > len(body):
+                                raise CloudFormatError("ply: truncated body")
+                            k = int(np.frombuffer(body, "<" + lt, 1, pos)[0])
+                            pos += np.dtype(lt).itemsize
+                        pos += k * np.dtype(t).itemsize
+            continue
+        if any(lt is not None for _, _, lt in props):
+            raise CloudFormatError("ply: a list property in the vertex element")
+        names = [p for p, _, _ in props]
+        for axis in "xyz":
+            if names.count(axis) != 1 or props[names.index(axis)][1] not in ("f4", "f8"):
+                raise CloudFormatError(f"ply: the vertex element has no float or double {axis}")
+        if fmt == "ascii":
+            if pos + count > len(rows):
+                raise CloudFormatError("ply: truncated body")
+            try:
+                tab = np.array([r.split() for r in rows[pos:pos + count]], dtype=np.float64).reshape(count, -1)
+            except ValueError as e:
+                raise CloudFormatError(f"ply: vertex rows: {e}") from e
+            if tab.shape[1] != len(props) and count:
+                raise CloudFormatError("ply: a vertex row's length")
+            cols = [tab[:, names.index(a)] if count else np.zeros(0) for a in "xyz"]
+        else:
+            dt = np.dtype([(f"{i}_{p}", "<" + t) for i, (p, t, _) in enumerate(props)])
+            if pos + count * dt.itemsize > len(body):
+                raise CloudFormatError("ply: truncated body")
+            rec = np.frombuffer(body, dt, count, pos)
+            cols = [rec[f"{names.index(a)}_{a}"] for a in "xyz"]
+        return np.ascontiguousarray(np.stack(cols, axis=1).astype(np.float32))
+    raise CloudFormatError("ply: no vertex element")
+
+
 def load_kitti_bin(path: str) -> np.ndarray:
     """KITTI velodyne scan: packed float32 (x, y, z, reflectance) records; the kitti2pcd step
     of bash/kitti2pcd_no_ground.sh keeps x, y, z for PointXYZ."""

@@ -1350,13 +1350,13 @@ static void crop_box_frame(const float origin[16], float inv[9], float t[3], flo
   crop_rotation_inverse(R, inv, rpy);
 }
 
-// the crop kernels on n device points; kept points (input order) to host out, capacity cap
-static int crop_device(aicp_hip_ctx* ctx, const float4* din, size_t n, const float inv[9], const float t[3], float mn,
-                       float mx, float* out, size_t cap, size_t* out_n) {
+// the crop kernels on n device points: the *m kept points (input order) at *dout in ctx->scratch,
+// the stream idle
+static int crop_device_run(aicp_hip_ctx* ctx, const float4* din, size_t n, const float inv[9], const float t[3],
+                           float mn, float mx, const float4** dout_p, uint32_t* m_out) {
   const size_t tiles = aicp::crop_tiles(n);
   const size_t tile_bytes = (2 * tiles * 4 + 255) & ~size_t(255);
   HIPC(ensure(ctx->scratch, 256 + tile_bytes + n * 16));
-  HIPC(ensure(ctx->pin_io, n * 16 + 16));
   char* d = ctx->scratch.as<char>();
   uint32_t* total = (uint32_t*)d;
   uint32_t* tcnt = (uint32_t*)(d + 256);
@@ -1368,6 +1368,19 @@ static int crop_device(aicp_hip_ctx* ctx, const float4* din, size_t n, const flo
   HIPC(hipMemcpyAsync(&m, total, 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   if (m > n) FAIL(AICP_ERR_HIP, "crop: kept count exceeds the input");
+  *dout_p = dout;
+  *m_out = m;
+  return AICP_OK;
+}
+
+// the crop kernels on n device points; kept points (input order) to host out, capacity cap
+static int crop_device(aicp_hip_ctx* ctx, const float4* din, size_t n, const float inv[9], const float t[3], float mn,
+                       float mx, float* out, size_t cap, size_t* out_n) {
+  HIPC(ensure(ctx->pin_io, n * 16 + 16));
+  const float4* dout = nullptr;
+  uint32_t m = 0;
+  const int rc = crop_device_run(ctx, din, n, inv, t, mn, mx, &dout, &m);
+  if (rc) return rc;
   if (m > cap) FAIL(AICP_ERR_INVALID, "crop: output capacity too small");
   float* h = ctx->pin_io.as<float>();
   if (m) HIPC(hipMemcpy(h, dout, (size_t)m * 16, hipMemcpyDeviceToHost));
@@ -1910,6 +1923,26 @@ int map_reserve(aicp_hip_ctx* ctx, aicp_hip_map* map, size_t add) {
   }
   release(map->pts);
   map->pts = nb;
+  return AICP_OK;
+}
+
+// aicp_hip_map_crop's crop with the kept points left on the device: dst (grown when it is too
+// small, untouched when the crop is empty) gets them device to device, *kept their number. Returns
+// with the stream idle.
+int map_crop_resident(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float mx, const float origin[16],
+                      DevBuf* dst, uint32_t* kept) {
+  *kept = 0;
+  if (!map->n) return AICP_OK;
+  float inv[9], t[3], rpy[3];
+  crop_box_frame(origin, inv, t, rpy);
+  const float4* dout = nullptr;
+  uint32_t m = 0;
+  const int rc = crop_device_run(ctx, map->pts.as<float4>(), map->n, inv, t, mn, mx, &dout, &m);
+  if (rc || !m) return rc;
+  HIPC(ensure(*dst, (size_t)m * 16));
+  HIPC(hipMemcpyAsync(dst->p, dout, (size_t)m * 16, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  *kept = m;
   return AICP_OK;
 }
 

@@ -397,6 +397,14 @@ struct GateRec {
 void launch_session_gate_promote(hipStream_t s, int n, const GateRec* gate, const double* origin, const float4* read,
                                  int32_t id, float4* ref, float* T, StreamState* S, StreamRec* rec,
                                  SessionHeader* hdr);
+// launch_session_promote / launch_session_gate_promote for a session that keeps aligned_map_
+// (aicp_hip_session_keep_aligned_map; app.cpp:458-468): what they write, and the same n points
+// also to dst[i], the map's tail with room for n points; nothing more when nothing is promoted.
+void launch_session_promote_map(hipStream_t s, int n, const StreamRec* rec, const float* T, const float4* read,
+                                int32_t id, float4* ref, float4* dst, SessionHeader* hdr);
+void launch_session_gate_promote_map(hipStream_t s, int n, const GateRec* gate, const double* origin,
+                                     const float4* read, int32_t id, float4* ref, float4* dst, float* T, StreamState* S,
+                                     StreamRec* rec, SessionHeader* hdr);
 // The gated branch in the live map sessions (aicp_hip_mapsession_create_risk), right behind
 // launch_svm_predict in the same way (n > 0: the reading's kept points). gate->gate == 0:
 // rec->append = 0, nothing else. Otherwise T = identity, rec = {status 0, accepted 1,

@@ -12,6 +12,10 @@
 // session, right behind k_svm_predict: the reading becomes the reference unmoved, by the gate the
 // classifier left in device memory.
 //
+// k_session_promote_map and k_session_gate_promote_map are these two for a session that keeps
+// App's aligned_map_ (app.cpp:310, 458-468): every point of the new reference is stored a second
+// time, behind the session's map.
+//
 // k_session_map_append is the same step for the live map sessions (map_stream.cpp): the reading
 // goes behind the caller's map instead (prior map: app.cpp:469-483, built map: app.cpp:383-391,
 // 458-465), where the host has made room before the reading's crop was enqueued.
@@ -28,20 +32,38 @@
 
 namespace aicp {
 
-// One point of the reading as it was registered, moved by its correction: one 128-bit load, one
-// 128-bit store (k_transform's expression). The body of both kernels below.
-__device__ __forceinline__ void move_point(const float (&Tl)[16], const float4* __restrict__ read,
-                                           float4* __restrict__ dst, int i) {
+// One point of the reading as it was registered, moved by its correction: one 128-bit load
+// (k_transform's expression), and the stores of the value it gives.
+__device__ __forceinline__ float4 moved_point(const float (&Tl)[16], const float4* __restrict__ read, int i) {
   const float4 p = read[i];
   float q[3];
   apply4(Tl, p.x, p.y, p.z, q);
-  dst[i] = make_float4(q[0], q[1], q[2], 1.f);
+  return make_float4(q[0], q[1], q[2], 1.f);
+}
+// One load, one 128-bit store. The body of k_session_promote and k_session_map_append.
+__device__ __forceinline__ void move_point(const float (&Tl)[16], const float4* __restrict__ read,
+                                           float4* __restrict__ dst, int i) {
+  dst[i] = moved_point(Tl, read, i);
+}
+// One load, the one value stored twice. The body of k_session_promote_map.
+__device__ __forceinline__ void move_point(const float (&Tl)[16], const float4* __restrict__ read,
+                                           float4* __restrict__ dst, float4* __restrict__ dst2, int i) {
+  const float4 q = moved_point(Tl, read, i);
+  dst[i] = q;
+  dst2[i] = q;
 }
 
 // One point of the reading as it was filtered, unmoved: its bytes, one 128-bit load, one 128-bit
 // store (apply4 by the identity would turn -0.0f into +0.0f). The body of the two gate kernels.
 __device__ __forceinline__ void copy_point(const float4* __restrict__ read, float4* __restrict__ dst, int i) {
   dst[i] = read[i];
+}
+// The same bytes stored twice, from one load. The body of k_session_gate_promote_map.
+__device__ __forceinline__ void copy_point(const float4* __restrict__ read, float4* __restrict__ dst,
+                                           float4* __restrict__ dst2, int i) {
+  const float4 p = read[i];
+  dst[i] = p;
+  dst2[i] = p;
 }
 
 // One thread per point of the reading: one 128-bit load, one 128-bit store. Every thread reads the
@@ -63,6 +85,28 @@ __global__ __launch_bounds__(256) void k_session_promote(int n, const StreamRec*
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   move_point(Tl, read, ref, i);
+}
+
+// k_session_promote for a session that keeps aligned_map_ (app.cpp:458-468: every new reference goes
+// behind the map): the same uniform reads, header and per-point value, stored to ref[i] and to the
+// map's tail dst[i] (room for n points was reserved before the reading was enqueued): one 128-bit
+// load, two 128-bit stores. Neither ref nor dst aliases read or the other.
+__global__ __launch_bounds__(256) void k_session_promote_map(int n, const StreamRec* __restrict__ rec,
+                                                             const float* __restrict__ T,
+                                                             const float4* __restrict__ read, int32_t id,
+                                                             float4* __restrict__ ref, float4* __restrict__ dst,
+                                                             SessionHeader* hdr) {
+  if (!rec->append) return;
+  float Tl[16];
+  for (int k = 0; k < 16; ++k) Tl[k] = T[k];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    hdr->count = (uint32_t)n;
+    hdr->id = id;
+    for (int k = 0; k < 3; ++k) hdr->origin[k] = rec->corrected_origin[k];
+  }
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  move_point(Tl, read, ref, dst, i);
 }
 
 // k_session_promote's per-point body with the destination the caller gives (the map's tail,
@@ -117,6 +161,40 @@ __global__ __launch_bounds__(256) void k_session_gate_promote(int n, const GateR
   copy_point(read, ref, i);
 }
 
+// k_session_gate_promote for a session that keeps aligned_map_: the gated reading's bytes go to
+// ref[i] and to the map's tail dst[i] (one 128-bit load, two 128-bit stores); everything thread 0 of
+// block 0 writes, and the branch not gated, are k_session_gate_promote's.
+__global__ __launch_bounds__(256) void k_session_gate_promote_map(int n, const GateRec* __restrict__ gate,
+                                                                  const double* __restrict__ origin,
+                                                                  const float4* __restrict__ read, int32_t id,
+                                                                  float4* __restrict__ ref, float4* __restrict__ dst,
+                                                                  float* __restrict__ T, StreamState* S,
+                                                                  StreamRec* rec, SessionHeader* hdr) {
+  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+  if (!gate->gate) {
+    if (first) rec->append = 0;
+    return;
+  }
+  if (first) {
+    rec->status = 0;
+    rec->accepted = 1;
+    rec->append = 1;
+    rec->refilter = 0;
+    hdr->count = (uint32_t)n;
+    hdr->id = id;
+    for (int k = 0; k < 3; ++k) {
+      const double o = origin[k];
+      rec->corrected_origin[k] = o;
+      hdr->origin[k] = o;
+    }
+    for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.f : 0.f;
+    S->count = 0;
+  }
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  copy_point(read, ref, dst, i);
+}
+
 // The gated branch for the live map sessions (built: app.cpp:401-411, 458-465; prior map:
 // app.cpp:401-411, 469-493) behind k_svm_predict. Every thread reads the gate from device memory
 // (one address for the whole grid: the branch is uniform). Not gated: thread 0 of block 0 clears
@@ -167,6 +245,17 @@ void launch_session_gate_promote(hipStream_t s, int n, const GateRec* gate, cons
                                  SessionHeader* hdr) {
   if (n > 0)
     k_session_gate_promote<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, gate, origin, read, id, ref, T, S, rec, hdr);
+}
+void launch_session_promote_map(hipStream_t s, int n, const StreamRec* rec, const float* T, const float4* read,
+                                int32_t id, float4* ref, float4* dst, SessionHeader* hdr) {
+  if (n > 0) k_session_promote_map<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, rec, T, read, id, ref, dst, hdr);
+}
+void launch_session_gate_promote_map(hipStream_t s, int n, const GateRec* gate, const double* origin,
+                                     const float4* read, int32_t id, float4* ref, float4* dst, float* T, StreamState* S,
+                                     StreamRec* rec, SessionHeader* hdr) {
+  if (n > 0)
+    k_session_gate_promote_map<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, gate, origin, read, id, ref, dst, T, S,
+                                                                           rec, hdr);
 }
 void launch_session_map_append(hipStream_t s, int n, const StreamRec* rec, const float* T, const float4* read,
                                float4* dst) {

@@ -897,6 +897,40 @@ int aicp_hip_map_session_start(aicp_hip_ctx* ctx, aicp_hip_map_session* s, aicp_
   return AICP_OK;
 }
 
+// goBackRequest (app_ros.cpp:329-357): the map App built becomes the prior map and the same App, with
+// its graph and its initialT_, localises on it. The count comes from the live session's counter of
+// accepted readings; initialT_ is copied from the live session's block device to device, behind
+// everything on the stream, and this session's mirror is read back from its own block.
+int aicp_hip_mapsession_start_go_back(aicp_hip_ctx* ctx, aicp_hip_map_session* s, aicp_hip_map* map,
+                                      const aicp_hip_session* from) {
+  if (!ctx || !s || !map || !from) return AICP_ERR_INVALID;
+  if (s->P.bm) FAIL(AICP_ERR_INVALID, "go-back: a built-map session localises on no prior map");
+  uint64_t n_clouds = 0;
+  const float* d_initT = nullptr;
+  int rc = session_go_back(ctx, from, &n_clouds, &d_initT);
+  if (rc) return rc;
+  if (n_clouds > (uint64_t)INT32_MAX) FAIL(AICP_ERR_INVALID, "go-back: the graph's count");
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  HIPC(hipStreamSynchronize(st));  // (the mirror is free)
+  char* h = s->pin.as<char>();
+  std::memset(h, 0, kSessBytes);
+  StreamState* hS = reinterpret_cast<StreamState*>(h);
+  ident4(hS->initT);
+  hS->count = (int32_t)n_clouds;  // aligned_clouds_graph_->getNbClouds()
+  *reinterpret_cast<float*>(h + kSessFifty) = 50.0f;  // octree_overlap_ on the prior map (app.cpp:123-127)
+  HIPC(hipMemcpyAsync(s->win.p, h, kSessBytes, hipMemcpyHostToDevice, st));
+  HIPC(hipMemcpyAsync(s->win.as<StreamState>()->initT, d_initT, 64, hipMemcpyDeviceToDevice, st));
+  HIPC(hipMemcpyAsync(hS, s->win.p, sizeof(StreamState), hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  s->map = map;
+  s->n_processed = 0;
+  s->started = true;
+  s->ended = false;
+  s->mon.none();
+  return AICP_OK;
+}
+
 int aicp_hip_mapsession_set_monitor(aicp_hip_ctx* ctx, aicp_hip_map_session* s, const aicp_monitor_params* prm) {
   if (!ctx || !s) return AICP_ERR_INVALID;
   return s->mon.set(ctx, prm);

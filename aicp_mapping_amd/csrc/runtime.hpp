@@ -486,6 +486,9 @@ int map_reserve(aicp_hip_ctx* ctx, aicp_hip_map* map, size_t add);
 int map_crop_pairs(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float mx, const aicp_cloud* readings,
                    const float* poses, size_t n, const double* read_origins, size_t* n_ok, const uint32_t** counts,
                    const uint32_t* dev_read_n = nullptr);
+// aicp_hip_map_crop with the kept points left on the device, in dst (session.cpp: a start on a map)
+int map_crop_resident(aicp_hip_ctx* ctx, const aicp_hip_map* map, float mn, float mx, const float origin[16],
+                      DevBuf* dst, uint32_t* kept);
 // a raw reading for the raw streams (map_stream.cpp): its rows uploaded, k_stream_ingest into the
 // pre-filter's input (d_initT / d_origin: debug mode, nullable), the pre-filter, and the kept
 // points copied device-to-device to dst (room for c.n points). Returns with ctx->stream idle up to
@@ -534,6 +537,9 @@ struct ReplayRisk {  // aicp_hip_sequence_run_risk's part
 int session_replay(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_sequence_params* prm,
                    const aicp_prefilter_params* pf, const ReplayRisk* risk, const aicp_cloud* first,
                    const aicp_cloud* readings, size_t n, float* out_T, aicp_sequence_result* out, size_t* n_done);
+// what a go-back takes from a live session (session.cpp): App's graph count and the device address
+// of its initialT_; AICP_ERR_INVALID for a session of another context, not started, or ended
+int session_go_back(aicp_hip_ctx* ctx, const aicp_hip_session* s, uint64_t* n_clouds, const float** d_initT);
 int risk_params_check(aicp_hip_ctx* ctx, const aicp_risk_params* prm);  // its pre-filter's pf_check
 // the gate's pose rules (aicp_hip.cpp: fromMatrix4fToIsometry3d(T) * prior, removePitchRollCorrection)
 void pose_moved(const float* T, const double* prior, double* out);

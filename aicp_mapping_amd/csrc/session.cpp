@@ -31,6 +31,21 @@
 // was and a larger reference never needs a copy. Its identity in the reference cache is a number
 // taken from the cache for every new reference (RefCache::owner): no host copy, no compare.
 //
+// aligned_map_ (aicp_hip_session_keep_aligned_map; app.cpp:310, 458-468): the session owns an
+// aicp_hip_map made from the first cloud's reference bytes, and k_session_promote_map /
+// k_session_gate_promote_map store every new reference a second time behind it. The host makes room
+// (map_reserve) after the reading's pre-filter and before its batch, when the mirrored count says
+// the reading is promoted if accepted (a risk session: every reading), and adds the kept points to
+// the map's size after the call's one read-back, when the record says `append`. The go-back
+// (app_ros.cpp:329-357) takes the map out of the session (aicp_hip_session_take_aligned_map) and
+// starts a prior-map session at App's graph count and initialT_ (session_go_back below,
+// aicp_hip_mapsession_start_go_back in map_stream.cpp).
+//
+// aicp_hip_session_start_on_map is load_map_from_file without localize_against_prior_map
+// (app.cpp:43-59, 392-399): the reference is a map's crop around the first reading's prior pose, the
+// graph is empty, and the first reading runs without the drop test and is promoted whatever the
+// frequency (StreamRules by value for that call: max_corr = +inf, freq = 1).
+//
 // The two offline App-order entry points (aicp_hip_sequence_run_raw in debug mode,
 // aicp_hip_sequence_run_risk; aicp_hip.cpp) are session_replay below: the same step, reading after
 // reading, on a session private to the call.
@@ -97,6 +112,16 @@ struct aicp_hip_session {
   // the reference changes), the counters, and the last call's result
   MonState mon;
   MonRefTree mon_tree;
+  // aligned_map_ (aicp_hip_session_keep_aligned_map): the session's own map, and where this
+  // reading's points go if it is promoted (null: no room was made, the mirrored count rules it out)
+  aicp_hip_ctx* owner = nullptr;
+  bool keep_map = false;
+  aicp_hip_map* amap = nullptr;
+  float4* tail = nullptr;
+  // App's graph (aligned_clouds_graph_->getNbClouds()): the readings accepted since the start, gated
+  // ones included, beside the first cloud, which a start on a map does not have
+  uint64_t n_accepted = 0;
+  bool on_map = false, first_on_map = false;  // started on a map; and its first reading is still to come
 };
 
 namespace {
@@ -135,6 +160,62 @@ int end_session(aicp_hip_ctx* ctx, aicp_hip_session* s, int rc) {
   return rc;
 }
 
+// a map of its own from n points that lie on the device, behind everything enqueued on ctx->stream:
+// exactly the cloud, as aicp_hip_map_create sizes it (n = 0: an empty map, grown by its first append)
+int map_from_device(aicp_hip_ctx* ctx, const float4* src, size_t n, aicp_hip_map** out) {
+  aicp_hip_map* m = new aicp_hip_map();
+  if (n) {
+    const size_t nb = std::max<size_t>(256, n * 16);
+    hipError_t e = hipMalloc(&m->pts.p, nb);
+    if (e == hipSuccess) {
+      m->pts.cap = nb;
+      e = hipMemcpyAsync(m->pts.p, src, n * 16, hipMemcpyDeviceToDevice, ctx->stream);
+    }
+    if (e != hipSuccess) {
+      release(m->pts);
+      delete m;
+      FAIL(AICP_ERR_HIP, std::string("session: aligned map allocation: ") + hipGetErrorString(e));
+    }
+  }
+  m->n = n;
+  *out = m;
+  return AICP_OK;
+}
+
+// A start that can no longer fail on its inputs: the spare buffer's `kept` points are reference -1
+// with the sensor origin `origin`, the state is App's at its start (count = 0, initialT_ = I, no
+// record), and map (nullable: keeping is off) replaces the session's aligned map. on_map: the
+// reference is a map's crop and the graph holds no first cloud (aicp_hip_session_start_on_map).
+int begin_state(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, const double origin[3], aicp_hip_map* map,
+                bool on_map) {
+  hipStream_t st = ctx->stream;
+  aicp_hip_map_free(ctx, s->amap);  // (waits for the stream)
+  s->amap = map;
+  s->tail = nullptr;
+  s->cur = 1 - s->cur;
+  s->ref_n = kept;
+  s->ref_id = -1;
+  for (int k = 0; k < 3; ++k) s->ref_origin[k] = origin[k];
+  s->gen = ctx->refc.next_owner++;
+  s->mon_tree.invalidate();
+  s->mon.none();
+  s->n_processed = s->n_accepted = 0;
+  s->on_map = s->first_on_map = on_map;
+  s->started = true;
+  s->ended = false;
+  // count = 0, initialT_ = I, no record, the header of reference -1
+  char* h = s->pin.as<char>();
+  std::memset(h, 0, kWinBytes);
+  ident4(host_state(s)->initT);
+  SessionHeader* hh = reinterpret_cast<SessionHeader*>(h + kOffHdr);
+  hh->count = kept;
+  hh->id = -1;
+  for (int k = 0; k < 3; ++k) hh->origin[k] = origin[k];
+  HIPC(hipMemcpyAsync(s->win.p, h, kWinBytes, hipMemcpyHostToDevice, st));
+  HIPC(hipStreamSynchronize(st));
+  return AICP_OK;
+}
+
 // first_pose: a risk session's (nullable otherwise): the reference's pose through updateCloud
 // (app.cpp:293-299), set once nothing can fail any more
 int start_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, const double* first_pose) {
@@ -153,27 +234,29 @@ int start_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, const doub
     HIPC(hipStreamSynchronize(st));
     FAIL(AICP_ERR_INVALID, "session: the first cloud keeps no point after the pre-filter");
   }
-  s->cur = 1 - s->cur;
-  s->ref_n = kept;
-  s->ref_id = -1;
-  for (int k = 0; k < 3; ++k) s->ref_origin[k] = r.origin[k];
-  s->gen = ctx->refc.next_owner++;
-  s->mon_tree.invalidate();
-  s->mon.none();
-  s->n_processed = 0;
-  s->started = true;
-  s->ended = false;
-  // count = 0, initialT_ = I, no record, the header of reference -1
-  char* h = s->pin.as<char>();
-  std::memset(h, 0, kWinBytes);
-  ident4(host_state(s)->initT);
-  SessionHeader* hh = reinterpret_cast<SessionHeader*>(h + kOffHdr);
-  hh->count = kept;
-  hh->id = -1;
-  for (int k = 0; k < 3; ++k) hh->origin[k] = r.origin[k];
-  HIPC(hipMemcpyAsync(s->win.p, h, kWinBytes, hipMemcpyHostToDevice, st));
-  HIPC(hipStreamSynchronize(st));
+  // aligned_map_ starts as the first cloud's reference (app.cpp:310): its bytes, device to device
+  aicp_hip_map* map = nullptr;
+  if (s->keep_map) {
+    rc = map_from_device(ctx, dst.as<float4>(), kept, &map);
+    if (rc) return rc;
+  }
+  rc = begin_state(ctx, s, kept, r.origin, map, false);
+  if (rc) return rc;
   if (first_pose) pose_fix_pitch_roll(first_pose, first_pose, s->ref_pose);
+  return AICP_OK;
+}
+
+// Room behind the aligned map for this reading's kept points, between its pre-filter and its batch
+// (nothing that reads the map is in flight; growing synchronises and may move the map, so the tail
+// is taken afterwards), when the reading is promoted if it is accepted: the mirrored count reaches
+// `freq` (k_stream_commit's rule), or `every` (a risk session: the gate can promote any reading). A
+// map that cannot grow is the call's error: the map and the session stay as they were.
+int reserve_tail(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, int32_t freq, bool every) {
+  s->tail = nullptr;
+  if (!s->amap || !(every || host_state(s)->count + 1 == freq)) return AICP_OK;
+  const int rc = map_reserve(ctx, s->amap, kept);
+  if (rc) return rc;
+  s->tail = s->amap->pts.as<float4>() + s->amap->n;
   return AICP_OK;
 }
 
@@ -263,7 +346,7 @@ int ingest_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, const 
   return AICP_OK;
 }
 
-int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, int32_t id, int rc,
+int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, const StreamRules& rules, uint32_t kept, int32_t id, int rc,
                    std::chrono::steady_clock::time_point t0, aicp_sequence_result* out, bool* promoted);
 
 int process_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, float* out_T, aicp_sequence_result* out,
@@ -274,6 +357,15 @@ int process_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, float* o
   uint32_t kept = 0;
   double prior[16];
   int rc = ingest_reading(ctx, s, r, nullptr, out_T, out, kept_out, &kept, prior);
+  if (rc) return rc;
+  // the first reading after a start on a map (app.cpp:366-369, 383-399): the graph is empty, so no
+  // drop test, and the accepted reading is the next reference whatever the frequency
+  StreamRules rules = s->rules;
+  if (s->first_on_map) {
+    rules.max_corr = INFINITY;
+    rules.freq = 1;
+  }
+  rc = reserve_tail(ctx, s, kept, rules.freq, false);
   if (rc) return rc;
   // the one-pair batch: both clouds are on the device already
   const int flags = AICP_RUN_ICP | (s->prm.flags & (AICP_RUN_OVERLAP | AICP_RUN_TIME_NN));
@@ -287,13 +379,13 @@ int process_rows(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, float* o
   }
   out->icp = stats;
   out->status = out->icp.status = rc;
-  return commit_reading(ctx, s, kept, id, rc, t0, out, nullptr);
+  return commit_reading(ctx, s, rules, kept, id, rc, t0, out, nullptr);
 }
 
 // Behind the batch that registered the reading (rc: its status, out->icp filled): App's bookkeeping
 // and the promotion, on the device; one read-back. *promoted (nullable): the reading is the new
 // reference (the buffers are flipped, a new owner number is taken).
-int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, int32_t id, int rc,
+int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, const StreamRules& rules, uint32_t kept, int32_t id, int rc,
                    std::chrono::steady_clock::time_point t0, aicp_sequence_result* out, bool* promoted) {
   hipStream_t st = ctx->stream;
   char* h = s->pin.as<char>();
@@ -320,9 +412,13 @@ int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, int32_
     if (!mon_ran) mon_err = ctx->err;
     ctx->err = why;
   }
-  launch_stream_commit(st, 1, ctx->state.as<PairState>(), ctx->outT.as<float>(), dOrg, s->rules, dS, dRec);
-  launch_session_promote(st, (int)kept, dRec, ctx->outT.as<float>(), s->read.as<float4>(), id, spare.as<float4>(),
-                         dHdr);
+  launch_stream_commit(st, 1, ctx->state.as<PairState>(), ctx->outT.as<float>(), dOrg, rules, dS, dRec);
+  if (s->tail)  // (aligned_map_: the new reference also goes behind the map, app.cpp:458-468)
+    launch_session_promote_map(st, (int)kept, dRec, ctx->outT.as<float>(), s->read.as<float4>(), id,
+                               spare.as<float4>(), s->tail, dHdr);
+  else
+    launch_session_promote(st, (int)kept, dRec, ctx->outT.as<float>(), s->read.as<float4>(), id, spare.as<float4>(),
+                           dHdr);
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(s->ev_end, st));
   HIPC(hipMemcpyAsync(h, d, mon_ran ? kReadBackMon : kReadBack, hipMemcpyDeviceToHost, st));
@@ -343,11 +439,17 @@ int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, int32_
   }
   out->accepted = rec.accepted;
   for (int k = 0; k < 3; ++k) out->corrected_origin[k] = rec.corrected_origin[k];
+  if (rec.accepted) ++s->n_accepted;
   if (rec.append) {  // the corrected reading is the next reference (app.cpp:375-391)
     if (hdr.count != kept || hdr.id != id) {
       (void)end_session(ctx, s, AICP_ERR_HIP);
       FAIL(AICP_ERR_HIP, "session: the promoted reference's header");
     }
+    if (s->amap && !s->tail) {
+      (void)end_session(ctx, s, AICP_ERR_HIP);
+      FAIL(AICP_ERR_HIP, "session: the device's count left its mirror");
+    }
+    if (s->tail) s->amap->n += kept;
     out->is_reference = 1;
     s->cur = 1 - s->cur;
     s->ref_n = kept;
@@ -360,6 +462,7 @@ int commit_reading(aicp_hip_ctx* ctx, aicp_hip_session* s, uint32_t kept, int32_
   s->mon.take(ctx, &s->mon_tree, mon_ran, h + kOffMon, mon_err);
   if (rec.append) s->mon_tree.invalidate();  // (the monitor's trees are the old reference's)
   ++s->n_processed;
+  s->first_on_map = false;
   return AICP_OK;
 }
 
@@ -389,6 +492,8 @@ int process_rows_risk(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, con
   GateRec* dGate = reinterpret_cast<GateRec*>(d + kOffGate);
   prec->n_read = kept;
   out->icp.overlap_percent = -1.f;
+  rc = reserve_tail(ctx, s, kept, s->rules.freq, true);
+  if (rc) return rc;
   // 1. computeOverlap: an overlap-only batch, the poses' translations are the sensor origins (app.cpp:229)
   aicp_icp_stats ost{};
   ost.status = -1;
@@ -405,8 +510,12 @@ int process_rows_risk(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, con
   if (rc) return failed(rc, "risk gate: ");
   DevBuf& spare = s->ref[1 - s->cur];
   HIPC(ensure(spare, (size_t)kept * 16));
-  launch_session_gate_promote(st, (int)kept, dGate, dOrg, s->read.as<float4>(), id, spare.as<float4>(),
-                              ctx->outT.as<float>(), dS, dRec, dHdr);
+  if (s->tail)  // (aligned_map_: a gated reading is a new reference too, app.cpp:401-411, 458-468)
+    launch_session_gate_promote_map(st, (int)kept, dGate, dOrg, s->read.as<float4>(), id, spare.as<float4>(), s->tail,
+                                    ctx->outT.as<float>(), dS, dRec, dHdr);
+  else
+    launch_session_gate_promote(st, (int)kept, dGate, dOrg, s->read.as<float4>(), id, spare.as<float4>(),
+                                ctx->outT.as<float>(), dS, dRec, dHdr);
   HIPC(hipGetLastError());
   HIPC(hipEventRecord(s->ev_end, st));
   HIPC(hipMemcpyAsync(h, d, kReadBackGate, hipMemcpyDeviceToHost, st));
@@ -437,6 +546,8 @@ int process_rows_risk(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, con
     out->icp = ist;
     out->accepted = out->is_reference = 1;
     for (int k = 0; k < 3; ++k) out->corrected_origin[k] = rec.corrected_origin[k];
+    if (s->tail) s->amap->n += kept;
+    ++s->n_accepted;
     s->cur = 1 - s->cur;
     s->ref_n = kept;
     s->ref_id = id;
@@ -459,7 +570,7 @@ int process_rows_risk(aicp_hip_ctx* ctx, aicp_hip_session* s, const Rows& r, con
   out->icp = ist;
   out->status = out->icp.status = rc;
   bool promoted = false;
-  rc = commit_reading(ctx, s, kept, id, rc, t0, out, &promoted);
+  rc = commit_reading(ctx, s, s->rules, kept, id, rc, t0, out, &promoted);
   if (rc) return rc;
   if (promoted) {  // App's corrected pose, in double on the host (aligned_cloud.cpp:31-74)
     double corrected[16];
@@ -505,6 +616,7 @@ int create_session(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_seq
                    double threshold, aicp_hip_session** out) {
   HIPC(hipSetDevice(ctx->device));
   aicp_hip_session* s = new aicp_hip_session();
+  s->owner = ctx;
   s->cfg = *cfg;
   s->prm = *prm;
   if (pf) s->pf = *pf;
@@ -566,7 +678,71 @@ int aicp::rt::session_replay(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, cons
   return rc;
 }
 
+// What a go-back takes from a live session (aicp_hip_mapsession_start_go_back, map_stream.cpp;
+// declared in runtime.hpp): App's graph count, from the host's counter of accepted readings, and
+// where initialT_ lies on the device. Nothing else of the session is read.
+int aicp::rt::session_go_back(aicp_hip_ctx* ctx, const aicp_hip_session* s, uint64_t* n_clouds,
+                              const float** d_initT) {
+  if (s->owner != ctx) FAIL(AICP_ERR_INVALID, "go-back: the session lives on another context");
+  if (!s->started) FAIL(AICP_ERR_INVALID, "go-back: the session has not started");
+  if (s->ended) FAIL(AICP_ERR_INVALID, "go-back: the session ended at reading " + std::to_string(s->ended_at));
+  *n_clouds = (s->on_map ? 0 : 1) + s->n_accepted;
+  *d_initT = reinterpret_cast<const StreamState*>(s->win.as<char>() + kOffState)->initT;
+  return AICP_OK;
+}
+
 extern "C" {
+
+int aicp_hip_session_keep_aligned_map(aicp_hip_ctx* ctx, aicp_hip_session* s, int on) {
+  if (!ctx || !s) return AICP_ERR_INVALID;
+  s->keep_map = on != 0;
+  if (!on && s->amap) {  // (the map goes at once: nothing would keep it up to date)
+    HIPC(hipSetDevice(ctx->device));
+    aicp_hip_map_free(ctx, s->amap);
+    s->amap = nullptr;
+    s->tail = nullptr;
+  }
+  return AICP_OK;
+}
+
+int aicp_hip_session_aligned_map(aicp_hip_ctx* ctx, aicp_hip_session* s, aicp_hip_map** out) {
+  if (!ctx || !s || !out) return AICP_ERR_INVALID;
+  *out = nullptr;
+  if (!s->keep_map) FAIL(AICP_ERR_INVALID, "session: the aligned map is not kept");
+  if (!s->started || !s->amap) FAIL(AICP_ERR_INVALID, "session: no aligned map before the next start");
+  *out = s->amap;
+  return AICP_OK;
+}
+
+int aicp_hip_session_take_aligned_map(aicp_hip_ctx* ctx, aicp_hip_session* s, aicp_hip_map** out) {
+  const int rc = aicp_hip_session_aligned_map(ctx, s, out);
+  if (rc) return rc;
+  s->amap = nullptr;  // (the caller's now; the session goes on without one until its next start)
+  s->tail = nullptr;
+  return AICP_OK;
+}
+
+int aicp_hip_session_start_on_map(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_hip_map* map,
+                                  const float first_pose[16], float crop_min, float crop_max) {
+  if (!ctx || !s || !map || !first_pose) return AICP_ERR_INVALID;
+  if (kind_check(ctx, s, false)) return AICP_ERR_INVALID;
+  HIPC(hipSetDevice(ctx->device));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  // the reference: the map around the first reading's prior pose (setReference, app.cpp:43-58), into
+  // the spare buffer: an empty crop leaves the session as it was
+  uint32_t kept = 0;
+  int rc = map_crop_resident(ctx, map, crop_min, crop_max, first_pose, &s->ref[1 - s->cur], &kept);
+  if (rc) return rc;
+  if (!kept) FAIL(AICP_ERR_INVALID, "session: empty map crop");
+  // aligned_map_ starts empty: there is no first cloud (app.cpp:310 is not reached)
+  aicp_hip_map* amap = nullptr;
+  if (s->keep_map) {
+    rc = map_from_device(ctx, nullptr, 0, &amap);
+    if (rc) return rc;
+  }
+  const double origin[3] = {first_pose[12], first_pose[13], first_pose[14]};
+  return begin_state(ctx, s, kept, origin, amap, true);
+}
 
 int aicp_hip_session_create(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_sequence_params* prm,
                             const aicp_prefilter_params* pf, aicp_hip_session** out) {
@@ -603,6 +779,7 @@ void aicp_hip_session_free(aicp_hip_ctx* ctx, aicp_hip_session* s) {
   release(s->ref[0]);
   release(s->ref[1]);
   release(s->read);
+  aicp_hip_map_free(nullptr, s->amap);  // (the stream was waited for above)
   s->mon_tree.release_all();
   if (s->ev_begin) (void)hipEventDestroy(s->ev_begin);
   if (s->ev_end) (void)hipEventDestroy(s->ev_end);

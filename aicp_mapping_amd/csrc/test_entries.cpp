@@ -1189,4 +1189,57 @@ int aicp_hip_test_monitor_resident(aicp_hip_ctx* ctx, const aicp_monitor_params*
   return AICP_OK;
 }
 
+// The live session's promotion kernels (session.cpp's four launches) on a made-up block: the
+// reading, the reference buffer and the map in guarded device buffers of their own, the block in a
+// call-local copy of the session's layout.
+int aicp_hip_test_promote_map(aicp_hip_ctx* ctx, int32_t kernel, const float* read4, size_t n, size_t tail,
+                              int32_t id, void* block, float* ref4, float* map4, uint64_t* dirty) {
+  constexpr size_t kBlock = 448, kRec = 128, kHdr = 192, kGate = 256, kT = 320, kOrg = 384;
+  if (!ctx || !read4 || !block || !ref4 || !map4 || !dirty || kernel < 0 || kernel > 3 || n == 0 ||
+      n + tail >= (1ull << 24))
+    return AICP_ERR_INVALID;
+  *dirty = 0;
+  HIPC(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  HIPC(hipStreamSynchronize(s));
+  CallBufs loc;
+  loc.sync = s;
+  Guarded gread, gref, gmap;
+  HIPC(gread.alloc(loc, 4 * n, 0xA5A5A5A5u));
+  HIPC(gref.alloc(loc, 4 * n, 0xA5A5A5A5u));
+  HIPC(gmap.alloc(loc, 4 * (tail + n), 0xA5A5A5A5u));
+  DevBuf& blk = loc.get();
+  HIPC(ensure(blk, kBlock));
+  for (const Guarded* g : {&gread, &gref, &gmap}) HIPC(g->refill(s));
+  HIPC(hipStreamSynchronize(s));
+  HIPC(hipMemcpy(gread.payload(), read4, n * 16, hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(blk.p, block, kBlock, hipMemcpyHostToDevice));
+  char* d = blk.as<char>();
+  StreamState* dS = reinterpret_cast<StreamState*>(d);
+  StreamRec* dRec = reinterpret_cast<StreamRec*>(d + kRec);
+  SessionHeader* dHdr = reinterpret_cast<SessionHeader*>(d + kHdr);
+  const GateRec* dGate = reinterpret_cast<const GateRec*>(d + kGate);
+  float* dT = reinterpret_cast<float*>(d + kT);
+  const double* dOrg = reinterpret_cast<const double*>(d + kOrg);
+  const float4* dread = static_cast<const float4*>(gread.payload());
+  float4* dref = static_cast<float4*>(gref.payload());
+  float4* dtail = static_cast<float4*>(gmap.payload()) + tail;
+  switch (kernel) {
+    case 0: launch_session_promote(s, (int)n, dRec, dT, dread, id, dref, dHdr); break;
+    case 1: launch_session_gate_promote(s, (int)n, dGate, dOrg, dread, id, dref, dT, dS, dRec, dHdr); break;
+    case 2: launch_session_promote_map(s, (int)n, dRec, dT, dread, id, dref, dtail, dHdr); break;
+    default: launch_session_gate_promote_map(s, (int)n, dGate, dOrg, dread, id, dref, dtail, dT, dS, dRec, dHdr);
+  }
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(s));
+  HIPC(hipMemcpy(block, blk.p, kBlock, hipMemcpyDeviceToHost));
+  std::vector<uint32_t> back;
+  std::vector<float> in(4 * n);
+  if (gref.fetch(back, ref4, *dirty) != hipSuccess) return AICP_ERR_HIP;
+  if (gmap.fetch(back, map4, *dirty) != hipSuccess) return AICP_ERR_HIP;
+  if (gread.fetch(back, in.data(), *dirty) != hipSuccess) return AICP_ERR_HIP;
+  *dirty += std::memcmp(in.data(), read4, n * 16) != 0;
+  return AICP_OK;
+}
+
 }  // extern "C"

@@ -94,6 +94,13 @@ class MapSession(L.SessionMonitor):
         as it is now."""
         self.ctx.check(L.lib.aicp_hip_map_session_start(self.ctx.h, self.h, self.map.h))
 
+    def start_go_back(self, app_session) -> None:
+        """The node's go-back (app_ros.cpp:329-357) for a session on a PriorMap: start() with App's
+        state in place of a fresh one, the count at app_session's graph size (its first cloud and
+        its accepted readings) and its initialT_, copied device to device. The map is usually
+        app_session.take_aligned_map()."""
+        self.ctx.check(L.lib.aicp_hip_mapsession_start_go_back(self.ctx.h, self.h, self.map.h, app_session.h))
+
     def process(self, reading, pose, raise_on_error=True):
         """One reading ((N, 3|4|8|12) float32 rows, or a SweepAccumulator, which is left as it is)
         with its 4x4 row-major prior pose, whose translation is the reading's sensor origin.

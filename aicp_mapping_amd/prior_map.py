@@ -51,9 +51,21 @@ class PriorMap:
         self.ctx = ctx
         self.h = h
 
+    @classmethod
+    def from_handle(cls, ctx: "L.Context", h, owning: bool = True) -> "PriorMap":
+        """A PriorMap over an aicp_hip_map that already lies on the device (a live session's
+        aligned map). owning=False: a borrowed view, which never frees the handle and is valid
+        only as long as its owner keeps the map."""
+        m = cls.__new__(cls)
+        m.ctx = ctx
+        m.h = h
+        m.borrowed = not owning
+        return m
+
     def free(self):
         if getattr(self, "h", None):
-            L.lib.aicp_hip_map_free(self.ctx.h, self.h)
+            if not getattr(self, "borrowed", False) and getattr(self.ctx, "h", None):
+                L.lib.aicp_hip_map_free(self.ctx.h, self.h)
             self.h = None
 
     def __del__(self):
@@ -150,6 +162,18 @@ class PriorMap:
         """map = regionGrowingUniformPlaneSegmentationFilter(map) on device."""
         prm = params or L.default_prefilter()
         self.ctx.check(L.lib.aicp_hip_map_prefilter(self.ctx.h, self.h, C.byref(prm)))
+
+
+def load_map_from_file(ctx: "L.Context", path: str, prefilter=None) -> PriorMap:
+    """The node's map loading (app_ros.cpp:301-315): the PLY file's points
+    (cloud_io.load_ply_xyz, pcl::io::loadPLYFile<PointXYZ>) as a device-resident map, pre-filtered
+    once with `prefilter` (PrefilterParams; None: the defaults) as the node pre-filters the loaded
+    map before it hands it to App."""
+    from .cloud_io import load_ply_xyz
+
+    m = PriorMap(ctx, load_ply_xyz(path))
+    m.prefilter(prefilter)
+    return m
 
 
 def localization_update(prior_map: PriorMap, read_prefiltered, correction, n_clouds: int,

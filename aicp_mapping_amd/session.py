@@ -20,6 +20,18 @@ session takes 4x4 prior poses in place of origins:
 
     session.start(first, pose=first_pose)
     T, result, kept, record = session.process(reading, pose=prior_pose)
+
+With ``keep_aligned_map=True`` the session also keeps App's ``aligned_map_`` (app.cpp:310, 458-468)
+on the device: the first cloud's reference and every later reference, appended where the promotion
+happens. ``aligned_map`` is a borrowed view of it, and the go-back of the node
+(app_ros.cpp:329-357) moves no point over the bus:
+
+    prior = session.take_aligned_map()           # the session's map, now the caller's PriorMap
+    loc = MapSession(ctx, prior, params=L.default_localization_params())
+    loc.start_go_back(session)                   # App's graph count and initialT_, device to device
+
+``start_on_map(prior_map, pose)`` is ``load_map_from_file`` without localising (app.cpp:43-59,
+392-399): the reference is the loaded map's crop around the first reading's prior pose.
 """
 from __future__ import annotations
 
@@ -34,7 +46,8 @@ from .accumulator import SweepAccumulator
 class AppSession(L.SessionMonitor):
     _monitor_kind = "session"
 
-    def __init__(self, ctx: "L.Context", cfg=None, params=None, prefilter=None, risk=None, monitor=None):
+    def __init__(self, ctx: "L.Context", cfg=None, params=None, prefilter=None, risk=None, monitor=None,
+                 keep_aligned_map=False):
         """cfg: IcpConfig (default_config() when None; a point-to-point chain is accepted); params:
         SequenceParams (flags: AICP_RUN_OVERLAP | AICP_SEQ_DEBUG | AICP_RUN_TIME_NN); prefilter:
         None when the clouds are already pre-filtered, PrefilterParams (or True for the defaults)
@@ -42,7 +55,8 @@ class AppSession(L.SessionMonitor):
         dict(model=SvmModel (kept alive by the session), threshold=float (default 0.5),
         params=RiskParams (default_risk_params() when left out)) for failure_prediction_mode;
         monitor: None (off), True or dict(quantile=, max_accepted_dist=, paired=) for the quality
-        monitor per reading (set_monitor, last_monitor, monitor_counters)."""
+        monitor per reading (set_monitor, last_monitor, monitor_counters); keep_aligned_map: keep
+        App's aligned_map_ on the device from the next start on (aligned_map, take_aligned_map)."""
         mon = L.monitor_argument(monitor)  # (a bad argument before anything is made)
         cfg = cfg or L.default_config()
         prm = params or L.default_sequence_params()
@@ -65,6 +79,41 @@ class AppSession(L.SessionMonitor):
         self.h = h
         if mon is not None:
             self.set_monitor(mon)
+        if keep_aligned_map:
+            self.keep_aligned_map(True)
+
+    def keep_aligned_map(self, on=True) -> None:
+        """aicp_hip_session_keep_aligned_map: from the next start on (off: a map held is freed)."""
+        self.ctx.check(L.lib.aicp_hip_session_keep_aligned_map(self.ctx.h, self.h, 1 if on else 0))
+
+    @property
+    def aligned_map(self):
+        """App's aligned_map_ as a borrowed PriorMap view (len, getCloud, crop, capacity), valid
+        until the next start, take_aligned_map or close. AicpError when keeping is off, the session
+        has not started, or the map was taken."""
+        from .prior_map import PriorMap
+
+        h = C.c_void_p()
+        self.ctx.check(L.lib.aicp_hip_session_aligned_map(self.ctx.h, self.h, C.byref(h)))
+        return PriorMap.from_handle(self.ctx, h, owning=False)
+
+    def take_aligned_map(self):
+        """The aligned map as an owning PriorMap; nothing is copied. The session keeps running
+        and no longer accumulates until its next start."""
+        from .prior_map import PriorMap
+
+        h = C.c_void_p()
+        self.ctx.check(L.lib.aicp_hip_session_take_aligned_map(self.ctx.h, self.h, C.byref(h)))
+        return PriorMap.from_handle(self.ctx, h, owning=True)
+
+    def start_on_map(self, prior_map, pose, crop=15.0) -> None:
+        """load_map_from_file without localising (app.cpp:43-59, 392-399): the reference is
+        prior_map cropped to [-crop, crop]^3 around pose (the first reading's 4x4 prior pose); the
+        first reading is registered against it without the drop test and becomes the next
+        reference whatever the frequency. A plain session's call."""
+        p = np.ascontiguousarray(np.asarray(pose, np.float32).reshape(4, 4).T.reshape(16))
+        self.ctx.check(L.lib.aicp_hip_session_start_on_map(self.ctx.h, self.h, prior_map.h, L._fptr(p),
+                                                           -float(crop), float(crop)))
 
     def close(self):
         if getattr(self, "h", None):

@@ -1166,6 +1166,63 @@ int aicp_hip_mapsession_process_accum_risk(aicp_hip_ctx* ctx, aicp_hip_map_sessi
                                            const double pose[16], float out_T[16], void* out,
                                            aicp_pipeline_record* rec, uint32_t* kept);
 
+/* ---- the mapping session's built map: aligned_map_, the go-back, the start on a loaded map --------
+ * App appends every reference to aligned_map_ (app.cpp:310 for the first cloud, app.cpp:458-468
+ * after every promotion), the node publishes it, and on a go-back request turns it into the prior
+ * map and switches the same App, with its initialT_ and its graph, to localize_against_prior_map
+ * (app_ros.cpp:329-357). All of it stays on the device.
+ *
+ * aicp_hip_session_keep_aligned_map: on != 0: every later start (start, start_accum, start_pose,
+ * start_accum_pose, start_on_map) gives the session an aicp_hip_map of its own, made device to
+ * device from the bytes of the first cloud's reference (app.cpp:310; a start on a map: empty). A
+ * start that fails leaves the old map as it was, one that succeeds replaces it. Default: off; a
+ * process call then enqueues what it always did. on == 0: a map the session holds is freed at
+ * once. Allowed on plain and risk sessions, after create and before the next start.
+ *
+ * Append rule (app.cpp:458-468): after a process call whose reading became the reference (the
+ * result's is_reference: a frequency promotion, or a risk session's gated reading) the new
+ * reference's points lie behind the map in order, the same bytes the call wrote into the reference:
+ * the reading as registered moved by its correction (aicp_hip_transform's float expression, w = 1),
+ * or, gated, the unmoved bytes. A dropped reading, a reading that ends the session and an accepted
+ * reading that is not promoted append nothing. Room is made before the reading is registered, when
+ * the count says the reading would be promoted if accepted (a risk session: for every reading); a
+ * map that cannot grow is the call's error (AICP_ERR_HIP, or AICP_ERR_INVALID past 2^31 - 1
+ * points) with the map and the session as they were, the session not ended. The call ends in the
+ * read-backs it always had.
+ *
+ * aicp_hip_session_aligned_map: a borrowed handle, valid until the session's next start, take or
+ * free; between two process calls the read-only map calls (aicp_hip_map_size, _download, _crop,
+ * _capacity) may use it. AICP_ERR_INVALID when keeping is off, before the first start with it on,
+ * or after a take.
+ * aicp_hip_session_take_aligned_map: the map is the caller's (aicp_hip_map_free); nothing is copied.
+ * The session keeps running without a map until its next start. */
+int aicp_hip_session_keep_aligned_map(aicp_hip_ctx* ctx, aicp_hip_session* s, int on);
+int aicp_hip_session_aligned_map(aicp_hip_ctx* ctx, aicp_hip_session* s, aicp_hip_map** out);
+int aicp_hip_session_take_aligned_map(aicp_hip_ctx* ctx, aicp_hip_session* s, aicp_hip_map** out);
+/* The go-back (app_ros.cpp:329-357): aicp_hip_map_session_start on `map` for a prior-map session,
+ * with App's state instead of a fresh one: the count starts at from's getNbClouds() (1 for the
+ * first cloud, none after aicp_hip_session_start_on_map, plus the readings accepted since its
+ * start, gated ones included), and initialT_ is from's, copied device to device in stream order.
+ * So the drop test is live from the first localisation reading (app.cpp:366-369) and the merge and
+ * re-filter phases follow (n_clouds - 1) % f of App's graph (app.cpp:469-493). Neither handle
+ * needs the other afterwards. AICP_ERR_INVALID, with nothing changed: ms was made with the
+ * built-map policy; from is not started, or ended (App's worker is dead then); from lives on
+ * another context. */
+int aicp_hip_mapsession_start_go_back(aicp_hip_ctx* ctx, aicp_hip_map_session* ms, aicp_hip_map* map,
+                                      const aicp_hip_session* from);
+/* load_map_from_file without localize_against_prior_map (app.cpp:43-59, 392-399), plain sessions
+ * only (a risk session: AICP_ERR_INVALID, nothing changed). The reference is `map` cropped to
+ * [crop_min, crop_max]^3 around first_pose (column-major; aicp_hip_map_crop's crop, device to
+ * device), its id -1, its origin the pose's translation; initialT_ = I, the count 0, nothing
+ * processed, the graph empty. An empty crop: AICP_ERR_INVALID, the session as it was. With keeping
+ * on the aligned map starts empty (app.cpp:310 is not reached). The first process call after it
+ * runs without the drop test (getNbClouds() == 0, app.cpp:366-369) and its accepted reading is the
+ * next reference whatever the frequency (app.cpp:383-399); the overlap runs against the crop as
+ * against any reference. From the second reading on the session is an ordinary one. `map` is only
+ * read, and not needed after the call. */
+int aicp_hip_session_start_on_map(aicp_hip_ctx* ctx, aicp_hip_session* s, const aicp_hip_map* map,
+                                  const float first_pose[16], float crop_min, float crop_max);
+
 /* ---- kernel-level entry points (parity tests and diagnostics) --------------------------- */
 /* kd-tree over pts (as given, no centring) + k-NN of queries: libnabo
  * KDTreeUnbalancedPtInLeavesImplicitBoundsStackOpt order, ALLOW_SELF_MATCH.
@@ -1444,6 +1501,19 @@ int aicp_hip_test_monitor_resident(aicp_hip_ctx* ctx, const aicp_monitor_params*
                                    const float* ref_xyz, size_t n_ref, const float* read_xyz, size_t n_read,
                                    const float T[16], int32_t runs, aicp_monitor_result* result, uint64_t* dirty,
                                    uint64_t counters[4]);
+/* The live session's promotion kernels alone, on a made-up block. block (448 bytes, in and out):
+ * the stream state at 0 (initialT_ 16 floats, count int32 at 64), the record at 128 (status,
+ * accepted, append, refilter int32; corrected_origin 3 doubles at 144), the reference's header at
+ * 192 (count uint32, id int32, origin 3 doubles at 208), the gate's record at 256 (its int32 gate
+ * at 280), the correction T at 320 (16 floats), the prior origin at 384 (3 doubles). read4: n
+ * float4 points, taken as their bytes. kernel: 0 k_session_promote, 1 k_session_gate_promote,
+ * 2 k_session_promote_map, 3 k_session_gate_promote_map, each behind its production launch with
+ * the reference id `id`. ref4 (4 n floats out): the reference buffer; map4 (4 (tail + n) floats
+ * out): the map with its tail at `tail` points (kernels 0 and 1 are given no map). Both buffers and
+ * 64 guard words on each side of them are filled with 0xA5 bytes first; *dirty: guard words that
+ * changed, plus 1 when read4's bytes on the device changed. */
+int aicp_hip_test_promote_map(aicp_hip_ctx* ctx, int32_t kernel, const float* read4, size_t n, size_t tail,
+                              int32_t id, void* block, float* ref4, float* map4, uint64_t* dirty);
 
 #ifdef __cplusplus
 }
