@@ -73,6 +73,7 @@ EXPORTS = [
     "aicp_hip_mapsession_create_risk", "aicp_hip_mapsession_process_risk", "aicp_hip_mapsession_process_accum_risk",
     "aicp_hip_session_keep_aligned_map", "aicp_hip_session_aligned_map", "aicp_hip_session_take_aligned_map",
     "aicp_hip_mapsession_start_go_back", "aicp_hip_session_start_on_map", "aicp_hip_test_promote_map",
+    "aicp_hip_parse_pm_chain", "aicp_hip_chain_uniform", "aicp_hip_chain_filter", "aicp_hip_register_chain",
 ]
 
 
@@ -118,7 +119,9 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_mapsession_process_accum_risk",  # the live map sessions with the risk gate
            "aicp_hip_session_keep_aligned_map", "aicp_hip_session_aligned_map", "aicp_hip_session_take_aligned_map",
            "aicp_hip_mapsession_start_go_back", "aicp_hip_session_start_on_map",
-           "aicp_hip_test_promote_map"}  # the mapping session's built map, the go-back, the start on a map
+           "aicp_hip_test_promote_map",  # the mapping session's built map, the go-back, the start on a map
+           "aicp_hip_parse_pm_chain", "aicp_hip_chain_uniform", "aicp_hip_chain_filter",
+           "aicp_hip_register_chain"}  # the sampled chains
 
 
 class IcpConfig(C.Structure):
@@ -169,6 +172,75 @@ class Pair(C.Structure):
         ("ref_origin", C.c_double * 3),
         ("read_origin", C.c_double * 3),
     ]
+
+
+AICP_CHAIN_MAX_FILTERS = 4
+AICP_CHAIN_REFERENCE, AICP_CHAIN_READING = 0, 1
+AICP_FILTER_NONE, AICP_FILTER_SURFACE_NORMAL, AICP_FILTER_MIN_DIST = 0, 1, 2
+AICP_FILTER_RANDOM_SAMPLING, AICP_FILTER_MAX_DENSITY = 3, 4
+AICP_OUTLIER_TRIMMED_DIST, AICP_OUTLIER_MAX_DIST = 0, 1
+
+
+class ChainFilter(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("knn", C.c_int32),
+        ("keep_densities", C.c_int32),
+        ("dim", C.c_int32),
+        ("min_dist", C.c_float),
+        ("prob", C.c_float),
+        ("max_density", C.c_float),
+        ("pad", C.c_int32),
+    ]
+
+
+class Chain(C.Structure):
+    """aicp_chain: per side (reference, reading) a list of at most 4 data-point filters, the
+    outlier rule and the draws' seed. Chain() is "no filters, TrimmedDist"."""
+    _fields_ = [
+        ("filters", (ChainFilter * AICP_CHAIN_MAX_FILTERS) * 2),
+        ("n_filters", C.c_int32 * 2),
+        ("outlier", C.c_int32),
+        ("outlier_limit_d2", C.c_float),
+        ("seed", C.c_uint64),
+    ]
+
+    def add(self, side, kind, **kw):
+        """Appends a filter to a side's list: libpointmatcher's defaults, then the keywords."""
+        n = self.n_filters[side]
+        if n >= AICP_CHAIN_MAX_FILTERS:
+            raise ValueError("at most 4 filters on a side")
+        f = self.filters[side][n]
+        f.kind, f.knn, f.keep_densities, f.dim = kind, 5, 0, -1
+        f.min_dist, f.prob, f.max_density = 1.0, 0.75, 10.0
+        for k, v in kw.items():
+            if not hasattr(f, k):
+                raise AttributeError(f"aicp_chain_filter has no field {k}")
+            setattr(f, k, v)
+        self.n_filters[side] = n + 1
+        return self
+
+    def side(self, side):
+        """The side's list as dicts: the kind and the parameters that kind reads."""
+        names = {AICP_FILTER_SURFACE_NORMAL: ("knn", "keep_densities"), AICP_FILTER_MIN_DIST: ("dim", "min_dist"),
+                 AICP_FILTER_RANDOM_SAMPLING: ("prob",), AICP_FILTER_MAX_DENSITY: ("max_density",)}
+        out = []
+        for q in range(self.n_filters[side]):
+            f = self.filters[side][q]
+            out.append(dict(kind=f.kind, **{k: getattr(f, k) for k in names.get(f.kind, ())}))
+        return out
+
+
+class ChainStats(C.Structure):
+    _fields_ = [
+        ("n_in", C.c_uint64 * 2),
+        ("n_out", (C.c_uint64 * AICP_CHAIN_MAX_FILTERS) * 2),
+        ("n_kept", C.c_uint64 * 2),
+    ]
+
+    def as_dict(self):
+        return {"n_in": [int(x) for x in self.n_in], "n_out": [[int(x) for x in row] for row in self.n_out],
+                "n_kept": [int(x) for x in self.n_kept]}
 
 
 class PrefilterParams(C.Structure):
@@ -507,6 +579,13 @@ def _load():
     L.aicp_hip_default_config.argtypes = [cfgp]
     L.aicp_hip_default_config.restype = None
     L.aicp_hip_parse_pm_yaml.argtypes = [C.c_char_p, cfgp]
+    if hasattr(L, "aicp_hip_parse_pm_chain"):
+        chp = C.POINTER(Chain)
+        L.aicp_hip_parse_pm_chain.argtypes = [C.c_char_p, cfgp, chp]
+        L.aicp_hip_chain_uniform.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
+        L.aicp_hip_chain_uniform.restype = C.c_float
+        L.aicp_hip_chain_filter.argtypes = [vp, chp, C.c_int, fp, sz, sz, up, up, ip, fp, fp]
+        L.aicp_hip_register_chain.argtypes = [vp, cfgp, chp, pp, fp, stp, C.POINTER(ChainStats)]
     L.aicp_hip_replace_ratio_config_file.argtypes = [C.c_char_p, C.c_char_p, C.c_float]
     L.aicp_hip_autotune_ratio.argtypes = [C.c_float]
     L.aicp_hip_autotune_ratio.restype = C.c_float
@@ -816,6 +895,18 @@ def parse_pm_yaml(path: str):
     c = IcpConfig()
     rc = lib.aicp_hip_parse_pm_yaml(path.encode(), C.byref(c))
     return rc, c
+
+
+def parse_pm_chain(path: str):
+    """aicp_hip_parse_pm_chain: (rc, IcpConfig, Chain). The chain's seed is 0."""
+    c, ch = IcpConfig(), Chain()
+    rc = lib.aicp_hip_parse_pm_chain(path.encode(), C.byref(c), C.byref(ch))
+    return rc, c, ch
+
+
+def chain_uniform(seed: int, slot: int, i: int) -> float:
+    """aicp_hip_chain_uniform: the sampled chains' draw, k * 2^-24 in [0, 1)."""
+    return float(lib.aicp_hip_chain_uniform(int(seed), int(slot), int(i)))
 
 
 def autotune_ratio(overlap_percent: float) -> float:
@@ -1187,6 +1278,47 @@ class Context:
         st = IcpStats()
         self.check(lib.aicp_hip_register(self.h, C.byref(cfg), C.byref(p), _fptr(outT), C.byref(st)))
         return outT.reshape(4, 4).T.copy(), st.as_dict()
+
+    def chain_filter(self, chain, side, pts, indices=True, densities=False, normals=False):
+        """aicp_hip_chain_filter (DataPointsFilters::apply of one side's list): a dict with `n`
+        (kept points), `counts` (points after each filter of the list) and, as asked, `index` (the
+        kept points' input indices), `densities` (at the SurfaceNormal's position, for the cloud
+        there) and `normals` (of the kept points)."""
+        pts = as_points(pts)
+        n = pts.shape[0]
+        out_n = C.c_uint64()
+        counts = (C.c_uint64 * AICP_CHAIN_MAX_FILTERS)()
+        idx = np.zeros(n, np.int32) if indices else None
+        dens = np.zeros(n, np.float32) if densities else None
+        nrm = np.zeros((n, 3), np.float32) if normals else None
+        self.check(lib.aicp_hip_chain_filter(
+            self.h, C.byref(chain), int(side), _fptr(pts), n, pts.shape[1] * 4, C.byref(out_n), counts,
+            idx.ctypes.data_as(C.POINTER(C.c_int32)) if indices else None, _fptr(dens) if densities else None,
+            _fptr(nrm) if normals else None))
+        k = int(out_n.value)
+        nf = chain.n_filters[side]
+        out = {"n": k, "counts": [int(counts[q]) for q in range(nf)]}
+        if indices:
+            out["index"] = idx[:k].copy()
+        if densities:
+            # the cloud at the SurfaceNormal: what the filters before it left
+            sn = next(q for q in range(nf) if chain.filters[side][q].kind == AICP_FILTER_SURFACE_NORMAL)
+            out["densities"] = dens[:(out["counts"][sn - 1] if sn else n)].copy()
+        if normals:
+            out["normals"] = nrm[:k].copy()
+        return out
+
+    def register_chain(self, ref, read, cfg, chain, raise_on_error=True):
+        """aicp_hip_register_chain: both clouds through the chain's filters, then the ICP core on
+        what they leave. Returns (T 4x4 row-major, stats dict, chain stats dict, rc)."""
+        p, keep = make_pair(ref, read)
+        outT = np.zeros(16, np.float32)
+        st, cs = IcpStats(), ChainStats()
+        rc = lib.aicp_hip_register_chain(self.h, C.byref(cfg), C.byref(chain), C.byref(p), _fptr(outT), C.byref(st),
+                                         C.byref(cs))
+        if raise_on_error:
+            self.check(rc)
+        return outT.reshape(4, 4).T.copy(), st.as_dict(), cs.as_dict(), rc
 
     def overlap(self, ref, read, ref_origin=(0, 0, 0), read_origin=(0, 0, 0), resolution=0.2):
         """aicp_hip_overlap (computeOverlap + getOverlap for one pair): the overlap in percent."""

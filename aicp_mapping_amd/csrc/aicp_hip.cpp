@@ -513,7 +513,7 @@ double ev_ms(hipEvent_t a, hipEvent_t b) {
 }
 
 int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, double res,
-              int flags, float* outT, aicp_icp_stats* stats, float* out_overlap) {
+              int flags, float* outT, aicp_icp_stats* stats, float* out_overlap, const ChainRun* chain) {
   const auto t_start = std::chrono::steady_clock::now();
   int rc = check_cfg(ctx, cfg, flags);
   if (rc) return rc;
@@ -529,6 +529,10 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
   // PointToPointErrorMinimizer: no SurfaceNormal on the reference, so no raw-coordinate tree, no
   // normals kNN and no normals scatter; the matcher tree alone serves the loop
   const bool p2p = doIcp && cfg->knn_normals == 0;
+  // a sampled chain's reference (chain.cpp): its normals are given, in its input order, so as for
+  // point-to-point the matcher tree alone is built; they reach bnrm by one gather (below)
+  const bool given_nrm = doIcp && !p2p && chain && chain->ref_normals;
+  if (chain && (P != 1 || doOvl || rcache.use)) FAIL(AICP_ERR_UNSUPPORTED, "a chain runs one pair, without overlap or cache");
   hipStream_t s = ctx->stream;
   // the events that order this context's streams release at device scope; ev[1], which the host
   // waits on before it reads the key boxes copied to pinned memory, keeps the system-scope fence
@@ -687,7 +691,7 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
     // s3 (worker thread; it still polls its levels in a polled redo): centroid, centred
     // reference, matcher tree, pair frames
     const int plan1 = plan_levels(n_ref_max, ctx->tb[1], ctx->opt.tree_plan);
-    if (p2p) {
+    if (p2p || given_nrm) {
       // the matcher tree alone. s2 has no work of its own before the loop's set-up; it still
       // records the events that the later code and the phase times read (ev[13] is waited on only
       // by a matcher worker that is given it, below)
@@ -768,7 +772,10 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
     launch_prepare_read(s2, B->m_read, dDesc, readS, readc);
     // normals from the raw tree's bucket order into the matcher tree's bucket order (a cached
     // reference's are there already)
-    if (!p2p) {
+    if (given_nrm) {
+      launch_chain_gather_normals(s2, (uint32_t)B->total_ref, bpts, chain->ref_normals, bnrm);
+      launch_pairs_degenerate_part(s2, (int)P, dDesc, dState, nullptr, 2);  // (the count: chain->degenerate, below)
+    } else if (!p2p) {
       HIPC(ensure(ctx->inv, B->total_ref * 4));
       if (!hit_trees)
         launch_normals_to_matcher(s2, (int)R, (uint32_t)B->total_ref, dRdesc, bpts, ctx->bpts_raw.as<float4>(),
@@ -852,7 +859,9 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
         y.host_n = ctx->poll_dev + it + 1;
         if (polled(it + 1)) pending.push_back(it + 1);
       }
-      if (sel_pair)
+      if (chain && chain->max_dist)
+        launch_chain_select_maxdist(s, (int)P, dState, chain->limit_d2);
+      else if (sel_pair)
         launch_icp_select_pair(s, (int)P, dDesc, dState, ctx->d2.as<float>(), ctx->sel_cand.as<uint32_t>(), y);
       else if (sel_ff > 0 && it >= sel_ff)
         launch_icp_select_fused(s, B->m_sel, dDesc, dState, ctx->d2.as<float>(), ctx->sel_hist.as<uint32_t>(),
@@ -885,7 +894,7 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
   HIPC(hipStreamSynchronize(s));
   if (doIcp && !hit_trees) {  // planned tree builds: errors recorded on the device
     rcache.trees = false;
-    rc = p2p ? AICP_OK : device_trees_check(ctx->tb[0], ctx->err);  // (no raw tree was built)
+    rc = p2p || given_nrm ? AICP_OK : device_trees_check(ctx->tb[0], ctx->err);  // (no raw tree was built)
     if (!rc) rc = device_trees_check(ctx->tb[1], ctx->err);
     if (rc) return rc;
     if (ctx->tl_total && (ctx->tb[1].pin_ctl.as<TreeCtl>()->error & 4))
@@ -919,7 +928,7 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
       o.status = status;
       o.iterations = st.iters;
       o.converged = st.converged;
-      o.degenerate_normals = st.degenerate;
+      o.degenerate_normals = given_nrm ? chain->degenerate : st.degenerate;
       o.inlier_ratio = st.inlier_ratio;
       o.trimmed_ratio = st.ratio;
       o.overlap_percent = st.overlap;
@@ -1088,6 +1097,8 @@ void aicp_hip_destroy(aicp_hip_ctx* ctx) {
   release(ctx->refc.gst);
   release(ctx->pin_crop);
   release(ctx->pin_maps);
+  for (auto& c : ctx->chain) c.release_all();
+  release(ctx->pin_chain);
   if (ctx->poll_host) (void)hipHostFree(ctx->poll_host);
   delete ctx->pool;
   seq_state_free(ctx->seq);

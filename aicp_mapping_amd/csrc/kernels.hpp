@@ -156,6 +156,47 @@ void launch_crop_scatter_multi(hipStream_t s, int n, int n_crops, const void* ar
                                const uint32_t* tile_off, const uint32_t* base_of, float4* out);
 void launch_solve6(hipStream_t s, const double* A, const double* b, double* x, int32_t* path);
 
+// ---- sampled chains (kernels_chain.hip, chain.cpp): data-point filters, MaxDist select -------
+constexpr int kChainMaxFilters = 4;  // AICP_CHAIN_MAX_FILTERS
+constexpr int kChainMinDist = 2, kChainRandom = 3, kChainMaxDensity = 4;  // AICP_FILTER_*
+struct ChainCtl {  // one side's control block on the device
+  uint32_t n[kChainMaxFilters + 1];  // points of the cloud as given, then after each filter of the list
+  uint32_t max_bits, n_sat;          // MaxDensity: lastDensity (float bits), nbSaturated
+  uint32_t degenerate;               // SurfaceNormal's rank-deficient points
+};
+struct ChainFilterArgs {
+  int32_t kind, pos;  // pos: the filter's position in its list (it receives ctl->n[pos] points)
+  int32_t dim;
+  float min_dist, prob, max_density;
+  uint32_t slot;      // of the draw: 4 * side + pos
+  uint32_t pad;
+  uint64_t seed;
+};
+size_t chain_tiles(size_t n);
+// pts[i].w = i for the n uploaded points; ctl = {n, 0, ...}
+void launch_chain_begin(hipStream_t s, uint32_t n, float4* pts, ChainCtl* ctl);
+// a filter that keeps every point (SurfaceNormal): ctl->n[pos + 1] = ctl->n[pos]; st (nullable):
+// the state launch_normals counted the degenerate points in
+void launch_chain_pass(hipStream_t s, int pos, ChainCtl* ctl, const PairState* st);
+// One MinDist / RandomSampling / MaxDensity filter on the ctl->n[a.pos] rows of pts: the kept rows
+// to out in input order, with their normals and densities (carried where nrm_out / dens_out is
+// given, from nrm / dens; dens alone serves the MaxDensity's own test), the kept count to
+// ctl->n[a.pos + 1]. cap: the points of the cloud as given (sizes every array; flag: cap bytes;
+// tile_cnt / tile_off: chain_tiles(cap) words). MaxDensity reads dens.
+void launch_chain_filter(hipStream_t s, uint32_t cap, const ChainFilterArgs& a, ChainCtl* ctl, uint8_t* flag,
+                         uint32_t* tile_cnt, uint32_t* tile_off, const float4* pts, float4* out, const float4* nrm,
+                         float4* nrm_out, const float* dens, float* dens_out);
+// SurfaceNormal's outputs of an n-point cloud's raw tree (bpts; ids: launch_knn_ids / launch_normals;
+// bnrm: launch_normals, read only with nrm) into the cloud's order: nrm, dens (each nullable)
+bool launch_chain_sn_out(hipStream_t s, uint32_t n, int knn, const float4* bpts, const int32_t* ids, const float4* bnrm,
+                         float4* nrm, float* dens);
+// bnrm[j] = given[input id of bpts[j]] for the n points of one reference's matcher tree
+void launch_chain_gather_normals(hipStream_t s, uint32_t n, const float4* bpts, const float4* given, float4* bnrm);
+// out[i] = (x, y, z, 1) of in[i]: filtered rows as upload_pairs stores a cloud
+void launch_chain_rows(hipStream_t s, uint32_t n, const float4* in, float4* out);
+// MaxDistOutlierFilter: st[p].limit = limit_d2 for the active pairs (the trimmed select's output)
+void launch_chain_select_maxdist(hipStream_t s, int n_pairs, PairState* st, float limit_d2);
+
 // ---- sweep accumulator (kernels_accum.hip): VelodyneAccumulatorROS::processLidar ---------------
 struct AccumSweep {
   CropBoxArgs box;  // identity frame, crop_min / crop_max (velodyne_accumulator.cpp:59-60)

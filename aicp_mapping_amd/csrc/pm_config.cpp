@@ -3,6 +3,8 @@
 //   aicp_hip_parse_pm_yaml            the libpointmatcher chain subset loaded by
 //                                     PointmatcherRegistration::applyConfig
 //                                     (pointmatcher_registration.cpp:48-68, icp_.loadFromYaml)
+//   aicp_hip_parse_pm_chain           the same files with their data-point filter lists and the
+//                                     MaxDist outlier rule
 //   aicp_hip_replace_ratio_config_file fileIO.cpp:179-214 (text rewrite, byte for byte)
 //   aicp_hip_autotune_ratio           app.cpp:197-205 + the ostream/lexical_cast round trip
 //
@@ -20,6 +22,7 @@
 #include <vector>
 
 #include "../../include/aicp_hip.h"
+#include "chain_draw.hpp"
 
 namespace {
 
@@ -219,6 +222,50 @@ bool single(const Y* y, std::string& name, const Y*& params) {
 
 const Y* param(const Y* params, const char* k) { return params ? params->get(k) : nullptr; }
 
+// One data-point filter of a side's list into the chain (aicp_hip_parse_pm_chain): its values,
+// libpointmatcher's defaults where the file names none, and the checks of DESIGN §4.8.
+// have_densities: a SurfaceNormal with keepDensities: 1 came earlier on this side.
+int chain_filter_item(const std::string& name, const Y* prm, aicp_chain* ch, int side, bool& have_densities) {
+  int32_t& n = ch->n_filters[side];
+  aicp_chain_filter f;
+  std::memset(&f, 0, sizeof(f));
+  if (name == "SurfaceNormalDataPointsFilter") {
+    for (int q = 0; q < n; ++q)
+      if (ch->filters[side][q].kind == AICP_FILTER_SURFACE_NORMAL) return AICP_ERR_UNSUPPORTED;
+    f.kind = AICP_FILTER_SURFACE_NORMAL;
+    f.knn = 5;
+    to_int(param(prm, "knn"), f.knn);
+    to_int(param(prm, "keepDensities"), f.keep_densities);
+    f.keep_densities = f.keep_densities ? 1 : 0;
+    if (f.keep_densities) have_densities = true;
+  } else if (name == "MinDistDataPointsFilter") {
+    f.kind = AICP_FILTER_MIN_DIST;
+    f.dim = -1;
+    f.min_dist = 1.f;
+    to_int(param(prm, "dim"), f.dim);
+    to_float(param(prm, "minDist"), f.min_dist);
+    if (f.dim < -1 || f.dim > 2) return AICP_ERR_INVALID;
+  } else if (name == "RandomSamplingDataPointsFilter") {
+    f.kind = AICP_FILTER_RANDOM_SAMPLING;
+    f.prob = 0.75f;
+    to_float(param(prm, "prob"), f.prob);
+    if (!(f.prob >= 0.f && f.prob <= 1.f)) return AICP_ERR_INVALID;
+  } else if (name == "MaxDensityDataPointsFilter") {
+    f.kind = AICP_FILTER_MAX_DENSITY;
+    f.max_density = 10.f;
+    to_float(param(prm, "maxDensity"), f.max_density);
+    if (!(f.max_density > 0.f)) return AICP_ERR_INVALID;
+    if (!have_densities) return AICP_ERR_INVALID;  // libpointmatcher: InvalidField (no "densities" descriptor)
+  } else {
+    return AICP_ERR_UNSUPPORTED;
+  }
+  if (n >= AICP_CHAIN_MAX_FILTERS) return AICP_ERR_UNSUPPORTED;
+  ch->filters[side][n++] = f;
+  return AICP_OK;
+}
+
+int parse_pm_file(const char* path, aicp_icp_config* out, aicp_chain* chain);
+
 }  // namespace
 
 extern "C" {
@@ -239,6 +286,23 @@ void aicp_hip_default_config(aicp_icp_config* c) {
 
 int aicp_hip_parse_pm_yaml(const char* path, aicp_icp_config* out) {
   if (!path || !out) return AICP_ERR_INVALID;
+  return parse_pm_file(path, out, nullptr);
+}
+
+int aicp_hip_parse_pm_chain(const char* path, aicp_icp_config* out, aicp_chain* chain) {
+  if (!path || !out || !chain) return AICP_ERR_INVALID;
+  return parse_pm_file(path, out, chain);
+}
+
+float aicp_hip_chain_uniform(uint64_t seed, uint32_t slot, uint32_t i) { return aicp::chain_uniform(seed, slot, i); }
+
+}  // extern "C"
+
+namespace {
+
+// chain == nullptr: aicp_hip_parse_pm_yaml, which refuses every data-point filter but SurfaceNormal
+// and every outlier filter but TrimmedDist
+int parse_pm_file(const char* path, aicp_icp_config* out, aicp_chain* chain) {
   std::ifstream f(path);
   if (!f.good()) return AICP_ERR_INVALID;  // "Cannot open config file" -> exit(1)
   std::vector<Line> L = lex(f);
@@ -260,13 +324,25 @@ int aicp_hip_parse_pm_yaml(const char* path, aicp_icp_config* out) {
   bool haveRefNormals = false, haveCounter = false, haveDifferential = false;
   bool pointToPoint = false, refNormalsDropped = false;
   std::vector<std::pair<std::string, const Y*>> items;
+  aicp_chain ch;
+  std::memset(&ch, 0, sizeof(ch));
+  bool sampled = false;  // the file holds an element that only the chain parser serves
 
   for (auto& kv : root.map) {
     const std::string& key = kv.first;
     const Y* v = &kv.second;
     if (key == "readingDataPointsFilters" || key == "referenceDataPointsFilters") {
       if (!list_items(v, items)) return AICP_ERR_INVALID;
+      const int side = key == "referenceDataPointsFilters" ? AICP_CHAIN_REFERENCE : AICP_CHAIN_READING;
+      bool haveDensities = false;
       for (auto& it : items) {
+        if (chain) {
+          if (const int rc = chain_filter_item(it.first, it.second, &ch, side, haveDensities)) return rc;
+          if (it.first != "SurfaceNormalDataPointsFilter") {
+            sampled = true;
+            continue;
+          }
+        }
         if (it.first != "SurfaceNormalDataPointsFilter") return AICP_ERR_UNSUPPORTED;
         float eps = 0;
         if (to_float(param(it.second, "epsilon"), eps) && eps != 0.f) return AICP_ERR_UNSUPPORTED;
@@ -296,6 +372,16 @@ int aicp_hip_parse_pm_yaml(const char* path, aicp_icp_config* out) {
       if (c.knn_match != 1) return AICP_ERR_UNSUPPORTED;
     } else if (key == "outlierFilters") {
       if (!list_items(v, items)) return AICP_ERR_INVALID;
+      if (chain && items.size() == 1 && items[0].first == "MaxDistOutlierFilter") {
+        float maxDist = 1.f;
+        to_float(param(items[0].second, "maxDist"), maxDist);
+        // a finite limit: with +inf the readings without a match (d2 = inf) would pass d2 <= limit
+        if (!(maxDist >= 0.f) || !std::isfinite(maxDist)) return AICP_ERR_INVALID;
+        ch.outlier = AICP_OUTLIER_MAX_DIST;
+        ch.outlier_limit_d2 = maxDist;  // libpointmatcher 1.2.x: compared with the squared distance as written
+        sampled = true;
+        continue;
+      }
       if (items.size() != 1 || items[0].first != "TrimmedDistOutlierFilter") return AICP_ERR_UNSUPPORTED;
       to_float(param(items[0].second, "ratio"), c.trimmed_ratio);
     } else if (key == "errorMinimizer") {
@@ -350,9 +436,29 @@ int aicp_hip_parse_pm_yaml(const char* path, aicp_icp_config* out) {
     c.min_diff_trans = -1.f;
     c.smooth_length = 1;
   }
+  if (chain && sampled) {
+    // a SurfaceNormal whose output is used (a point-to-plane reference's normals, the densities
+    // of a later MaxDensity) runs on the device's kNN: knn 10, 20 or 30. A file without the new
+    // elements keeps aicp_hip_parse_pm_yaml's answer; the registration calls check its knn.
+    for (int side = 0; side < 2; ++side) {
+      bool consumed = side == AICP_CHAIN_REFERENCE && !pointToPoint;
+      const aicp_chain_filter* sn = nullptr;
+      for (int q = 0; q < ch.n_filters[side]; ++q) {
+        const aicp_chain_filter& f = ch.filters[side][q];
+        if (f.kind == AICP_FILTER_SURFACE_NORMAL) sn = &f;
+        if (f.kind == AICP_FILTER_MAX_DENSITY) consumed = true;
+      }
+      if (sn && consumed && sn->knn != 10 && sn->knn != 20 && sn->knn != 30) return AICP_ERR_UNSUPPORTED;
+    }
+  }
   *out = c;
+  if (chain) *chain = ch;
   return AICP_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int aicp_hip_replace_ratio_config_file(const char* in_file, const char* out_file, float ratio) {
   if (!in_file || !out_file) return AICP_ERR_INVALID;

@@ -393,8 +393,28 @@ inline bool valid_cloud(const aicp_cloud& c) {
 // the batch pipeline (aicp_hip.cpp), for the entry points that compose a batch on the device
 int upload_pairs(aicp_hip_ctx* ctx, const aicp_pair* pairs, size_t n, aicp_hip_batch* B, bool refs_on_device,
                  bool skip_refs = false, bool skip_reads = false, bool nosync = false);
+// What a sampled chain (chain.cpp) adds to a one-pair run_batch; without it run_batch
+// does what it did before there were chains.
+struct ChainRun {
+  // the one reference's normals, in its input order on the device (SurfaceNormal ran earlier in
+  // the chain, on the cloud before the later filters): they replace raw tree -> kNN ->
+  // k_scatter_normals by one gather through the matcher tree's input index. nullptr: not given
+  const float4* ref_normals = nullptr;
+  int32_t degenerate = 0;  // their rank-deficient count (aicp_icp_stats::degenerate_normals)
+  bool max_dist = false;   // MaxDistOutlierFilter: the select step writes limit_d2
+  float limit_d2 = 0.f;
+};
 int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, double res, int flags, float* outT,
-              aicp_icp_stats* stats, float* out_overlap);
+              aicp_icp_stats* stats, float* out_overlap, const ChainRun* chain = nullptr);
+// one side's buffers of the sampled chains (chain.cpp): the cloud and its descriptors ping-pong
+// between two sets as the filters compact them
+struct ChainBufs {
+  DevBuf pts[2], nrm[2], dens[2], dens_sn, flag, tile_cnt, tile_off, ctl;
+  void release_all() {
+    for (DevBuf* b : {&pts[0], &pts[1], &nrm[0], &nrm[1], &dens[0], &dens[1], &dens_sn, &flag, &tile_cnt, &tile_off, &ctl})
+      release(*b);
+  }
+};
 void free_batch(aicp_hip_batch* B);
 // the batch's overlap after its key boxes (overlap.cpp): voxel maps, or sorted key words where they do not fit
 int overlap_maps(aicp_hip_ctx* ctx, aicp_hip_batch* B, size_t P, size_t G, PairDesc* dDesc, PairState* dState,
@@ -603,6 +623,8 @@ struct aicp_hip_ctx {
   aicp::rt::DevBuf isync;              // fused ICP iteration: arrival counters (icp_sync_words)
   aicp::rt::PinBuf pin_crop;
   aicp::rt::PinBuf pin_maps;  // upload_pairs' block maps
+  aicp::rt::ChainBufs chain[2];  // the sampled chains' filtered clouds: [reference], [reading] (chain.cpp)
+  aicp::rt::PinBuf pin_chain;    // their control blocks read back
   aicp::rt::RefCache refc;  // the drop-in path's resident reference (runtime.hpp)
   aicp::rt::OvlProbe ovl_probe;  // aicp_hip_test_overlap (off in every other call)
   aicp::rt::ReadCache rdc;  // and its last reading

@@ -92,6 +92,9 @@ class HipRegistration(AbstractRegistrator):
         self.params_ = params
         self._ctx = ctx
         self.cfg = _lib.default_config()
+        self.chain = None  # the chain file's filter lists, when it has sampling filters or MaxDist
+        self.chain_seed = 0  # seed of their draws: the same seed gives the same sample on every call
+        self.chain_stats = None
         self.stats = None
         self.monitor = None  # the quality monitor's result of the last registration (printOutputStatistics)
         self._read = None
@@ -103,6 +106,14 @@ class HipRegistration(AbstractRegistrator):
             # icp_.setDefault() uses RandomSampling / SamplingSurfaceNormal: not in this core
             raise _lib.AicpError(_lib.AICP_ERR_UNSUPPORTED, "empty chain file (setDefault) unsupported")
         rc, cfg = _lib.parse_pm_yaml(path)
+        self.chain = None
+        if rc == _lib.AICP_ERR_UNSUPPORTED:
+            # a sampled chain (MinDist / RandomSampling / MaxDensity filters, MaxDistOutlierFilter):
+            # served by register_chain, its draws seeded with chain_seed
+            rc, cfg, chain = _lib.parse_pm_chain(path)
+            if rc == _lib.AICP_OK:
+                chain.seed = int(self.chain_seed)
+                self.chain = chain
         if rc == _lib.AICP_ERR_INVALID:
             print(f"[Pointmatcher] Cannot open config file {path}", file=sys.stderr)
             sys.exit(1)
@@ -131,8 +142,13 @@ class HipRegistration(AbstractRegistrator):
         if ref.shape[1] == 12 or read.shape[1] == 12:
             return final_transform
         self.applyConfig()
-        T, stats, rc = self.ctx.align_batch([dict(ref=ref, read=read)], self.cfg, flags=AICP_RUN_ICP,
-                                            raise_on_error=False)
+        if self.chain is not None:
+            T1, st1, self.chain_stats, rc = self.ctx.register_chain(ref, read, self.cfg, self.chain,
+                                                                    raise_on_error=False)
+            T, stats = T1[None], [st1]
+        else:
+            T, stats, rc = self.ctx.align_batch([dict(ref=ref, read=read)], self.cfg, flags=AICP_RUN_ICP,
+                                                raise_on_error=False)
         self.stats = stats[0]
         if rc != _lib.AICP_OK:
             self.ctx.check(rc)

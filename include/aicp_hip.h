@@ -186,6 +186,96 @@ int aicp_hip_replace_ratio_config_file(const char* in_path, const char* out_path
  * round trip of replaceRatioConfigFile + lexical_cast<float>. */
 float aicp_hip_autotune_ratio(float overlap_percent);
 
+/* ---- sampled chains: the data-point filters and the MaxDist outlier rule -------
+ * What a chain file holds beside aicp_icp_config: per side an ordered list of data-point filters,
+ * and the outlier rule. An all-zero aicp_chain means "no filters, TrimmedDist". Rules are those of
+ * libpointmatcher 1.2.x; every filter keeps the order of the points it keeps.
+ *   SurfaceNormal   knn in {10, 20, 30} where its output is used (normals of a point-to-plane
+ *                   reference, densities of a later MaxDensity); keep_densities as keepDensities
+ *   MinDist         dim -1: keep sqrtf((x*x + y*y) + z*z) > fabsf(min_dist); dim 0..2: keep
+ *                   fabsf(coord[dim]) > min_dist
+ *   RandomSampling  every point draws r; keep r < prob
+ *   MaxDensity      density <= max_density: kept without a draw; else keep r < max_density /
+ *                   density, times (1 - nbSaturated / nbPointsIn) in integer division for the
+ *                   points whose density equals the cloud's maximum
+ * The draw is r = aicp_hip_chain_uniform(seed, slot, i): slot = 4 * side + the filter's position
+ * in its list, i = the point's index in the cloud as that filter receives it. It is a pure function:
+ * the same seed gives the same sample on every call, on the host and on the device; a caller who
+ * wants fresh samples changes the seed. (libpointmatcher draws std::rand(), which the reference
+ * reseeds from the clock in every pre-filter, so its own samples cannot be reproduced.) */
+#define AICP_CHAIN_MAX_FILTERS 4
+#define AICP_CHAIN_REFERENCE 0
+#define AICP_CHAIN_READING 1
+#define AICP_FILTER_NONE 0
+#define AICP_FILTER_SURFACE_NORMAL 1
+#define AICP_FILTER_MIN_DIST 2
+#define AICP_FILTER_RANDOM_SAMPLING 3
+#define AICP_FILTER_MAX_DENSITY 4
+#define AICP_OUTLIER_TRIMMED_DIST 0 /* limit: the quantile cfg->trimmed_ratio of the finite d2 */
+#define AICP_OUTLIER_MAX_DIST 1     /* limit: outlier_limit_d2 */
+typedef struct {
+  int32_t kind;           /* AICP_FILTER_* */
+  int32_t knn;            /* SurfaceNormal.knn                      (5)    */
+  int32_t keep_densities; /* SurfaceNormal.keepDensities            (0)    */
+  int32_t dim;            /* MinDist.dim: -1 radius, 0 / 1 / 2 axis (-1)   */
+  float min_dist;         /* MinDist.minDist                        (1)    */
+  float prob;             /* RandomSampling.prob                    (0.75) */
+  float max_density;      /* MaxDensity.maxDensity                  (10)   */
+  int32_t pad;
+} aicp_chain_filter;
+typedef struct {
+  aicp_chain_filter filters[2][AICP_CHAIN_MAX_FILTERS]; /* [AICP_CHAIN_REFERENCE], [_READING] */
+  int32_t n_filters[2];
+  int32_t outlier;        /* AICP_OUTLIER_* */
+  /* MaxDist: a pair is kept when its squared matcher distance d2 <= outlier_limit_d2. The parser
+   * stores MaxDistOutlierFilter.maxDist as written: libpointmatcher 1.2.x compares the matcher's
+   * squared distance with the parameter itself. Later versions square the parameter; a caller who
+   * wants that rule stores maxDist * maxDist here. */
+  float outlier_limit_d2;
+  uint64_t seed;          /* of the draws; the parser sets 0 */
+} aicp_chain;
+typedef struct {
+  uint64_t n_in[2];                            /* points of the reference / the reading as given */
+  uint64_t n_out[2][AICP_CHAIN_MAX_FILTERS];   /* points after each filter of the side's list   */
+  uint64_t n_kept[2];                          /* points the ICP core ran on                     */
+} aicp_chain_stats;
+/* As aicp_hip_parse_pm_yaml, with the filter lists and the outlier rule in *chain. Accepts every
+ * file that call accepts (same aicp_icp_config; the chain then holds at most the SurfaceNormal
+ * entries) and MinDist / RandomSampling / MaxDensity data-point filters and MaxDistOutlierFilter.
+ * AICP_ERR_INVALID: MaxDensity with no earlier SurfaceNormal with keepDensities: 1 on its side,
+ * prob outside [0, 1], maxDensity <= 0, dim outside {-1, 0, 1, 2}, a MaxDistOutlierFilter.maxDist
+ * that is negative or not finite (the registration call checks outlier_limit_d2 the same way: a
+ * reading without a match has d2 = inf, which an infinite limit would keep). AICP_ERR_UNSUPPORTED: more than
+ * 4 filters or two SurfaceNormals on a side, a file with one of the new elements whose used
+ * SurfaceNormal has knn outside {10, 20, 30}, and whatever aicp_hip_parse_pm_yaml refuses beyond
+ * the elements named here (SamplingSurfaceNormal among them). */
+int aicp_hip_parse_pm_chain(const char* path, aicp_icp_config* out, aicp_chain* chain);
+/* The filters' draw: k * 2^-24 with k in [0, 2^24), so exact in float and in [0, 1). */
+float aicp_hip_chain_uniform(uint64_t seed, uint32_t slot, uint32_t i);
+/* DataPointsFilters::apply of one side's list (side: AICP_CHAIN_REFERENCE / _READING) on one
+ * cloud. The filtered cloud stays on the device; the host gets the kept count, the count after
+ * each filter, and through nullable pointers: the kept points' input indices (ascending; capacity
+ * n), the densities at the SurfaceNormal's position in the order of the cloud there (capacity n;
+ * only with keep_densities), and the kept points' normals (3 floats each, capacity n; only with a
+ * SurfaceNormal of knn 10 / 20 / 30: they are the normals of the cloud at the SurfaceNormal's
+ * position, carried through the later filters). A cloud that a filter empties is AICP_OK with
+ * *out_n = 0. Invalidates the context's reference cache. */
+int aicp_hip_chain_filter(aicp_hip_ctx* ctx, const aicp_chain* chain, int side, const float* pts, size_t n,
+                          size_t stride, uint64_t* out_n, uint64_t out_counts[AICP_CHAIN_MAX_FILTERS],
+                          int32_t* out_index /* nullable */, float* out_densities /* nullable */,
+                          float* out_normals /* nullable */);
+/* Filters both clouds of the pair, then runs the ICP core on the filtered clouds where they lie on
+ * the device. A reference whose list has a SurfaceNormal hands the core the normals computed at
+ * that position (those of the cloud before the later filters); the matcher tree is built over the
+ * survivors. stats->inlier_ratio is over the filtered reading. A side left without a point:
+ * AICP_ERR_CONVERGENCE, the side named in aicp_hip_last_error. A chain with no filter but
+ * SurfaceNormal and the TrimmedDist rule gives aicp_hip_register's bits (reference cache off).
+ * The call neither uses nor keeps the reference cache, and drops it. Chains are served here only:
+ * the batch, multi-GPU, stream and session calls take aicp_icp_config alone. */
+int aicp_hip_register_chain(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_chain* chain,
+                            const aicp_pair* pair, float out_T[16], aicp_icp_stats* stats /* nullable */,
+                            aicp_chain_stats* chain_stats /* nullable */);
+
 /* ---- registration / overlap (host buffers) ---------------------------------------------- */
 int aicp_hip_register(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_pair* pair,
                       float out_T[16], aicp_icp_stats* stats /* nullable */);
