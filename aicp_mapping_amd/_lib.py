@@ -74,6 +74,7 @@ EXPORTS = [
     "aicp_hip_session_keep_aligned_map", "aicp_hip_session_aligned_map", "aicp_hip_session_take_aligned_map",
     "aicp_hip_mapsession_start_go_back", "aicp_hip_session_start_on_map", "aicp_hip_test_promote_map",
     "aicp_hip_parse_pm_chain", "aicp_hip_chain_uniform", "aicp_hip_chain_filter", "aicp_hip_register_chain",
+    "aicp_hip_align_chain_batch", "aicp_hip_test_chain_batch",
 ]
 
 
@@ -121,7 +122,8 @@ _NEWEST = {"aicp_hip_reference_cache_stats", "aicp_hip_default_options", "aicp_h
            "aicp_hip_mapsession_start_go_back", "aicp_hip_session_start_on_map",
            "aicp_hip_test_promote_map",  # the mapping session's built map, the go-back, the start on a map
            "aicp_hip_parse_pm_chain", "aicp_hip_chain_uniform", "aicp_hip_chain_filter",
-           "aicp_hip_register_chain"}  # the sampled chains
+           "aicp_hip_register_chain",  # the sampled chains
+           "aicp_hip_align_chain_batch", "aicp_hip_test_chain_batch"}  # and their batch form
 
 
 class IcpConfig(C.Structure):
@@ -586,6 +588,11 @@ def _load():
         L.aicp_hip_chain_uniform.restype = C.c_float
         L.aicp_hip_chain_filter.argtypes = [vp, chp, C.c_int, fp, sz, sz, up, up, ip, fp, fp]
         L.aicp_hip_register_chain.argtypes = [vp, cfgp, chp, pp, fp, stp, C.POINTER(ChainStats)]
+    if hasattr(L, "aicp_hip_align_chain_batch"):
+        L.aicp_hip_align_chain_batch.argtypes = [vp, cfgp, C.POINTER(Chain), pp, sz, C.c_double, C.c_int, fp, stp,
+                                                 C.POINTER(ChainStats)]
+        L.aicp_hip_test_chain_batch.argtypes = [vp, C.POINTER(Chain), C.c_int32, sz, C.POINTER(C.c_uint32), fp, up, up,
+                                                ip, fp, fp]
     L.aicp_hip_replace_ratio_config_file.argtypes = [C.c_char_p, C.c_char_p, C.c_float]
     L.aicp_hip_autotune_ratio.argtypes = [C.c_float]
     L.aicp_hip_autotune_ratio.restype = C.c_float
@@ -1319,6 +1326,65 @@ class Context:
         if raise_on_error:
             self.check(rc)
         return outT.reshape(4, 4).T.copy(), st.as_dict(), cs.as_dict(), rc
+
+    def align_chain_batch(self, pairs, cfg, chain, resolution=0.2, flags=AICP_RUN_ICP, raise_on_error=True):
+        """aicp_hip_align_chain_batch: register_chain for every pair of `pairs` (dicts as align_batch
+        takes them) in one call; with AICP_RUN_OVERLAP the overlap of the clouds as given sets each
+        pair's ratio. Pairs that pass the same `ref` array share it. Returns (T[n,4,4] row-major,
+        list of stats dicts, list of chain stats dicts, rc)."""
+        arr = (Pair * len(pairs))()
+        keep = []
+        refs = {}  # the same array object -> one packed copy, so that the pointers are equal too
+        for i, pr in enumerate(pairs):
+            if id(pr["ref"]) not in refs:
+                refs[id(pr["ref"])] = as_points(pr["ref"])
+            ref = refs[id(pr["ref"])]
+            p, k = make_pair(ref, pr["read"], pr.get("ref_origin", (0, 0, 0)), pr.get("read_origin", (0, 0, 0)),
+                             pr.get("init_T"))
+            arr[i] = p
+            keep.append((k, pr["ref"]))
+        outT = np.zeros((len(pairs), 16), np.float32)
+        st = (IcpStats * len(pairs))()
+        cs = (ChainStats * len(pairs))()
+        rc = lib.aicp_hip_align_chain_batch(self.h, C.byref(cfg), C.byref(chain), arr, len(pairs), float(resolution),
+                                            int(flags), _fptr(outT), st, cs)
+        if raise_on_error:
+            self.check(rc)
+        T = outT.reshape(-1, 4, 4).transpose(0, 2, 1).copy()
+        return T, [s.as_dict() for s in st], [c.as_dict() for c in cs], rc
+
+    def test_chain_batch(self, chain, side, clouds, normals=False, densities=False):
+        """aicp_hip_test_chain_batch: one side's list over the clouds at once. Returns one dict per
+        cloud, as chain_filter's: n, counts, index and, as asked, normals and densities."""
+        clouds = [as_points(c) for c in clouds]
+        counts = np.array([len(c) for c in clouds], np.uint32)
+        pts = np.ascontiguousarray(np.concatenate([c[:, :3] for c in clouds]), np.float32)
+        total, nc = len(pts), len(clouds)
+        oc = np.zeros(4 * nc, np.uint64)
+        on = np.zeros(nc, np.uint64)
+        idx = np.zeros(total, np.int32)
+        nrm = np.zeros((total, 3), np.float32) if normals else None
+        dens = np.zeros(total, np.float32) if densities else None
+        self.check(lib.aicp_hip_test_chain_batch(
+            self.h, C.byref(chain), int(side), nc, counts.ctypes.data_as(C.POINTER(C.c_uint32)), _fptr(pts),
+            oc.ctypes.data_as(C.POINTER(C.c_uint64)), on.ctypes.data_as(C.POINTER(C.c_uint64)),
+            idx.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(nrm) if normals else None,
+            _fptr(dens) if densities else None))
+        nf = chain.n_filters[side]
+        sn = next((q for q in range(nf) if chain.filters[side][q].kind == AICP_FILTER_SURFACE_NORMAL), None)
+        out, k, kd = [], 0, 0
+        for c in range(nc):
+            n = int(on[c])
+            d = {"n": n, "counts": [int(oc[4 * c + q]) for q in range(nf)], "index": idx[k:k + n].copy()}
+            if normals:
+                d["normals"] = nrm[k:k + n].copy()
+            if densities:
+                m = d["counts"][sn - 1] if sn else int(counts[c])
+                d["densities"] = dens[kd:kd + m].copy()
+                kd += m
+            k += n
+            out.append(d)
+        return out
 
     def overlap(self, ref, read, ref_origin=(0, 0, 0), read_origin=(0, 0, 0), resolution=0.2):
         """aicp_hip_overlap (computeOverlap + getOverlap for one pair): the overlap in percent."""

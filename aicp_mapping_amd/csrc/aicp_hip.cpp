@@ -133,8 +133,12 @@ int check_cfg(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, int flags) {
 // serves every reading of the call): not packed, not uploaded.
 // nosync: the caller synchronises the stream before the pinned staging is written again (a one-shot
 // call does, at its end); otherwise this returns once the copies are done
+// ref_ids (nullable; with skip_refs, whose references are not read): pair i's reference is number
+// ref_ids[i], and pairs with the same number share it; the ref pointers are then neither compared
+// nor read (they may be null)
 int upload_pairs(aicp_hip_ctx* ctx, const aicp_pair* pairs, size_t n, aicp_hip_batch* B, bool refs_on_device,
-                 bool skip_refs, bool skip_reads, bool nosync) {
+                 bool skip_refs, bool skip_reads, bool nosync, const int32_t* ref_ids) {
+  if (ref_ids && !skip_refs) FAIL(AICP_ERR_INVALID, "reference numbers without skip_refs");
   if (!pairs || n == 0) FAIL(AICP_ERR_INVALID, "no pairs");
   B->P = n;
   B->desc.assign(n, PairDesc{});
@@ -148,12 +152,19 @@ int upload_pairs(aicp_hip_ctx* ctx, const aicp_pair* pairs, size_t n, aicp_hip_b
   std::vector<size_t> rep;  // representative pair of each distinct reference
   for (size_t i = 0; i < n; ++i) {
     const aicp_pair& p = pairs[i];
-    if (!valid_pair(p)) FAIL(AICP_ERR_INVALID, "invalid pair " + std::to_string(i));
+    if (ref_ids) {
+      aicp_pair q = p;
+      q.ref = q.read;  // (the reference pointer is not part of the pair here)
+      if (!valid_pair(q)) FAIL(AICP_ERR_INVALID, "invalid pair " + std::to_string(i));
+    } else if (!valid_pair(p)) {
+      FAIL(AICP_ERR_INVALID, "invalid pair " + std::to_string(i));
+    }
     PairDesc& d = B->desc[i];
     int32_t rid = -1;
     for (size_t r = 0; r < rep.size() && !refs_on_device; ++r) {
       const aicp_pair& q = pairs[rep[r]];
-      if (q.ref == p.ref && q.n_ref == p.n_ref && q.ref_stride == p.ref_stride) {
+      if (ref_ids ? ref_ids[rep[r]] == ref_ids[i] && q.n_ref == p.n_ref
+                  : q.ref == p.ref && q.n_ref == p.n_ref && q.ref_stride == p.ref_stride) {
         rid = (int32_t)r;
         break;
       }
@@ -532,7 +543,9 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
   // a sampled chain's reference (chain.cpp): its normals are given, in its input order, so as for
   // point-to-point the matcher tree alone is built; they reach bnrm by one gather (below)
   const bool given_nrm = doIcp && !p2p && chain && chain->ref_normals;
-  if (chain && (P != 1 || doOvl || rcache.use)) FAIL(AICP_ERR_UNSUPPORTED, "a chain runs one pair, without overlap or cache");
+  // (aicp_hip_align_chain_batch computes its overlap on the clouds as given, in a run of its own)
+  if (chain && ((P != 1 && !chain->batch) || doOvl || rcache.use))
+    FAIL(AICP_ERR_UNSUPPORTED, "a chain runs one pair, without overlap or cache");
   hipStream_t s = ctx->stream;
   // the events that order this context's streams release at device scope; ev[1], which the host
   // waits on before it reads the key boxes copied to pinned memory, keeps the system-scope fence
@@ -549,6 +562,8 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
     }
   std::vector<PairDesc> desc = B->desc;
   for (auto& d : desc) d.ratio = cfg->trimmed_ratio;
+  if (chain && chain->ratios)
+    for (size_t i = 0; i < P; ++i) desc[i].ratio = chain->ratios[i];
   HIPC(ensure(ctx->desc, P * sizeof(PairDesc)));
   HIPC(ensure(ctx->state, P * sizeof(PairState)));
   if (P > (size_t)kMaxPairs) FAIL(AICP_ERR_UNSUPPORTED, "more than 4096 pairs in one batch");
@@ -773,7 +788,7 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
     // normals from the raw tree's bucket order into the matcher tree's bucket order (a cached
     // reference's are there already)
     if (given_nrm) {
-      launch_chain_gather_normals(s2, (uint32_t)B->total_ref, bpts, chain->ref_normals, bnrm);
+      launch_chain_gather_normals(s2, (int)R, dRdesc, (uint32_t)B->total_ref, bpts, chain->ref_normals, bnrm);
       launch_pairs_degenerate_part(s2, (int)P, dDesc, dState, nullptr, 2);  // (the count: chain->degenerate, below)
     } else if (!p2p) {
       HIPC(ensure(ctx->inv, B->total_ref * 4));
@@ -928,7 +943,7 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
       o.status = status;
       o.iterations = st.iters;
       o.converged = st.converged;
-      o.degenerate_normals = given_nrm ? chain->degenerate : st.degenerate;
+      o.degenerate_normals = given_nrm ? (chain->degenerate ? chain->degenerate[desc[i].ref_id] : 0) : st.degenerate;
       o.inlier_ratio = st.inlier_ratio;
       o.trimmed_ratio = st.ratio;
       o.overlap_percent = st.overlap;
@@ -1077,6 +1092,7 @@ void aicp_hip_destroy(aicp_hip_ctx* ctx) {
   ctx->tb_mon.release_all();
   ctx->mon_scratch.release_all();
   free_batch(ctx->oneshot);
+  free_batch(ctx->chainbatch);
   free_batch(ctx->mapbatch);
   release(ctx->crop_ws);
   release(ctx->ovl_sp);

@@ -190,12 +190,43 @@ void launch_chain_filter(hipStream_t s, uint32_t cap, const ChainFilterArgs& a, 
 // bnrm: launch_normals, read only with nrm) into the cloud's order: nrm, dens (each nullable)
 bool launch_chain_sn_out(hipStream_t s, uint32_t n, int knn, const float4* bpts, const int32_t* ids, const float4* bnrm,
                          float4* nrm, float* dens);
-// bnrm[j] = given[input id of bpts[j]] for the n points of one reference's matcher tree
-void launch_chain_gather_normals(hipStream_t s, uint32_t n, const float4* bpts, const float4* given, float4* bnrm);
+// bnrm[j] = given[ref_off + input id of bpts[j]] for the n points of the n_refs matcher trees (rd:
+// their descriptors, ascending ref_off; given: each reference's normals at its ref_off)
+void launch_chain_gather_normals(hipStream_t s, int n_refs, const PairDesc* rd, uint32_t n, const float4* bpts,
+                                 const float4* given, float4* bnrm);
 // out[i] = (x, y, z, 1) of in[i]: filtered rows as upload_pairs stores a cloud
 void launch_chain_rows(hipStream_t s, uint32_t n, const float4* in, float4* out);
 // MaxDistOutlierFilter: st[p].limit = limit_d2 for the active pairs (the trimmed select's output)
 void launch_chain_select_maxdist(hipStream_t s, int n_pairs, PairState* st, float limit_d2);
+// The batch form: one side's clouds concatenated. Cloud c holds n[q] rows at off[q] of the side's
+// buffers at stage q (as given, then after each filter); the clouds follow each other without gaps.
+struct ChainCloud {
+  uint32_t n[kChainMaxFilters + 1], off[kChainMaxFilters + 1];
+  uint32_t max_bits, n_sat;  // MaxDensity: the cloud's own lastDensity (float bits) and nbSaturated
+  uint32_t degenerate;       // SurfaceNormal's rank-deficient points of the cloud
+  int32_t sn_slot;           // the cloud's tree among those SurfaceNormal built (-1: it had no point)
+  uint32_t pad[2];
+};
+struct ChainSeg {  // launch_chainb_rows: n rows from src to dst
+  uint32_t dst, src, n, pad;
+};
+// cl: n[0] / off[0] set by the host, the rest zero. Row i of cloud c from src[src_off[c] + i] (the
+// clouds where an upload left them) to pts[off[0] + i], w = i; ctl = {total, 0, ...}
+void launch_chainb_begin(hipStream_t s, int n_clouds, const ChainCloud* cl, uint32_t total, const float4* src,
+                         const uint32_t* src_off, float4* pts, ChainCtl* ctl);
+void launch_chainb_pass(hipStream_t s, int pos, int n_clouds, ChainCloud* cl, ChainCtl* ctl, const PairState* st);
+// launch_chain_filter over the concatenation: every cloud filtered by its own indices, counts and
+// MaxDensity maximum; cl[c].n / off [a.pos + 1] and ctl->n[a.pos + 1] (the total) written. cap: the
+// side's rows as given.
+void launch_chainb_filter(hipStream_t s, uint32_t cap, const ChainFilterArgs& a, int n_clouds, ChainCloud* cl,
+                          ChainCtl* ctl, uint8_t* flag, uint32_t* tile_cnt, uint32_t* tile_off, const float4* pts,
+                          float4* out, const float4* nrm, float4* nrm_out, const float* dens, float* dens_out);
+// launch_chain_sn_out over n_trees raw trees (pd: ref_off / n_ref, ascending, tiling [0, total))
+bool launch_chainb_sn_out(hipStream_t s, int n_trees, const PairDesc* pd, uint32_t total, int knn, const float4* bpts,
+                          const int32_t* ids, const float4* bnrm, float4* nrm, float* dens);
+// launch_chain_rows over segments (ascending dst, tiling [0, total)); nrm -> nrm_out beside (nullable)
+void launch_chainb_rows(hipStream_t s, int n_segs, const ChainSeg* sg, uint32_t total, const float4* in, float4* out,
+                        const float4* nrm, float4* nrm_out);
 
 // ---- sweep accumulator (kernels_accum.hip): VelodyneAccumulatorROS::processLidar ---------------
 struct AccumSweep {

@@ -26,10 +26,11 @@ constexpr int kChainTile = 1024;  // 4 rounds of 256, the crop's tile (its scan 
 // the oracle's by up to 7 ulp, the radius being cubed)
 __device__ __forceinline__ float sqrt_rn(float x) { return (float)sqrt((double)x); }
 
-// The keep rule of filter `a` for point i of the n it receives.
+// The keep rule of filter `a` for point i of the n its cloud holds there. pts / dens: that cloud's
+// rows; maxsat: the cloud's {max_bits, n_sat} (ChainCtl's, or one ChainCloud's of a batch).
 __device__ __forceinline__ bool chain_keep(const ChainFilterArgs& a, uint32_t i, uint32_t n,
                                            const float4* __restrict__ pts, const float* __restrict__ dens,
-                                           const ChainCtl* __restrict__ ctl) {
+                                           const uint32_t* __restrict__ maxsat) {
   switch (a.kind) {
     case kChainMinDist: {
       const float4 p = pts[i];
@@ -49,7 +50,7 @@ __device__ __forceinline__ bool chain_keep(const ChainFilterArgs& a, uint32_t i,
       float accept = __fdiv_rn(a.max_density, d);
       // the saturated points (density == the cloud's maximum): integer division, so the factor is
       // 1 unless every point is saturated, and 0 then
-      if (d == __uint_as_float(ctl->max_bits)) accept = __fmul_rn(accept, (float)(1 - (int32_t)(ctl->n_sat / n)));
+      if (d == __uint_as_float(maxsat[0])) accept = __fmul_rn(accept, (float)(1 - (int32_t)(maxsat[1] / n)));
       return chain_uniform(a.seed, a.slot, i) < accept;
     }
     default:
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(kChainThreads) void k_chain_flag(ChainFilterArgs a,
   for (int r = 0; r < kChainTile / kChainThreads; ++r) {
     const uint32_t i = base + r * kChainThreads + threadIdx.x;
     if (i < n) {
-      const bool keep = chain_keep(a, i, n, pts, dens, ctl);
+      const bool keep = chain_keep(a, i, n, pts, dens, &ctl->max_bits);
       flag[i] = keep ? 1 : 0;
       c += keep ? 1u : 0u;
     }
@@ -176,13 +177,12 @@ __global__ void k_chain_pass(int pos, ChainCtl* ctl, const PairState* st) {
 // densities from the kNN ids k_knn_ids wrote (bucket positions, -1 past the cloud's size), as
 // libpointmatcher computes them: the float mean of the neighbours in list order, the largest float
 // norm of the centred neighbours, the ball's volume in double, realKnn / volume in float.
+// One slot s (< n) of one cloud's tree: bpts / ids / bnrm / nrm / dens are that cloud's (a batch
+// passes them moved by the cloud's offset).
 template <int K>
-__global__ __launch_bounds__(256) void k_chain_sn_out(uint32_t n, const float4* __restrict__ bpts,
-                                                      const int32_t* __restrict__ ids,
-                                                      const float4* __restrict__ bnrm, float4* __restrict__ nrm,
-                                                      float* __restrict__ dens) {
-  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= n) return;
+__device__ __forceinline__ void chain_sn_slot(uint32_t n, uint32_t s, const float4* __restrict__ bpts,
+                                              const int32_t* __restrict__ ids, const float4* __restrict__ bnrm,
+                                              float4* __restrict__ nrm, float* __restrict__ dens) {
   const uint32_t id = (uint32_t)__float_as_int(bpts[s].w);
   if (id >= n) return;  // (never: the tree's ids are the cloud's positions)
   if (nrm) nrm[id] = bnrm[s];
@@ -217,14 +217,245 @@ __global__ __launch_bounds__(256) void k_chain_sn_out(uint32_t n, const float4* 
   dens[id] = __fdiv_rn(fk, vol);  // far == 0: +inf
 }
 
-// bnrm (the matcher tree's bucket order) from the reference's given normals (its input order)
-__global__ __launch_bounds__(256) void k_chain_gather_normals(uint32_t n, const float4* __restrict__ bpts,
+template <int K>
+__global__ __launch_bounds__(256) void k_chain_sn_out(uint32_t n, const float4* __restrict__ bpts,
+                                                      const int32_t* __restrict__ ids,
+                                                      const float4* __restrict__ bnrm, float4* __restrict__ nrm,
+                                                      float* __restrict__ dens) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < n) chain_sn_slot<K>(n, s, bpts, ids, bnrm, nrm, dens);
+}
+
+// bnrm (the matcher trees' bucket order) from the references' given normals (each in its input
+// order, at the reference's ref_off): slot j's reference by search over the ascending ref_off
+__global__ __launch_bounds__(256) void k_chain_gather_normals(int n_refs, const PairDesc* __restrict__ rd, uint32_t n,
+                                                              const float4* __restrict__ bpts,
                                                               const float4* __restrict__ given,
                                                               float4* __restrict__ bnrm) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
+  int lo = 0, hi = n_refs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (rd[mid].ref_off <= j) lo = mid;
+    else hi = mid - 1;
+  }
+  const uint32_t off = rd[lo].ref_off;
   const uint32_t id = (uint32_t)__float_as_int(bpts[j].w);
-  if (id < n) bnrm[j] = given[id];
+  if (id < rd[lo].n_ref) bnrm[j] = given[off + id];  // off + id < off + n_ref <= n
+}
+
+// ---- the batch form: one side's clouds concatenated ("chains in batches") ---------
+// Stage q of the side holds cloud c at rows [cl[c].off[q], + cl[c].n[q]); the clouds follow each
+// other without gaps, so an order-preserving compaction of the whole concatenation keeps every cloud
+// contiguous and in order, and the kept rows before a cloud's first row are its next offset.
+// ChainCtl::n holds the concatenation's totals. A point finds its cloud by search over the offsets.
+
+// the last cloud whose offset at stage q is <= i: the one that holds row i (an emptied cloud shares
+// its offset with the cloud behind it, which the search prefers)
+__device__ __forceinline__ int chainb_cloud_of(const ChainCloud* __restrict__ cl, int n_clouds, int q, uint32_t i) {
+  int lo = 0, hi = n_clouds - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (cl[mid].off[q] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// rows of the clouds as uploaded (w = 1) -> the side's first buffer, w = the index in the own cloud
+__global__ __launch_bounds__(256) void k_chainb_begin(int n_clouds, const ChainCloud* __restrict__ cl, uint32_t total,
+                                                      const float4* __restrict__ src, const uint32_t* __restrict__ src_off,
+                                                      float4* __restrict__ pts, ChainCtl* ctl) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) {
+    ctl->n[0] = total;
+    for (int q = 1; q <= kChainMaxFilters; ++q) ctl->n[q] = 0;
+    ctl->max_bits = 0;
+    ctl->n_sat = 0;
+    ctl->degenerate = 0;
+  }
+  if (i >= total) return;
+  const int c = chainb_cloud_of(cl, n_clouds, 0, i);
+  const uint32_t k = i - cl[c].off[0];
+  float4 p = src[src_off[c] + k];  // (k < cl[c].n[0]: inside the cloud's rows of the upload)
+  p.w = __int_as_float((int32_t)k);
+  pts[i] = p;
+}
+
+__global__ __launch_bounds__(kChainThreads) void k_chainb_flag(ChainFilterArgs a, int n_clouds,
+                                                               const ChainCloud* __restrict__ cl,
+                                                               const ChainCtl* __restrict__ ctl,
+                                                               const float4* __restrict__ pts,
+                                                               const float* __restrict__ dens, uint8_t* __restrict__ flag,
+                                                               uint32_t* __restrict__ tile_cnt) {
+  __shared__ uint32_t wsum[kChainThreads / 64];
+  const uint32_t n = ctl->n[a.pos];
+  const uint32_t base = blockIdx.x * kChainTile;
+  uint32_t c = 0;
+  if (base < n) {
+    // the tile's first cloud once; a lane steps on from there (a 1024-row tile and a 64-lane wave can
+    // hold rows of several clouds)
+    const int c0 = chainb_cloud_of(cl, n_clouds, a.pos, base);
+#pragma unroll 1
+    for (int r = 0; r < kChainTile / kChainThreads; ++r) {
+      const uint32_t i = base + r * kChainThreads + threadIdx.x;
+      if (i < n) {
+        int cc = c0;
+        while (cc + 1 < n_clouds && cl[cc + 1].off[a.pos] <= i) ++cc;
+        const uint32_t off = cl[cc].off[a.pos];
+        const bool keep = chain_keep(a, i - off, cl[cc].n[a.pos], pts + off, dens ? dens + off : nullptr, &cl[cc].max_bits);
+        flag[i] = keep ? 1 : 0;
+        c += keep ? 1u : 0u;
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// kept rows before row b of the stage the filter received (b <= its total n): the scanned tile
+// offset plus the flags of the tile's rows before b, summed by one wave
+__device__ __forceinline__ uint32_t chainb_rank(uint32_t b, uint32_t n, uint32_t n_next,
+                                                const uint8_t* __restrict__ flag,
+                                                const uint32_t* __restrict__ tile_off, int lane) {
+  if (b >= n) return n_next;  // (uniform over the wave)
+  const uint32_t t = b / kChainTile;
+  uint32_t c = 0;
+  for (uint32_t i = t * kChainTile + lane; i < b; i += 64) c += flag[i];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  return tile_off[t] + c;
+}
+
+// one wave per cloud, behind the scan: the cloud's next offset and count
+__global__ __launch_bounds__(64) void k_chainb_counts(int pos, int n_clouds, ChainCloud* cl,
+                                                      const ChainCtl* __restrict__ ctl,
+                                                      const uint8_t* __restrict__ flag,
+                                                      const uint32_t* __restrict__ tile_off) {
+  const int c = blockIdx.x;
+  if (c >= n_clouds) return;
+  const uint32_t n = ctl->n[pos], n_next = ctl->n[pos + 1];
+  const uint32_t b0 = cl[c].off[pos], b1 = b0 + cl[c].n[pos];
+  const uint32_t r0 = chainb_rank(b0, n, n_next, flag, tile_off, threadIdx.x);
+  const uint32_t r1 = chainb_rank(b1, n, n_next, flag, tile_off, threadIdx.x);
+  if (threadIdx.x == 0) {
+    cl[c].off[pos + 1] = r0;
+    cl[c].n[pos + 1] = r1 - r0;
+  }
+}
+
+// MaxDensity's lastDensity and nbSaturated per cloud, over as many workgroups as the side has
+// tiles: densities are never negative (k / volume, +inf for a zero radius), so their bits order as
+// they do, and a maximum and a count of exact matches are the same in any order: integer atomics,
+// one per wave where the wave lies inside one cloud
+__global__ void k_chainb_density_reset(int n_clouds, ChainCloud* cl) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < n_clouds) {
+    cl[c].max_bits = 0;
+    cl[c].n_sat = 0;
+  }
+}
+
+template <bool kCount>
+__global__ __launch_bounds__(kChainThreads) void k_chainb_density(int pos, int n_clouds, ChainCloud* cl,
+                                                                 const ChainCtl* __restrict__ ctl,
+                                                                 const float* __restrict__ dens) {
+  const uint32_t n = ctl->n[pos];
+  const uint32_t base = blockIdx.x * kChainTile;
+  if (base >= n) return;
+  const int c0 = chainb_cloud_of(cl, n_clouds, pos, base);
+#pragma unroll 1
+  for (int r = 0; r < kChainTile / kChainThreads; ++r) {
+    const uint32_t i = base + r * kChainThreads + threadIdx.x;
+    const bool in = i < n;
+    int cc = c0;
+    uint32_t v = 0;
+    if (in) {
+      while (cc + 1 < n_clouds && cl[cc + 1].off[pos] <= i) ++cc;
+      const uint32_t bits = __float_as_uint(dens[i]);
+      v = kCount ? (bits == cl[cc].max_bits ? 1u : 0u) : bits;
+    }
+    // a wave whose live lanes share one cloud: one atomic for the wave
+    const int cf = __shfl(cc, __ffsll((unsigned long long)__ballot(in)) - 1, 64);
+    if (__all(!in || cc == cf)) {
+      uint32_t w = v;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t u = __shfl_xor(w, o, 64);
+        w = kCount ? w + u : (u > w ? u : w);
+      }
+      if (__ballot(in) && (threadIdx.x & 63) == 0) {
+        if (kCount) {
+          if (w) atomicAdd(&cl[cf].n_sat, w);
+        } else {
+          atomicMax(&cl[cf].max_bits, w);
+        }
+      }
+    } else if (in) {
+      if (kCount) {
+        if (v) atomicAdd(&cl[cc].n_sat, 1u);
+      } else {
+        atomicMax(&cl[cc].max_bits, v);
+      }
+    }
+  }
+}
+
+// a SurfaceNormal keeps every point of every cloud; st (nullable): the states launch_normals counted
+// the degenerate points in, one per cloud that had points (cl[c].sn_slot, -1: none)
+__global__ void k_chainb_pass(int pos, int n_clouds, ChainCloud* cl, ChainCtl* ctl, const PairState* st) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c == 0) ctl->n[pos + 1] = ctl->n[pos];
+  if (c >= n_clouds) return;
+  cl[c].n[pos + 1] = cl[c].n[pos];
+  cl[c].off[pos + 1] = cl[c].off[pos];
+  if (st && cl[c].sn_slot >= 0) cl[c].degenerate = (uint32_t)st[cl[c].sn_slot].degenerate;
+}
+
+// k_chain_sn_out over the trees of the clouds that had points (pd: ascending ref_off, the cloud's
+// offset at the filter, where its rows, normals and densities lie too)
+template <int K>
+__global__ __launch_bounds__(256) void k_chainb_sn_out(int n_trees, const PairDesc* __restrict__ pd, uint32_t total,
+                                                       const float4* __restrict__ bpts,
+                                                       const int32_t* __restrict__ ids,
+                                                       const float4* __restrict__ bnrm, float4* __restrict__ nrm,
+                                                       float* __restrict__ dens) {
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= total) return;
+  int lo = 0, hi = n_trees - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (pd[mid].ref_off <= s) lo = mid;
+    else hi = mid - 1;
+  }
+  const uint32_t off = pd[lo].ref_off, n = pd[lo].n_ref;
+  if (s - off >= n) return;  // (never: the trees tile [0, total))
+  chain_sn_slot<K>(n, s - off, bpts + off, ids + (size_t)off * K, bnrm + off, nrm ? nrm + off : nullptr,
+                   dens ? dens + off : nullptr);
+}
+
+// the kept rows of the clouds that run, as upload_pairs stores clouds: segment g's n rows from
+// in + src to out + dst (x, y, z, 1), the normals beside them (nullable)
+__global__ __launch_bounds__(256) void k_chainb_rows(int n_segs, const ChainSeg* __restrict__ sg, uint32_t total,
+                                                     const float4* __restrict__ in, float4* __restrict__ out,
+                                                     const float4* __restrict__ nrm, float4* __restrict__ nrm_out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  int lo = 0, hi = n_segs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (sg[mid].dst <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  const uint32_t k = i - sg[lo].dst;
+  if (k >= sg[lo].n) return;  // (never: the segments tile [0, total))
+  const float4 p = in[sg[lo].src + k];
+  out[i] = make_float4(p.x, p.y, p.z, 1.f);
+  if (nrm_out) nrm_out[i] = nrm[sg[lo].src + k];
 }
 
 // the filtered rows as an uploaded cloud holds them: x, y, z, 1
@@ -281,8 +512,9 @@ bool launch_chain_sn_out(hipStream_t s, uint32_t n, int knn, const float4* bpts,
   return true;
 }
 
-void launch_chain_gather_normals(hipStream_t s, uint32_t n, const float4* bpts, const float4* given, float4* bnrm) {
-  if (n) k_chain_gather_normals<<<grid_of(n), 256, 0, s>>>(n, bpts, given, bnrm);
+void launch_chain_gather_normals(hipStream_t s, int n_refs, const PairDesc* rd, uint32_t n, const float4* bpts,
+                                 const float4* given, float4* bnrm) {
+  if (n && n_refs > 0) k_chain_gather_normals<<<grid_of(n), 256, 0, s>>>(n_refs, rd, n, bpts, given, bnrm);
 }
 
 void launch_chain_rows(hipStream_t s, uint32_t n, const float4* in, float4* out) {
@@ -291,6 +523,53 @@ void launch_chain_rows(hipStream_t s, uint32_t n, const float4* in, float4* out)
 
 void launch_chain_select_maxdist(hipStream_t s, int n_pairs, PairState* st, float limit_d2) {
   k_chain_select_maxdist<<<(n_pairs + 63) / 64, 64, 0, s>>>(n_pairs, st, limit_d2);
+}
+
+// ---- the batch form ---------------------------------------------------------------------------
+void launch_chainb_begin(hipStream_t s, int n_clouds, const ChainCloud* cl, uint32_t total, const float4* src,
+                         const uint32_t* src_off, float4* pts, ChainCtl* ctl) {
+  k_chainb_begin<<<std::max(1u, grid_of(total)), 256, 0, s>>>(n_clouds, cl, total, src, src_off, pts, ctl);
+}
+
+void launch_chainb_pass(hipStream_t s, int pos, int n_clouds, ChainCloud* cl, ChainCtl* ctl, const PairState* st) {
+  k_chainb_pass<<<(n_clouds + 63) / 64, 64, 0, s>>>(pos, n_clouds, cl, ctl, st);
+}
+
+void launch_chainb_filter(hipStream_t s, uint32_t cap, const ChainFilterArgs& a, int n_clouds, ChainCloud* cl,
+                          ChainCtl* ctl, uint8_t* flag, uint32_t* tile_cnt, uint32_t* tile_off, const float4* pts,
+                          float4* out, const float4* nrm, float4* nrm_out, const float* dens, float* dens_out) {
+  const int tiles = (int)chain_tiles(cap);
+  if (tiles == 0) {
+    launch_chainb_pass(s, a.pos, n_clouds, cl, ctl, nullptr);
+    return;
+  }
+  if (a.kind == kChainMaxDensity) {
+    k_chainb_density_reset<<<(n_clouds + 63) / 64, 64, 0, s>>>(n_clouds, cl);
+    k_chainb_density<false><<<tiles, kChainThreads, 0, s>>>(a.pos, n_clouds, cl, ctl, dens);
+    k_chainb_density<true><<<tiles, kChainThreads, 0, s>>>(a.pos, n_clouds, cl, ctl, dens);
+  }
+  k_chainb_flag<<<tiles, kChainThreads, 0, s>>>(a, n_clouds, cl, ctl, pts, dens, flag, tile_cnt);
+  launch_tile_scan(s, tiles, tile_cnt, tile_off, &ctl->n[a.pos + 1]);
+  k_chainb_counts<<<n_clouds, 64, 0, s>>>(a.pos, n_clouds, cl, ctl, flag, tile_off);
+  // (the one-pair scatter: the concatenation is one stream of ctl->n[pos] rows)
+  k_chain_scatter<<<tiles, kChainThreads, 0, s>>>(a.pos, ctl, flag, tile_off, pts, out, nrm, nrm_out, dens, dens_out);
+}
+
+bool launch_chainb_sn_out(hipStream_t s, int n_trees, const PairDesc* pd, uint32_t total, int knn, const float4* bpts,
+                          const int32_t* ids, const float4* bnrm, float4* nrm, float* dens) {
+  if (!total || n_trees < 1) return true;
+  switch (knn) {
+    case 10: k_chainb_sn_out<10><<<grid_of(total), 256, 0, s>>>(n_trees, pd, total, bpts, ids, bnrm, nrm, dens); break;
+    case 20: k_chainb_sn_out<20><<<grid_of(total), 256, 0, s>>>(n_trees, pd, total, bpts, ids, bnrm, nrm, dens); break;
+    case 30: k_chainb_sn_out<30><<<grid_of(total), 256, 0, s>>>(n_trees, pd, total, bpts, ids, bnrm, nrm, dens); break;
+    default: return false;
+  }
+  return true;
+}
+
+void launch_chainb_rows(hipStream_t s, int n_segs, const ChainSeg* sg, uint32_t total, const float4* in, float4* out,
+                        const float4* nrm, float4* nrm_out) {
+  if (total && n_segs > 0) k_chainb_rows<<<grid_of(total), 256, 0, s>>>(n_segs, sg, total, in, out, nrm, nrm_out);
 }
 
 }  // namespace aicp

@@ -392,17 +392,22 @@ inline bool valid_cloud(const aicp_cloud& c) {
 
 // the batch pipeline (aicp_hip.cpp), for the entry points that compose a batch on the device
 int upload_pairs(aicp_hip_ctx* ctx, const aicp_pair* pairs, size_t n, aicp_hip_batch* B, bool refs_on_device,
-                 bool skip_refs = false, bool skip_reads = false, bool nosync = false);
+                 bool skip_refs = false, bool skip_reads = false, bool nosync = false,
+                 const int32_t* ref_ids = nullptr);
 // What a sampled chain (chain.cpp) adds to a one-pair run_batch; without it run_batch
 // does what it did before there were chains.
 struct ChainRun {
-  // the one reference's normals, in its input order on the device (SurfaceNormal ran earlier in
-  // the chain, on the cloud before the later filters): they replace raw tree -> kNN ->
-  // k_scatter_normals by one gather through the matcher tree's input index. nullptr: not given
+  // the references' normals, each in its input order at its rdesc ref_off on the device
+  // (SurfaceNormal ran earlier in the chain, on the cloud before the later filters): they replace
+  // raw tree -> kNN -> k_scatter_normals by one gather through the matcher trees' input index.
+  // nullptr: not given
   const float4* ref_normals = nullptr;
-  int32_t degenerate = 0;  // their rank-deficient count (aicp_icp_stats::degenerate_normals)
+  // their rank-deficient counts, one per distinct reference (aicp_icp_stats::degenerate_normals)
+  const int32_t* degenerate = nullptr;
   bool max_dist = false;   // MaxDistOutlierFilter: the select step writes limit_d2
   float limit_d2 = 0.f;
+  bool batch = false;      // aicp_hip_align_chain_batch: any number of pairs (else one)
+  const float* ratios = nullptr;  // per pair, instead of cfg->trimmed_ratio (the overlap's auto-tuned ones)
 };
 int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, double res, int flags, float* outT,
               aicp_icp_stats* stats, float* out_overlap, const ChainRun* chain = nullptr);
@@ -410,11 +415,35 @@ int run_batch(aicp_hip_ctx* ctx, aicp_hip_batch* B, const aicp_icp_config* cfg, 
 // between two sets as the filters compact them
 struct ChainBufs {
   DevBuf pts[2], nrm[2], dens[2], dens_sn, flag, tile_cnt, tile_off, ctl;
+  // the batch form: the clouds' records, where each lies in the upload, the SurfaceNormal trees'
+  // descriptors, the segments of the clouds that run; their pinned staging
+  DevBuf clouds, src_off, segs;
+  PinBuf pin_cl, pin_desc, pin_seg;
   void release_all() {
-    for (DevBuf* b : {&pts[0], &pts[1], &nrm[0], &nrm[1], &dens[0], &dens[1], &dens_sn, &flag, &tile_cnt, &tile_off, &ctl})
+    for (DevBuf* b : {&pts[0], &pts[1], &nrm[0], &nrm[1], &dens[0], &dens[1], &dens_sn, &flag, &tile_cnt, &tile_off, &ctl,
+                      &clouds, &src_off, &segs})
       release(*b);
+    for (PinBuf* b : {&pin_cl, &pin_desc, &pin_seg}) release(*b);
   }
 };
+// One side's filter list over C clouds at once (chain.cpp; DESIGN §4.8, the batch form). The clouds
+// lie on the device as an upload left them: cloud c's n_in[c] rows (float4) at dsrc + src_off[c].
+// Everything is enqueued on ctx->stream, the records' copy to the host last; nothing is waited for
+// unless a SurfaceNormal whose outputs are used sits behind a dropping filter (its trees are sized
+// by the counts there). Once the stream has been waited for, o->cl[c] holds cloud c's counts and
+// offsets per stage: the kept rows lie at ctx->chain[side].pts[o->cur] + cl[c].off[nf], the normals
+// (o->nrm) and, until a MaxDensity consumed them, the densities beside them; dens_sn (o->dens_sn)
+// holds the densities at the SurfaceNormal, cloud c's at cl[c].off[o->sn_pos].
+struct ChainBatchSide {
+  size_t C = 0;
+  uint64_t total = 0;
+  int nf = 0, cur = 0, sn_pos = -1;
+  bool nrm = false, dens_sn = false;
+  const ChainCloud* cl = nullptr;  // pinned; valid until the side runs again
+};
+int chain_batch_side(aicp_hip_ctx* ctx, const aicp_chain* chain, int side, size_t C, const uint32_t* n_in,
+                     const float4* dsrc, const uint32_t* src_off, bool want_nrm, bool want_dens, ChainBatchSide* o);
+int chain_check(aicp_hip_ctx* ctx, const aicp_chain* c);  // the chain as the registration calls accept it
 void free_batch(aicp_hip_batch* B);
 // the batch's overlap after its key boxes (overlap.cpp): voxel maps, or sorted key words where they do not fit
 int overlap_maps(aicp_hip_ctx* ctx, aicp_hip_batch* B, size_t P, size_t G, PairDesc* dDesc, PairState* dState,
@@ -624,6 +653,7 @@ struct aicp_hip_ctx {
   aicp::rt::PinBuf pin_crop;
   aicp::rt::PinBuf pin_maps;  // upload_pairs' block maps
   aicp::rt::ChainBufs chain[2];  // the sampled chains' filtered clouds: [reference], [reading] (chain.cpp)
+  aicp_hip_batch* chainbatch = nullptr;  // aicp_hip_align_chain_batch: the clouds as given (the filtered ones: oneshot)
   aicp::rt::PinBuf pin_chain;    // their control blocks read back
   aicp::rt::RefCache refc;  // the drop-in path's resident reference (runtime.hpp)
   aicp::rt::OvlProbe ovl_probe;  // aicp_hip_test_overlap (off in every other call)

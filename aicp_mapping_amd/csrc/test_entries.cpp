@@ -1242,4 +1242,74 @@ int aicp_hip_test_promote_map(aicp_hip_ctx* ctx, int32_t kernel, const float* re
   return AICP_OK;
 }
 
+int aicp_hip_test_chain_batch(aicp_hip_ctx* ctx, const aicp_chain* chain, int32_t side, size_t n_clouds,
+                              const uint32_t* counts, const float* pts, uint64_t* out_counts, uint64_t* out_n,
+                              int32_t* out_index, float* out_normals, float* out_densities) {
+  if (!ctx) return AICP_ERR_INVALID;
+  uint64_t total = 0;
+  if (!chain || !counts || !pts || !out_counts || !out_n || !out_index || n_clouds == 0 ||
+      n_clouds > (size_t)kMaxPairs || (side != AICP_CHAIN_REFERENCE && side != AICP_CHAIN_READING) ||
+      !count_check(counts, n_clouds, 1ull << 28, &total))
+    FAIL(AICP_ERR_INVALID, "test_chain_batch arguments");
+  int rc = chain_check(ctx, chain);
+  if (rc) return rc;
+  bool sn = false, sn_dens = false;
+  for (int q = 0; q < chain->n_filters[side]; ++q)
+    if (chain->filters[side][q].kind == AICP_FILTER_SURFACE_NORMAL) {
+      sn = true;
+      sn_dens = chain->filters[side][q].keep_densities != 0;
+    }
+  if (out_normals && !sn) FAIL(AICP_ERR_INVALID, "normals asked of a side without SurfaceNormal");
+  if (out_densities && !sn_dens) FAIL(AICP_ERR_INVALID, "densities asked of a side without keepDensities");
+  HIPC(hipSetDevice(ctx->device));
+  CallBufs loc;
+  loc.sync = ctx->stream;
+  DevBuf& src = loc.get();
+  HIPC(ensure(src, total * 16));
+  std::vector<float> pk;
+  HIPC(upload_xyz4(pk, pts, total, src.p));
+  std::vector<uint32_t> off(n_clouds);
+  uint32_t run = 0;
+  for (size_t c = 0; c < n_clouds; ++c) {
+    off[c] = run;
+    run += counts[c];
+  }
+  ChainBatchSide sb;
+  rc = chain_batch_side(ctx, chain, side, n_clouds, counts, src.as<float4>(), off.data(), out_normals != nullptr,
+                        out_densities != nullptr, &sb);
+  if (rc) return rc;
+  HIPC(hipStreamSynchronize(ctx->stream));
+  const int nf = chain->n_filters[side];
+  const ChainBufs& cb = ctx->chain[side];
+  std::vector<float> rows(4 * (size_t)total), nrm, dens;
+  HIPC(hipMemcpy(rows.data(), cb.pts[sb.cur].p, (size_t)total * 16, hipMemcpyDeviceToHost));
+  if (out_normals) {
+    if (!sb.nrm) FAIL(AICP_ERR_HIP, "chain normals missing");
+    nrm.resize(4 * (size_t)total);
+    HIPC(hipMemcpy(nrm.data(), cb.nrm[sb.cur].p, (size_t)total * 16, hipMemcpyDeviceToHost));
+  }
+  if (out_densities && sb.dens_sn) {
+    dens.resize((size_t)total);
+    HIPC(hipMemcpy(dens.data(), cb.dens_sn.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+  }
+  uint64_t k = 0, kd = 0;
+  for (size_t c = 0; c < n_clouds; ++c) {
+    const ChainCloud& cl = sb.cl[c];
+    for (int q = 0; q < AICP_CHAIN_MAX_FILTERS; ++q) out_counts[4 * c + q] = q < nf ? cl.n[q + 1] : 0;
+    out_n[c] = cl.n[nf];
+    if (cl.n[nf] > counts[c] || cl.off[nf] + (uint64_t)cl.n[nf] > total) FAIL(AICP_ERR_HIP, "chain filter count");
+    for (uint32_t i = 0; i < cl.n[nf]; ++i, ++k) {
+      const size_t row = (size_t)cl.off[nf] + i;
+      std::memcpy(&out_index[k], &rows[4 * row + 3], 4);
+      if (out_normals)
+        for (int d = 0; d < 3; ++d) out_normals[3 * k + d] = nrm[4 * row + d];
+    }
+    if (out_densities && sb.dens_sn && sb.sn_pos >= 0) {
+      if (cl.off[sb.sn_pos] + (uint64_t)cl.n[sb.sn_pos] > total) FAIL(AICP_ERR_HIP, "chain filter count");
+      for (uint32_t i = 0; i < cl.n[sb.sn_pos]; ++i) out_densities[kd++] = dens[(size_t)cl.off[sb.sn_pos] + i];
+    }
+  }
+  return AICP_OK;
+}
+
 }  // extern "C"

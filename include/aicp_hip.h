@@ -270,11 +270,42 @@ int aicp_hip_chain_filter(aicp_hip_ctx* ctx, const aicp_chain* chain, int side, 
  * survivors. stats->inlier_ratio is over the filtered reading. A side left without a point:
  * AICP_ERR_CONVERGENCE, the side named in aicp_hip_last_error. A chain with no filter but
  * SurfaceNormal and the TrimmedDist rule gives aicp_hip_register's bits (reference cache off).
- * The call neither uses nor keeps the reference cache, and drops it. Chains are served here only:
- * the batch, multi-GPU, stream and session calls take aicp_icp_config alone. */
+ * The call neither uses nor keeps the reference cache, and drops it. Chains are served here and,
+ * for many pairs at once, by aicp_hip_align_chain_batch below; the multi-GPU, stream and session
+ * calls take aicp_icp_config alone. */
 int aicp_hip_register_chain(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_chain* chain,
                             const aicp_pair* pair, float out_T[16], aicp_icp_stats* stats /* nullable */,
                             aicp_chain_stats* chain_stats /* nullable */);
+/* aicp_hip_register_chain for n_pairs pairs in one call: pair i gets exactly what the one-pair
+ * call on that pair returns (same seed), out_T bit for bit. flags: AICP_RUN_ICP, or AICP_RUN_ICP |
+ * AICP_RUN_OVERLAP; anything else is AICP_ERR_INVALID.
+ *   Filters. Every cloud is filtered by its side's list on its own: the draw's index i, MaxDensity's
+ *   maximum and saturated count and SurfaceNormal's neighbourhoods are those of the point's own
+ *   cloud, never the batch's. Pairs that pass the same reference array (pointer, count, stride)
+ *   share it: its filters, its matcher tree and its normals run once.
+ *   AICP_RUN_OVERLAP. App's order: the octree overlap is computed on the clouds as given, with the
+ *   pair's origins, at `resolution` (not read otherwise); the pair's TrimmedDist ratio is
+ *   aicp_hip_autotune_ratio(overlap) and cfg->trimmed_ratio is not read. stats[i].overlap_percent,
+ *   overlap_keys and trimmed_ratio are filled as aicp_hip_align_batch fills them, with the MaxDist
+ *   rule too (which does not read the ratio).
+ *   A pair whose filters leave a side without a point: stats[i].status = AICP_ERR_CONVERGENCE,
+ *   the identity in out_T, its chain_stats filled, nothing else of it runs; the other pairs are
+ *   not affected. An emptied shared reference ends all its pairs.
+ *   Returns the first non-zero pair status in pair order; aicp_hip_last_error names that pair
+ *   ("pair 3: ...") and, for an emptied one, the side in aicp_hip_register_chain's words.
+ *   stats[i].inlier_ratio is over the filtered reading; degenerate_normals is the count of the cloud
+ *   the reference's SurfaceNormal ran on.
+ * Limits: 4096 pairs, 2^28 reference points and 2^31 reading points in all (AICP_ERR_UNSUPPORTED).
+ * One corner where a pair does not get the one-pair call's answer: a SurfaceNormal whose output is
+ * used and whose knn is outside {10, 20, 30} (a chain the parser refuses) ends the whole call with
+ * AICP_ERR_UNSUPPORTED as soon as any cloud of the side reaches it with a point, also for a pair that
+ * the filters in front of it had emptied (the one-pair call on that pair: AICP_ERR_CONVERGENCE).
+ * A chain with no filter but SurfaceNormal and the TrimmedDist rule takes aicp_hip_align_batch's
+ * path and gives its bits. The call neither uses nor keeps the reference cache, and drops it. */
+int aicp_hip_align_chain_batch(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_chain* chain,
+                               const aicp_pair* pairs, size_t n_pairs, double resolution, int flags,
+                               float* out_T /* 16 * n_pairs */, aicp_icp_stats* stats /* n_pairs, nullable */,
+                               aicp_chain_stats* chain_stats /* n_pairs, nullable */);
 
 /* ---- registration / overlap (host buffers) ---------------------------------------------- */
 int aicp_hip_register(aicp_hip_ctx* ctx, const aicp_icp_config* cfg, const aicp_pair* pair,
@@ -1604,6 +1635,26 @@ int aicp_hip_test_monitor_resident(aicp_hip_ctx* ctx, const aicp_monitor_params*
  * changed, plus 1 when read4's bytes on the device changed. */
 int aicp_hip_test_promote_map(aicp_hip_ctx* ctx, int32_t kernel, const float* read4, size_t n, size_t tail,
                               int32_t id, void* block, float* ref4, float* map4, uint64_t* dirty);
+/* Test surface: one side's filter list (side: AICP_CHAIN_REFERENCE / _READING) over n_clouds clouds
+ * at once, through the kernels aicp_hip_align_chain_batch runs. counts: the clouds' sizes (each >=
+ * 1); pts: their points laid end to end, 3 floats each. Out, per cloud c:
+ *   out_counts[4 c + q]  points after filter q of the list (0 past the list's end)
+ *   out_n[c]             kept points
+ *   out_index            the kept points' indices in their own cloud, the clouds' kept points laid
+ *                        end to end (cloud c's start at the sum of out_n before it); capacity total
+ *   out_normals          nullable: 3 floats per kept point, laid out as out_index (a SurfaceNormal
+ *                        of knn 10 / 20 / 30 on the side)
+ *   out_densities        nullable: the densities at the SurfaceNormal, in the order of each cloud
+ *                        there, the clouds end to end (cloud c holds as many as it had points at
+ *                        that position); capacity total (keep_densities on the side)
+ * AICP_ERR_INVALID, before any device work: a null pointer, no cloud or more than 4096, a count of
+ * 0, total >= 2^28, a wrong side, normals / densities asked of a side that has none, and whatever
+ * the chain check refuses. Invalidates the context's reference cache. */
+int aicp_hip_test_chain_batch(aicp_hip_ctx* ctx, const aicp_chain* chain, int32_t side, size_t n_clouds,
+                              const uint32_t* counts, const float* pts, uint64_t* out_counts /* 4 * n_clouds */,
+                              uint64_t* out_n /* n_clouds */, int32_t* out_index /* total */,
+                              float* out_normals /* 3 * total, nullable */,
+                              float* out_densities /* total, nullable */);
 
 #ifdef __cplusplus
 }
